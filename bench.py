@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """Headline benchmark: fcgan training-step images/sec (deconv G + 3x PatchGAN D, 512x512, bs=1/GPU)
-on N MI355X, with the dominant kernel's roofline fraction and a CPU baseline timed in the same run.
+on N MI355X.  With --full the same run also reports the dominant kernel's roofline fraction, the per-kernel
+table, the pinned-host-input regime and a CPU baseline.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+--dump-outputs DIR writes, as DIR/<name>.npy, one more step of the timed path (graph replay, optimizer updates on) on a
+fresh, seeded copy of the model and the last timed step's batch: its visuals, losses and the gradients each optimizer
+received (see dump_outputs).  Inputs, weights, latents and the image pool's draws are seeded, so two builds run with the
+same arguments can be compared output for output, to float-atomic rounding.
 
 One "step" = FCGANModel.optimize_parameters() of the README fcgan recipe (README.md:33: n_update_D=1,
 n_update_G=2, pool_size=50) on one synthetic 3x512x512 batch taken from a ring of 64 pinned host tensors: the
@@ -15,6 +21,7 @@ import argparse
 import contextlib
 import json
 import os
+import random
 import sys
 import time
 
@@ -399,6 +406,72 @@ def committed_profile_of(kernel):
     return traffic, us, src
 
 
+DUMP_BUDGET = 60 << 20      # bytes of array data: the files, .npy headers included, stay under the 64 MB --dump-outputs promises
+OPTIMIZERS = ("optimizer_D", "optimizer_D1", "optimizer_D2", "optimizer_G")
+
+
+def nets_of(model, two):
+    """Generator-side and discriminator-side networks of a trainer."""
+    if two:
+        return {"G": [model.netG1, model.netG2, model.netF2], "D": model.netD1 + model.netD2}
+    return {"G": [model.netG], "D": model.netD}
+
+
+def dump_outputs(model, eager, batch, out_dir):
+    """--dump-outputs: one more step of the timed path -- hipGraph replay (the eager step with --eager), optimizer updates on -- taken
+    on `model`, a fresh copy of the benchmarked trainer (seeded weights, latents and pool), fed `batch`, the last timed step's input.
+    The graph is cut at the step's data-parallel hand-off points (grad_sync, as with N > 1 ranks; the same kernels in the same
+    order): at each, between a backward pass and the optimizer step that consumes it, the gradients are read, and at the first, before
+    any update, the visuals (get_current_visuals).  Written: those visuals, the step's losses (float64) and the gradients each
+    optimizer received, flattened over its arenas (float32; above its share of DUMP_BUDGET a fixed, seeded sample).
+    Not the state the timed steps leave behind: the kernels' weight-gradient and statistics reductions are float atomics, so a step
+    is reproducible only to float-atomic rounding, and Adam's first updates (~lr * sign(g)) and the GAN dynamics grow that to O(1)
+    within a few steps.  For the same reason the capture's eager warm-up steps run with the optimizer updates suppressed (the
+    captured step is the real one), so the dumped step starts from the seeded state.  Its values are reproducible to float-atomic
+    rounding."""
+    import numpy as np
+    names = {id(getattr(model, n)): n for n in OPTIMIZERS if hasattr(model, n)}
+    visuals, grads, armed = {}, {}, [False]
+
+    def hand_off(optimizer):
+        if not armed[0]:
+            return
+        if not visuals:
+            visuals.update(("visual_" + k, v.detach().float().cpu().numpy()) for k, v in model.get_current_visuals().items())
+        name = names[id(optimizer)]
+        if name not in grads:      # n_update_G > 1: the first generator update's
+            grads[name] = torch.cat([g.reshape(-1) for _, g in optimizer.segments()]).float().cpu().numpy()
+    model.grad_sync = hand_off
+    if eager:
+        armed[0] = True
+        model.set_input(batch)
+        model.optimize_parameters()
+    else:
+        from supervised_gan_amd.graph_step import GraphedStep
+        opts = [getattr(model, n) for n in OPTIMIZERS if hasattr(model, n)]
+        for o in opts:
+            o.step = lambda real=o.step: real() if torch.cuda.is_current_stream_capturing() else None
+        gs = GraphedStep(model)
+        gs.capture(batch)
+        for o in opts:
+            del o.step
+        armed[0] = True
+        gs.step(batch)
+    torch.cuda.synchronize()
+    assert visuals and len(grads) == len(names), (list(visuals), list(grads))
+    arrays = dict(visuals)
+    arrays.update({"loss_" + k: np.array([v], dtype=np.float64) for k, v in model.get_current_errors().items()})
+    share = (DUMP_BUDGET - sum(a.nbytes for a in arrays.values())) // (4 * len(grads))
+    for name, flat in grads.items():
+        if flat.size > share:
+            flat = flat[np.sort(np.random.default_rng(0).choice(flat.size, share, replace=False))]
+        arrays["grad_" + name] = flat
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def main():
     if os.environ.get("SGAN_BENCH_WATCHDOG"):      # debugging aid: dump every thread's stack and exit
         import faulthandler
@@ -412,12 +485,20 @@ def main():
     ap.add_argument("--skip_wasted_D_wgrad", action="store_true")
     ap.add_argument("--no_d_streams", action="store_true")
     ap.add_argument("--no_group", action="store_true")
-    ap.add_argument("--no_cpu_baseline", action="store_true")
-    ap.add_argument("--no_kernel_profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel table and roofline, pinned-host-input regime, "
+                         "CPU baseline")
+    ap.add_argument("--no_cpu_baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no_kernel_profile", action="store_true", help="with --full: skip the per-kernel table and roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR", dest="dump_outputs",
+                    help="after the run, one more step of the timed path on a fresh, seeded model and the last timed batch: its visuals, "
+                         "losses and gradients as DIR/<name>.npy (rank 0; see dump_outputs)")
     ap.add_argument("--workload", default="fcgan", choices=["fcgan", "cgan", "twostage_cycle"],
                     help="fcgan = the headline metric (BASELINE configs[1]); cgan = BASELINE configs[2], twostage_cycle = configs[4], "
                          "each reported under its own metric name")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:      # no launcher: be the launcher (nothing has touched a GPU yet)
         return spawn_ranks(args.gpus)
@@ -436,23 +517,25 @@ def main():
     two = args.workload == "twostage_cycle"
     if two:
         args.no_cpu_baseline = True
-        model = build_twostage(args, rank)
-        sdist.broadcast_parameters([model.netG1, model.netG2, model.netF2] + model.netD1 + model.netD2)
-    else:
-        model = build_cgan(args, rank) if cgan else build_model(args, rank)
-        sdist.broadcast_parameters([model.netG] + model.netD)
+
+    random.seed(rank)          # ImagePool's swap draws (Python's random, as in the reference): the same history on every run
+
+    def make_model():
+        return build_twostage(args, rank) if two else build_cgan(args, rank) if cgan else build_model(args, rank)
+    model = make_model()
+    nets = nets_of(model, two)
+    sdist.broadcast_parameters(nets["G"] + nets["D"])
     ring = synthetic_ring(64, rank, device)
 
     kern = None
-    if rank == 0 and not args.no_kernel_profile:     # a few un-synchronised steps on rank 0 only (no collective inside) ...
+    if args.full and rank == 0 and not args.no_kernel_profile:     # a few un-synchronised steps on rank 0 only (no collective inside) ...
         kern = profile_kernels(model, ring, workload=args.workload)
     if kern is not None:                             # ... whose optimizer moments must not leak into the measured run
-        for name in ("optimizer_D", "optimizer_D1", "optimizer_D2", "optimizer_G"):
+        for name in OPTIMIZERS:
             if hasattr(model, name):
                 getattr(model, name).reset_state()
     if world > 1:                                    # ... and every rank is handed rank 0's weights again before the timed run
-        nets = [model.netG1, model.netG2, model.netF2] + model.netD1 + model.netD2 if two else [model.netG] + model.netD
-        sdist.broadcast_parameters(nets)
+        sdist.broadcast_parameters(nets["G"] + nets["D"])
         model.grad_sync = sdist.GradAverager()
 
     if os.environ.get("SGAN_FORCE_SEGMENTS") and model.grad_sync is None:     # diagnostic: the N > 1 graph cuts without the collectives
@@ -495,31 +578,34 @@ def main():
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     ms_median = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (per_step[len(per_step) // 2 - 1] + per_step[len(per_step) // 2])
     gs_bytes, gs_calls = getattr(getattr(model, "grad_sync", None), "bytes", 0), getattr(getattr(model, "grad_sync", None), "calls", 0)      # of the timed steps
-    # the same steps with the batches in pinned host memory (round 2's headline regime: the input gather reads over PCIe inside the step)
-    host_ring = synthetic_ring(8, rank, device, where="host")
-    kh = min(args.steps, 100)
-    for s_ in host_ring:      # untimed: the first device access of a freshly pinned buffer is not PCIe time (2.05 vs 2.87 ms/step seen without)
-        if args.eager:
-            model.set_input(s_); model.optimize_parameters()
-        else:
-            gs.step(s_)
-    barrier()
-    th0 = time.perf_counter()
-    for i in range(kh):
-        s_ = host_ring[i % len(host_ring)]
-        if args.eager:
-            model.set_input(s_); model.optimize_parameters()
-        else:
-            gs.step(s_)
-    barrier()
-    dt_host = (time.perf_counter() - th0) / kh
+    errs = model.get_current_errors()
+    dt_host = None
+    if args.full:
+        # the same steps with the batches in pinned host memory (round 2's headline regime: the input gather reads over PCIe inside the step)
+        host_ring = synthetic_ring(8, rank, device, where="host")
+        kh = min(args.steps, 100)
+        for s_ in host_ring:      # untimed: the first device access of a freshly pinned buffer is not PCIe time (2.05 vs 2.87 ms/step seen without)
+            if args.eager:
+                model.set_input(s_); model.optimize_parameters()
+            else:
+                gs.step(s_)
+        barrier()
+        th0 = time.perf_counter()
+        for i in range(kh):
+            s_ = host_ring[i % len(host_ring)]
+            if args.eager:
+                model.set_input(s_); model.optimize_parameters()
+            else:
+                gs.step(s_)
+        barrier()
+        dt_host = (time.perf_counter() - th0) / kh
+        errs = model.get_current_errors()
     if os.environ.get("SGAN_BENCH_HOST"):      # diagnostic: is the host (graph launches, pool policy) or the device the longer leg?
         print(f"[bench] host enqueue {host_busy / args.steps * 1e3:.3f} ms/step of {dt / args.steps * 1e3:.3f} ms/step", file=sys.stderr)
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
-    errs = model.get_current_errors()
     assert all(v == v and abs(v) < 1e4 for v in errs.values()), errs     # finite losses after the run
     rccl = None
     if world > 1:      # what the collective layer itself reports: ranks that took part in a real all-reduce, bytes reduced per step
@@ -552,9 +638,7 @@ def main():
             "metric": ("train-step images/sec, twostage_cycle 512x512 bs=1/GPU" if two else
                        "train-step images/sec, cgan unet_256 512x512 bs=1/GPU" if cgan else "train-step images/sec, fcgan 512x512 bs=1/GPU"),
             "value": ips, "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * dt / args.steps, "ms_per_step_median": ms_median,
-            "host_input": {"ms_per_step": 1e3 * dt_host, "value": world / dt_host, "steps": kh,
-                           "note": "same step with the batch in pinned host memory: the input gather kernel reads it over PCIe inside the timed region"}, "ms_per_step_min": per_step[0],
+            "ms_per_step": 1e3 * dt / args.steps, "ms_per_step_median": ms_median, "ms_per_step_min": per_step[0],
             "ms_per_step_max": per_step[-1], "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": dtype_label, "data": "synthetic",
             "config": {"workload": workload,
@@ -564,6 +648,10 @@ def main():
                        "achieved_tflops_per_gpu_reference_executed": fl * ips / world / 1e12},
             "losses": {k: round(v, 5) for k, v in errs.items()},
         }
+        if dt_host is not None:
+            out["host_input"] = {"ms_per_step": 1e3 * dt_host, "value": world / dt_host, "steps": kh,
+                                 "note": "same step with the batch in pinned host memory: the input gather kernel reads it over PCIe "
+                                         "inside the timed region"}
         if rccl:
             out["collective"] = rccl
         if kern:
@@ -592,8 +680,10 @@ def main():
                                "measured": "every conv call of one step captured 8x back to back into a hipGraph and replayed: device time "
                                            "per call (HIP events on the replay stream), launch boundary and any second kernel of the call included"}
             out["kernels"] = {k: {kk: round(vv, 4) for kk, vv in v.items()} for k, v in sorted(kern.items())}
-        if not args.no_cpu_baseline and world == 1:      # the CPU baseline is timed at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # the CPU baseline is timed at N = 1 only
             out["cpu_baseline"] = cpu_baseline_cgan(args.n_update_G) if cgan else cpu_baseline(args.n_update_G)
+        if args.dump_outputs:
+            dump_outputs(make_model(), args.eager, ring[(args.warmup + args.steps - 1) % len(ring)], args.dump_outputs)
         print(json.dumps(out))
     if world > 1:
         torch.distributed.barrier()

@@ -1,6 +1,7 @@
 #!/bin/bash
 # usage: tools/r3_run.sh <tag> [pytest -k expr | "all" | "none"]   -> gpurun_out/r3/<tag>.*  (tests, then the bench with its per-call table)
 T=$1; K=${2:-all}
+BENCH_ARGS="--full ${BENCH_ARGS}"      # SGAN_BENCH_CALLS and the roofline read below come from the --full run
 mkdir -p gpurun_out/r3
 if [ "$K" = all ]; then timeout -k 10 600 python -m pytest -m gpu -x -q > gpurun_out/r3/$T.test.log 2>&1; rc=$?
 elif [ "$K" != none ]; then timeout -k 10 600 python -m pytest -m gpu -x -q -k "$K" > gpurun_out/r3/$T.test.log 2>&1; rc=$?; else rc=0; fi
