@@ -87,11 +87,18 @@ typedef struct sgan_conv_desc {
      *                      gradients): ~5e-6 per layer, inside the 1e-3 contract.  Needs the job's `w_packed` copy of the
      *                      weights (sgan_pack_weights) and fails without it; layers the split kernels do not cover (stored
      *                      channels not a multiple of 8 or under 16, maps under 256 pixels, 4-channel heads) run the fp32
-     *                      kernels whatever this field says. */
+     *                      kernels whatever this field says.
+     *   SGAN_MATH_BF16X1 : one 16-bit plane, the speed mode (what torch.autocast trades): a product is hi(a) * hi(b) alone, one
+     *                      MFMA instead of three, on the planes SGAN_MATH_BF16X3 uses -- forward fp16 of the activation x fp16 of
+     *                      w * 2^10 (the hi half of `w_packed`); backward-data and backward-weight bf16, or fp16 of dout * 2^s where
+     *                      `dout_amax` is given.  Storage, accumulation, statistics and everything outside the conv products stay
+     *                      fp32.  ~2^-9 (bf16) / 2^-12 (fp16) relative per operand.  Covers exactly the layers SGAN_MATH_BF16X3
+     *                      covers (same packed copies, same fallbacks to the exact-fp32 kernels). */
     int32_t math;
 } sgan_conv_desc;
 #define SGAN_MATH_F32 0
 #define SGAN_MATH_BF16X3 1
+#define SGAN_MATH_BF16X1 2
 
 const char* sgan_version(void);
 const char* sgan_last_error(void);
@@ -157,7 +164,7 @@ typedef struct sgan_conv_fwd_job {
     float* out; int32_t out_ld;
     double* out_stats;
     int32_t out_stats_sq_stride;  /* distance from sum[n] to sumsq[n] in out_stats; 0 = Cout */
-    const void* w_packed;         /* SGAN_MATH_BF16X3: the `packed_fwd` copy of `w` (sgan_pack_weights), same element offset; else NULL */
+    const void* w_packed;         /* SGAN_MATH_BF16X3 / _BF16X1: the `packed_fwd` copy of `w` (sgan_pack_weights), same element offset; else NULL */
     int32_t out_stats_rep_stride; /* > 0: out_stats is the first of SGAN_STAT_REPLICAS copies this far apart (sgan_norm_desc.rep_stride) */
 } sgan_conv_fwd_job;
 typedef struct sgan_conv_dgrad_job {
@@ -172,7 +179,7 @@ typedef struct sgan_conv_dgrad_job {
     int32_t w_transposed;         /* 1: `w` is the transposed master copy [kh*kw][Cin_s][Cout_s] (sgan_transpose_weights): the
                                    * reduction channel (Cout) is then contiguous and backward-data stages its weights with
                                    * 16-byte LDS stores like the forward pass */
-    const void* w_packed;         /* SGAN_MATH_BF16X3: the `packed_bwd` copy of the weights (sgan_pack_weights); else NULL */
+    const void* w_packed;         /* SGAN_MATH_BF16X3 / _BF16X1: the `packed_bwd` copy of the weights (sgan_pack_weights); else NULL */
     int32_t bwd_sums_rep_stride;  /* > 0: bwd_sums is the first of SGAN_STAT_REPLICAS copies this far apart */
     const float* dout_amax;       /* device scalar max|dout| (sgan_norm_bwd_apply_multi publishes it) or NULL.  With it (and w_packed_f16)
                                    * SGAN_MATH_BF16X3 runs backward-data on fp16 planes of dout * 2^s, s from the exponent of the maximum:
@@ -199,7 +206,9 @@ int sgan_conv_wgrad_grouped(const sgan_conv_wgrad_job* jobs, int32_t n, void* wo
  * is not covered by the fused kernel (the caller then issues the two grouped calls; nothing was written), < 0 on error.
  * dgrad_math: SGAN_MATH_* of the backward-data half, or -1 for the descriptors' own (the two job lists usually point at the
  * same descriptors, and backward-data into a layer without a normalisation runs exact fp32 next to a split-bf16
- * backward-weight: DESIGN.md R2.3); the backward-weight half must be SGAN_MATH_BF16X3. */
+ * backward-weight: DESIGN.md R2.3); the backward-weight half must be SGAN_MATH_BF16X3 or SGAN_MATH_BF16X1.  A SGAN_MATH_BF16X1
+ * backward-weight half fuses with a SGAN_MATH_BF16X1 or SGAN_MATH_BF16X3 backward-data half; a SGAN_MATH_BF16X1 backward-data half
+ * beside a SGAN_MATH_BF16X3 backward-weight half answers 1. */
 int sgan_conv_bwd_fused(const sgan_conv_dgrad_job* djobs, int32_t nd, const sgan_conv_wgrad_job* wjobs, int32_t nw,
                         int32_t dgrad_math, void* stream);
 /* The same with a workspace: a pair whose backward-data half is a deep reduction on a small map (generator 256 -> 128 at 32 x 32, the

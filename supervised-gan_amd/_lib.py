@@ -8,7 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGAN_HIP_LIB") or os.path.join(_HERE, "csrc", "libsgan_hip.so")
 
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
-MATH_F32, MATH_BF16X3 = 0, 1
+MATH_F32, MATH_BF16X3, MATH_BF16X1 = 0, 1, 2
 CONV, CONVT = 0, 1
 
 

@@ -286,10 +286,10 @@ class ChainNet(nn.Module):
 
     def _wb(self, L: LayerSpec):
         """(weight, bias) of layer L for the forward pass; the weight slice carries the matching slice of the split-bf16
-        forward copy for the bf16x3 kernels."""
+        forward copy for the 16-bit kernels (bf16x3, bf16x1)."""
         n = L.k * L.k * L.cout_s * L.cin_s
         w = self._flat[L.w_off: L.w_off + n]
-        if ops.get_math() == "bf16x3":
+        if ops.uses_16bit():
             self._refresh_derived()
             ops.with_packed(w, self._pk_f[L.w_off: L.w_off + n])
         b = self._flat[L.b_off: L.b_off + L.cout_s] if L.bias else None
@@ -568,9 +568,12 @@ def _dgrad_math(P, douts=()):
     of the split products stay 5e-6.  Without one (the first PatchGAN layer) the result is used as is, and the layer's bias
     gradient sums it over every pixel -- terms that cancel to a small residual (the gradient that reaches it left a normalisation
     as a zero-sum field) while unbiased element errors do not: measured 7e-3 of the bias gradient against the fp64 reference,
-    where the reference's own fp32 is at 7e-6.  Those launches run on the exact-fp32 kernel (one per discriminator pass)."""
+    where the reference's own fp32 is at 7e-6.  Those launches run on the exact-fp32 kernel (one per discriminator pass).
+    In the one-plane mode (bf16x1) the same launches keep exactly that route -- bf16x3 on fp16 planes, or f32 -- for the same reason:
+    the cancellation in the bias gradient would amplify its per-element product errors most of all."""
+    x1 = ops.get_math() == "bf16x1"
     if douts and all(ops.has_amax(d) for d in douts):
-        return None
+        return "bf16x3" if (x1 and not P.norm) else None
     return None if P.norm else "f32"
 
 

@@ -19,17 +19,20 @@
 //         fp16 planes scaled by the gradient's published maximum -- an fp32-equivalent product at the split kernels' speed;
 // WV: 1 = backward-weight 64 x 64 tiles, 2 = 32 x 128
 // F16: the backward-data half on fp16 planes (every job brought the maximum of its gradient tensor); the backward-weight half is bf16
-template <int DV, int WV, bool WPRO, bool F16>
+// DX1 / WX1: the backward-data / backward-weight half on one plane (SGAN_MATH_BF16X1).  Instantiated: both halves split, both on one
+// plane, and a one-plane backward-weight half beside a split backward-data half (backward-data into a layer without a normalisation
+// keeps its bf16x3 route in the one-plane mode: chain._dgrad_math)
+template <int DV, int WV, bool WPRO, bool F16, bool DX1 = false, bool WX1 = false>
 __global__ __launch_bounds__(256) void sg_bwd_fused_kernel(const SgIgemmParams G, const SgWgradParams W, int ndg, int wx, int wy, int wmode, int dks) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     sg_warm_kernargs<(int)(sizeof(SgIgemmParams) + sizeof(SgWgradParams))>();
     const int b = blockIdx.x;
     if (b < ndg) {
-        if constexpr (DV == 1) sg_igemm3p_body<64, 2, false, F16>(G, smem, b, ndg);
-        else if constexpr (DV == 2) sg_igemm3p_body<64, 4, false, F16>(G, smem, b, ndg);
-        else if constexpr (DV == 3) sg_igemm3_body<64, 64, 2, 2, false, F16, true>(G, smem, b % (ndg / dks), ndg / dks, b / (ndg / dks));      // (tile, k split)
-        else if constexpr (DV == 5) sg_igemm3p_body<64, 6, false, F16, true>(G, smem, b, ndg);
-        else sg_igemm3_body<128, 32, 4, 1, false, F16, false>(G, smem, b, ndg, 0);
+        if constexpr (DV == 1) sg_igemm3p_body<64, 2, false, F16, false, 1, DX1>(G, smem, b, ndg);
+        else if constexpr (DV == 2) sg_igemm3p_body<64, 4, false, F16, false, 1, DX1>(G, smem, b, ndg);
+        else if constexpr (DV == 3) sg_igemm3_body<64, 64, 2, 2, false, F16, true, DX1>(G, smem, b % (ndg / dks), ndg / dks, b / (ndg / dks));      // (tile, k split)
+        else if constexpr (DV == 5) sg_igemm3p_body<64, 6, false, F16, true, 1, DX1>(G, smem, b, ndg);
+        else sg_igemm3_body<128, 32, 4, 1, false, F16, false, DX1>(G, smem, b, ndg, 0);
     } else {
         // wmode 1 (SGAN_FUSED_WXCD=1, off by default): the backward-weight workgroups start at a multiple of 8 and every XCD takes a
         // CONTIGUOUS range of the pixel-range-major order, so that an L2 holds a few pixel ranges of dOut / x instead of all of them.
@@ -41,25 +44,35 @@ __global__ __launch_bounds__(256) void sg_bwd_fused_kernel(const SgIgemmParams G
         int w = b - ndp;
         if (wmode) w = sg_xcd_remap(w, (int)gridDim.x - ndp);
         const int bx = w % wx, by = (w / wx) % wy, bz = w / (wx * wy);
-        if constexpr (WV == 1) sg_wgrad3_body<64, 64, 2, 2, WPRO, false>(W, smem, bx, by, bz);
-        else sg_wgrad3_body<32, 128, 1, 4, WPRO, false>(W, smem, bx, by, bz);
+        if constexpr (WV == 1) sg_wgrad3_body<64, 64, 2, 2, WPRO, false, WX1>(W, smem, bx, by, bz);
+        else sg_wgrad3_body<32, 128, 1, 4, WPRO, false, WX1>(W, smem, bx, by, bz);
     }
 }
 
-template <int DV, int WV>
-static void sg_fused_launch(const SgIgemmParams& P, const SgWgradParams& W, const SgFusePlan& pd, const SgFusePlan& pw, hipStream_t st) {
+template <int DV, int WV, bool DX1, bool WX1>
+static void sg_fused_launch_m(const SgIgemmParams& P, const SgWgradParams& W, const SgFusePlan& pd, const SgFusePlan& pw, hipStream_t st) {
     static const int wmode = getenv("SGAN_FUSED_WXCD") ? (atoi(getenv("SGAN_FUSED_WXCD")) != 0) : 0;      // tuning knob (see the kernel)
     const dim3 grid((wmode ? ((pd.nblocks + 7) & ~7) : pd.nblocks) + pw.nblocks);
     const size_t lds = pd.lds > pw.lds ? pd.lds : pw.lds;
     if constexpr (DV == 6) {       // fp16 planes are asked for where they matter: backward-data into a layer without a normalisation
         if (P.planes_f16) {
-            if (pw.pro) hipLaunchKernelGGL((sg_bwd_fused_kernel<DV, WV, true, true>), grid, dim3(256), lds, st, P, W, pd.nblocks, pw.gx, pw.gy, wmode, pd.ks);
-            else hipLaunchKernelGGL((sg_bwd_fused_kernel<DV, WV, false, true>), grid, dim3(256), lds, st, P, W, pd.nblocks, pw.gx, pw.gy, wmode, pd.ks);
+            if (pw.pro) hipLaunchKernelGGL((sg_bwd_fused_kernel<DV, WV, true, true, DX1, WX1>), grid, dim3(256), lds, st, P, W, pd.nblocks, pw.gx, pw.gy, wmode, pd.ks);
+            else hipLaunchKernelGGL((sg_bwd_fused_kernel<DV, WV, false, true, DX1, WX1>), grid, dim3(256), lds, st, P, W, pd.nblocks, pw.gx, pw.gy, wmode, pd.ks);
             return;
         }
     }
-    if (pw.pro) hipLaunchKernelGGL((sg_bwd_fused_kernel<DV, WV, true, false>), grid, dim3(256), lds, st, P, W, pd.nblocks, pw.gx, pw.gy, wmode, pd.ks);
-    else hipLaunchKernelGGL((sg_bwd_fused_kernel<DV, WV, false, false>), grid, dim3(256), lds, st, P, W, pd.nblocks, pw.gx, pw.gy, wmode, pd.ks);
+    if (pw.pro) hipLaunchKernelGGL((sg_bwd_fused_kernel<DV, WV, true, false, DX1, WX1>), grid, dim3(256), lds, st, P, W, pd.nblocks, pw.gx, pw.gy, wmode, pd.ks);
+    else hipLaunchKernelGGL((sg_bwd_fused_kernel<DV, WV, false, false, DX1, WX1>), grid, dim3(256), lds, st, P, W, pd.nblocks, pw.gx, pw.gy, wmode, pd.ks);
+}
+
+// dx1 / wx1: which halves run on one plane (a one-plane backward-data half beside a split backward-weight half is not instantiated:
+// the caller does not launch it)
+template <int DV, int WV>
+static void sg_fused_launch(const SgIgemmParams& P, const SgWgradParams& W, const SgFusePlan& pd, const SgFusePlan& pw, hipStream_t st,
+                            bool dx1, bool wx1) {
+    if (dx1) sg_fused_launch_m<DV, WV, true, true>(P, W, pd, pw, st);
+    else if (wx1) sg_fused_launch_m<DV, WV, false, true>(P, W, pd, pw, st);
+    else sg_fused_launch_m<DV, WV, false, false>(P, W, pd, pw, st);
 }
 
 // 0: launched; 1: this pair is not covered (launch sgan_conv_dgrad_grouped and sgan_conv_wgrad_grouped instead); < 0: error.
@@ -85,8 +98,11 @@ static int sg_conv_bwd_fused_impl(const sgan_conv_dgrad_job* djobs, int32_t nd, 
     if (rc) return rc;
     rc = sg_build_wgrad_params(wjobs, nw, W, false);         // the backward-weight half of a fused launch stays on bf16 planes
     if (rc) return rc;
-    if (wjobs[0].d->math != SGAN_MATH_BF16X3 || sg_dgrad_is_skinny(P)) return query ? 0 : 1;
+    const int wmath = wjobs[0].d->math;
+    if ((wmath != SGAN_MATH_BF16X3 && wmath != SGAN_MATH_BF16X1) || sg_dgrad_is_skinny(P)) return query ? 0 : 1;
     if (dgrad_math >= 0) P.math = dgrad_math;      // the two job lists may share descriptors: the backward-data mode comes apart
+    const bool wx1 = wmath == SGAN_MATH_BF16X1, dx1 = P.math == SGAN_MATH_BF16X1;
+    if (dx1 && !wx1) return query ? 0 : 1;      // one-plane backward-data beside a split backward-weight: not instantiated (two launches)
     const int e3 = sg_igemm3_eligible(P);
     if (e3 < 0) return e3;
     SgFusePlan pd, pw;
@@ -99,7 +115,7 @@ static int sg_conv_bwd_fused_impl(const sgan_conv_dgrad_job* djobs, int32_t nd, 
         sg_igemm3_fuse_plan(P, &pd);
     }
     if (pd.variant == 0 || pd.nblocks == 0) return query ? 0 : 1;
-    sg_wgrad3_fuse_plan(W, &pw);
+    sg_wgrad3_fuse_plan(W, &pw, wx1);
     if (pw.variant == 0 || pw.nblocks == 0) return query ? 0 : 1;
     if ((pd.lds > pw.lds ? pd.lds : pw.lds) > 160 * 1024) return query ? 0 : 1;     // the CU's LDS (the split kernels with two k-tiles per barrier take a little over 64 KB)
     const int64_t slab = (int64_t)P.q[0].Hout * P.q[0].Wout * P.N;
@@ -112,19 +128,19 @@ static int sg_conv_bwd_fused_impl(const sgan_conv_dgrad_job* djobs, int32_t nd, 
     hipStream_t st = (hipStream_t)stream;
     sg_prof_begin(st);
     switch (pd.variant * 10 + pw.variant) {
-        case 11: sg_fused_launch<1, 1>(P, W, pd, pw, st); break;
-        case 12: sg_fused_launch<1, 2>(P, W, pd, pw, st); break;
-        case 21: sg_fused_launch<2, 1>(P, W, pd, pw, st); break;
-        case 22: sg_fused_launch<2, 2>(P, W, pd, pw, st); break;
-        case 31: sg_fused_launch<3, 1>(P, W, pd, pw, st); break;
-        case 32: sg_fused_launch<3, 2>(P, W, pd, pw, st); break;
-        case 51: sg_fused_launch<5, 1>(P, W, pd, pw, st); break;
-        case 52: sg_fused_launch<5, 2>(P, W, pd, pw, st); break;
-        case 61: sg_fused_launch<6, 1>(P, W, pd, pw, st); break;
-        default: sg_fused_launch<6, 2>(P, W, pd, pw, st); break;
+        case 11: sg_fused_launch<1, 1>(P, W, pd, pw, st, dx1, wx1); break;
+        case 12: sg_fused_launch<1, 2>(P, W, pd, pw, st, dx1, wx1); break;
+        case 21: sg_fused_launch<2, 1>(P, W, pd, pw, st, dx1, wx1); break;
+        case 22: sg_fused_launch<2, 2>(P, W, pd, pw, st, dx1, wx1); break;
+        case 31: sg_fused_launch<3, 1>(P, W, pd, pw, st, dx1, wx1); break;
+        case 32: sg_fused_launch<3, 2>(P, W, pd, pw, st, dx1, wx1); break;
+        case 51: sg_fused_launch<5, 1>(P, W, pd, pw, st, dx1, wx1); break;
+        case 52: sg_fused_launch<5, 2>(P, W, pd, pw, st, dx1, wx1); break;
+        case 61: sg_fused_launch<6, 1>(P, W, pd, pw, st, dx1, wx1); break;
+        default: sg_fused_launch<6, 2>(P, W, pd, pw, st, dx1, wx1); break;
     }
     SGAN_LAUNCH_CHECK();
-    g_sgan_last_kernel = "sg_bwd_fused_kernel";
+    g_sgan_last_kernel = dx1 ? "sg_bwd_fused_kernel<x1>" : (wx1 ? "sg_bwd_fused_kernel<wgrad x1>" : "sg_bwd_fused_kernel");
     sg_prof_end(st, g_sgan_last_kernel);
     if (pd.ks > 1) return sg_launch_splitk_epilogue(P, st);      // sum of the slabs + the backward-data epilogue (activation derivative, norm-backward sums)
     return SGAN_OK;

@@ -62,6 +62,24 @@ __device__ __forceinline__ void sg_split8(const f32x4 v0, const f32x4 v1, u32x4&
     }
 }
 
+// The hi plane alone (SGAN_MATH_BF16X1): hi = RNE(x) as above, the lo plane is never formed.
+template <bool F16>
+__device__ __forceinline__ u32x4 sg_hi8(const f32x4 v0, const f32x4 v1) {
+    u32x4 hi;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const f32x2 p = {v0[2 * i], v0[2 * i + 1]}, q = {v1[2 * i], v1[2 * i + 1]};
+        if constexpr (F16) {
+            hi[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(p, sg_f16x2));
+            hi[2 + i] = __builtin_bit_cast(unsigned, __builtin_convertvector(q, sg_f16x2));
+        } else {
+            hi[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(p, sg_bf16x2));
+            hi[2 + i] = __builtin_bit_cast(unsigned, __builtin_convertvector(q, sg_bf16x2));
+        }
+    }
+    return hi;
+}
+
 template <bool F16>
 __device__ __forceinline__ f32x16 sg3_mfma(const u32x4 a, const u32x4 b, const f32x16 c) {
     if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(sg_f16x8, a), __builtin_bit_cast(sg_f16x8, b), c, 0, 0, 0);
@@ -213,16 +231,19 @@ __device__ __forceinline__ void sg3_epilogue(const SgLocal& P, f32x16 (&acc)[MB]
 }
 
 // F16: operand planes are fp16 (forward pass: fp32-equivalent products) instead of bf16 (backward-data)
+// X1: one plane (SGAN_MATH_BF16X1): a product is a_hi * b_hi, one MFMA instead of three.  The LDS layout stays the split one with the
+// lo slots left unused; the lo plane of A is never formed and that of B (the packed weight rows) never loaded.
 // KB2: two k-tiles per barrier (four LDS buffers): with 16-bit MFMAs a 32-deep k-tile is only 192 MFMA cycles per wave, less than
 // what a barrier interval costs in waits and bookkeeping; two tiles per interval halve that overhead per flop.
 // The kernel body takes its workgroup id, grid size and split index as arguments so that sg_bwd_fused_kernel (sgan_fused.hip) can run
 // it on a slice of a launch it shares with the backward-weight body.
-template <int BM, int BN, int WGM, int WGN, bool PRO, bool F16, bool KB2>
+template <int BM, int BN, int WGM, int WGN, bool PRO, bool F16, bool KB2, bool X1 = false>
 __device__ __forceinline__ void sg_igemm3_body(const SgIgemmParams& G, char* smem, const int bid, const int nblocks, const int split) {
     constexpr int NT = 64 * WGM * WGN;
     constexpr int WTM = BM / WGM, WTN = BN / WGN, MB = WTM / 32, NB = WTN / 32;
     constexpr int A_IT = BM * 4 / NT;              // tasks of 8 consecutive k of one row (two 16-byte loads) per thread
-    constexpr int B_IT = (BN * 8 + NT - 1) / NT;   // 16-byte chunks of the packed weight rows per thread
+    constexpr int BCH = X1 ? 4 : 8;                // 16-byte chunks staged per packed weight row and k-tile (X1: the hi halves)
+    constexpr int B_IT = (BN * BCH + NT - 1) / NT; // 16-byte chunks of the packed weight rows per thread
     static_assert(BM * 4 % NT == 0 && A_IT >= 1, "A tile");
     static_assert(WTM % 32 == 0 && WTN % 32 == 0, "wave tile");
 
@@ -308,8 +329,8 @@ __device__ __forceinline__ void sg_igemm3_body(const SgIgemmParams& G, char* sme
 #pragma unroll
     for (int it = 0; it < B_IT; ++it) {
         const int e = tid + it * NT;
-        const int n = e >> 3, t = e & 7;             // t & 3 == kg; plane = t >> 2
-        b_rowok[it] = (B_IT * NT == BN * 8 || e < BN * 8) && n0 + n < N;
+        const int n = e / BCH, t = e % BCH;          // t & 3 == kg; plane = t >> 2
+        b_rowok[it] = (B_IT * NT == BN * BCH || e < BN * BCH) && n0 + n < N;
         b_base[it] = (n0 + n) * P.w_ns + 4 * (t >> 2);
         b_dst[it] = sg3_off(n, 2 * (t & 3) + (t >> 2));
     }
@@ -416,6 +437,10 @@ __device__ __forceinline__ void sg_igemm3_body(const SgIgemmParams& G, char* sme
                 for (int j = 0; j < 4; ++j) { v0[j] = fmaxf(p0[j], q0[j]); v1[j] = fmaxf(p1[j], q1[j]); }
             }
             if constexpr (F16 && !PRO) { v0 *= P.a_scale; v1 *= P.a_scale; }     // backward-data on fp16 planes: the gradient times 2^s
+            if constexpr (X1) {
+                if (!(SG3_ABL & 4) || G.nprob > 100) *reinterpret_cast<u32x4*>(Ab + a_dst[it]) = sg_hi8<F16>(v0, v1);
+                continue;
+            }
             u32x4 hi, lo;
             if constexpr (SG3_ABL & 2) { hi = __builtin_bit_cast(u32x4, v0); lo = __builtin_bit_cast(u32x4, v1); }
             else sg_split8<F16>(v0, v1, hi, lo);
@@ -427,7 +452,7 @@ __device__ __forceinline__ void sg_igemm3_body(const SgIgemmParams& G, char* sme
 #pragma unroll
         for (int it = 0; it < B_IT; ++it) {
             const int e = tid + it * NT;
-            if ((!(SG3_ABL & 4) || G.nprob > 100) && (B_IT * NT == BN * 8 || e < BN * 8)) *reinterpret_cast<u32x4*>(Bb + b_dst[it]) = b_reg[S][it];
+            if ((!(SG3_ABL & 4) || G.nprob > 100) && (B_IT * NT == BN * BCH || e < BN * BCH)) *reinterpret_cast<u32x4*>(Bb + b_dst[it]) = b_reg[S][it];
         }
     };
 
@@ -474,12 +499,12 @@ __device__ __forceinline__ void sg_igemm3_body(const SgIgemmParams& G, char* sme
 #pragma unroll
             for (int i = 0; i < MB; ++i) {
                 ah[s][i] = *reinterpret_cast<const u32x4*>(Ab + i * 32 * 128 + f_off[s][0]);
-                al[s][i] = *reinterpret_cast<const u32x4*>(Ab + i * 32 * 128 + f_off[s][1]);
+                if constexpr (!X1) al[s][i] = *reinterpret_cast<const u32x4*>(Ab + i * 32 * 128 + f_off[s][1]);
             }
 #pragma unroll
             for (int j = 0; j < NB; ++j) {
                 bh[s][j] = *reinterpret_cast<const u32x4*>(Bb + j * 32 * 128 + f_off[s][0]);
-                bl[s][j] = *reinterpret_cast<const u32x4*>(Bb + j * 32 * 128 + f_off[s][1]);
+                if constexpr (!X1) bl[s][j] = *reinterpret_cast<const u32x4*>(Bb + j * 32 * 128 + f_off[s][1]);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -492,12 +517,14 @@ __device__ __forceinline__ void sg_igemm3_body(const SgIgemmParams& G, char* sme
 #pragma unroll
                 for (int j = 0; j < NB; ++j) {
                     if constexpr (SG3_ABL & 16) { acc[i][j][0] += __builtin_bit_cast(f32x4, al[s][i])[0] + __builtin_bit_cast(f32x4, ah[s][i])[1] + __builtin_bit_cast(f32x4, bl[s][j])[2] + __builtin_bit_cast(f32x4, bh[s][j])[3]; continue; }
-                    acc[i][j] = sg3_mfma<F16>(al[s][i], bh[s][j], acc[i][j]);
-                    acc[i][j] = sg3_mfma<F16>(ah[s][i], bl[s][j], acc[i][j]);
+                    if constexpr (!X1) {
+                        acc[i][j] = sg3_mfma<F16>(al[s][i], bh[s][j], acc[i][j]);
+                        acc[i][j] = sg3_mfma<F16>(ah[s][i], bl[s][j], acc[i][j]);
+                    }
                     acc[i][j] = sg3_mfma<F16>(ah[s][i], bh[s][j], acc[i][j]);
                 }
         if constexpr (!(SG3_ABL & 8)) next_addrs();
-        constexpr int NMFMA = 6 * MB * NB;
+        constexpr int NMFMA = (X1 ? 2 : 6) * MB * NB;
         constexpr int PER = (40 + 6 * A_IT + 2 * B_IT + NMFMA - 1) / NMFMA;   // next_addrs is ~40 + 6 A_IT + 2 B_IT VALU / SALU
 #pragma unroll
         for (int q = 0; q < NMFMA; ++q) {
@@ -540,11 +567,11 @@ __device__ __forceinline__ void sg_igemm3_body(const SgIgemmParams& G, char* sme
     });
 }
 
-template <int BM, int BN, int WGM, int WGN, bool PRO, bool F16, bool KB2 = false>
+template <int BM, int BN, int WGM, int WGN, bool PRO, bool F16, bool KB2 = false, bool X1 = false>
 __global__ __launch_bounds__(64 * WGM * WGN) void sg_igemm3_kernel(const SgIgemmParams G) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     sg_warm_kernargs<(int)sizeof(SgIgemmParams)>();
-    sg_igemm3_body<BM, BN, WGM, WGN, PRO, F16, KB2>(G, smem, blockIdx.x, gridDim.x, blockIdx.z);
+    sg_igemm3_body<BM, BN, WGM, WGN, PRO, F16, KB2, X1>(G, smem, blockIdx.x, gridDim.x, blockIdx.z);
 }
 
 
@@ -598,11 +625,13 @@ extern "C" int sgan_debug_stamps(void* dst, int n) {
 // each with its own patch and weight buffers, in lockstep (every barrier is the whole workgroup's); group 1 hands its accumulators to
 // group 0 through LDS at the end.  For launches of 64 - 256 workgroups (the generator at batch 1): the serial chain of a tile
 // halves and the CU runs two waves per SIMD instead of one.
-template <int BN, int A_IT, bool PRO, bool F16, bool S2 = false, int KW = 1>
+// X1: one plane (SGAN_MATH_BF16X1), as in sg_igemm3_body: the patch and weight tiles keep their layout with the lo slots unused.
+template <int BN, int A_IT, bool PRO, bool F16, bool S2 = false, int KW = 1, bool X1 = false>
 __device__ __forceinline__ void sg_igemm3p_body(const SgIgemmParams& G, char* smem, const int bid, const int nblocks) {
     constexpr int NT = 256, WGN = 2, WTM = 32, WTN = BN / WGN, MB = 1, NB = WTN / 32;
     static_assert(KW == 1 || KW == 2, "wave groups");
-    constexpr int B_IT = BN * 8 / NT;
+    constexpr int BCH = X1 ? 4 : 8;      // 16-byte chunks staged per packed weight row and step (X1: the hi halves)
+    constexpr int B_IT = BN * BCH / NT;
     // weight-tile register ring (even: the LDS buffer of a step is its slot's parity).  BN = 128 (wave tile 32 x 64, ring of 2)
     // compiles but measured slower on every layer tried (D 128 -> 256 @65^2 x 6: dgrad 73 us against 63.5): the halved workgroup
     // count costs more than the better MFMA : LDS ratio returns, so the dispatcher only uses BN = 64.
@@ -713,6 +742,10 @@ __device__ __forceinline__ void sg_igemm3p_body(const SgIgemmParams& G, char* sm
                 for (int j = 0; j < 4; ++j) { v0[j] = fmaxf(p0[j], q0[j]); v1[j] = fmaxf(p1[j], q1[j]); }
             }
             if constexpr (F16 && !PRO) { v0 *= P.a_scale; v1 *= P.a_scale; }     // backward-data on fp16 planes: the gradient times 2^s
+            if constexpr (X1) {
+                if (a_dst[it] >= 0) *reinterpret_cast<u32x4*>(Ap + a_dst[it]) = sg_hi8<F16>(v0, v1);
+                continue;
+            }
             u32x4 hi, lo;
             sg_split8<F16>(v0, v1, hi, lo);
             if (a_dst[it] >= 0) {
@@ -728,7 +761,7 @@ __device__ __forceinline__ void sg_igemm3p_body(const SgIgemmParams& G, char* sm
 #pragma unroll
     for (int it = 0; it < B_IT; ++it) {
         const int e = tid + it * NT;
-        const int n = e >> 3, t = e & 7;
+        const int n = e / BCH, t = e % BCH;
         b_rowok[it] = n0 + n < N;
         b_base[it] = (n0 + n) * P.w_ns + 8 * (t & 3) + 4 * (t >> 2);
         b_dst[it] = sg3_off(n, 2 * (t & 3) + (t >> 2));
@@ -800,19 +833,21 @@ __device__ __forceinline__ void sg_igemm3p_body(const SgIgemmParams& G, char* sm
     auto read_half = [&](auto H_, const char* Ab, const char* Bb) {
         constexpr int s = decltype(H_)::value;
         ah[s] = *reinterpret_cast<const u32x4*>(Ab + s * 64);
-        al[s] = *reinterpret_cast<const u32x4*>(Ab + s * 64 + 16);
+        if constexpr (!X1) al[s] = *reinterpret_cast<const u32x4*>(Ab + s * 64 + 16);
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
             bh[s][j] = *reinterpret_cast<const u32x4*>(Bb + j * 32 * 128 + f_off[s][0]);
-            bl[s][j] = *reinterpret_cast<const u32x4*>(Bb + j * 32 * 128 + f_off[s][1]);
+            if constexpr (!X1) bl[s][j] = *reinterpret_cast<const u32x4*>(Bb + j * 32 * 128 + f_off[s][1]);
         }
     };
     auto mfma_half = [&](auto H_) {
         constexpr int s = decltype(H_)::value;
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
-            acc[0][j] = sg3_mfma<F16>(al[s], bh[s][j], acc[0][j]);
-            acc[0][j] = sg3_mfma<F16>(ah[s], bl[s][j], acc[0][j]);
+            if constexpr (!X1) {
+                acc[0][j] = sg3_mfma<F16>(al[s], bh[s][j], acc[0][j]);
+                acc[0][j] = sg3_mfma<F16>(ah[s], bl[s][j], acc[0][j]);
+            }
             acc[0][j] = sg3_mfma<F16>(ah[s], bh[s][j], acc[0][j]);
         }
     };
@@ -915,11 +950,11 @@ __device__ __forceinline__ void sg_igemm3p_body(const SgIgemmParams& G, char* sm
 #endif
 }
 
-template <int BN, int A_IT, bool PRO, bool F16, bool S2 = false, int KW = 1>
+template <int BN, int A_IT, bool PRO, bool F16, bool S2 = false, int KW = 1, bool X1 = false>
 __global__ __launch_bounds__(256 * KW) void sg_igemm3p_kernel(const SgIgemmParams G) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     sg_warm_kernargs<(int)sizeof(SgIgemmParams)>();
-    sg_igemm3p_body<BN, A_IT, PRO, F16, S2, KW>(G, smem, blockIdx.x, gridDim.x);
+    sg_igemm3p_body<BN, A_IT, PRO, F16, S2, KW, X1>(G, smem, blockIdx.x, gridDim.x);
 }
 
 #ifndef SG_KERNELS_ONLY      // sgan_fused.hip includes this file for the kernel bodies only
@@ -928,9 +963,10 @@ __global__ __launch_bounds__(256 * KW) void sg_igemm3p_kernel(const SgIgemmParam
 // ------------------------------------------------------------------------------------------
 static inline int sg3_cdiv(int a, int b) { return (a + b - 1) / b; }
 
-// 1: runs on the split-bf16 kernels; 0: not covered (the fp32 kernels serve it); < 0: asked for, covered, but a job lacks its packed weights
+// 1: runs on the split-bf16 kernels (SGAN_MATH_BF16X3, or their one-plane instantiations for SGAN_MATH_BF16X1); 0: not covered (the
+// fp32 kernels serve it); < 0: asked for, covered, but a job lacks its packed weights
 int sg_igemm3_eligible(const SgIgemmParams& P) {
-    if (P.math != SGAN_MATH_BF16X3 || P.w_ks != 1 || (P.Ck & 7) || P.Ck < 16 || P.N < 16 || P.w_ns != P.Ck) return 0;
+    if ((P.math != SGAN_MATH_BF16X3 && P.math != SGAN_MATH_BF16X1) || P.w_ks != 1 || (P.Ck & 7) || P.Ck < 16 || P.N < 16 || P.w_ns != P.Ck) return 0;
     // Tiny maps stay on the exact-fp32 kernels: they cost nothing (latency bound), and an InstanceNorm over a 2x2 .. 8x8 map
     // (the inner U-Net levels) divides by the standard deviation of a handful of values -- it amplifies the 5e-6 of the
     // split products by orders of magnitude where it leaves the 3e-7 of the fp32 chain inside the 1e-3 contract.
@@ -938,7 +974,8 @@ int sg_igemm3_eligible(const SgIgemmParams& P) {
         if (P.q[g].Hin * P.q[g].Win < SGAN_BF16X3_MIN_PIXELS || P.q[g].Hout * P.q[g].Wout < SGAN_BF16X3_MIN_PIXELS) return 0;
     for (int g = 0; g < P.nprob; ++g)
         if (!P.q[g].wp)
-            return sgan_fail(SGAN_ERR_INVALID, "SGAN_MATH_BF16X3: job %d has no w_packed copy of its weights (sgan_pack_weights)", g);
+            return sgan_fail(SGAN_ERR_INVALID, "%s: job %d has no w_packed copy of its weights (sgan_pack_weights)",
+                             P.math == SGAN_MATH_BF16X1 ? "SGAN_MATH_BF16X1" : "SGAN_MATH_BF16X3", g);
     return 1;
 }
 
@@ -963,7 +1000,7 @@ static Sg3Tile sg3_pick_tile(const SgIgemmParams& P) {
     return {64, 64};
 }
 
-template <int BM, int BN, int WGM, int WGN, bool KB2 = false>
+template <int BM, int BN, int WGM, int WGN, bool KB2 = false, bool X1 = false>
 static int sg3_launch(SgIgemmParams& P, hipStream_t st, float* ws, int64_t ws_bytes, const char* name) {
     constexpr int NT = 64 * WGM * WGN;
     const int tiles = sg_fill_tiles(P, BM);
@@ -981,11 +1018,11 @@ static int sg3_launch(SgIgemmParams& P, hipStream_t st, float* ws, int64_t ws_by
     for (int g = 0; g < P.nprob; ++g) pro = pro || P.q[g].pro_stats != nullptr;
     sg_prof_begin(st);
     if (P.planes_f16) {
-        if (pro) hipLaunchKernelGGL((sg_igemm3_kernel<BM, BN, WGM, WGN, true, true, KB2>), grid, dim3(NT), lds, st, P);
-        else hipLaunchKernelGGL((sg_igemm3_kernel<BM, BN, WGM, WGN, false, true, KB2>), grid, dim3(NT), lds, st, P);
+        if (pro) hipLaunchKernelGGL((sg_igemm3_kernel<BM, BN, WGM, WGN, true, true, KB2, X1>), grid, dim3(NT), lds, st, P);
+        else hipLaunchKernelGGL((sg_igemm3_kernel<BM, BN, WGM, WGN, false, true, KB2, X1>), grid, dim3(NT), lds, st, P);
     } else {
-        if (pro) hipLaunchKernelGGL((sg_igemm3_kernel<BM, BN, WGM, WGN, true, false, KB2>), grid, dim3(NT), lds, st, P);
-        else hipLaunchKernelGGL((sg_igemm3_kernel<BM, BN, WGM, WGN, false, false, KB2>), grid, dim3(NT), lds, st, P);
+        if (pro) hipLaunchKernelGGL((sg_igemm3_kernel<BM, BN, WGM, WGN, true, false, KB2, X1>), grid, dim3(NT), lds, st, P);
+        else hipLaunchKernelGGL((sg_igemm3_kernel<BM, BN, WGM, WGN, false, false, KB2, X1>), grid, dim3(NT), lds, st, P);
     }
     SGAN_LAUNCH_CHECK();
     g_sgan_last_kernel = name;
@@ -1055,7 +1092,7 @@ static bool sg3p_wanted(const Sg3pPlan& pl) {
     return pl.min_taps >= 4 && pl.waste < 1.3;
 }
 
-template <int BN, int A_IT, bool S2 = false>
+template <int BN, int A_IT, bool S2 = false, bool X1 = false>
 static int sg3p_launch(SgIgemmParams& P, hipStream_t st, const char* name) {   // BN: 64, or 128 (wave tile 32 x 64) for wide results
     int t = 0, maxlds = 0;
     for (int g = 0; g < P.nprob; ++g)
@@ -1084,21 +1121,21 @@ static int sg3p_launch(SgIgemmParams& P, hipStream_t st, const char* name) {   /
     if constexpr (!S2 && A_IT == 2 && BN == 64) {
         if (kw2) {
             if (P.planes_f16) {
-                if (pro) hipLaunchKernelGGL((sg_igemm3p_kernel<BN, A_IT, true, true, false, 2>), grid, dim3(512), lds, st, P);
-                else hipLaunchKernelGGL((sg_igemm3p_kernel<BN, A_IT, false, true, false, 2>), grid, dim3(512), lds, st, P);
+                if (pro) hipLaunchKernelGGL((sg_igemm3p_kernel<BN, A_IT, true, true, false, 2, X1>), grid, dim3(512), lds, st, P);
+                else hipLaunchKernelGGL((sg_igemm3p_kernel<BN, A_IT, false, true, false, 2, X1>), grid, dim3(512), lds, st, P);
             } else {
-                if (pro) hipLaunchKernelGGL((sg_igemm3p_kernel<BN, A_IT, true, false, false, 2>), grid, dim3(512), lds, st, P);
-                else hipLaunchKernelGGL((sg_igemm3p_kernel<BN, A_IT, false, false, false, 2>), grid, dim3(512), lds, st, P);
+                if (pro) hipLaunchKernelGGL((sg_igemm3p_kernel<BN, A_IT, true, false, false, 2, X1>), grid, dim3(512), lds, st, P);
+                else hipLaunchKernelGGL((sg_igemm3p_kernel<BN, A_IT, false, false, false, 2, X1>), grid, dim3(512), lds, st, P);
             }
         }
     }
     if (kw2) { /* launched above */ }
     else if (P.planes_f16) {
-        if (pro) hipLaunchKernelGGL((sg_igemm3p_kernel<BN, A_IT, true, true, S2>), grid, dim3(256), lds, st, P);
-        else hipLaunchKernelGGL((sg_igemm3p_kernel<BN, A_IT, false, true, S2>), grid, dim3(256), lds, st, P);
+        if (pro) hipLaunchKernelGGL((sg_igemm3p_kernel<BN, A_IT, true, true, S2, 1, X1>), grid, dim3(256), lds, st, P);
+        else hipLaunchKernelGGL((sg_igemm3p_kernel<BN, A_IT, false, true, S2, 1, X1>), grid, dim3(256), lds, st, P);
     } else {
-        if (pro) hipLaunchKernelGGL((sg_igemm3p_kernel<BN, A_IT, true, false, S2>), grid, dim3(256), lds, st, P);
-        else hipLaunchKernelGGL((sg_igemm3p_kernel<BN, A_IT, false, false, S2>), grid, dim3(256), lds, st, P);
+        if (pro) hipLaunchKernelGGL((sg_igemm3p_kernel<BN, A_IT, true, false, S2, 1, X1>), grid, dim3(256), lds, st, P);
+        else hipLaunchKernelGGL((sg_igemm3p_kernel<BN, A_IT, false, false, S2, 1, X1>), grid, dim3(256), lds, st, P);
     }
     SGAN_LAUNCH_CHECK();
     g_sgan_last_kernel = name;
@@ -1111,6 +1148,7 @@ static int sg3p_launch(SgIgemmParams& P, hipStream_t st, const char* name) {   /
 int sg_igemm3_fuse_plan(SgIgemmParams& P, SgFusePlan* out) {
     out->variant = 0;
     out->ks = 1;
+    const bool x1 = P.math == SGAN_MATH_BF16X1;
     if (P.pro_act != SGAN_ACT_NONE) return 0;
     for (int g = 0; g < P.nprob; ++g)
         if (P.q[g].pro_stats) return 0;
@@ -1131,7 +1169,7 @@ int sg_igemm3_fuse_plan(SgIgemmParams& P, SgFusePlan* out) {
         out->variant = pl.a_it == 2 ? 1 : (pl.a_it == 4 ? 2 : 5);
         out->nblocks = t * sg3_cdiv(P.N, 64);
         out->lds = (size_t)maxlds + (size_t)2 * 64 * 128 + (size_t)4 * 64 * 4 + SGAN_MAX_TAPS * 16 + (size_t)2 * P.Ck * 4;
-        out->name = pl.a_it == 6 ? "sg_igemm3p_kernel<64,s2>" : "sg_igemm3p_kernel<64>";
+        out->name = pl.a_it == 6 ? (x1 ? "sg_igemm3p_kernel<64,s2,x1>" : "sg_igemm3p_kernel<64,s2>") : (x1 ? "sg_igemm3p_kernel<64,x1>" : "sg_igemm3p_kernel<64>");
         return 0;
     }
     const Sg3Tile tl = sg3_pick_tile(P);
@@ -1140,7 +1178,7 @@ int sg_igemm3_fuse_plan(SgIgemmParams& P, SgFusePlan* out) {
         out->variant = 6;
         out->nblocks = tiles * sg3_cdiv(P.N, 32);
         out->lds = (size_t)2 * (128 + 32) * 128 + (size_t)4 * 32 * 4 + SGAN_MAX_TAPS * 16 + (size_t)2 * P.Ck * 4;
-        out->name = "sg_igemm3_kernel<128,32,4,1>";
+        out->name = x1 ? "sg_igemm3_kernel<128,32,4,1,x1>" : "sg_igemm3_kernel<128,32,4,1>";
         return 0;
     }
     // a launch that would have been split-K on its own runs unsplit here when the split is shallow: the backward-weight
@@ -1168,24 +1206,33 @@ int sg_igemm3_fuse_plan(SgIgemmParams& P, SgFusePlan* out) {
     out->ks = ks;
     out->nblocks = tiles * sg3_cdiv(P.N, 64) * ks;
     out->lds = (size_t)4 * (64 + 64) * 128 + (size_t)4 * 64 * 4 + SGAN_MAX_TAPS * 16 + (size_t)2 * P.Ck * 4;
-    out->name = "sg_igemm3_kernel<64,64,2,2>";
+    out->name = x1 ? "sg_igemm3_kernel<64,64,2,2,x1>" : "sg_igemm3_kernel<64,64,2,2>";
     return 0;
 }
 
-int sg_launch_igemm3(SgIgemmParams& P, hipStream_t st, float* ws, int64_t ws_bytes) {
+// X1: the one-plane instantiations (SGAN_MATH_BF16X1); same plans and tiles, names with an ",x1" suffix
+#define SG3_NAME(base) (X1 ? base ",x1>" : base ">")
+template <bool X1>
+static int sg_launch_igemm3_mode(SgIgemmParams& P, hipStream_t st, float* ws, int64_t ws_bytes) {
     const Sg3pPlan pl = sg3p_plan(P);
     if (sg3p_wanted(pl)) {
-        if (pl.a_it == 2) return sg3p_launch<64, 2>(P, st, "sg_igemm3p_kernel<64>");
-        if (pl.a_it == 6) return sg3p_launch<64, 6, true>(P, st, "sg_igemm3p_kernel<64,s2>");
-        return sg3p_launch<64, 4>(P, st, "sg_igemm3p_kernel<64>");
+        if (pl.a_it == 2) return sg3p_launch<64, 2, false, X1>(P, st, SG3_NAME("sg_igemm3p_kernel<64"));
+        if (pl.a_it == 6) return sg3p_launch<64, 6, true, X1>(P, st, SG3_NAME("sg_igemm3p_kernel<64,s2"));
+        return sg3p_launch<64, 4, false, X1>(P, st, SG3_NAME("sg_igemm3p_kernel<64"));
     }
     const Sg3Tile t = sg3_pick_tile(P);
-    if (t.BN == 32) return sg3_launch<128, 32, 4, 1>(P, st, ws, ws_bytes, "sg_igemm3_kernel<128,32,4,1>");
-    if (t.BM == 128 && t.BN == 128) return sg3_launch<128, 128, 2, 4>(P, st, ws, ws_bytes, "sg_igemm3_kernel<128,128,2,4>");
-    if (t.BM == 128) return sg3_launch<128, 64, 2, 2>(P, st, ws, ws_bytes, "sg_igemm3_kernel<128,64,2,2>");
+    if (t.BN == 32) return sg3_launch<128, 32, 4, 1, false, X1>(P, st, ws, ws_bytes, SG3_NAME("sg_igemm3_kernel<128,32,4,1"));
+    if (t.BM == 128 && t.BN == 128) return sg3_launch<128, 128, 2, 4, false, X1>(P, st, ws, ws_bytes, SG3_NAME("sg_igemm3_kernel<128,128,2,4"));
+    if (t.BM == 128) return sg3_launch<128, 64, 2, 2, false, X1>(P, st, ws, ws_bytes, SG3_NAME("sg_igemm3_kernel<128,64,2,2"));
     static const int kb2 = getenv("SGAN_KB2") ? atoi(getenv("SGAN_KB2")) : 1;      // tuning knob
-    if (kb2) return sg3_launch<64, 64, 2, 2, true>(P, st, ws, ws_bytes, "sg_igemm3_kernel<64,64,2,2>");
-    return sg3_launch<64, 64, 2, 2>(P, st, ws, ws_bytes, "sg_igemm3_kernel<64,64,2,2>");
+    if (kb2) return sg3_launch<64, 64, 2, 2, true, X1>(P, st, ws, ws_bytes, SG3_NAME("sg_igemm3_kernel<64,64,2,2"));
+    return sg3_launch<64, 64, 2, 2, false, X1>(P, st, ws, ws_bytes, SG3_NAME("sg_igemm3_kernel<64,64,2,2"));
+}
+#undef SG3_NAME
+
+int sg_launch_igemm3(SgIgemmParams& P, hipStream_t st, float* ws, int64_t ws_bytes) {
+    if (P.math == SGAN_MATH_BF16X1) return sg_launch_igemm3_mode<true>(P, st, ws, ws_bytes);
+    return sg_launch_igemm3_mode<false>(P, st, ws, ws_bytes);
 }
 
 int64_t sg_igemm3_workspace_need(const SgIgemmParams& P) {

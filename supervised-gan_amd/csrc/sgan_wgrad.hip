@@ -819,8 +819,8 @@ extern "C" int sgan_conv_wgrad_grouped(const sgan_conv_wgrad_job* jobs, int32_t 
         }
     }
     if (workspace_bytes == -1) return 0;   // the tiled kernels combine their splits with atomics: no workspace
-    if (d0->math == SGAN_MATH_BF16X3) {      // split-bf16 MFMA (sgan_wgrad3.hip) where it covers the layer
-        const int r3 = sg_launch_wgrad3(P, st);
+    if (d0->math == SGAN_MATH_BF16X3 || d0->math == SGAN_MATH_BF16X1) {      // 16-bit MFMA (sgan_wgrad3.hip) where it covers the layer
+        const int r3 = sg_launch_wgrad3(P, st, d0->math == SGAN_MATH_BF16X1);
         if (r3 != 0) return r3 < 0 ? r3 : SGAN_OK;
     }
     if (d0->Cout <= 16) return sg_launch_wgrad<16, 128, 1, 4>(P, st);

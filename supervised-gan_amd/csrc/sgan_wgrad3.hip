@@ -50,6 +50,22 @@ __device__ __forceinline__ void sgw_split8(const f32x4 v0, const f32x4 v1, u32x4
     }
 }
 template <bool F16>
+__device__ __forceinline__ u32x4 sgw_hi8(const f32x4 v0, const f32x4 v1) {   // the hi plane alone, as sg_hi8 (sgan_igemm3.hip)
+    u32x4 hi;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const f32x2 p = {v0[2 * i], v0[2 * i + 1]}, q = {v1[2 * i], v1[2 * i + 1]};
+        if constexpr (F16) {
+            hi[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(p, sgw_f16x2));
+            hi[2 + i] = __builtin_bit_cast(unsigned, __builtin_convertvector(q, sgw_f16x2));
+        } else {
+            hi[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(p, sg_bf16x2));
+            hi[2 + i] = __builtin_bit_cast(unsigned, __builtin_convertvector(q, sg_bf16x2));
+        }
+    }
+    return hi;
+}
+template <bool F16>
 __device__ __forceinline__ f32x16 sgw_mfma(const sg_bf16x8 a, const sg_bf16x8 b, const f32x16 c) {
     if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(sgw_f16x8, a), __builtin_bit_cast(sgw_f16x8, b), c, 0, 0, 0);
     else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
@@ -68,7 +84,8 @@ __device__ __forceinline__ sg_bf16x8 sgw_tr8(const char* p) {
 // body with explicit workgroup coordinates: sg_bwd_fused_kernel (sgan_fused.hip) runs it beside the backward-data body in one launch
 // F16: fp16 planes (dout times 2^s, s from its published maximum; x is a post-normalisation activation): 11 + 11 significant bits, an
 // fp32-equivalent product; else bf16 planes (8 + 8)
-template <int BCO, int BKC, int WGC, int WGK, bool PRO, bool F16 = false>
+// X1: the hi plane alone (SGAN_MATH_BF16X1): one MFMA per product; the LDS layout keeps its lo planes, unused
+template <int BCO, int BKC, int WGC, int WGK, bool PRO, bool F16 = false, bool X1 = false>
 __device__ __forceinline__ void sg_wgrad3_body(const SgWgradParams& G, char* smem, const int bx, const int by, const int bz) {
     constexpr int BP = 32;
     constexpr int WTC = BCO / WGC, WTK = BKC / WGK, MB = WTC / 32, NB = WTK / 32;
@@ -240,6 +257,10 @@ __device__ __forceinline__ void sg_wgrad3_body(const SgWgradParams& G, char* sme
 #pragma unroll
                 for (int j = 0; j < 4; ++j) { v0[j] = fmaxf(p0[j], q0[j]); v1[j] = fmaxf(p1[j], q1[j]); }
             }
+            if constexpr (X1) {
+                if (BKC / 32 % 2 == 0 || a_blk[it] < BKC / 32) *reinterpret_cast<u32x4*>(Ab + a_blk[it] * 2048 + s_dst) = sgw_hi8<F16>(v0, v1);
+                continue;
+            }
             u32x4 hi, lo;
             sgw_split8<F16>(v0, v1, hi, lo);
             if (BKC / 32 % 2 == 0 || a_blk[it] < BKC / 32) {
@@ -251,6 +272,11 @@ __device__ __forceinline__ void sg_wgrad3_body(const SgWgradParams& G, char* sme
         for (int it = 0; it < D_IT; ++it) {
             bacc[it][0] += d_reg[S][it][0];
             bacc[it][1] += d_reg[S][it][1];
+            if constexpr (X1) {
+                const u32x4 hi = F16 ? sgw_hi8<true>(d_reg[S][it][0] * d_scale, d_reg[S][it][1] * d_scale) : sgw_hi8<false>(d_reg[S][it][0], d_reg[S][it][1]);
+                if (BCO / 32 % 2 == 0 || d_blk[it] < BCO / 32) *reinterpret_cast<u32x4*>(Db + d_blk[it] * 2048 + s_dst) = hi;
+                continue;
+            }
             u32x4 hi, lo;
             if constexpr (F16) sgw_split8<true>(d_reg[S][it][0] * d_scale, d_reg[S][it][1] * d_scale, hi, lo);
             else sgw_split8<false>(d_reg[S][it][0], d_reg[S][it][1], hi, lo);
@@ -292,12 +318,12 @@ __device__ __forceinline__ void sg_wgrad3_body(const SgWgradParams& G, char* sme
 #pragma unroll
             for (int i = 0; i < MB; ++i) {
                 dh[s][i] = sgw_tr8(Db + i * 2048 + s * 16 * 64);
-                dl[s][i] = sgw_tr8(Db + D_PLANE + i * 2048 + s * 16 * 64);
+                if constexpr (!X1) dl[s][i] = sgw_tr8(Db + D_PLANE + i * 2048 + s * 16 * 64);
             }
 #pragma unroll
             for (int j = 0; j < NB; ++j) {
                 ah[s][j] = sgw_tr8(Ab + j * 2048 + s * 16 * 64);
-                al[s][j] = sgw_tr8(Ab + A_PLANE + j * 2048 + s * 16 * 64);
+                if constexpr (!X1) al[s][j] = sgw_tr8(Ab + A_PLANE + j * 2048 + s * 16 * 64);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -309,12 +335,14 @@ __device__ __forceinline__ void sg_wgrad3_body(const SgWgradParams& G, char* sme
             for (int i = 0; i < MB; ++i)
 #pragma unroll
                 for (int j = 0; j < NB; ++j) {
-                    acc[i][j] = sgw_mfma<F16>(dl[s][i], ah[s][j], acc[i][j]);
-                    acc[i][j] = sgw_mfma<F16>(dh[s][i], al[s][j], acc[i][j]);
+                    if constexpr (!X1) {
+                        acc[i][j] = sgw_mfma<F16>(dl[s][i], ah[s][j], acc[i][j]);
+                        acc[i][j] = sgw_mfma<F16>(dh[s][i], al[s][j], acc[i][j]);
+                    }
                     acc[i][j] = sgw_mfma<F16>(dh[s][i], ah[s][j], acc[i][j]);
                 }
         next_addrs();
-        constexpr int NMFMA = 6 * MB * NB;
+        constexpr int NMFMA = (X1 ? 2 : 6) * MB * NB;
         constexpr int PER = (24 + 8 * A_IT + 2 * D_IT + NMFMA - 1) / NMFMA;
 #pragma unroll
         for (int q = 0; q < NMFMA; ++q) {
@@ -387,11 +415,11 @@ __device__ __forceinline__ void sg_wgrad3_body(const SgWgradParams& G, char* sme
     }
 }
 
-template <int BCO, int BKC, int WGC, int WGK, bool PRO, bool F16 = false>
+template <int BCO, int BKC, int WGC, int WGK, bool PRO, bool F16 = false, bool X1 = false>
 __global__ __launch_bounds__(256) void sg_wgrad3_kernel(const SgWgradParams G) {
     sg_warm_kernargs<(int)sizeof(SgWgradParams)>();      // sgan_common.h: the scalar-cache misses of the parameter block, taken together
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    sg_wgrad3_body<BCO, BKC, WGC, WGK, PRO, F16>(G, smem, blockIdx.x, blockIdx.y, blockIdx.z);
+    sg_wgrad3_body<BCO, BKC, WGC, WGK, PRO, F16, X1>(G, smem, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
 #ifndef SG_KERNELS_ONLY      // sgan_fused.hip includes this file for the kernel bodies only
@@ -433,7 +461,7 @@ static bool sgw3_prepare(SgWgradParams& P, int BCO, int BKC, dim3* grid_out, siz
     return true;
 }
 
-template <int BCO, int BKC, int WGC, int WGK>
+template <int BCO, int BKC, int WGC, int WGK, bool X1 = false>
 static int sgw3_launch(SgWgradParams& P, hipStream_t st, const char* name) {
     dim3 grid;
     size_t lds;
@@ -441,11 +469,11 @@ static int sgw3_launch(SgWgradParams& P, hipStream_t st, const char* name) {
     if (!sgw3_prepare(P, BCO, BKC, &grid, &lds, &pro)) return 1;
     sg_prof_begin(st);
     if (P.planes_f16) {
-        if (pro) hipLaunchKernelGGL((sg_wgrad3_kernel<BCO, BKC, WGC, WGK, true, true>), grid, dim3(256), lds, st, P);
-        else hipLaunchKernelGGL((sg_wgrad3_kernel<BCO, BKC, WGC, WGK, false, true>), grid, dim3(256), lds, st, P);
+        if (pro) hipLaunchKernelGGL((sg_wgrad3_kernel<BCO, BKC, WGC, WGK, true, true, X1>), grid, dim3(256), lds, st, P);
+        else hipLaunchKernelGGL((sg_wgrad3_kernel<BCO, BKC, WGC, WGK, false, true, X1>), grid, dim3(256), lds, st, P);
     } else {
-        if (pro) hipLaunchKernelGGL((sg_wgrad3_kernel<BCO, BKC, WGC, WGK, true, false>), grid, dim3(256), lds, st, P);
-        else hipLaunchKernelGGL((sg_wgrad3_kernel<BCO, BKC, WGC, WGK, false, false>), grid, dim3(256), lds, st, P);
+        if (pro) hipLaunchKernelGGL((sg_wgrad3_kernel<BCO, BKC, WGC, WGK, true, false, X1>), grid, dim3(256), lds, st, P);
+        else hipLaunchKernelGGL((sg_wgrad3_kernel<BCO, BKC, WGC, WGK, false, false, X1>), grid, dim3(256), lds, st, P);
     }
     hipError_t e_ = hipGetLastError();
     if (e_ != hipSuccess) return sgan_fail(SGAN_ERR_HIP, "%s:%d: %s", __FILE__, __LINE__, hipGetErrorString(e_));
@@ -461,8 +489,9 @@ static bool sgw3_covers(const SgWgradParams& P) {
     return true;
 }
 
-// Plan of a backward-weight launch for sg_bwd_fused_kernel: variant 1 = 64 x 64 tiles, 2 = 32 x 128, 0 = not covered / nothing to do
-int sg_wgrad3_fuse_plan(SgWgradParams& P, SgFusePlan* out) {
+// Plan of a backward-weight launch for sg_bwd_fused_kernel: variant 1 = 64 x 64 tiles, 2 = 32 x 128, 0 = not covered / nothing to do.
+// x1: the one-plane body (SGAN_MATH_BF16X1)
+int sg_wgrad3_fuse_plan(SgWgradParams& P, SgFusePlan* out, bool x1) {
     out->variant = 0;
     if (!sgw3_covers(P)) return 0;
     dim3 grid;
@@ -471,12 +500,17 @@ int sg_wgrad3_fuse_plan(SgWgradParams& P, SgFusePlan* out) {
     out->variant = narrow ? 2 : 1;
     out->gx = grid.x; out->gy = grid.y; out->gz = grid.z;
     out->nblocks = grid.x * grid.y * grid.z;
-    out->name = narrow ? "sg_wgrad3_kernel<32,128,1,4>" : "sg_wgrad3_kernel<64,64,2,2>";
+    out->name = narrow ? (x1 ? "sg_wgrad3_kernel<32,128,1,4,x1>" : "sg_wgrad3_kernel<32,128,1,4>")
+                       : (x1 ? "sg_wgrad3_kernel<64,64,2,2,x1>" : "sg_wgrad3_kernel<64,64,2,2>");
     return 0;
 }
 
-int sg_launch_wgrad3(SgWgradParams& P, hipStream_t st) {
+int sg_launch_wgrad3(SgWgradParams& P, hipStream_t st, bool x1) {
     if (!sgw3_covers(P)) return 0;
+    if (x1) {
+        if (P.Cout < 64) return sgw3_launch<32, 128, 1, 4, true>(P, st, "sg_wgrad3_kernel<32,128,1,4,x1>");
+        return sgw3_launch<64, 64, 2, 2, true>(P, st, "sg_wgrad3_kernel<64,64,2,2,x1>");
+    }
     if (P.Cout < 64) return sgw3_launch<32, 128, 1, 4>(P, st, "sg_wgrad3_kernel<32,128,1,4>");
     return sgw3_launch<64, 64, 2, 2>(P, st, "sg_wgrad3_kernel<64,64,2,2>");
 }

@@ -17,9 +17,11 @@ def pad4(c: int) -> int:
 
 
 # Arithmetic of the MFMA conv kernels (sgan_conv_desc.math): "bf16x3" = split-bf16 (fp32-equivalent, ~2^-16 per product,
-# 16/3 of the fp32 matrix rate; the default), "f32" = exact fp32 MFMA (the parity mode).  SGAN_MATH selects at start-up,
-# set_math() at run time (every conv call stamps the current mode into its descriptor).
-_MATH_NAMES = {"f32": L.MATH_F32, "fp32": L.MATH_F32, "bf16x3": L.MATH_BF16X3}
+# 16/3 of the fp32 matrix rate; the default), "f32" = exact fp32 MFMA (the parity mode), "bf16x1" (alias "bf16") = one 16-bit
+# plane, hi(a) * hi(b), the speed mode (~2^-9 per bf16 operand; storage, accumulation, norms, losses and Adam stay fp32).
+# SGAN_MATH selects at start-up, set_math() at run time (every conv call stamps the current mode into its descriptor).
+_MATH_NAMES = {"f32": L.MATH_F32, "fp32": L.MATH_F32, "bf16x3": L.MATH_BF16X3, "bf16x1": L.MATH_BF16X1, "bf16": L.MATH_BF16X1}
+_MATH_LABEL = {L.MATH_F32: "f32", L.MATH_BF16X3: "bf16x3", L.MATH_BF16X1: "bf16x1"}
 _math = _MATH_NAMES[__import__("os").environ.get("SGAN_MATH", "bf16x3").lower()]
 
 
@@ -32,7 +34,13 @@ def set_math(name: str):
 
 
 def get_math() -> str:
-    return "bf16x3" if _math == L.MATH_BF16X3 else "f32"
+    return _MATH_LABEL[_math]
+
+
+def uses_16bit() -> bool:
+    """Does the current mode run the 16-bit MFMA kernels (bf16x3 or bf16x1)?  They read the packed weight copies and the published
+    gradient maxima; the f32 mode reads neither."""
+    return _math != L.MATH_F32
 
 
 class math_scope:
@@ -64,17 +72,17 @@ def with_packed(w: torch.Tensor, packed, packed_f16=None) -> torch.Tensor:
 def _amax(t):
     """Device scalar max|t| when the producer published one (norm_bwd_apply*), else None."""
     a = getattr(t, "_sgan_amax", None)
-    return a.data_ptr() if (a is not None and _math == L.MATH_BF16X3) else None
+    return a.data_ptr() if (a is not None and uses_16bit()) else None
 
 
 def _pk16(w):
     pk = getattr(w, "_sgan_pk16", None)
-    return pk.data_ptr() if (pk is not None and _math == L.MATH_BF16X3) else None
+    return pk.data_ptr() if (pk is not None and uses_16bit()) else None
 
 
 def _pk(w):
     pk = getattr(w, "_sgan_pk", None)
-    return pk.data_ptr() if (pk is not None and _math == L.MATH_BF16X3) else None
+    return pk.data_ptr() if (pk is not None and uses_16bit()) else None
 
 
 def _stream():
@@ -329,7 +337,7 @@ def conv_wgrad_grouped(jobs):
 def conv_bwd_grouped(djobs, wjobs, dgrad_math=None):
     """A layer's backward-weight and backward-data (job lists as for the two calls above): one fused launch where
     sgan_conv_bwd_fused covers the layer, the two grouped launches otherwise.  dgrad_math: arithmetic of the backward-data half
-    ("f32" / "bf16x3"; None = the current mode)."""
+    ("f32" / "bf16x3" / "bf16x1"; None = the current mode)."""
     dm = _DGRAD_MATH if _DGRAD_MATH is not None else (_MATH_NAMES[dgrad_math] if dgrad_math else _math)
     d0 = djobs[0][0]
     if d0.Cout == 4 and d0.Cout_logical == 1 and d0.kind == L.CONV and d0.stride == 1 and len(djobs) == len(wjobs) and djobs[0][4] is not None:
@@ -340,7 +348,7 @@ def conv_bwd_grouped(djobs, wjobs, dgrad_math=None):
             return True
         if rc < 0:
             L.check(rc, "sgan_conv_head_bwd")
-    if _math == L.MATH_BF16X3:
+    if uses_16bit():
         _check_dgrad_jobs(djobs)
         _check_wgrad_jobs(wjobs)
         da, wa = _dgrad_array(djobs), _wgrad_array(wjobs)
@@ -400,7 +408,7 @@ def norm_bwd_apply_multi(jobs, publish_amax=False):
         part = jobs[i0:i0 + 8]
         arr = (L.NormBwdJob * len(part))()
         am = None
-        if publish_amax and _math == L.MATH_BF16X3 and not _NO_F16_BWD:
+        if publish_amax and uses_16bit() and not _NO_F16_BWD:
             am = stat_arena(len(part), part[0][0].device).view(torch.float32)      # one zeroed 8-byte slot per job (low word = the maximum)
         for i, job in enumerate(part):
             dy, x, x_norm, sums, dg, db = job[:6]
@@ -417,7 +425,7 @@ _NO_F16_BWD = __import__("os").environ.get("SGAN_NO_F16_BWD", "0") not in ("", "
 
 
 def has_amax(t) -> bool:
-    return getattr(t, "_sgan_amax", None) is not None and _math == L.MATH_BF16X3
+    return getattr(t, "_sgan_amax", None) is not None and uses_16bit()
 
 
 def norm_apply_fwd(u, u_norm, t, mask=None, noise=None, sigma=0.0):

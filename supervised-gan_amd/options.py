@@ -112,6 +112,11 @@ class BaseOptions:
         a('--hip_graph', action='store_true', help='capture the training step into hipGraphs')
         a('--no_group', action='store_true', help='launch every discriminator chain on its own instead of grouped kernels')
         a('--no_d_streams', action='store_true', help='run the discriminator chains on one stream instead of one each')
+        a('--math', type=str, default=None, choices=['f32', 'bf16x3', 'bf16x1'],
+          help='arithmetic of the conv kernels: f32 (exact fp32 MFMA), bf16x3 (split 16-bit planes, fp32-equivalent) or bf16x1 '
+               '(one 16-bit plane: faster, ~bf16 products, fp32 storage and accumulation).  Unset: SGAN_MATH, else bf16x3.  '
+               'Set when the options are parsed, before the model is built; a captured step (--hip_graph) replays the mode '
+               'that was current when it was captured')
         self.initialized = True
 
     def parse(self, args=None, save=True, verbose=True):
@@ -119,6 +124,9 @@ class BaseOptions:
             self.initialize()
         self.opt = self.parser.parse_args(args)
         self.opt.isTrain = self.isTrain
+        if self.opt.math is not None:
+            from . import ops
+            ops.set_math(self.opt.math)
         str_ids = self.opt.gpu_ids.split(',')
         self.opt.gpu_ids = [int(s) for s in str_ids if int(s) >= 0]
         if len(self.opt.gpu_ids) > 0 and torch.cuda.is_available():

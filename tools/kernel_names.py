@@ -9,21 +9,30 @@ def short(name):
     m = re.match(r"(sg_igemm_kernel)<(\d+,\d+,\d+,\d+,(?:true|false)),(?:true|false)(?:,\d+)?>$", n)   # prologue flag, wave groups
     if m:
         return f"{m.group(1)}<{m.group(2)}>"
-    m = re.match(r"(sg_igemm3_kernel)<(\d+,\d+,\d+,\d+),(?:true|false),(?:true|false)>$", n)   # prologue flag, fp16 / bf16 planes
+    # prologue flag, fp16 / bf16 planes, two k-tiles per barrier, one plane (SGAN_MATH_BF16X1: ",x1")
+    m = re.match(r"(sg_igemm3_kernel)<(\d+,\d+,\d+,\d+),(?:true|false),(?:true|false)(?:,(?:true|false))?(?:,(true|false))?>$", n)
     if m:
-        return f"{m.group(1)}<{m.group(2)}>"
-    m = re.match(r"(sg_igemm3p)(?:_kw2)?_kernel<(\d+),(.*)>$", n)      # N tile, staging passes, prologue flag, plane type, stride-2 flag
+        return f"{m.group(1)}<{m.group(2)}{',x1' if m.group(3) == 'true' else ''}>"
+    m = re.match(r"(sg_igemm3p)(?:_kw2)?_kernel<(\d+),(.*)>$", n)      # N tile, staging passes, prologue flag, plane type, stride-2 flag, wave groups, one plane
     if m:
-        return f"{m.group(1)}_kernel<{m.group(2)},s2>" if m.group(3).endswith(",true") and m.group(3).count(",") == 3 else f"{m.group(1)}_kernel<{m.group(2)}>"
+        a = m.group(3).split(",")
+        s2 = len(a) >= 4 and a[3] == "true"
+        x1 = len(a) >= 6 and a[5] == "true"
+        return f"{m.group(1)}_kernel<{m.group(2)}{',s2' if s2 else ''}{',x1' if x1 else ''}>"
     m = re.match(r"(sg_igemm3p_kernel)<(\d+),.*>$", n)
     if m:
         return f"{m.group(1)}<{m.group(2)}>"
-    m = re.match(r"(sg_wgrad3_kernel)<(\d+,\d+,\d+,\d+),(?:true|false)>$", n)
+    m = re.match(r"(sg_wgrad3_kernel)<(\d+,\d+,\d+,\d+),(?:true|false)(?:,(?:true|false))?(?:,(true|false))?>$", n)      # prologue, fp16, one plane
     if m:
-        return f"{m.group(1)}<{m.group(2)}>"
-    m = re.match(r"sg_bwd_fused_kernel<(\d+),\d+,(?:true|false)(?:,(?:true|false))?>$", n)      # backward-data variant, backward-weight tile, prologue flag, fp16 planes
+        return f"{m.group(1)}<{m.group(2)}{',x1' if m.group(3) == 'true' else ''}>"
+    # backward-data variant, backward-weight tile, prologue flag, fp16 planes, one-plane backward-data / backward-weight half
+    m = re.match(r"sg_bwd_fused_kernel<(\d+),\d+,(?:true|false)(?:,(?:true|false))?(?:,(true|false))?(?:,(true|false))?>$", n)
     if m:
-        return "sg_bwd_fused_kernel<f32 dgrad>" if m.group(1) == "4" else "sg_bwd_fused_kernel"
+        if m.group(1) == "4":
+            return "sg_bwd_fused_kernel<f32 dgrad>"
+        if m.group(2) == "true":
+            return "sg_bwd_fused_kernel<x1>"
+        return "sg_bwd_fused_kernel<wgrad x1>" if m.group(3) == "true" else "sg_bwd_fused_kernel"
     m = re.match(r"(sg_wgrad_kernel)<(.*),(true|false)>$", n)
     if m:
         return f"{m.group(1)}<{m.group(2)}>"
