@@ -538,6 +538,61 @@ int sgan_normal_fill_nhwc_pair(float* dst_a, float* dst_b, int32_t C, int32_t H,
                                uint64_t* offset_dev, void* zero, int64_t zero_bytes, void* stream);
 int sgan_rng_advance(uint64_t* offset_dev, uint64_t by, void* stream);
 
+/* ---- L-BFGS advance (latent reconstruction): torch.optim.LBFGS(lr, max_iter, max_eval, tolerance_grad, tolerance_change,
+ * history_size, line_search_fn=None).step(closure) as a state machine that consumes ONE closure evaluation per call.
+ * Replaces: optim.LBFGS([noise], lr=0.1).step(closure) x 50 of models/fcgan_model.py:278-302.
+ * Each call takes (loss[j], grad[j]) evaluated at the current x[j] of every problem j < J and runs torch's step() logic forward to the
+ * point where torch would call the closure again: a fresh step() when the last one ended (phase START), or the evaluation after a move
+ * (phase AFTER_MOVE).  x is updated in place.  A problem whose n_steps step() calls have finished is `done` and left untouched.
+ * Nothing is read back: the call is capturable.  One workgroup per problem; vectors fp32, dot products accumulated in fp64.
+ * State (one sgan_lbfgs_state per problem, device memory): the host fills the hyperparameters, zeroes everything else and sets
+ * h_diag = 1; the kernel owns the rest.  Buffers (device, fp32, rows of n): d [J][n], prev_grad [J][n], hist_s / hist_y
+ * [J][history_cap][n], hist_rho [J][history_cap]; x rows x_ld apart, grad rows g_ld apart, loss [J]; history_size <= history_cap. */
+#define SGAN_LBFGS_MAX_PROBLEMS 8
+#define SGAN_LBFGS_MAX_HISTORY 1024
+#define SGAN_LBFGS_PHASE_START 0
+#define SGAN_LBFGS_PHASE_AFTER_MOVE 1
+/* last_exit: why the last finished step() ended */
+#define SGAN_LBFGS_EXIT_NONE 0
+#define SGAN_LBFGS_EXIT_OPT_START 1    /* max|g| <= tolerance_grad at the step's first evaluation */
+#define SGAN_LBFGS_EXIT_GTD 2          /* g . d > -tolerance_change: no move */
+#define SGAN_LBFGS_EXIT_MAX_ITER 3     /* the max_iter-th move (not re-evaluated) */
+#define SGAN_LBFGS_EXIT_MAX_EVAL 4     /* evaluations of this step >= max_eval */
+#define SGAN_LBFGS_EXIT_OPT_COND 5     /* max|g| <= tolerance_grad after a move */
+#define SGAN_LBFGS_EXIT_SMALL_STEP 6   /* max|d t| <= tolerance_change */
+#define SGAN_LBFGS_EXIT_NO_PROGRESS 7  /* |loss - prev_loss| < tolerance_change */
+typedef struct sgan_lbfgs_state {
+    /* hyperparameters (host) */
+    float lr;
+    float tolerance_grad;
+    double tolerance_change;
+    int32_t max_iter;
+    int32_t max_eval;
+    int32_t history_size;
+    int32_t n_steps;        /* step() calls to run; then the problem is done */
+    /* counters: torch's state['func_evals'], state['n_iter'], finished step() calls */
+    int32_t func_evals;
+    int32_t n_iter;
+    int32_t steps;
+    int32_t phase;          /* SGAN_LBFGS_PHASE_* of the NEXT evaluation */
+    int32_t done;
+    int32_t iter_in_step;   /* step()'s local n_iter */
+    int32_t evals_in_step;  /* step()'s current_evals */
+    int32_t hist_len;       /* (s, y, rho) pairs in the ring */
+    int32_t hist_head;      /* ring slot of the oldest pair */
+    int32_t last_exit;      /* SGAN_LBFGS_EXIT_* */
+    int32_t n_skipped;      /* memory updates skipped (y . s <= 1e-10) */
+    int32_t reserved0;
+    /* scalars carried across evaluations and step() calls */
+    float t;
+    float h_diag;
+    double prev_loss;
+    int32_t reserved[8];
+} sgan_lbfgs_state;         /* 128 bytes */
+int sgan_lbfgs_advance(sgan_lbfgs_state* state, int32_t J, int64_t n, float* x, int64_t x_ld, const float* grad, int64_t g_ld,
+                       const float* loss, float* d, float* prev_grad, float* hist_s, float* hist_y, float* hist_rho,
+                       int32_t history_cap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -684,9 +684,11 @@ def can_group(nets) -> bool:
     return 1 < len(nets) <= 8 and all(_same_architecture(nets[0], n) for n in nets[1:])
 
 
-def _grouped_forward(nets, xs, given=None):
+def _grouped_forward(nets, xs, given=None, update_running=True):
     """nets[j] applied to xs[j] ([H,W,Cs] buffers); per layer ONE grouped launch.  Returns per-job (outs, stats).
-    given[j] = (outs, stats) of job j supplied by the caller (forward_pair: the buffers of a kept forward, statistics zeroed), None = fresh."""
+    given[j] = (outs, stats) of job j supplied by the caller (forward_pair: the buffers of a kept forward, statistics zeroed), None = fresh.
+    update_running=False: the BatchNorm running statistics are left alone (a train-mode forward does not read them; latent
+    reconstruction runs thousands of forwards through a generator it must hand back unchanged)."""
     dev = xs[0].device
     J = len(nets)
     given = given or [None] * J
@@ -727,7 +729,7 @@ def _grouped_forward(nets, xs, given=None):
             cur[j] = out
         ops.conv_fwd_grouped(jobs, nets[0].final_act if li == nL - 1 else ACT_NONE)
     for j, net in enumerate(nets):
-        if net._bn_boxes:
+        if update_running and net._bn_boxes:
             rl = []
             for li, L in enumerate(net.layers):
                 if L.norm == "bn":
@@ -738,7 +740,8 @@ def _grouped_forward(nets, xs, given=None):
     return outs, stats
 
 
-def _grouped_backward(nets, xs, outs, stats, douts, need_dx, want_wgrad):
+def _grouped_backward(nets, xs, outs, stats, douts, need_dx, want_wgrad, dx_out=None):
+    """dx_out[j]: buffer the input gradient of job j is written into (None: a fresh one)."""
     dev = xs[0].device
     J = len(nets)
     geos = [n._geometry(x.shape[0], x.shape[1]) for n, x in zip(nets, xs)]
@@ -808,7 +811,7 @@ def _grouped_backward(nets, xs, outs, stats, douts, need_dx, want_wgrad):
                 for j in dj:
                     L = nets[j].layers[0]
                     desc, h, w, ho, wo = geos[j][0]
-                    dxs[j] = torch.empty((h, w, L.cin_s), dtype=torch.float32, device=dev)
+                    dxs[j] = dx_out[j] if dx_out is not None else torch.empty((h, w, L.cin_s), dtype=torch.float32, device=dev)
                     jobs.append((desc, dcur[j], nets[j]._wt(L), dxs[j], None, None, None, 0, False, True))
                 if pair0:
                     ops.conv_bwd_grouped(jobs, wjobs)

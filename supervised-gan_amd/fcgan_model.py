@@ -14,6 +14,7 @@ from collections import OrderedDict
 import torch
 
 from . import networks, ops
+from ._lib import SganError
 from .base_model import BaseModel
 from .image_pool import ImagePool
 from .optim import FusedAdam
@@ -294,6 +295,85 @@ class FCGANModel(BaseModel):
             out['real'] = self.real.detach()
         out['fake'] = self.fake.detach()
         return out
+
+    # ---- latent reconstruction (fcgan_model.py:238-319) ---------------------------------------------------------------------------
+    def _draw_latent_buffer(self):
+        """The next latent in the model's stream (or from `noise_source`), as a copy of the padded NHWC buffer the generator reads."""
+        self._draw_noise()
+        return self._noise_buf.clone()
+
+    def _reconstructor(self, real, z0, n_steps, lr, graph, lbfgs_kw):
+        """One reconstructor -- and so one captured program -- per (image buffer and shape, trial count, settings, arithmetic mode):
+        the next image of the same shape only loads its latents and resets the optimizer state."""
+        from .reconstruct import LatentReconstructor
+        if self._noise_buf is None:
+            raise SganError("reconstruction runs on the GPU path with batchSize 1")
+        key = (tuple(z0.shape), real.data_ptr(), tuple(real.shape), tuple(real.stride()), int(n_steps), float(lr), bool(graph),
+               tuple(sorted(lbfgs_kw.items())), ops.get_math(), self.netG._flat.data_ptr())
+        cache = self.__dict__.setdefault('_recon_cache', OrderedDict())
+        rec = cache.get(key)
+        if rec is None:
+            rec = LatentReconstructor(self.netG, real, z0, self.opt.noise_nc, n_steps=n_steps, lr=lr, graph=graph, **lbfgs_kw)
+            cache[key] = rec
+            while len(cache) > 2:
+                cache.popitem(last=False)
+        else:
+            cache.move_to_end(key)
+            rec.reset(z0, real)
+        return rec
+
+    def reconstruction(self, num_trials=3, n_steps=50, lr=0.1, graph=True, **lbfgs_kw):
+        """Fit latents to `input` by L-BFGS (the reference: 3 trials x 50 step() calls of LBFGS(lr=0.1) with torch's defaults), all
+        trials at once.  Returns (rec_error_best, ll_noise_best, ll_noise_init_best): the BCE of the best trial's reconstruction and
+        -log N(z; 0, I) of its final and initial latent; sets `fake`, `fake_init` and `noise`.  The best trial is the first with the
+        strictly smallest error.  The generator's parameters and buffers are left exactly as they were."""
+        from .lbfgs import neg_log_likelihood
+        self.real = self.input
+        nc = self.opt.noise_nc
+        z0 = torch.stack([self._draw_latent_buffer() for _ in range(num_trials)])
+        rec = self._reconstructor(self.real, z0, n_steps, lr, graph, lbfgs_kw)
+        rec.run()
+        imgs_init = rec.images(z0)
+        imgs = rec.images(rec.Z)
+        errs = rec.errors(imgs)
+        ll = [neg_log_likelihood(ops.logical_view(rec.Z[j], nc)) for j in range(num_trials)]
+        ll_init = [neg_log_likelihood(ops.logical_view(z0[j], nc)) for j in range(num_trials)]
+        best, err_best, ll_best, ll_init_best = None, float('inf'), float('inf'), float('inf')
+        for j in range(num_trials):
+            if errs[j] < err_best:
+                best, err_best, ll_best, ll_init_best = j, errs[j], ll[j], ll_init[j]
+        if best is None:        # every error NaN: the reference leaves zero images behind
+            self.fake, self.fake_init = torch.zeros_like(self.real), torch.zeros_like(self.real)
+        else:
+            self.fake, self.fake_init = imgs[best].clone(), imgs_init[best].clone()
+            self.noise = ops.logical_view(rec.Z[best].clone(), nc)
+        self.recon_trials = dict(errors=errs, ll=ll, ll_init=ll_init, best=best, closures=rec.closures,
+                                 latents=[ops.logical_view(rec.Z[j].clone(), nc) for j in range(num_trials)],
+                                 latents_init=[ops.logical_view(z0[j], nc) for j in range(num_trials)], counters=rec.opt.counters())
+        return err_best, ll_best, ll_init_best
+
+    def reconstruct_cells(self, img, netG, opt, n_bfgs_iter=100, lbfgs_lr=0.1, graph=True, **lbfgs_kw):
+        """One trial (fcgan_model.py:278-302): a fresh latent, `n_bfgs_iter` L-BFGS step() calls against `img`.
+        Returns (noise_init, noise), logical [1, noise_nc, h, w] tensors."""
+        assert netG is self.netG and opt.noise_nc == self.opt.noise_nc
+        z0 = self._draw_latent_buffer().unsqueeze(0)
+        rec = self._reconstructor(img, z0, n_bfgs_iter, lbfgs_lr, graph, lbfgs_kw)
+        rec.run()
+        return ops.logical_view(z0[0], opt.noise_nc), ops.logical_view(rec.Z[0].clone(), opt.noise_nc)
+
+    def interpolate(self, alpha):
+        """fake = G(alpha * fixed_noiseB + (1 - alpha) * fixed_noiseA)  (fcgan_model.py:304-308)."""
+        noise = alpha * self.fixed_noiseB + (1 - alpha) * self.fixed_noiseA
+        with torch.no_grad():
+            self.fake = self.netG.forward(noise.contiguous())
+        self.real = self.input
+
+    def set_fixed_noise(self, which_one):
+        """The latent of the last reconstruction becomes fixed_noiseA ('A') or fixed_noiseB (anything else)  (fcgan_model.py:310-314)."""
+        if which_one == 'A':
+            self.fixed_noiseA = self.noise
+        else:
+            self.fixed_noiseB = self.noise
 
     def save(self, label):
         self.save_network(self.netG, 'G', label, gpu_ids=self.gpu_ids)

@@ -738,6 +738,24 @@ def sgd_multi(segs, lr_dev, momentum):
     L.check(L.lib().sgan_sgd_multi(arr, len(segs), _ptr(lr_dev), float(momentum), _stream()), "sgan_sgd_multi")
 
 
+def lbfgs_advance(state, J, n, x, grad, loss, d, prev_grad, hist_s, hist_y, hist_rho):
+    """One sgan_lbfgs_advance launch over J problems of n unknowns (supervised_gan_amd.lbfgs.DeviceLBFGS owns the buffers).
+    x, grad: [J, >= n] fp32 with unit element stride; loss: [J] fp32."""
+    from .lbfgs import LbfgsState
+    m = hist_rho.shape[1]
+    assert 1 <= J <= 8 and n >= 1 and state.dtype == torch.uint8 and tuple(state.shape) == (J, C.sizeof(LbfgsState))
+    for t, what in ((x, "x"), (grad, "grad")):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != J or t.shape[1] < n or t.stride(1) != 1 or (J - 1) * t.stride(0) + n > _avail(t):
+            raise L.SganError(f"lbfgs_advance: {what} must be a [J={J}, >= {n}] fp32 tensor with unit element stride, got "
+                              f"{tuple(t.shape)} / {tuple(t.stride())} {t.dtype}; nothing was launched")
+    for t, shape in ((loss, (J,)), (d, (J, n)), (prev_grad, (J, n)), (hist_s, (J, m, n)), (hist_y, (J, m, n)), (hist_rho, (J, m))):
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape, (tuple(t.shape), shape)
+    for t in (state, x, grad, loss, d, prev_grad, hist_s, hist_y, hist_rho):
+        require_gpu(t, "lbfgs_advance")
+    L.check(L.lib().sgan_lbfgs_advance(_ptr(state), J, n, _ptr(x), x.stride(0), _ptr(grad), grad.stride(0), _ptr(loss), _ptr(d),
+                                       _ptr(prev_grad), _ptr(hist_s), _ptr(hist_y), _ptr(hist_rho), m, _stream()), "sgan_lbfgs_advance")
+
+
 def normal_fill(dst, seed, offset_dev=None, advance=True):
     assert dst.is_contiguous() and dst.dtype == torch.float32
     L.check(L.lib().sgan_normal_fill(_ptr(dst), dst.numel(), C.c_uint64(seed & (2 ** 64 - 1)), _ptr(offset_dev), int(bool(advance)),
