@@ -5,14 +5,11 @@ networks.py, which re-exports everything here."""
 from __future__ import annotations
 
 import math
-import os
 from dataclasses import dataclass
 from typing import List, Optional
 
-import numpy as np
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from . import ops
 from ._lib import ACT_LRELU, ACT_NONE, ACT_RELU, ACT_TANH, CONV, CONVT, SganError
@@ -77,7 +74,8 @@ class _BwdArena:
     """Zeroed fp64 scratch for the backward sums, carved from the same fill as the forward statistics.  A second
     backward through the same forward (retain_graph) gets a fresh zeroed buffer."""
 
-    def __init__(self, buf, rep=0, dev=None):
+    def __init__(self, buf, rep=0, dev=None, final_act=None):
+        self.final_act, self.drop = final_act, {}      # of the forward it belongs to: fused output activation, {layer: (t, mask)}
         self.buf, self.dev = buf, (buf.device if buf is not None else dev)      # buf None: every backward takes its sums from the step's pool
         self.rep = rep           # replica stride of the forward statistics AND of `buf` (they share one ops.stat_arena)
         self.rep_bwd = rep       # replica stride of what take() handed out last
@@ -378,25 +376,17 @@ class ChainNet(nn.Module):
         b = self._gflat[L.b_off: L.b_off + L.cout_s] if L.bias else None
         return w, b
 
-    def _norm_of(self, li, stats, count):
-        """How a consumer reads layer li's raw output: its norm (from `stats`) + activation."""
+    def _norm_of(self, li, stats, count, drop=()):
+        """How a consumer reads layer li's raw output: its norm (from `stats`) + activation.  li in drop: the consumer reads the
+        materialised dropout tensor of layer li instead, and only the activation is left to apply."""
         L = self.layers[li]
-        if L.norm is None:
+        if L.norm is None or li in drop:
             return ops.norm_desc(None, None, None, count, 0.0, L.act, L.slope)
         st = stats[li]
         rep = getattr(stats[-1], "rep", 0)      # the statistics live in an ops.stat_arena (replicated sums)
         if L.norm == "bn":
-            g = self._flat[L.g_off: L.g_off + L.cout_s]
-            be = self._flat[L.be_off: L.be_off + L.cout_s]
-            return ops.norm_desc(st, g, be, count, BN_EPS, L.act, L.slope, 0, rep)
+            return ops.norm_desc(st, *self._bn_affine(L), count, BN_EPS, L.act, L.slope, 0, rep)
         return ops.norm_desc(st, None, None, count, IN_EPS, L.act, L.slope, 0, rep)
-
-    def _norm_in(self, li, stats, count, drop):
-        """_norm_of for a consumer that may read the materialised dropout tensor of layer li: only the activation is left to apply."""
-        if li in drop:
-            L = self.layers[li]
-            return ops.norm_desc(None, None, None, count, 0.0, L.act, L.slope)
-        return self._norm_of(li, stats, count)
 
     # ---- forward / backward programs ----------------------------------------------------------
     def _kept_arena(self, n_stats, device, zeroed=False):
@@ -412,6 +402,39 @@ class ChainNet(nn.Module):
             ops.zero_multi([full])
         return full[:max(n_stats, 1)]
 
+    def _bn_affine(self, L: LayerSpec, grads=False):
+        """(gamma, beta) of layer L's BatchNorm in the parameter storage; grads: (dgamma, dbeta) in the gradient storage."""
+        flat = self._gflat if grads else self._flat
+        return flat[L.g_off: L.g_off + L.cout_s], flat[L.be_off: L.be_off + L.cout_s]
+
+    def _bn_running_jobs(self, geo, stats):
+        """ops.bn_running_update's job list for one forward of this net."""
+        boxes = self._bn_boxes
+        return [(stats[li], boxes[L.key].running_mean, boxes[L.key].running_var, boxes[L.key].num_batches_tracked, L.cout,
+                 geo[li][3] * geo[li][4], L.cout_s, stats[-1].rep) for li, L in enumerate(self.layers) if L.norm == "bn"]
+
+    def _dropout_fwd(self, li, out, stats, drop):
+        """Dropout behind layer li (norm -> Dropout(p) -> ReLU, the AutoEncoder's): the mask commutes with the ReLU, so the masked
+        normalised tensor t = norm(y) * mask is materialised by one pass (sgan_norm_apply_fwd) and the consumer reads ReLU(t) with no
+        norm.  Records drop[li] = (t, mask); returns (t, Philox words drawn)."""
+        L, dev = self.layers[li], out.device
+        if getattr(self, "_rng_offset", None) is None or self._rng_offset.device != dev:
+            self._rng_offset = torch.zeros(1, dtype=torch.int64, device=dev)
+        mask, drawn = torch.empty_like(out), 0
+        src = getattr(self, "mask_source", None)        # tests inject the reference's masks
+        if src is not None:
+            mask.copy_(src(li, tuple(out.shape)))
+        else:
+            ops.dropout_mask(mask, L.drop, getattr(self, "_rng_seed", 0) + li, self._rng_offset, advance=False)
+            drawn = (mask.numel() + 3) // 4
+        t = torch.empty_like(out)
+        # BatchNorm -> Dropout (the fcgan generator's blocks): the affine goes into the materialised tensor
+        g, be = self._bn_affine(L) if L.norm == "bn" else (None, None)
+        raw = ops.norm_desc(stats[li], g, be, out.shape[0] * out.shape[1], BN_EPS if L.norm == "bn" else IN_EPS, ACT_NONE, 0.0, 0, stats[-1].rep)
+        ops.norm_apply_fwd(out, raw, t, mask)
+        drop[li] = (t, mask)
+        return t, drawn
+
     def run_forward(self, x: torch.Tensor, update_running=True, keep=False):
         """x: [H, W, Cs] NHWC buffer.  Returns (outs, stats): raw conv outputs and per-layer stats.
         keep: remember this call's buffers as `self._kept` (input, outputs, statistics in an allocation of their own, backward sums
@@ -419,137 +442,14 @@ class ChainNet(nn.Module):
         ops.require_gpu(x, type(self).__name__)
         if self._flat.device != x.device:
             raise SganError(f"module parameters are on {self._flat.device}, input on {x.device}")
-        H, W, Cs = x.shape
-        assert Cs == self.layers[0].cin_s, (Cs, self.layers[0].cin_s)
-        geo = self._geometry(H, W)
-        final_act = self._take_call_act()
-        n_stats = sum(2 * L.cout_s for L in self.layers if L.norm)
-        if keep:
-            assert not any(L.drop > 0 for L in self.layers), "a kept forward has no dropout state"
-            arena = self._kept_arena(n_stats, x.device)
-        else:
-            # one zero-fill serves the forward statistics and the backward sums (second half, consumed by run_backward)
-            arena = ops.stat_arena(2 * n_stats, x.device)
-        rep = ops.stat_rep(arena)
-        stats, o = [], 0
-        for L in self.layers:
-            if L.norm:
-                stats.append(arena[o: o + 2 * L.cout_s])
-                o += 2 * L.cout_s
-            else:
-                stats.append(None)
-        stats.append(_BwdArena(None, rep, x.device) if keep else _BwdArena(arena[n_stats:], rep))
-        stats[-1].final_act = final_act
-        outs = []
-        cur = x
-        # Dropout layers (norm -> Dropout(p) -> ReLU, the AutoEncoder's): the mask commutes with the ReLU, so the masked normalised
-        # tensor t = norm(y) * mask is materialised by one pass (sgan_norm_apply_fwd) and the consumer reads ReLU(t) with no norm.
-        drop = {}
-        if self.training and any(L.drop > 0 for L in self.layers):
-            if getattr(self, "_rng_offset", None) is None or self._rng_offset.device != x.device:
-                self._rng_offset = torch.zeros(1, dtype=torch.int64, device=x.device)
-            drawn = 0
-        for li, L in enumerate(self.layers):
-            desc, h, w, ho, wo = geo[li]
-            out = torch.empty((ho, wo, L.cout_s), dtype=torch.float32, device=x.device)
-            in_norm = self._norm_in(li - 1, stats, h * w, drop) if li > 0 else None
-            wt, b = self._wb(L)
-            last = li == len(self.layers) - 1
-            ops.conv_fwd(desc, cur, in_norm, wt, b, out, final_act if last else ACT_NONE, stats[li], 0, rep)
-            outs.append(out)
-            cur = out
-            if self.training and L.drop > 0:
-                mask = torch.empty((ho, wo, L.cout_s), dtype=torch.float32, device=x.device)
-                src = getattr(self, "mask_source", None)        # tests inject the reference's masks
-                if src is not None:
-                    mask.copy_(src(li, (ho, wo, L.cout_s)))
-                else:
-                    ops.dropout_mask(mask, L.drop, getattr(self, "_rng_seed", 0) + li, self._rng_offset, advance=False)
-                    drawn = max(drawn, (mask.numel() + 3) // 4)
-                t = torch.empty_like(out)
-                if L.norm == "bn":      # BatchNorm -> Dropout (the fcgan generator's blocks): the affine goes into the materialised tensor
-                    raw = ops.norm_desc(stats[li], self._flat[L.g_off: L.g_off + L.cout_s], self._flat[L.be_off: L.be_off + L.cout_s],
-                                        ho * wo, BN_EPS, ACT_NONE, 0.0, 0, rep)
-                else:
-                    raw = ops.norm_desc(stats[li], None, None, ho * wo, IN_EPS, ACT_NONE, 0.0, 0, rep)
-                ops.norm_apply_fwd(out, raw, t, mask)
-                drop[li] = (t, mask)
-                cur = t
-        if drop and getattr(self, "mask_source", None) is None:
-            ops.rng_advance(self._rng_offset, drawn)
-        stats[-1].drop = drop
-        if update_running and self._bn_boxes:
-            rl = []
-            for li, L in enumerate(self.layers):
-                if L.norm == "bn":
-                    nb = self._bn_boxes[L.key]
-                    _, _, _, ho, wo = geo[li]
-                    rl.append((stats[li], nb.running_mean, nb.running_var, nb.num_batches_tracked, L.cout, ho * wo, L.cout_s, rep))
-            ops.bn_running_update(rl, BN_MOMENTUM)
-        if keep:
-            self._kept = dict(x=x, outs=outs, stats=stats, n_stats=n_stats, final_act=final_act)
-        return outs, stats
+        assert x.shape[2] == self.layers[0].cin_s, (x.shape[2], self.layers[0].cin_s)
+        outs, stats = _grouped_forward([self], [x], update_running=update_running, final_act=self._take_call_act(), keep=keep)
+        return outs[0], stats[0]
 
     def run_backward(self, x, outs, stats, dout, need_dx: bool, want_wgrad: bool):
         """dout: gradient w.r.t. the net output (after final_act), [Ho, Wo, Cs].  Returns dx or None."""
-        geo = self._geometry(x.shape[0], x.shape[1])
-        nL = len(self.layers)
-        dev = x.device
-        if want_wgrad:
-            self._ensure_grads()
-        dcur = dout
-        if getattr(stats[-1], "final_act", self.final_act) == ACT_TANH:
-            d2 = torch.empty_like(outs[-1])
-            ops.tanh_bwd(dcur.contiguous(), outs[-1], d2)
-            dcur = d2
-        n_sums = sum(2 * L.cout_s for L in self.layers if L.norm)
-        arena = stats[-1].take(max(n_sums, 1))
-        brep = stats[-1].rep_bwd
-        sums, o = [], 0
-        for L in self.layers:
-            if L.norm:
-                sums.append(arena[o: o + 2 * L.cout_s])
-                o += 2 * L.cout_s
-            else:
-                sums.append(None)
-        dx = None
-        drop = getattr(stats[-1], "drop", {})
-        for li in range(nL - 1, -1, -1):
-            L = self.layers[li]
-            desc, h, w, ho, wo = geo[li]
-            dropped = (li - 1) in drop
-            src = (drop[li - 1][0] if dropped else outs[li - 1]) if li > 0 else x
-            in_norm = self._norm_in(li - 1, stats, h * w, drop) if li > 0 else None
-            wt, _ = self._wb(L)
-            wjob = [(desc, src, in_norm, dcur) + self._gwb(L)] if want_wgrad else None
-            if li > 0:
-                P = self.layers[li - 1]
-                din = torch.empty((h, w, P.cout_s), dtype=torch.float32, device=dev)
-                djob = [(desc, dcur, self._wt(L), din, src, in_norm, None if dropped else sums[li - 1], 0, False, True, brep)]
-                dm = _dgrad_math(P, [dcur])
-                if wjob:
-                    ops.conv_bwd_grouped(djob, wjob, dm)      # both halves in one launch where the fused kernel covers the layer
-                else:
-                    with ops.math_scope(dm):
-                        ops.conv_dgrad_grouped(djob)
-                if dropped:      # din = d t * ReLU'(t); through the mask, with the two norm-backward sums of the masked gradient
-                    raw_norm = self._norm_of(li - 1, stats, h * w)
-                    ops.norm_apply_bwd_sums(din, outs[li - 1], raw_norm, sums[li - 1], drop[li - 1][1])      # adds to the first copy only
-                    dg = self._gflat[P.g_off: P.g_off + P.cout_s] if (P.norm == "bn" and want_wgrad) else None
-                    db = self._gflat[P.be_off: P.be_off + P.cout_s] if (P.norm == "bn" and want_wgrad) else None
-                    ops.norm_bwd_apply(din, outs[li - 1], raw_norm, sums[li - 1], dg, db, 0, brep)
-                elif P.norm:
-                    dg = self._gflat[P.g_off: P.g_off + P.cout_s] if (P.norm == "bn" and want_wgrad) else None
-                    db = self._gflat[P.be_off: P.be_off + P.cout_s] if (P.norm == "bn" and want_wgrad) else None
-                    ops.norm_bwd_apply(din, src, in_norm, sums[li - 1], dg, db, 0, brep, publish_amax=_wants_amax(self.layers, li - 1))
-                dcur = din
-                continue
-            if wjob:
-                ops.conv_wgrad_grouped(wjob)
-            if need_dx:
-                dx = torch.empty((h, w, L.cin_s), dtype=torch.float32, device=dev)
-                ops.conv_dgrad(desc, dcur, self._wt(L), dx, None, None, None, w_transposed=True)
-        return dx
+        return _grouped_backward([self], [x], [outs], [stats], [dout], [need_dx], [want_wgrad],
+                                 final_act=stats[-1].final_act, single_chain=True)[0]
 
 
 def _wants_amax(layers, li):
@@ -654,16 +554,8 @@ def forward_pair(net: "ChainNet", x_a, x_b, arena_zeroed=False):
     xb = net._prepare_input(x_b.detach())["chain_in"]
     assert xb.data_ptr() == kept["x"].data_ptr() and tuple(xa.shape) == tuple(xb.shape)
     arena = net._kept_arena(kept["n_stats"], xb.device, arena_zeroed)      # zeroed here (one launch) unless the caller did
-    stats_b, o = [], 0
-    for L in net.layers:
-        if L.norm:
-            stats_b.append(arena[o: o + 2 * L.cout_s])
-            o += 2 * L.cout_s
-        else:
-            stats_b.append(None)
-    stats_b.append(_BwdArena(None, ops.stat_rep(arena), xb.device))
-    stats_b[-1].final_act = net.final_act
-    stats_b[-1].drop = {}
+    stats_b = _carve(net.layers, arena)
+    stats_b.append(_BwdArena(None, ops.stat_rep(arena), xb.device, net.final_act))
     kept["stats"], kept["final_act"] = stats_b, net.final_act
     with torch.no_grad():
         outs, _ = _grouped_forward([net, net], [xa, xb], given=[None, (kept["outs"], stats_b)])
@@ -684,36 +576,40 @@ def can_group(nets) -> bool:
     return 1 < len(nets) <= 8 and all(_same_architecture(nets[0], n) for n in nets[1:])
 
 
-def _grouped_forward(nets, xs, given=None, update_running=True):
-    """nets[j] applied to xs[j] ([H,W,Cs] buffers); per layer ONE grouped launch.  Returns per-job (outs, stats).
+def _carve(layers, arena, base=0):
+    """The per-layer [sum | sum of squares] slices of a flat statistics arena from offset `base` on (None: a layer without a norm)."""
+    out, o = [], base
+    for L in layers:
+        out.append(arena[o: o + 2 * L.cout_s] if L.norm else None)
+        o += 2 * L.cout_s if L.norm else 0
+    return out
+
+
+def _grouped_forward(nets, xs, given=None, update_running=True, final_act=None, keep=False):
+    """The forward walk of every plain chain: nets[j] applied to xs[j] ([H,W,Cs] buffers), J >= 1 nets of one architecture; per layer
+    ONE grouped launch.  Returns per-job (outs, stats); stats[j][-1] is the _BwdArena (backward sums, `final_act`, `drop`, strides).
     given[j] = (outs, stats) of job j supplied by the caller (forward_pair: the buffers of a kept forward, statistics zeroed), None = fresh.
     update_running=False: the BatchNorm running statistics are left alone (a train-mode forward does not read them; latent
-    reconstruction runs thousands of forwards through a generator it must hand back unchanged)."""
-    dev = xs[0].device
-    J = len(nets)
+    reconstruction runs thousands of forwards through a generator it must hand back unchanged).
+    final_act: activation fused into the last layer (None: nets[0].final_act; a single chain passes its per-call value).
+    keep (one chain): the statistics live in the net's kept arena, not in the step's pool, and the call is recorded as net._kept."""
+    dev, J = xs[0].device, len(nets)
     given = given or [None] * J
+    final_act = nets[0].final_act if final_act is None else final_act
     geos = [n._geometry(x.shape[0], x.shape[1]) for n, x in zip(nets, xs)]
     per_job = sum(2 * L.cout_s for L in nets[0].layers if L.norm)
     fresh = [j for j in range(J) if given[j] is None]
-    arena = ops.stat_arena(2 * per_job * len(fresh), dev)   # forward statistics | backward sums, in replicated copies
-    rep = ops.stat_rep(arena)
-    bwd = _BwdArena(arena[per_job * len(fresh):], rep)
-    stats = []
-    for j in range(J):
-        if given[j] is not None:
-            stats.append(given[j][1])
-            continue
-        st, o = [], fresh.index(j) * per_job
-        for L in nets[j].layers:
-            if L.norm:
-                st.append(arena[o: o + 2 * L.cout_s])
-                o += 2 * L.cout_s
-            else:
-                st.append(None)
-        st.append(bwd)
-        stats.append(st)
+    assert not keep or (J == 1 and not any(L.drop > 0 for L in nets[0].layers)), "a kept forward is one chain and has no dropout state"
+    if keep:
+        arena = nets[0]._kept_arena(per_job, dev)
+        bwd = _BwdArena(None, ops.stat_rep(arena), dev, final_act)
+    else:
+        arena = ops.stat_arena(2 * per_job * len(fresh), dev)   # forward statistics | backward sums, in replicated copies: one zero-fill
+        bwd = _BwdArena(arena[per_job * len(fresh):], ops.stat_rep(arena), final_act=final_act)
+    stats = [given[j][1] if given[j] is not None else _carve(nets[j].layers, arena, fresh.index(j) * per_job) + [bwd] for j in range(J)]
     outs = [[] for _ in range(J)]
     cur = list(xs)
+    drops, drawn = [stats[j][-1].drop for j in range(J)], [0] * J
     nL = len(nets[0].layers)
     for li in range(nL):
         jobs = []
@@ -722,35 +618,45 @@ def _grouped_forward(nets, xs, given=None, update_running=True):
             desc, h, w, ho, wo = geos[j][li]
             out = given[j][0][li] if given[j] is not None else torch.empty((ho, wo, L.cout_s), dtype=torch.float32, device=dev)
             assert tuple(out.shape) == (ho, wo, L.cout_s)
-            in_norm = net._norm_of(li - 1, stats[j], h * w) if li > 0 else None
+            in_norm = net._norm_of(li - 1, stats[j], h * w, drops[j]) if li > 0 else None
             wt, b = net._wb(L)
             jobs.append((desc, cur[j], in_norm, wt, b, out, stats[j][li], 0, stats[j][-1].rep))
             outs[j].append(out)
             cur[j] = out
-        ops.conv_fwd_grouped(jobs, nets[0].final_act if li == nL - 1 else ACT_NONE)
+        ops.conv_fwd_grouped(jobs, final_act if li == nL - 1 else ACT_NONE)
+        for j, net in enumerate(nets):
+            if net.training and net.layers[li].drop > 0:
+                assert J == 1, "dropout state belongs to one chain: such nets are not grouped"
+                cur[j], words = net._dropout_fwd(li, outs[j][li], stats[j], drops[j])
+                drawn[j] = max(drawn[j], words)
     for j, net in enumerate(nets):
+        if drops[j] and getattr(net, "mask_source", None) is None:
+            ops.rng_advance(net._rng_offset, drawn[j])
         if update_running and net._bn_boxes:
-            rl = []
-            for li, L in enumerate(net.layers):
-                if L.norm == "bn":
-                    nb = net._bn_boxes[L.key]
-                    _, _, _, ho, wo = geos[j][li]
-                    rl.append((stats[j][li], nb.running_mean, nb.running_var, nb.num_batches_tracked, L.cout, ho * wo, L.cout_s, stats[j][-1].rep))
-            ops.bn_running_update(rl, BN_MOMENTUM)
+            ops.bn_running_update(net._bn_running_jobs(geos[j], stats[j]), BN_MOMENTUM)
+    if keep:
+        nets[0]._kept = dict(x=xs[0], outs=outs[0], stats=stats[0], n_stats=per_job, final_act=final_act)
     return outs, stats
 
 
-def _grouped_backward(nets, xs, outs, stats, douts, need_dx, want_wgrad, dx_out=None):
-    """dx_out[j]: buffer the input gradient of job j is written into (None: a fresh one)."""
-    dev = xs[0].device
-    J = len(nets)
+def _grouped_backward(nets, xs, outs, stats, douts, need_dx, want_wgrad, dx_out=None, final_act=None, single_chain=False):
+    """The backward walk.  douts[j]: gradient w.r.t. the output of job j (after final_act); returns the per-job input gradients.
+    dx_out[j]: buffer the input gradient of job j is written into (None: a fresh one).  final_act: as in _grouped_forward.
+    single_chain selects between two launch sequences that are both measured parts of a step and stay as they are:
+      True  -- ChainNet.run_backward (every _ChainFn / _AdoptFn node): the first layer issues backward-weight, then a separate
+               one-job backward-data (never the paired call), and a layer's norm backward is ops.norm_bwd_apply, which reaches
+               the non-multi C entry under SGAN_NO_STAT_REPLICAS=1;
+      False -- the groups of multi_forward and the reconstruction closure: first-layer backward-weight and backward-data of the
+               SAME jobs are one ops.conv_bwd_grouped call, and a layer's norm backward is one ops.norm_bwd_apply_multi."""
+    dev, J = xs[0].device, len(nets)
+    final_act = nets[0].final_act if final_act is None else final_act
     geos = [n._geometry(x.shape[0], x.shape[1]) for n, x in zip(nets, xs)]
     nL = len(nets[0].layers)
     for j, net in enumerate(nets):
         if want_wgrad[j]:
             net._ensure_grads()
     dcur = list(douts)
-    if nets[0].final_act == ACT_TANH:
+    if final_act == ACT_TANH:
         for j in range(J):
             d2 = torch.empty_like(outs[j][-1])
             ops.tanh_bwd(dcur[j].contiguous(), outs[j][-1], d2)
@@ -758,65 +664,58 @@ def _grouped_backward(nets, xs, outs, stats, douts, need_dx, want_wgrad, dx_out=
     per_job = sum(2 * L.cout_s for L in nets[0].layers if L.norm)
     arena = stats[0][-1].take(max(per_job * J, 1))
     brep = stats[0][-1].rep_bwd
-    sums = []
-    for j in range(J):
-        sm, o = [], j * per_job
-        for L in nets[j].layers:
-            if L.norm:
-                sm.append(arena[o: o + 2 * L.cout_s])
-                o += 2 * L.cout_s
-            else:
-                sm.append(None)
-        sums.append(sm)
+    sums = [_carve(nets[j].layers, arena, j * per_job) for j in range(J)]
+    drops = [stats[j][-1].drop for j in range(J)]
     dxs = [None] * J
-    for li in range(nL - 1, -1, -1):
-        srcs = [outs[j][li - 1] if li > 0 else xs[j] for j in range(J)]
-        norms = [nets[j]._norm_of(li - 1, stats[j], geos[j][li][1] * geos[j][li][2]) if li > 0 else None for j in range(J)]
-        wj = [j for j in range(J) if want_wgrad[j]]
-        wjobs = [(geos[j][li][0], srcs[j], norms[j], dcur[j]) + nets[j]._gwb(nets[j].layers[li]) for j in wj]
-        pair0 = li == 0 and bool(wjobs) and wj == [j for j in range(J) if need_dx[j]]      # first layer, both gradients of the same jobs:
-        if wjobs and li == 0 and not pair0:                                                  # one launch below (ops.conv_bwd_grouped)
-            ops.conv_wgrad_grouped(wjobs)
-        if li > 0:
-            jobs, dins = [], []
-            for j, net in enumerate(nets):
-                Pv = net.layers[li - 1]
-                desc, h, w, ho, wo = geos[j][li]
-                din = torch.empty((h, w, Pv.cout_s), dtype=torch.float32, device=dev)
-                dins.append(din)
-                jobs.append((desc, dcur[j], net._wt(net.layers[li]), din, srcs[j], norms[j], sums[j][li - 1], 0, False, True, brep))
-            dm = _dgrad_math(nets[0].layers[li - 1], dcur)
-            if wjobs:
-                ops.conv_bwd_grouped(jobs, wjobs, dm)
-            else:
-                if wjobs:
-                    ops.conv_wgrad_grouped(wjobs)
-                with ops.math_scope(dm):
-                    ops.conv_dgrad_grouped(jobs)
-            nb = []
-            for j, net in enumerate(nets):
-                Pv = net.layers[li - 1]
-                if Pv.norm:
-                    bn = Pv.norm == "bn" and want_wgrad[j]
-                    dg = net._gflat[Pv.g_off: Pv.g_off + Pv.cout_s] if bn else None
-                    db = net._gflat[Pv.be_off: Pv.be_off + Pv.cout_s] if bn else None
-                    nb.append((dins[j], srcs[j], norms[j], sums[j][li - 1], dg, db, 0, brep))
-                dcur[j] = dins[j]
-            if nb:
-                ops.norm_bwd_apply_multi(nb, publish_amax=_wants_amax(nets[0].layers, li - 1))
+    for li in range(nL - 1, 0, -1):
+        jobs, wjobs, nb, masked, dins = [], [], [], [], []
+        for j, net in enumerate(nets):
+            desc, h, w, _, _ = geos[j][li]
+            P, sm = net.layers[li - 1], sums[j][li - 1]
+            drop = drops[j].get(li - 1)      # (t, mask): layer li read the materialised dropout tensor of layer li - 1
+            src = drop[0] if drop else outs[j][li - 1]
+            norm = net._norm_of(li - 1, stats[j], h * w, drops[j])
+            din = torch.empty((h, w, P.cout_s), dtype=torch.float32, device=dev)
+            jobs.append((desc, dcur[j], net._wt(net.layers[li]), din, src, norm, None if drop else sm, 0, False, True, brep))
+            if want_wgrad[j]:
+                wjobs.append((desc, src, norm, dcur[j]) + net._gwb(net.layers[li]))
+            dg, db = net._bn_affine(P, grads=True) if (P.norm == "bn" and want_wgrad[j]) else (None, None)
+            if drop:
+                masked.append((din, outs[j][li - 1], net._norm_of(li - 1, stats[j], h * w), sm, dg, db, drop[1]))
+            elif P.norm:
+                nb.append((din, src, norm, sm, dg, db, 0, brep))
+            dins.append(din)
+        dm = _dgrad_math(nets[0].layers[li - 1], dcur)
+        if wjobs:
+            ops.conv_bwd_grouped(jobs, wjobs, dm)      # both halves in one launch where the fused kernel covers the layer
         else:
-            dj = [j for j in range(J) if need_dx[j]]
-            if dj:
-                jobs = []
-                for j in dj:
-                    L = nets[j].layers[0]
-                    desc, h, w, ho, wo = geos[j][0]
-                    dxs[j] = dx_out[j] if dx_out is not None else torch.empty((h, w, L.cin_s), dtype=torch.float32, device=dev)
-                    jobs.append((desc, dcur[j], nets[j]._wt(L), dxs[j], None, None, None, 0, False, True))
-                if pair0:
-                    ops.conv_bwd_grouped(jobs, wjobs)
-                else:
-                    ops.conv_dgrad_grouped(jobs)
+            with ops.math_scope(dm):
+                ops.conv_dgrad_grouped(jobs)
+        for din, u, raw_norm, sm, dg, db, mask in masked:      # din = d t * ReLU'(t); through the mask, with the two norm-backward
+            ops.norm_apply_bwd_sums(din, u, raw_norm, sm, mask)      # sums of the masked gradient (added to the first copy only)
+            ops.norm_bwd_apply(din, u, raw_norm, sm, dg, db, 0, brep)
+        amax = _wants_amax(nets[0].layers, li - 1)
+        if nb and single_chain:
+            ops.norm_bwd_apply(*nb[0], publish_amax=amax)
+        elif nb:
+            ops.norm_bwd_apply_multi(nb, publish_amax=amax)
+        dcur = dins
+    # first layer
+    wj, dj = [j for j in range(J) if want_wgrad[j]], [j for j in range(J) if need_dx[j]]
+    wjobs = [(geos[j][0][0], xs[j], None, dcur[j]) + nets[j]._gwb(nets[j].layers[0]) for j in wj]
+    jobs = []
+    for j in dj:
+        L = nets[j].layers[0]
+        desc, h, w, ho, wo = geos[j][0]
+        dxs[j] = dx_out[j] if dx_out is not None else torch.empty((h, w, L.cin_s), dtype=torch.float32, device=dev)
+        jobs.append((desc, dcur[j], nets[j]._wt(L), dxs[j], None, None, None, 0, False, True))
+    if wjobs and wj == dj and not single_chain:      # both gradients of the same jobs: one call
+        ops.conv_bwd_grouped(jobs, wjobs)
+    else:
+        if wjobs:
+            ops.conv_wgrad_grouped(wjobs)
+        if jobs:
+            ops.conv_dgrad_grouped(jobs)
     return dxs
 
 

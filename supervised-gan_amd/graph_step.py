@@ -37,6 +37,7 @@ class GraphedStep:
         assert opt.batchSize == 1
         self._captured = False
         self._warmup_steps = warmup_steps
+        self._arenas = ops.ArenaPool()      # a captured program owns the pool its arenas came from: the graphs point into its slots
         self._prefetch = (not hasattr(model, "graph_spec") and hasattr(model, "prefetch_supported") and model.prefetch_supported()
                           and os.environ.get("SGAN_NO_G_PREFETCH", "0") in ("", "0"))
 
@@ -66,6 +67,12 @@ class GraphedStep:
                     set_overrides=lambda views: setattr(m, "_pool_override", views[0]), program=self._program())
 
     def capture(self, example_input):
+        """Warm-up steps, the eager run of the graph's own program and every capture draw their arenas from this step's own pool;
+        replays do not touch a pool on the host."""
+        with ops.arena_scope(self._arenas):
+            self._capture_all(example_input)
+
+    def _capture_all(self, example_input):
         m = self.m
         assert getattr(m, "noise_source", None) is None, "graphed step draws its latents on the device"
         spec = self._spec()

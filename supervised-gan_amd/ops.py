@@ -3,6 +3,7 @@
 Activation tensors are `[H, W, Cs]` fp32 CUDA tensors (NHWC, batch 1, Cs = stored channels, a
 multiple of 4; `tensor.stride(1)` is the pixel stride so channel slices of wider buffers work).
 Everything here launches on torch's current stream and never synchronises."""
+import contextlib
 import ctypes as C
 import weakref
 
@@ -168,13 +169,15 @@ def stat_replicas():
 _STAT_REPLICATED = __import__("os").environ.get("SGAN_NO_STAT_REPLICAS", "0") in ("", "0")      # diagnostics switch
 
 
-class _ArenaPool:
+class ArenaPool:
     """The statistics arenas of a training step, zeroed by ONE launch at its start (round 2: one aten fill per network call, 6-9 per
     step).  A step asks for the same sequence of arenas every time, so the pool is a list walked by a cursor: begin_step() zeroes
     every slot handed out since the last call (sgan_zero_multi) and rewinds; stat_arena() takes the next slot when it is clean and
     of the right size, anything else (first step, a changed sequence, no begin_step at all) falls back to torch.zeros.  Each slot is
     its own allocation (a pool carved from one buffer measured +35 us per step in round 2: the arenas' atomics then share memory
-    channels).  Slots stay alive for the life of the process; an autograd graph must not outlive the step it was built in."""
+    channels).  Slots stay alive as long as the pool; an autograd graph must not outlive the step it was built in.  A captured program
+    keeps raw pointers into the slots it was handed, and take() replaces a slot in place when a caller asks for another sequence: so
+    a captured program owns the pool its arenas came from (arena_scope) and holds it for as long as it can be replayed."""
     MAX_SLOTS = 128
 
     def __init__(self):
@@ -214,7 +217,26 @@ class _ArenaPool:
 
 
 _NO_ARENA_POOL = __import__("os").environ.get("SGAN_NO_ARENA_POOL", "0") not in ("", "0")      # diagnostics: one aten fill per arena
-_ARENAS = _ArenaPool()
+_ARENAS = ArenaPool()      # the process-wide pool of the eager training step; arena_scope() puts another in its place
+
+
+def arenas():
+    """The ArenaPool that stat_arena() and begin_step() reach right now."""
+    return _ARENAS
+
+
+@contextlib.contextmanager
+def arena_scope(pool, begin=True):
+    """Inside the block stat_arena() and begin_step() use `pool` (begin: entered with pool.begin_step(), which zeroes what the
+    pool's previous user left dirty); the pool in use before comes back on exit, also when the block raises."""
+    global _ARENAS
+    saved, _ARENAS = _ARENAS, pool
+    try:
+        if begin:
+            pool.begin_step()
+        yield pool
+    finally:
+        _ARENAS = saved
 
 
 def begin_step(also_zero=()):

@@ -6,7 +6,7 @@ one launch per layer for all trials -- then one BCE kernel per trial (loss and g
 chain into the latent-gradient buffers, then ONE sgan_lbfgs_advance launch for all trials.  No weight gradients, no BatchNorm
 running-statistics updates: the generator comes out bit-identical.  That program is captured once into a hipGraph and replayed; the
 `done` flags of the trials are read every `check_every` replays.  The graph owns what it points into: its statistics arenas are
-allocated (and zero-filled) inside the capture from a private arena pool, never from the process-wide pool of the training step.
+allocated (and zero-filled) inside the capture from a private arena pool (ops.arena_scope), never from the pool of a training step.
 Every eager pass of a reconstruction (closures, the final images) takes its arenas from a second private pool, so a reconstruction
 never touches the arenas a training step -- eager or captured -- holds.  One reconstructor serves every image of the same shape and
 trial count (reset() loads the next latents and fresh optimizer state; the captured program is reused).
@@ -47,8 +47,8 @@ class LatentReconstructor:
         self.opt = DeviceLBFGS(self.n, self.J, lr=lr, n_steps=n_steps, device=self.dev, **lbfgs_kw)
         self.closures = 0
         self._graph = None
-        self._arenas = ops._ArenaPool()         # the captured program's arenas (allocated inside the capture)
-        self._eager_arenas = ops._ArenaPool()   # every eager pass of this reconstructor
+        self._arenas = ops.ArenaPool()         # the captured program's arenas (allocated inside the capture)
+        self._eager_arenas = ops.ArenaPool()   # every eager pass of this reconstructor
 
     def reset(self, z0, real=None):
         """Next image: new initial latents (and image), fresh optimizer state; a captured program stays valid as long as the image
@@ -58,20 +58,6 @@ class LatentReconstructor:
             self.real = real
         self.opt.reset()
         self.closures = 0
-
-    class _Private:
-        """ops.stat_arena() draws from `pool` inside the block; begin_step() zeroes what the previous block used."""
-
-        def __init__(self, pool, begin=True):
-            self.pool, self.begin = pool, begin
-
-        def __enter__(self):
-            self.saved, ops._ARENAS = ops._ARENAS, self.pool
-            if self.begin:
-                self.pool.begin_step()
-
-        def __exit__(self, *exc):
-            ops._ARENAS = self.saved
 
     # ---- one closure evaluation of every trial: loss[j], G[j] = d loss_j / d Z[j] ---------------------------------------------
     def _closure_grouped(self):
@@ -111,11 +97,11 @@ class LatentReconstructor:
         stream = torch.cuda.Stream(device=self.dev)
         stream.wait_stream(torch.cuda.current_stream())
         self.netG._refresh_derived()
-        with torch.cuda.stream(stream), self._Private(self._eager_arenas):
+        with torch.cuda.stream(stream), ops.arena_scope(self._eager_arenas):
             self._closure_grouped()             # warm-up closure (no advance): lazy state exists before the capture
         stream.synchronize()
         self._graph = torch.cuda.CUDAGraph()
-        with self._Private(self._arenas, begin=False):
+        with ops.arena_scope(self._arenas, begin=False):
             with torch.cuda.graph(self._graph, stream=stream):
                 self._program()
         torch.cuda.current_stream().wait_stream(stream)
@@ -138,7 +124,7 @@ class LatentReconstructor:
                     if self.graph:
                         self._graph.replay()
                     else:
-                        with self._Private(self._eager_arenas):
+                        with ops.arena_scope(self._eager_arenas):
                             self._program()
                 self.closures += k
                 if all(self.opt.done()):
@@ -152,7 +138,7 @@ class LatentReconstructor:
 
     def images(self, Z):
         """G(Z[j]) for every row of Z ([K, h, w, Cs], K <= 8): logical [1, C, H, W] tensors, no running-statistics update."""
-        with torch.no_grad(), self._Private(self._eager_arenas):
+        with torch.no_grad(), ops.arena_scope(self._eager_arenas):
             if self.grouped:
                 outs, _ = _grouped_forward([self.netG] * Z.shape[0], [Z[k] for k in range(Z.shape[0])], update_running=False)
                 return [ops.logical_view(o[-1], self.C) for o in outs]

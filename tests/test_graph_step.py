@@ -100,3 +100,55 @@ def test_graphed_step_equals_eager(argv, hw, out):
     # two eager runs drift 3-8 % apart here and the figure itself varies run to run; a replay that dropped or reordered work
     # gives uncorrelated outputs (relative L2 ~ 1.4) or NaNs
     assert drift_graph < max(0.15, 4 * drift_eager)
+
+
+def test_captured_step_keeps_its_arenas_through_a_foreign_eager_step():
+    """A captured program owns the pool its statistics arenas came from (ops.arena_scope in GraphedStep.capture): an eager step of
+    another model in the same process -- another arena sequence, which makes ArenaPool.take() replace slots in place -- leaves
+    every slot the graphs point into alive at its address, shares no memory with them, and the replays after it still follow the
+    eager trajectory."""
+    if not torch.cuda.is_available():
+        pytest.fail("-m gpu tests need an MI355X; no CUDA/HIP device is visible")
+    from supervised_gan_amd import ops
+    from supervised_gan_amd.graph_step import GraphedStep
+    ring, seq = _ring(128), [0, 0, 1, 2, 3]
+    random.seed(11)
+    a = _build(FCGAN)
+    ea = []
+    for i in seq:
+        a.set_input(ring[i])
+        a.optimize_parameters()
+        ea.append(list(a.get_current_errors().values()))
+    random.seed(11)
+    b = _build(FCGAN)
+    gs = GraphedStep(b)
+    gs.capture(ring[0])
+    gs.step(ring[1])
+    eb = [list(b.get_current_errors().values())]
+    torch.cuda.synchronize()
+    own = gs._arenas
+    slots = list(own.slots)
+    spans = [(s.data_ptr(), s.data_ptr() + s.numel() * s.element_size()) for s in slots]
+    assert len(slots) >= 4 and own is not ops.arenas()      # the step's arenas: G forward(s), the D pass, the G passes
+    # the foreign step: its python-random pool draws must not shift the ones the fcgan trajectory is compared on
+    rnd = random.getstate()
+    other = _build(CGAN)
+    other.set_input(_ring(256, 1)[0])
+    other.optimize_parameters()
+    other.optimize_parameters()      # the second step walks the process-wide pool again: clean slots of the first are reused or replaced
+    torch.cuda.synchronize()
+    random.setstate(rnd)
+    foreign = ops.arenas().slots
+    assert len(foreign) >= 2 and [s.numel() for s in foreign] != [s.numel() for s in slots]      # it did use a pool, with another sequence
+    assert len(own.slots) == len(slots) and all(s is t for s, t in zip(own.slots, slots))
+    assert [(s.data_ptr(), s.data_ptr() + s.numel() * s.element_size()) for s in own.slots] == spans
+    for f in foreign:
+        f0, f1 = f.data_ptr(), f.data_ptr() + f.numel() * f.element_size()
+        assert all(f1 <= s0 or s1 <= f0 for s0, s1 in spans), "a slot of the process-wide pool overlaps one the graphs point into"
+    for i in seq[3:]:
+        gs.step(ring[i])
+        eb.append(list(b.get_current_errors().values()))
+    torch.cuda.synchronize()
+    ea, eb = np.asarray(ea[2:]), np.asarray(eb)
+    assert np.isfinite(eb).all()
+    assert np.abs(ea - eb).max() < 2e-2 * max(1.0, np.abs(ea).max()), (ea, eb)      # the tolerance of test_graphed_step_equals_eager

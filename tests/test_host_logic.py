@@ -232,3 +232,89 @@ def test_visualizer_and_html_page(tmp_path):
     wp.save()
     assert written == [str(tmp_path / "res" / "images" / "0007_x_fake_B.png")] and os.path.exists(written[0])
     assert "<h3>0007_x</h3>" in (tmp_path / "res" / "index.html").read_text()
+
+
+# ------------------------------------------------------------------------------------------------
+# ops.arena_scope: which ArenaPool stat_arena() / begin_step() reach (CPU tensors, the zeroing launch stubbed)
+# ------------------------------------------------------------------------------------------------
+@pytest.fixture
+def host_arenas(monkeypatch):
+    from supervised_gan_amd import ops
+    zeroed = []
+
+    def zero_multi(bufs):
+        zeroed.append([t.data_ptr() for t in bufs])
+        for t in bufs:
+            t.zero_()
+    monkeypatch.setattr(ops, "zero_multi", zero_multi)
+    monkeypatch.setattr(ops, "stat_replicas", lambda: 2)
+    with ops.arena_scope(ops.ArenaPool()):      # stands for the process-wide pool in these tests
+        yield ops, zeroed
+
+
+def test_arena_scope_nests_and_restores_the_outer_pool(host_arenas):
+    ops, _ = host_arenas
+    outer, a, b = ops.arenas(), ops.ArenaPool(), ops.ArenaPool()
+    with ops.arena_scope(a) as got:
+        assert got is a and ops.arenas() is a
+        ops.stat_arena(5, "cpu")
+        with ops.arena_scope(b):
+            assert ops.arenas() is b
+            ops.stat_arena(7, "cpu")
+            ops.stat_arena(9, "cpu")
+        assert ops.arenas() is a
+    assert ops.arenas() is outer
+    rep = ops.stat_replicas() if ops._STAT_REPLICATED else 1
+    assert [s.numel() for s in a.slots] == [5 * rep] and [s.numel() for s in b.slots] == [7 * rep, 9 * rep] and outer.slots == []
+
+
+def test_arena_scope_restores_the_pool_when_the_block_raises(host_arenas):
+    ops, _ = host_arenas
+    outer, a = ops.arenas(), ops.ArenaPool()
+    with pytest.raises(RuntimeError, match="inside"):
+        with ops.arena_scope(a):
+            raise RuntimeError("inside")
+    assert ops.arenas() is outer
+
+    class Broken(ops.ArenaPool):
+        def begin_step(self, also_zero=()):
+            raise RuntimeError("begin")
+    with pytest.raises(RuntimeError, match="begin"):
+        with ops.arena_scope(Broken()):
+            pass
+    assert ops.arenas() is outer
+
+
+def test_arena_scope_begin_runs_begin_step_of_the_scoped_pool_only(host_arenas):
+    ops, zeroed = host_arenas
+    outer, a = ops.arenas(), ops.ArenaPool()
+    dirty_outer = ops.stat_arena(3, "cpu")
+    with ops.arena_scope(a):
+        t = ops.stat_arena(4, "cpu")
+        t += 1.0
+    assert zeroed == [] and a.clean == [False] and a.cur == 1
+    with ops.arena_scope(a, begin=False):      # no begin_step: the cursor stays, the slot stays dirty
+        assert zeroed == [] and a.cur == 1 and a.clean == [False]
+        ops.begin_step()                        # the trainers' call reaches the scoped pool
+        assert zeroed == [[a.slots[0].data_ptr()]] and a.cur == 0
+        t2 = ops.stat_arena(4, "cpu")
+        assert t2.data_ptr() == t.data_ptr() and float(t2.abs().sum()) == 0.0
+    with ops.arena_scope(a):                    # begin=True: zeroes what the previous block used and rewinds
+        assert len(zeroed) == 2 and zeroed[1] == [a.slots[0].data_ptr()] and a.cur == 0 and a.clean == [True]
+    assert outer.clean == [False] and dirty_outer.data_ptr() == outer.slots[0].data_ptr()      # never touched from inside the scopes
+
+
+def test_two_pools_never_hand_out_each_others_slots(host_arenas):
+    ops, _ = host_arenas
+    outer, a = ops.arenas(), ops.ArenaPool()
+    with ops.arena_scope(a):
+        held = [ops.stat_arena(n, "cpu") for n in (6, 8, 10)]      # what a captured program would point into
+    ptrs = [s.data_ptr() for s in a.slots]
+    for _ in range(2):                             # a foreign step with another arena sequence, twice (take() replaces slots in place)
+        ops.begin_step()
+        got = [ops.stat_arena(n, "cpu") for n in (8, 6, 12, 4)]
+        assert not {g.data_ptr() for g in got} & set(ptrs)
+        assert not {s.data_ptr() for s in outer.slots} & set(ptrs)
+    assert [s.data_ptr() for s in a.slots] == ptrs and all(h.data_ptr() == p for h, p in zip(held, ptrs))
+    with ops.arena_scope(a):                       # the owner comes back: its own slots, in its own order
+        assert [ops.stat_arena(n, "cpu").data_ptr() for n in (6, 8, 10)] == ptrs
