@@ -93,7 +93,21 @@ typedef struct sgan_conv_desc {
      *                      w * 2^10 (the hi half of `w_packed`); backward-data and backward-weight bf16, or fp16 of dout * 2^s where
      *                      `dout_amax` is given.  Storage, accumulation, statistics and everything outside the conv products stay
      *                      fp32.  ~2^-9 (bf16) / 2^-12 (fp16) relative per operand.  Covers exactly the layers SGAN_MATH_BF16X3
-     *                      covers (same packed copies, same fallbacks to the exact-fp32 kernels). */
+     *                      covers (same packed copies, same fallbacks to the exact-fp32 kernels).
+     *   Operand domain of the two 16-bit modes, as the MAXIMUM MAGNITUDE of an operand (from a CPU model of this arithmetic on a
+     *   32 -> 64 k4 layer, tests/plane_model.py; the kernels follow that model at every scale below to within fp32 accumulation,
+     *   tests/test_hip_plane_range.py; each low edge is one power of two inside the last one that passes):
+     *     activation as it leaves the normalise / activate-on-load prologue (fp16 planes, UNSCALED: forward, and backward-weight
+     *       with `dout_amax`): 1e-3 contract for max|a| in [2^-11, 65504], fp32-equivalent for [2^-2, 65504]; any |a| > 65504
+     *       (65520 and up) makes the result non-finite.  Post-normalisation values are of order 1; a layer that loads with an
+     *       activation but no norm (the second PatchGAN conv) is inside only while its input is.
+     *     weights (fp16 planes of w * 2^10: forward, and backward-data with `dout_amax`): 1e-3 for max|w| in [2^-22, 2^5],
+     *       fp32-equivalent for [2^-12, 2^5]; |w| >= 64 makes the result non-finite.
+     *     gradients: with `dout_amax` (fp16 planes of dout * 2^s, |s| <= 100) 1e-3 for max|dout| in [2^-112, 2^115],
+     *       fp32-equivalent for [2^-102, 2^115]; without it (bf16 planes) ~5e-6 over the same range.
+     *   Under a low edge accuracy falls off by 2x per power of two (the lo plane, then the hi plane, go subnormal); nothing is
+     *   rerouted.  The 1e-3 contract covers SGAN_MATH_BF16X3 on either kind of plane and SGAN_MATH_BF16X1 on fp16 planes (~3e-4);
+     *   SGAN_MATH_BF16X1 on bf16 planes is ~2.5e-3 of the result at every scale. */
     int32_t math;
 } sgan_conv_desc;
 #define SGAN_MATH_F32 0

@@ -9,8 +9,8 @@ import os
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
+from plane_model import _bf16, _conv, _dgrad_ref, _f16, _prologue, _shift, _wgrad_ref
 from test_hip_bf16x3 import SHAPES, TILES, _select_tile
 
 pytestmark = pytest.mark.gpu
@@ -32,59 +32,6 @@ def ops():
 def _l2(a, b):
     a, b = a.detach().double().cpu(), b.detach().double().cpu()
     return float((a - b).norm() / (b.norm() + 1e-300))
-
-
-def _f16(t, shift=0):
-    """fp16 of t * 2^shift (round to nearest even, subnormals kept: v_cvt_pk_f16_f32), as a float64 tensor of the UNSCALED value."""
-    return (t.float() * (2.0 ** shift)).half().double() / (2.0 ** shift)
-
-
-def _bf16(t):
-    return t.float().bfloat16().double()
-
-
-def _shift(amax):
-    """sg_f16_shift: 2^s brings max|dY| under 2^15."""
-    e = int((np.float32(amax).view(np.uint32) >> 23) & 255)
-    return max(-100, min(100, 141 - e)) if e else 0
-
-
-def _prologue(x, st, gamma, beta, norm, act, count):
-    """The kernels' normalise-on-load in fp32: mean / rstd from the fp64 sums (sg_mean_rstd), y = x * sc + sh, activation."""
-    C = x.shape[1]
-    y = x.float()
-    if norm:
-        Cs = st.numel() // 2
-        s, q = st[:C].double().cpu(), st[Cs: Cs + C].double().cpu()
-        m = s / count
-        var = (q / count - m * m).clamp_min(0.0)
-        mean, rstd = m.float(), (1.0 / torch.sqrt(var + 1e-5)).float()
-        g = gamma.float() if gamma is not None else torch.ones(C)
-        b = beta.float() if beta is not None else torch.zeros(C)
-        sc = g * rstd
-        sh = b - mean * sc
-        y = y * sc.view(1, C, 1, 1) + sh.view(1, C, 1, 1)
-    if act == 1:
-        y = torch.clamp_min(y, 0.0)
-    elif act == 2:
-        y = torch.maximum(y, y * torch.tensor(0.2, dtype=torch.float32))
-    return y
-
-
-def _conv(tr, a, w, b, s, p):
-    return F.conv_transpose2d(a, w, b, stride=s, padding=p) if tr else F.conv2d(a, w, b, stride=s, padding=p)
-
-
-def _dgrad_ref(tr, dy, w, s, p, xshape):
-    x = torch.zeros(xshape, dtype=torch.float64, requires_grad=True)
-    (_conv(tr, x, w, None, s, p) * dy).sum().backward()
-    return x.grad
-
-
-def _wgrad_ref(tr, a, dy, wshape, s, p):
-    w = torch.zeros(wshape, dtype=torch.float64, requires_grad=True)
-    (_conv(tr, a, w, None, s, p) * dy).sum().backward()
-    return w.grad
 
 
 def _x1_name(name3):
