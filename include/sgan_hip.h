@@ -607,6 +607,43 @@ int sgan_lbfgs_advance(sgan_lbfgs_state* state, int32_t J, int64_t n, float* x, 
                        const float* loss, float* d, float* prev_grad, float* hist_s, float* hist_y, float* hist_rho,
                        int32_t history_cap, void* stream);
 
+/* ---- segmentation metrics on the device (accum_accs of the segmentation trainers: nothing comes back to the host per step) ---
+ * Replaces: util.compute_Rand_F_scores (skimage.measure.label + a pixel loop, util/util.py:86-128) and the confusion matrix of
+ * compute_current_accuracy (models/segm_model.py:309-331) of the reference.
+ * Every entry takes `dev_err`, one caller-owned int32 in device memory, zeroed by the caller: a kernel that has to give up (a bounded
+ * loop ran out, the pair table is full, a label is out of range) sets it nonzero and goes on without the offending pixel; the
+ * caller looks at it when it reads the results.  No kernel loops without a bound.
+ *
+ * sgan_ccl_label: the 8-connected components of the NON-wall pixels of one H x W plane; a pixel is wall when x > 0.5 (a NaN is not
+ *   wall).  Pixel (y, x) is read at plane[(y * W + x) * pix_stride], so channel 0 of an NHWC map is labelled where it lies.
+ *   labels (int32 [H * W]): 0 for a wall pixel, else 1 + (smallest raster index y * W + x of the pixel's component): independent of
+ *   scheduling, and numbered in scipy.ndimage.label's / skimage.measure.label's order.  H * W < 2^30.
+ *   Three launches: union-find per 64 x 16 tile in LDS; the links that cross a tile border (corners included) by atomicMin on the
+ *   label array; one pass that replaces every parent by its root.
+ * sgan_rand_f_workspace: bytes of the workspace sgan_rand_f_accumulate needs for an H x W pair (< 0: bad shape).
+ * sgan_rand_f_accumulate: from two label maps in sgan_ccl_label's form (t = truth, s = prediction) the exact integers
+ *   A2 = sum_i a_i^2 (a_i: pixels of truth region i), B2 = sum_j b_j^2 (b_j: pixels of prediction region j inside some truth region),
+ *   AB2 = sum_ij c_ij^2 (c_ij: pixels in truth region i and prediction region j), aux = pixels of a truth region on prediction wall;
+ *   then in fp64  prec = (AB2 + aux) / (B2 + aux), rec = (AB2 + aux) / A2, F = 2 / (1 / prec + 1 / rec)  (NaN when A2 == 0 or
+ *   B2 + aux == 0), which is util.compute_Rand_F_scores with the common 1 / n^2 cancelled; acc[0] += F, acc[1] += 1 (acc: 2 doubles,
+ *   caller-owned, running sum and image count).  sums_out (4 int64: A2, B2, AB2, aux) and f_out (1 double) are optional.
+ *   The workspace is caller-owned scratch; the call's own first launch zeroes it, so it may hold anything on entry, and one
+ *   workspace serves any number of calls on one stream.  Counts are atomic adds indexed by label; the pair counts live in an
+ *   open-addressing table of >= 2 H W slots with a probe bounded at SGAN_RAND_F_MAX_PROBE; a wave holds 64 pixels of a row and
+ *   adds each key it meets once (runs collapsed, then equal keys merged across the wave).  The squares are summed as (c + n)^2 - c^2 at each add, in 64-bit integers: exact in any order.
+ * sgan_confusion_accumulate: conf[truth * k + pred] += 1 per pixel, conf int64 [k * k], caller-owned.  pred = argmax over the C
+ *   logical channels (C <= 16) of x at pixel stride x_ld; truth = label[p] (int64 map) when label is given, else the argmax of y in
+ *   the same way.  add_background: class C = 1 - min(1, sum_c v_c) (fp32, summed in channel order) is appended to both channel
+ *   maps before the argmax and k = C + 1, else k = C.  Ties go to the first maximum and a NaN counts as the maximum, as in
+ *   torch.argmax. */
+#define SGAN_RAND_F_MAX_PROBE 1024
+int sgan_ccl_label(const float* plane, int64_t pix_stride, int32_t H, int32_t W, int32_t* labels, int32_t* dev_err, void* stream);
+int64_t sgan_rand_f_workspace(int32_t H, int32_t W);
+int sgan_rand_f_accumulate(const int32_t* t_labels, const int32_t* s_labels, int32_t H, int32_t W, void* workspace,
+                           int64_t workspace_bytes, double* acc, int64_t* sums_out, double* f_out, int32_t* dev_err, void* stream);
+int sgan_confusion_accumulate(const float* x, int32_t x_ld, int32_t C, const int64_t* label, const float* y, int32_t y_ld,
+                              int32_t add_background, int64_t npix, int64_t* conf, int32_t* dev_err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

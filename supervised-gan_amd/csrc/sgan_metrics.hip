@@ -1,0 +1,408 @@
+// Segmentation metrics on the device (include/sgan_hip.h, "segmentation metrics"): connected-component labelling of a thresholded
+// boundary map, the Rand F-score of two such labellings, and the confusion matrix of two class maps.  The trainers call these after
+// every optimizer step; nothing is read back until the accuracies are asked for.
+//
+// These kernels are bound by latency and atomics, not by arithmetic.  Three rules hold throughout:
+//   * every loop has a bound that does not depend on what other threads do: a union-find parent is always SMALLER than its child,
+//     so a walk to the root takes at most (index) steps and is cut at the pixel count anyway; a union retries only when another
+//     thread lowered the same parent in between, and is cut at SG_UNION_MAX_TRIES; a table probe is cut at SGAN_RAND_F_MAX_PROBE.
+//     A cut sets *dev_err and drops the pixel: a wrong label that is reported, never a hang.
+//   * what workgroups tell each other inside one launch goes through atomics at agent scope (the XCDs' L2s are not coherent for
+//     plain accesses); plain loads and stores carry data across launch boundaries only, or data that is valid whether old or new.
+//   * the results are integers, so they do not depend on the order the atomics arrive in.
+#include "sgan_common.h"
+
+#define SG_CCL_TW 64
+#define SG_CCL_TH 16
+#define SG_CCL_THREADS 256
+#define SG_UNION_MAX_TRIES (1 << 20)
+
+#define SG_LOAD_WG(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
+#define SG_LOAD_AGENT(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+
+__device__ __forceinline__ void sg_flag(int32_t* dev_err, int code) {
+    __hip_atomic_fetch_or(dev_err, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Connected components.  Every link between two 8-neighbours joins a pixel p to one of the four neighbours that precede it in raster
+// order: W, NW, N, NE.  Two of them are often implied by the others (N free: NW - N and N - NE are N's and NE's own W links; W free:
+// W - NW is W's own N link), so a pixel makes the links
+//     W if free;  N if free;  NW if free and neither N nor W is;  NE if free and N is not.
+// A link inside a tile is made by the tile kernel in LDS, a link across a tile border by the border kernel on the label array; the
+// rule holds for both because the links it relies on are made by one of the two as well.
+// Union-find with "the smaller index is the parent": the root of a component is its smallest raster index, which IS the canonical
+// label, so the outcome does not depend on the order the links are made in.
+// ------------------------------------------------------------------------------------------------------------------------------
+
+// LDS: P[i] = parent (tile-local index) of a free pixel, -1 for wall or outside the image
+__device__ __forceinline__ int sg_lds_find(int* P, int i) {
+    for (int it = 0; it < SG_CCL_TW * SG_CCL_TH; ++it) {
+        const int p = SG_LOAD_WG(&P[i]);
+        if (p == i) break;
+        i = p;
+    }
+    return i;
+}
+
+__device__ __forceinline__ void sg_lds_union(int* P, int a, int b, int32_t* dev_err) {
+    for (int it = 0; it < SG_UNION_MAX_TRIES; ++it) {
+        a = sg_lds_find(P, a);
+        b = sg_lds_find(P, b);
+        if (a == b) return;
+        if (a < b) { const int t = a; a = b; b = t; }
+        const int old = atomicMin(&P[a], b);      // a > b: hang the larger root under the smaller
+        if (old == a) return;
+        a = old;                                  // someone re-parented a meanwhile: its former parent still has to meet b
+    }
+    sg_flag(dev_err, 1);
+}
+
+// label array: L[i] = 0 for wall, else 1 + parent index
+__device__ __forceinline__ int sg_glb_find(int32_t* L, int i, int n) {
+    for (int it = 0; it < n; ++it) {
+        const int p = SG_LOAD_AGENT(&L[i]) - 1;
+        if (p == i || p < 0) break;
+        i = p;
+    }
+    return i;
+}
+
+__device__ __forceinline__ void sg_glb_union(int32_t* L, int a, int b, int n, int32_t* dev_err) {
+    for (int it = 0; it < SG_UNION_MAX_TRIES; ++it) {
+        a = sg_glb_find(L, a, n);
+        b = sg_glb_find(L, b, n);
+        if (a == b) return;
+        if (a < b) { const int t = a; a = b; b = t; }
+        const int old = atomicMin(&L[a], b + 1) - 1;
+        if (old == a) return;
+        a = old;
+    }
+    sg_flag(dev_err, 1);
+}
+
+__global__ __launch_bounds__(SG_CCL_THREADS) void sg_ccl_tile_kernel(const float* __restrict__ plane, int64_t pix_stride, int H, int W,
+                                                                     int32_t* __restrict__ L, int32_t* dev_err) {
+    __shared__ int P[SG_CCL_TW * SG_CCL_TH];
+    const int x0 = blockIdx.x * SG_CCL_TW, y0 = blockIdx.y * SG_CCL_TH;
+    for (int p = threadIdx.x; p < SG_CCL_TW * SG_CCL_TH; p += SG_CCL_THREADS) {
+        const int y = y0 + p / SG_CCL_TW, x = x0 + p % SG_CCL_TW;
+        bool is_free = false;
+        if (y < H && x < W) is_free = !(plane[((int64_t)y * W + x) * pix_stride] > 0.5f);
+        P[p] = is_free ? p : -1;
+    }
+    SG_SYNC();      // P[] initialised
+    for (int p = threadIdx.x; p < SG_CCL_TW * SG_CCL_TH; p += SG_CCL_THREADS) {
+        if (SG_LOAD_WG(&P[p]) < 0) continue;      // a free pixel's entry stays >= 0 whatever the other threads do to it
+        const int ly = p / SG_CCL_TW, lx = p % SG_CCL_TW;
+        const bool fw = lx > 0 && SG_LOAD_WG(&P[p - 1]) >= 0;
+        const bool fn = ly > 0 && SG_LOAD_WG(&P[p - SG_CCL_TW]) >= 0;
+        const bool fnw = ly > 0 && lx > 0 && SG_LOAD_WG(&P[p - SG_CCL_TW - 1]) >= 0;
+        const bool fne = ly > 0 && lx < SG_CCL_TW - 1 && SG_LOAD_WG(&P[p - SG_CCL_TW + 1]) >= 0;
+        if (fw) sg_lds_union(P, p, p - 1, dev_err);
+        if (fn) sg_lds_union(P, p, p - SG_CCL_TW, dev_err);
+        if (fnw && !fn && !fw) sg_lds_union(P, p, p - SG_CCL_TW - 1, dev_err);
+        if (fne && !fn) sg_lds_union(P, p, p - SG_CCL_TW + 1, dev_err);
+    }
+    SG_SYNC();      // every in-tile link made
+    for (int p = threadIdx.x; p < SG_CCL_TW * SG_CCL_TH; p += SG_CCL_THREADS) {
+        const int y = y0 + p / SG_CCL_TW, x = x0 + p % SG_CCL_TW;
+        if (y >= H || x >= W) continue;
+        int lab = 0;
+        if (P[p] >= 0) {
+            const int r = sg_lds_find(P, p);      // the tile-local order is the raster order, so r is the smallest raster index too
+            lab = 1 + (y0 + r / SG_CCL_TW) * W + x0 + r % SG_CCL_TW;
+        }
+        L[y * W + x] = lab;
+    }
+}
+
+__global__ __launch_bounds__(256) void sg_ccl_border_kernel(int32_t* L, int H, int W, int32_t* dev_err) {
+    const int i = blockIdx.x * 256 + threadIdx.x, n = H * W;
+    if (i >= n) return;
+    const int y = i / W, x = i % W, ly = y % SG_CCL_TH, lx = x % SG_CCL_TW;
+    if (ly != 0 && lx != 0 && lx != SG_CCL_TW - 1) return;      // no preceding neighbour in another tile
+    // wall or not never changes in this launch (a free entry stays >= 1), so plain loads may test it
+    if (L[i] == 0) return;
+    const bool fw = x > 0 && L[i - 1] != 0;
+    const bool fn = y > 0 && L[i - W] != 0;
+    const bool fnw = y > 0 && x > 0 && L[i - W - 1] != 0;
+    const bool fne = y > 0 && x < W - 1 && L[i - W + 1] != 0;
+    const bool cw = lx == 0, cn = ly == 0, cne = ly == 0 || lx == SG_CCL_TW - 1;      // which neighbours lie in another tile
+    if (fw && cw) sg_glb_union(L, i, i - 1, n, dev_err);
+    if (fn && cn) sg_glb_union(L, i, i - W, n, dev_err);
+    if (fnw && !fn && !fw && (cw || cn)) sg_glb_union(L, i, i - W - 1, n, dev_err);
+    if (fne && !fn && cne) sg_glb_union(L, i, i - W + 1, n, dev_err);
+}
+
+// Replaces every parent by the root.  In place: an entry another thread has already rewritten holds that pixel's root, which is as
+// good a parent as the one it held before, and an aligned 4-byte access is never torn.
+__global__ __launch_bounds__(256) void sg_ccl_flatten_kernel(int32_t* L, int n, int32_t* dev_err) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    int p = L[i] - 1;
+    if (p < 0 || p == i) return;
+    int it = 0;
+    for (; it < n; ++it) {
+        const int q = L[p] - 1;
+        if (q == p || q < 0) break;
+        p = q;
+    }
+    if (it == n) sg_flag(dev_err, 1);
+    L[i] = p + 1;
+}
+
+extern "C" int sgan_ccl_label(const float* plane, int64_t pix_stride, int32_t H, int32_t W, int32_t* labels, int32_t* dev_err, void* stream) {
+    SGAN_CHECK(plane && labels && dev_err, "null pointer");
+    SGAN_CHECK(H >= 1 && W >= 1 && (int64_t)H * W < (1ll << 30) && pix_stride >= 1, "bad shape %d x %d, pixel stride %lld", H, W,
+               (long long)pix_stride);
+    const dim3 tiles((W + SG_CCL_TW - 1) / SG_CCL_TW, (H + SG_CCL_TH - 1) / SG_CCL_TH);
+    SGAN_CHECK(tiles.y <= 65535, "more than 65535 tile rows");
+    const int n = H * W, nb = (n + 255) / 256;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(sg_ccl_tile_kernel, tiles, dim3(SG_CCL_THREADS), 0, st, plane, pix_stride, H, W, labels, dev_err);
+    SGAN_LAUNCH_CHECK();
+    if (tiles.x > 1 || tiles.y > 1) {
+        hipLaunchKernelGGL(sg_ccl_border_kernel, dim3(nb), dim3(256), 0, st, labels, H, W, dev_err);
+        SGAN_LAUNCH_CHECK();
+        hipLaunchKernelGGL(sg_ccl_flatten_kernel, dim3(nb), dim3(256), 0, st, labels, n, dev_err);
+        SGAN_LAUNCH_CHECK();
+    }
+    g_sgan_last_kernel = "sg_ccl_tile_kernel";
+    return SGAN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Rand F-score.  Workspace: [A2, B2, AB2, aux: 4 uint64][keys: slots uint64][cnt_a: np int32][cnt_b: np int32][cnt_ab: slots int32],
+// np = n + 1 rounded up to even, slots = the power of two >= max(2 n, 64).
+// ------------------------------------------------------------------------------------------------------------------------------
+struct SgRandLayout {
+    int64_t slots, np, bytes;
+    int log2_slots;
+};
+
+static SgRandLayout sg_rand_layout(int32_t H, int32_t W) {
+    SgRandLayout l;
+    const int64_t n = (int64_t)H * W;
+    l.log2_slots = 6;
+    while ((1ll << l.log2_slots) < 2 * n) ++l.log2_slots;
+    l.slots = 1ll << l.log2_slots;
+    l.np = (n + 2) & ~1ll;
+    l.bytes = 32 + 8 * l.slots + 4 * (2 * l.np + l.slots);      // a multiple of 16
+    return l;
+}
+
+__global__ __launch_bounds__(256) void sg_zero16_kernel(uint4* p, int64_t n16) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (int64_t)gridDim.x * 256) p[i] = make_uint4(0, 0, 0, 0);
+}
+
+__device__ __forceinline__ long long sg_wave_sum_i64(long long v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// n more pixels on a counter that held c:  (c + n)^2 - c^2
+__device__ __forceinline__ long long sg_square_growth(int c, int n) { return (2ll * c + n) * n; }
+
+// Lanes of one wave hold 64 consecutive pixels of a row.  `change`: this lane's value differs from its left neighbour's (lane 0: always;
+// the lanes past the row's end hold 0, so they end the row's last run).  Returns the length inside the wave of the run that starts
+// at this lane, or 0 when none starts here or `counted` is false.
+__device__ __forceinline__ int sg_run_length(bool change, bool counted, int lane) {
+    const unsigned long long changes = __ballot(change);
+    if (!change || !counted) return 0;
+    const unsigned long long later = lane == 63 ? 0ull : changes >> (lane + 1);
+    return later ? __builtin_ctzll(later) + 1 : 64 - lane;
+}
+
+// Lanes with len > 0 hold (key, len).  The lanes of one key elect their first lane, which gets the key's summed length; every other
+// lane gets 0.  A region that crosses the wave's 64 pixels several times (the one giant region of a percolating map crosses every
+// wave of the image) then costs one atomic per wave instead of one per run: on per-pixel noise the same-address atomics of that
+// region's counter were 94 % of the metric's time (kernel trace).  At most 64 rounds, one per distinct key.
+__device__ __forceinline__ int sg_wave_merge(unsigned long long key, int len, int lane) {
+    int total = 0;
+    bool pending = len > 0;
+    for (int it = 0; it < 64; ++it) {
+        const unsigned long long waiting = __ballot(pending);
+        if (waiting == 0) break;      // uniform
+        const int leader = __builtin_ctzll(waiting);
+        const unsigned lo = __shfl((unsigned)key, leader, 64), hi = __shfl((unsigned)(key >> 32), leader, 64);
+        const bool same = pending && key == (((unsigned long long)hi << 32) | lo);
+        int sum = same ? len : 0;
+        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+        if (same) {
+            pending = false;
+            if (lane == leader) total = sum;
+        }
+    }
+    return total;
+}
+
+__global__ __launch_bounds__(256) void sg_rand_count_kernel(const int32_t* __restrict__ T, const int32_t* __restrict__ S, int H, int W,
+                                                            unsigned long long* sums, unsigned long long* keys, int* cnt_a, int* cnt_b,
+                                                            int* cnt_ab, int log2_slots, int32_t* dev_err) {
+    const int lane = threadIdx.x & 63, segs = (W + 63) / 64;
+    const int64_t seg = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (seg >= (int64_t)H * segs) return;      // uniform over the wave
+    const int y = (int)(seg / segs), x = (int)(seg % segs) * 64 + lane;
+    const int n = H * W;
+    int t = 0, s = 0;       // a lane past the row's end looks like wall in both maps, and adds nothing
+    if (x < W) {
+        t = T[y * W + x];
+        s = S[y * W + x];
+        if (t < 0 || t > n || s < 0 || s > n) {
+            sg_flag(dev_err, 4);
+            t = s = 0;
+        }
+    }
+    const int tl = __shfl_up(t, 1, 64), sl = __shfl_up(s, 1, 64);
+    const bool first = lane == 0;
+    long long dA = 0, dB = 0, dAB = 0, aux = (t != 0 && s == 0) ? 1 : 0;
+    // a_i: runs of one truth label
+    int len = sg_wave_merge((unsigned)t, sg_run_length(first || tl != t, t != 0, lane), lane);
+    if (len) dA = sg_square_growth(atomicAdd(&cnt_a[t], len), len);
+    // b_j and c_ij: runs of one (truth, prediction) pair with both set.  Two neighbours that are both set in one map belong to one
+    // component there, so such a run ends only where one of the maps has wall: a run of the pair is a run of the prediction label too.
+    const bool both = t != 0 && s != 0;
+    const int run = sg_run_length(first || tl != t || sl != s, both, lane);
+    const unsigned long long key = ((unsigned long long)(unsigned)t << 32) | (unsigned)s;
+    len = sg_wave_merge((unsigned)s, run, lane);
+    if (len) dB = sg_square_growth(atomicAdd(&cnt_b[s], len), len);
+    len = sg_wave_merge(key, run, lane);
+    if (len) {
+        const unsigned long long mask = (1ull << log2_slots) - 1;
+        unsigned long long slot = (key * 0x9E3779B97F4A7C15ull) >> (64 - log2_slots);
+        int probe = 0;
+        for (; probe < SGAN_RAND_F_MAX_PROBE; ++probe) {
+            const unsigned long long seen = atomicCAS(&keys[slot], 0ull, key);      // t >= 1: a key is never 0
+            if (seen == 0ull || seen == key) break;
+            slot = (slot + 1) & mask;
+        }
+        if (probe < SGAN_RAND_F_MAX_PROBE) dAB = sg_square_growth(atomicAdd(&cnt_ab[slot], len), len);
+        else sg_flag(dev_err, 2);
+    }
+    dA = sg_wave_sum_i64(dA);
+    dB = sg_wave_sum_i64(dB);
+    dAB = sg_wave_sum_i64(dAB);
+    aux = sg_wave_sum_i64(aux);
+    if (lane == 0) {
+        if (dA) atomicAdd(&sums[0], (unsigned long long)dA);
+        if (dB) atomicAdd(&sums[1], (unsigned long long)dB);
+        if (dAB) atomicAdd(&sums[2], (unsigned long long)dAB);
+        if (aux) atomicAdd(&sums[3], (unsigned long long)aux);
+    }
+}
+
+__global__ void sg_rand_final_kernel(const unsigned long long* sums, double* acc, int64_t* sums_out, double* f_out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const unsigned long long A2 = sums[0], B2 = sums[1], AB2 = sums[2], aux = sums[3];
+    double f = __builtin_nan("");
+    if (A2 != 0 && B2 + aux != 0) {
+        const double num = (double)(AB2 + aux);
+        const double prec = num / (double)(B2 + aux), rec = num / (double)A2;
+        f = 2.0 / (1.0 / prec + 1.0 / rec);
+    }
+    acc[0] += f;
+    acc[1] += 1.0;
+    if (sums_out) {
+        sums_out[0] = (int64_t)A2;
+        sums_out[1] = (int64_t)B2;
+        sums_out[2] = (int64_t)AB2;
+        sums_out[3] = (int64_t)aux;
+    }
+    if (f_out) *f_out = f;
+}
+
+extern "C" int64_t sgan_rand_f_workspace(int32_t H, int32_t W) {
+    if (H < 1 || W < 1 || (int64_t)H * W >= (1ll << 30)) return sgan_fail(SGAN_ERR_INVALID, "bad shape %d x %d", H, W);
+    return sg_rand_layout(H, W).bytes;
+}
+
+extern "C" int sgan_rand_f_accumulate(const int32_t* t_labels, const int32_t* s_labels, int32_t H, int32_t W, void* workspace,
+                                      int64_t workspace_bytes, double* acc, int64_t* sums_out, double* f_out, int32_t* dev_err,
+                                      void* stream) {
+    SGAN_CHECK(t_labels && s_labels && workspace && acc && dev_err, "null pointer");
+    SGAN_CHECK(H >= 1 && W >= 1 && (int64_t)H * W < (1ll << 30), "bad shape %d x %d", H, W);
+    const SgRandLayout l = sg_rand_layout(H, W);
+    SGAN_CHECK(workspace_bytes >= l.bytes, "workspace of %lld bytes, %lld needed for %d x %d (sgan_rand_f_workspace); nothing was launched",
+               (long long)workspace_bytes, (long long)l.bytes, H, W);
+    SGAN_CHECK(((uintptr_t)workspace & 15) == 0, "workspace not 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* sums = (unsigned long long*)workspace;
+    unsigned long long* keys = sums + 4;
+    int* cnt_a = (int*)(keys + l.slots);
+    int* cnt_b = cnt_a + l.np;
+    int* cnt_ab = cnt_b + l.np;
+    const int64_t n16 = l.bytes / 16;
+    hipLaunchKernelGGL(sg_zero16_kernel, dim3((unsigned)((n16 + 255) / 256 < 2048 ? (n16 + 255) / 256 : 2048)), dim3(256), 0, st,
+                       (uint4*)workspace, n16);
+    SGAN_LAUNCH_CHECK();
+    const int64_t waves = (int64_t)H * ((W + 63) / 64);
+    SGAN_CHECK((waves + 3) / 4 < (1ll << 31), "too many rows");
+    hipLaunchKernelGGL(sg_rand_count_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, t_labels, s_labels, H, W, sums, keys,
+                       cnt_a, cnt_b, cnt_ab, l.log2_slots, dev_err);
+    SGAN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sg_rand_final_kernel, dim3(1), dim3(64), 0, st, sums, acc, sums_out, f_out);
+    SGAN_LAUNCH_CHECK();
+    g_sgan_last_kernel = "sg_rand_count_kernel";
+    return SGAN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Confusion matrix: a histogram of (truth, prediction) pairs, k <= 17 classes.  Per workgroup in LDS, then one 64-bit atomic add per
+// non-empty bin.
+// ------------------------------------------------------------------------------------------------------------------------------
+#define SG_CONF_MAX_K 17
+
+// argmax as torch.argmax: the first maximum, a NaN beats every number
+__device__ __forceinline__ void sg_argmax_step(float v, int c, float& best, int& arg) {
+    if (v > best || (v != v && best == best)) {
+        best = v;
+        arg = c;
+    }
+}
+
+__device__ __forceinline__ int sg_argmax_channels(const float* __restrict__ v, int C, bool add_background) {
+    float best = v[0], sum = v[0];
+    int arg = 0;
+    for (int c = 1; c < C; ++c) {
+        sg_argmax_step(v[c], c, best, arg);
+        sum += v[c];
+    }
+    if (add_background) sg_argmax_step(1.0f - (sum > 1.0f ? 1.0f : sum), C, best, arg);      // a NaN sum stays NaN, as torch.clamp
+    return arg;
+}
+
+__global__ __launch_bounds__(256) void sg_confusion_kernel(const float* __restrict__ x, int x_ld, int C, const int64_t* __restrict__ label,
+                                                           const float* __restrict__ y, int y_ld, int add_background, int64_t npix,
+                                                           unsigned long long* conf, int32_t* dev_err) {
+    __shared__ int hist[SG_CONF_MAX_K * SG_CONF_MAX_K];
+    const int k = C + (add_background ? 1 : 0);
+    for (int b = threadIdx.x; b < k * k; b += 256) hist[b] = 0;
+    SG_SYNC();      // hist[] zero
+    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < npix; p += (int64_t)gridDim.x * 256) {
+        const int pred = sg_argmax_channels(x + p * x_ld, C, add_background != 0);
+        int64_t truth = label ? label[p] : (int64_t)sg_argmax_channels(y + p * y_ld, C, add_background != 0);
+        if (truth < 0 || truth >= k) {
+            sg_flag(dev_err, 8);
+            continue;
+        }
+        atomicAdd(&hist[(int)truth * k + pred], 1);
+    }
+    SG_SYNC();      // hist[] complete
+    for (int b = threadIdx.x; b < k * k; b += 256)
+        if (hist[b]) atomicAdd(&conf[b], (unsigned long long)hist[b]);
+}
+
+extern "C" int sgan_confusion_accumulate(const float* x, int32_t x_ld, int32_t C, const int64_t* label, const float* y, int32_t y_ld,
+                                         int32_t add_background, int64_t npix, int64_t* conf, int32_t* dev_err, void* stream) {
+    SGAN_CHECK(x && conf && dev_err, "null pointer");
+    SGAN_CHECK((label != nullptr) != (y != nullptr), "exactly one of label and y");
+    SGAN_CHECK(C >= 1 && C <= 16 && x_ld >= C && (label || y_ld >= C), "C = %d (1..16), x_ld = %d, y_ld = %d", C, x_ld, y_ld);
+    SGAN_CHECK(npix >= 1 && npix < (1ll << 31), "npix = %lld", (long long)npix);      // a workgroup's int bins cannot overflow
+    const int64_t want = (npix + 255) / 256;
+    hipLaunchKernelGGL(sg_confusion_kernel, dim3((unsigned)(want < 512 ? want : 512)), dim3(256), 0, (hipStream_t)stream, x, x_ld, C, label,
+                       y, y_ld, add_background, npix, (unsigned long long*)conf, dev_err);
+    SGAN_LAUNCH_CHECK();
+    g_sgan_last_kernel = "sg_confusion_kernel";
+    return SGAN_OK;
+}

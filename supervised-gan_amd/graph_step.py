@@ -149,6 +149,17 @@ class GraphedStep:
         torch.cuda.synchronize()
         if self._prefetch:
             self._fake_last = m.fake      # the re-drawn sample of the step just finished: what `fake` is between steps
+        self._step_tensors = {k: v for k, v in vars(m).items() if torch.is_tensor(v)}
+
+    @property
+    def captured(self):
+        return self._captured
+
+    def reinstall(self):
+        """Point the trainer's tensor attributes at the captured step's tensors again.  An eager forward() between two replays (a
+        validation pass) leaves fake_B, logit, ... naming its own results, and a replay only writes the captured ones: call this
+        before the next step() so that whatever reads the attributes after it sees the step's results."""
+        vars(self.m).update(self._step_tensors)
 
     def _capture(self, fns, pool, mode="global"):
         g = torch.cuda.CUDAGraph()

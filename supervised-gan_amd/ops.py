@@ -890,3 +890,106 @@ def as_nhwc(t: torch.Tensor) -> torch.Tensor:
     L.check(L.lib().sgan_to_nhwc(_ptr(t), t.stride(1), t.stride(2), t.stride(3), H, W, Cr, _ptr(out), Cs, Cs, _stream()),
             "sgan_to_nhwc")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# Segmentation metrics (sgan_metrics.hip): labelling, Rand F-score sums, confusion matrix.  All three
+# only enqueue; `metric_err` is the one word the kernels raise when they had to give up on a pixel.
+# ------------------------------------------------------------------------------------------------
+_metric_err = {}
+_rand_ws = {}
+
+
+def metric_err(device):
+    """The zero-initialised int32 the metric kernels of `device` set nonzero on a bounded loop that ran out, a full pair table or a
+    label out of range (read it with check_metric_err when the results are read)."""
+    e = _metric_err.get(device.index)
+    if e is None:
+        e = _metric_err[device.index] = torch.zeros(1, dtype=torch.int32, device=device)
+    return e
+
+
+def check_metric_err(device):
+    """Synchronises.  Raises if a metric kernel flagged its result as incomplete since the last check."""
+    e = _metric_err.get(device.index)
+    code = int(e.item()) if e is not None else 0
+    if code:
+        e.zero_()
+        raise L.SganError(f"segmentation metric kernels gave up on part of their input (flags {code:#x}: 1 = union-find bound, "
+                          "2 = pair table full, 4 / 8 = label out of range); the accumulated values are incomplete")
+
+
+def _plane(t, what):
+    """A [H, W] fp32 view whose rows follow each other at the pixel stride (channel 0 of an NHWC buffer, or a contiguous map)."""
+    require_gpu(t, what)
+    assert t.dim() == 2 and t.dtype == torch.float32, (t.shape, t.dtype)
+    H, W = t.shape
+    if t.stride(1) < 1 or (H > 1 and t.stride(0) != W * t.stride(1)):
+        t = t.contiguous()
+    if (H * W - 1) * t.stride(1) + 1 > _avail(t):
+        raise L.SganError(f"{what}: plane {tuple(t.shape)} / {tuple(t.stride())} does not lie inside its storage; nothing was launched")
+    return t
+
+
+def ccl_label(plane, labels=None):
+    """8-connected components of the pixels of `plane` [H, W] that are NOT > 0.5 (sgan_ccl_label): int32 [H, W], 0 = wall, else
+    1 + the smallest raster index of the component.  `plane` is read in place when its rows are W pixel strides apart."""
+    plane = _plane(plane, "ccl_label")
+    H, W = plane.shape
+    if labels is None:
+        labels = torch.empty((H, W), dtype=torch.int32, device=plane.device)
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == H * W and labels.device == plane.device
+    L.check(L.lib().sgan_ccl_label(_ptr(plane), plane.stride(1), H, W, _ptr(labels), _ptr(metric_err(plane.device)), _stream()),
+            "sgan_ccl_label")
+    return labels
+
+
+def rand_f_workspace(H, W, device):
+    """The scratch of rand_f_accumulate for H x W maps, cached per (H, W, device); the kernels zero it themselves."""
+    key = (H, W, device.index)
+    ws = _rand_ws.get(key)
+    if ws is None:
+        nbytes = L.lib().sgan_rand_f_workspace(H, W)
+        if nbytes < 0:
+            raise L.SganError(f"sgan_rand_f_workspace({H}, {W}): {L.lib().sgan_last_error().decode()}")
+        ws = _rand_ws[key] = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
+    return ws
+
+
+def rand_f_accumulate(t_labels, s_labels, acc, sums_out=None, f_out=None, workspace=None):
+    """acc[0] += Rand F-score of the labelling s_labels (prediction) against t_labels (truth), acc[1] += 1 (sgan_rand_f_accumulate);
+    acc: float64[2] on the device.  sums_out (int64[4]: A2, B2, AB2, aux) and f_out (float64[1]) receive this pair's values."""
+    H, W = t_labels.shape
+    dev = t_labels.device
+    require_gpu(t_labels, "rand_f_accumulate")
+    for t in (t_labels, s_labels):
+        assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (H, W) and t.device == dev, (t.shape, t.dtype)
+    assert acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() == 2 and acc.device == dev
+    assert sums_out is None or (sums_out.dtype == torch.int64 and sums_out.is_contiguous() and sums_out.numel() == 4 and sums_out.device == dev)
+    assert f_out is None or (f_out.dtype == torch.float64 and f_out.numel() == 1 and f_out.device == dev)
+    ws = rand_f_workspace(H, W, dev) if workspace is None else workspace
+    L.check(L.lib().sgan_rand_f_accumulate(_ptr(t_labels), _ptr(s_labels), H, W, _ptr(ws), ws.numel() * ws.element_size(), _ptr(acc),
+                                           _ptr(sums_out), _ptr(f_out), _ptr(metric_err(dev)), _stream()), "sgan_rand_f_accumulate")
+
+
+def confusion_accumulate(x, C, conf, label=None, y=None, add_background=False):
+    """conf[truth, pred] += 1 per pixel (sgan_confusion_accumulate).  x, y: padded NHWC buffers [H, W, >= C]; pred = argmax of x's C
+    channels, truth = `label` (int64 map) or the argmax of y; add_background appends 1 - min(1, sum) as class C to both.
+    conf: int64 [k, k] on the device, k = C + add_background.
+    Equal to torch.argmax of the same maps; with add_background the fp32 sum is taken in channel order, which is torch's own
+    `sum(dim=1)` wherever that sum has one value (C <= 2, or sums that are exact) -- for C >= 3 and arbitrary floats torch's
+    reduction order is its own, and a pixel whose background value ties another class to the last bit may then fall differently."""
+    H, W, _ = _act(x).shape
+    require_gpu(x, "confusion_accumulate")
+    k = C + (1 if add_background else 0)
+    assert 1 <= C <= 16 and x.shape[2] >= C and (label is None) != (y is None)
+    assert conf.dtype == torch.int64 and conf.is_contiguous() and conf.numel() == k * k and conf.device == x.device
+    if (H * W - 1) * x.stride(1) + C > _avail(x):
+        raise L.SganError("confusion_accumulate: x does not lie inside its storage; nothing was launched")
+    if label is not None:
+        assert label.dtype == torch.int64 and label.is_contiguous() and label.numel() == H * W and label.device == x.device
+    else:
+        assert _act(y).shape[:2] == (H, W) and y.shape[2] >= C and y.device == x.device and (H * W - 1) * y.stride(1) + C <= _avail(y)
+    L.check(L.lib().sgan_confusion_accumulate(_ptr(x), x.stride(1), C, _ptr(label), _ptr(y), y.stride(1) if y is not None else 0,
+                                              int(bool(add_background)), H * W, _ptr(conf), _ptr(metric_err(x.device)), _stream()),
+            "sgan_confusion_accumulate")

@@ -64,6 +64,9 @@ class BaseOptions:
         a('--which_metric', default=['None'], nargs='+')
         a('--add_background_onehot', action='store_true')
         a('--add_background_onehot_acc', action='store_true')
+        a('--valSize', type=int, default=0)                   # train_ss.py: size of the validation images, 0 = loadSize (base_options.py:102)
+        a('--save_val_visuals', action='store_true')          # train_ss.py: write val/epochNNN/<name>_<label>.png
+        a('--best_metric', type=str, default='None')          # train_ss.py: keep a `best` checkpoint by this validation metric
         a('--upsample_mode', type=str, default='convt')
         a('--no_share_label_block_weights', action='store_true')
         a('--n_layers_CRN_block', type=int, default=1)

@@ -104,16 +104,22 @@ class SegmentationCycleModel(CGANCycleModel):
         CGANCycleModel.set_input(self, input)
         SegmentationModel._one_hot_label(self)
 
-    def forward(self):
-        """(:159-174)"""
+    def forward(self, val_mode=False):
+        """(:159-174); val_mode: G1's latent at --noiseSizeVal, as train_ss.py's validation pass asks for."""
         self.real_A, self.real_B = self.input_A, self.input_B
-        self.noise1, self.noise2 = self._draw(1).clone(), self._draw(2).clone()
+        self.noise1, self.noise2 = (self._draw_val() if val_mode else self._draw(1).clone()), self._draw(2).clone()
         self.logit = self.netG1.forward(self.real_A, self.noise1, activation=_identity)
         self.fake_B = torch.sigmoid(self.logit) if self.use_sigmoid_ss else softmax_channels(self.logit)
         self.fake_A = self.netG2.forward(self.real_B, self.noise2)
         self.recon_A = self.netG2.forward(self.fake_B, self.noise2)
 
     sample_noise = forward          # (:176-185) regenerates everything, fake_A included
+
+    def _draw_val(self):
+        o = self.opt
+        z = torch.empty((o.batchSize, o.noise_nc1, o.noiseSizeVal, o.noiseSizeVal), dtype=torch.float32, device=self.device)
+        ops.normal_fill(z, self._rng_seed + 977, self._rng_offset)
+        return z
 
     def test(self):
         with torch.no_grad():
@@ -194,7 +200,9 @@ class SegmentationCycleModel(CGANCycleModel):
         self.old_lr, self.old_lr1, self.old_lr2 = lr, lr1, lr2
 
     reset_accs = SegmentationModel.reset_accs
+    _acc_buffers = SegmentationModel._acc_buffers
     accum_accs = SegmentationModel.accum_accs
     compute_current_Rand_score = SegmentationModel.compute_current_Rand_score
     compute_current_accuracy = SegmentationModel.compute_current_accuracy
     get_current_accs = SegmentationModel.get_current_accs
+    compute_cross_entropy_loss = SegmentationModel.compute_cross_entropy_loss      # test_ss.py: sets loss_G_CE

@@ -11,10 +11,9 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import networks
+from . import networks, ops
 from .cgan_model import CGANModel
 from .losses import cross_entropy_logits, softmax_channels
-from .util import compute_Rand_F_scores
 
 
 def _identity(x):
@@ -57,14 +56,24 @@ class SegmentationModel(CGANModel):
             self.label = torch.empty_like(lab)        # persistent: a captured hipGraph keeps reading this buffer (label_, :61,138-139)
         self.label.copy_(lab)
 
-    def forward(self):
+    def forward(self, val_mode=False):
+        """val_mode: the validation pass of train_ss.py draws its latent at --noiseSizeVal (segm_model.py:145-155)."""
         self.real_A = self.input_A
         self.real_B = self.input_B
-        self.noise = self._draw_noise()
+        self.noise = self._draw_noise_val() if val_mode else self._draw_noise()
         self.logit = self.netG.forward(self.real_A, self.noise, activation=_identity)                 # :155
         self.fake_B = torch.sigmoid(self.logit) if self.use_sigmoid_ss else softmax_channels(self.logit)
 
     sample_noise = forward
+
+    def _draw_noise_val(self):
+        o = self.opt
+        if not hasattr(self.netG, 'noise_nc'):
+            return None
+        if getattr(self, 'noise_val_', None) is None:
+            self.noise_val_ = self.Tensor(o.batchSize, o.noise_nc, o.noiseSizeVal, o.noiseSizeVal)
+        ops.normal_fill(self.noise_val_, self._rng_seed + 977, self._rng_offset)
+        return self.noise_val_
 
     def test(self):
         with torch.no_grad():
@@ -106,9 +115,22 @@ class SegmentationModel(CGANModel):
                             ('prediction', three(self.fake_B.detach() * 2 - 1))])
 
     # ---- accuracy (segm_model.py:265-341) ---------------------------------------------------------------------------
+    # The accumulators live on the device: accum_accs() only enqueues kernels (sgan_metrics.hip) behind the step, so a training loop
+    # that accumulates after every step never waits for the GPU; get_current_accs() is the one place that synchronises and reads.
     def reset_accs(self):
         self.confusion, self.numAveragedPixels, self.numAveragedImages = 0, 0, 0
         self.pixelAcc = self.meanAcc = self.meanIU = self.RandScore = 0
+        for t in (getattr(self, '_acc_rand', None), getattr(self, '_acc_conf', None)):
+            if t is not None:
+                t.zero_()
+
+    def _acc_buffers(self):
+        if getattr(self, '_acc_rand', None) is None:
+            k = self.num_classes + 1 if self.opt.add_background_onehot_acc else self.num_classes
+            self._acc_rand = torch.zeros(2, dtype=torch.float64, device=self.device)          # sum of F, images
+            self._acc_conf = torch.zeros((k, k), dtype=torch.int64, device=self.device)       # [label, prediction]
+            self._acc_labels = None
+        return self._acc_rand, self._acc_conf
 
     def accum_accs(self):
         if 'RandScore' in self.opt.which_metric:
@@ -117,28 +139,49 @@ class SegmentationModel(CGANModel):
             self.compute_current_accuracy()
 
     def compute_current_Rand_score(self):
-        """Running mean of the Rand F-score of the predicted against the true boundary map (segm_model.py:299-307): a host metric
-        (connected components of a 512x512 map), computed on the CPU copy like the reference does."""
+        """Adds the Rand F-score (util.compute_Rand_F_scores, do_thin=False) of the predicted against the true boundary map to the
+        running sum on the device: two labellings, the contingency sums and the score itself are kernels on the current stream.
+
+        The score is taken on CHANNEL 0 of fake_B and real_B: the first picked label channel, the boundary map (the background
+        class of --add_background_onehot comes last).  The reference (segm_model.py:299-307) asserts num_classes == 2 and then hands
+        the whole 2-channel maps to a function that squeezes a channel axis of size one, which cannot run; this is our reading of
+        that call ("Segmentation metrics on the device").
+
+        Batch 1, like every kernel of this path.  An image whose truth map has no free pixel scores NaN, and the NaN stays in the
+        running sum until reset_accs(), as in the reference's running mean; nothing on the host sees it before get_current_accs()."""
         assert self.num_classes == 2      # binary segmentation only, as in the reference
-        RIs = compute_Rand_F_scores(self.fake_B.detach().cpu().numpy(), self.real_B.detach().cpu().numpy(), do_thin=False)
-        n = self.numAveragedImages
-        self.numAveragedImages = n + RIs.size
-        self.RandScore = (n * self.RandScore + RIs.sum()) / self.numAveragedImages
+        assert self.fake_B.shape[0] == 1, "the device metrics take batch 1, like every kernel of this path"
+        acc, _ = self._acc_buffers()
+        s, t = self.fake_B.detach()[0, 0], self.real_B.detach()[0, 0]
+        if self._acc_labels is None or self._acc_labels.shape[1:] != t.shape:
+            self._acc_labels = torch.empty((2,) + tuple(t.shape), dtype=torch.int32, device=self.device)
+        ops.ccl_label(t, self._acc_labels[0])
+        ops.ccl_label(s, self._acc_labels[1])
+        ops.rand_f_accumulate(self._acc_labels[0], self._acc_labels[1], acc)
 
     def compute_current_accuracy(self):
+        """conf[label, prediction] += 1 for every pixel, on the device (segm_model.py:309-331; the ratios are taken when the
+        accuracies are read)."""
+        _, conf = self._acc_buffers()
+        assert self.logit.shape[0] == 1, "the device metrics take batch 1, like every kernel of this path"
         if self.opt.add_background_onehot_acc:
-            bg = lambda t: torch.cat([t, 1.0 - torch.clamp(t.sum(dim=1, keepdim=True), max=1)], 1).argmax(dim=1)      # noqa: E731
-            labels, pred, k = bg(self.real_B), bg(self.fake_B.detach()), self.num_classes + 1
+            ops.confusion_accumulate(ops.as_nhwc(self.fake_B.detach()), self.num_classes, conf, y=ops.as_nhwc(self.real_B.detach()),
+                                     add_background=True)
         else:
-            labels, pred, k = self.label, self.logit.detach().argmax(dim=1), self.num_classes
-        conf = torch.bincount((labels.reshape(-1) * k + pred.reshape(-1)), minlength=k * k).reshape(k, k).double().cpu().numpy()
-        self.confusion = self.confusion + conf
-        self.numAveragedPixels += labels.numel()
-        rel, sel, tp = self.confusion.sum(axis=1), self.confusion.sum(axis=0), np.diag(self.confusion)
-        self.pixelAcc = tp.sum() / max(1, self.numAveragedPixels)
-        self.meanAcc = float(np.mean(tp / np.maximum(1, rel)))
-        self.meanIU = float(np.mean(tp / np.maximum(1, rel + sel - tp)))
+            ops.confusion_accumulate(ops.as_nhwc(self.logit.detach()), self.num_classes, conf, label=self.label)
 
     def get_current_accs(self):
+        """Reads the device accumulators (the only synchronisation of the metric path) and derives RandScore, pixelAcc, meanAcc and
+        meanIU from them."""
+        if getattr(self, '_acc_rand', None) is not None:
+            ops.check_metric_err(self.device)
+            rand, conf = self._acc_rand.cpu().numpy(), self._acc_conf.cpu().numpy().astype(np.float64)
+            self.numAveragedImages = int(rand[1])
+            self.RandScore = rand[0] / rand[1] if rand[1] else 0
+            self.confusion, self.numAveragedPixels = conf, int(conf.sum())
+            rel, sel, tp = conf.sum(axis=1), conf.sum(axis=0), np.diag(conf)
+            self.pixelAcc = tp.sum() / max(1, self.numAveragedPixels)
+            self.meanAcc = float(np.mean(tp / np.maximum(1, rel)))
+            self.meanIU = float(np.mean(tp / np.maximum(1, rel + sel - tp)))
         return OrderedDict(([('RandScore', self.RandScore)] if 'RandScore' in self.opt.which_metric else [])
                            + ([('meanIU', self.meanIU)] if 'meanIU' in self.opt.which_metric else []))

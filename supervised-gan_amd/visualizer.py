@@ -48,6 +48,14 @@ class Visualizer:
         with open(self.log_name, "a") as log_file:
             log_file.write('%s\n' % message)
 
+    def print_current_accs(self, epoch, i, accs, tag):
+        """One line of acc_log.txt beside loss_log.txt: the running accuracies of `tag` ('train' at a print interval, 'val' after an
+        epoch's validation pass).  Stands in for the reference's visdom accuracy panes (train_ss.py:83-85, :120)."""
+        message = '(%s, epoch: %d, iters: %d) ' % (tag, epoch, i) + ''.join('%s: %.6f ' % kv for kv in accs.items())
+        print(message)
+        with open(os.path.join(os.path.dirname(self.log_name), 'acc_log.txt'), "a") as log_file:
+            log_file.write('%s\n' % message)
+
     def save_images(self, webpage, visuals, image_path):
         """One header + one row of `<name>_<label>.png` on `webpage` (test.py's result page); returns the written paths."""
         image_dir = webpage.get_image_dir()
