@@ -631,6 +631,22 @@ int sgan_lbfgs_advance(sgan_lbfgs_state* state, int32_t J, int64_t n, float* x, 
  *   workspace serves any number of calls on one stream.  Counts are atomic adds indexed by label; the pair counts live in an
  *   open-addressing table of >= 2 H W slots with a probe bounded at SGAN_RAND_F_MAX_PROBE; a wave holds 64 pixels of a row and
  *   adds each key it meets once (runs collapsed, then equal keys merged across the wave).  The squares are summed as (c + n)^2 - c^2 at each add, in 64-bit integers: exact in any order.
+ * sgan_vinfo_workspace: bytes of the workspace sgan_vinfo_accumulate needs: the layout of sgan_rand_f_workspace, unchanged, and 32
+ *   bytes behind it (< 0: bad shape).
+ * sgan_vinfo_accumulate: the information-theoretic score that goes with the Rand F-score (V^Info of the ISBI-2012 segmentation
+ *   challenge), from the same label maps under the same conventions (truth wall left out, a pixel of a truth region on prediction
+ *   wall is a segment of its own), and from the SAME counting pass: zero, the count kernel of sgan_rand_f_accumulate, one reduction
+ *   over the counters it leaves in the workspace, one final thread.  With m = sum_i a_i and, over nonzero counts, natural log,
+ *     SA = sum_i a_i ln a_i,  SB = sum_j b_j ln b_j,  SAB = sum_ij c_ij ln c_ij   (singletons add 1 ln 1 = 0):
+ *     H_T = ln m - SA / m,  H_S = ln m - SB / m,  H_ST = ln m - SAB / m,  I = H_S + H_T - H_ST clamped to [0, min(H_S, H_T)],
+ *     VInfo = 2 I / (H_S + H_T),  split = I / H_S,  merge = I / H_T.
+ *   Degenerate cases come from the exact integers: m == 0 gives NaN; H_T is 0 iff A2 == m^2; H_S is 0 iff (aux == 0 and B2 == m^2)
+ *   or m == 1; both 0: VInfo = 1; one of them 0: VInfo = 0; split / merge are NaN when their own denominator is 0.
+ *   acc[0] += VInfo, acc[1] += 1.  acc_rand (optional, 2 doubles): acc_rand[0] += the Rand F-score of the pair, acc_rand[1] += 1 --
+ *   the value sgan_rand_f_accumulate adds, bit for bit (the same integers through the same expression).  parts_out (optional, 11
+ *   doubles): SA, SB, SAB, aux, m, H_S, H_T, I, VInfo, split, merge of this pair.  Workspace, dev_err, stream and capture as
+ *   sgan_rand_f_accumulate.  m and aux are exact; SA, SB, SAB are fp64 sums in an order that depends on scheduling (one wave-level
+ *   shuffle reduction, one fp64 atomic add per workgroup and sum), so they repeat to rounding (~H W 2^-53 relative), not to the bit.
  * sgan_confusion_accumulate: conf[truth * k + pred] += 1 per pixel, conf int64 [k * k], caller-owned.  pred = argmax over the C
  *   logical channels (C <= 16) of x at pixel stride x_ld; truth = label[p] (int64 map) when label is given, else the argmax of y in
  *   the same way.  add_background: class C = 1 - min(1, sum_c v_c) (fp32, summed in channel order) is appended to both channel
@@ -641,6 +657,9 @@ int sgan_ccl_label(const float* plane, int64_t pix_stride, int32_t H, int32_t W,
 int64_t sgan_rand_f_workspace(int32_t H, int32_t W);
 int sgan_rand_f_accumulate(const int32_t* t_labels, const int32_t* s_labels, int32_t H, int32_t W, void* workspace,
                            int64_t workspace_bytes, double* acc, int64_t* sums_out, double* f_out, int32_t* dev_err, void* stream);
+int64_t sgan_vinfo_workspace(int32_t H, int32_t W);
+int sgan_vinfo_accumulate(const int32_t* t_labels, const int32_t* s_labels, int32_t H, int32_t W, void* workspace,
+                          int64_t workspace_bytes, double* acc, double* acc_rand, double* parts_out, int32_t* dev_err, void* stream);
 int sgan_confusion_accumulate(const float* x, int32_t x_ld, int32_t C, const int64_t* label, const float* y, int32_t y_ld,
                               int32_t add_background, int64_t npix, int64_t* conf, int32_t* dev_err, void* stream);
 

@@ -142,6 +142,8 @@ SIGNATURES = {
     "sgan_ccl_label": [_P, _L, _I, _I, _P, _P, _P],
     "sgan_rand_f_workspace": [_I, _I],
     "sgan_rand_f_accumulate": [_P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _P],
+    "sgan_vinfo_workspace": [_I, _I],
+    "sgan_vinfo_accumulate": [_P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _P],
     "sgan_confusion_accumulate": [_P, _I, _I, _P, _P, _I, _I, _L, _P, _P, _P],
     "sgan_profile_enable": [_I],
     "sgan_profile_count": [],
@@ -149,7 +151,8 @@ SIGNATURES = {
     "sgan_profile_read": [_I, C.POINTER(C.c_char_p), C.POINTER(C.c_float)],
 }
 
-RESTYPES = {"sgan_image_resize_workspace": C.c_int64, "sgan_rand_f_workspace": C.c_int64}      # everything else returns an int status
+RESTYPES = {"sgan_image_resize_workspace": C.c_int64, "sgan_rand_f_workspace": C.c_int64,
+            "sgan_vinfo_workspace": C.c_int64}      # everything else returns an int status
 _lib = None
 
 

@@ -1,5 +1,5 @@
 // Segmentation metrics on the device (include/sgan_hip.h, "segmentation metrics"): connected-component labelling of a thresholded
-// boundary map, the Rand F-score of two such labellings, and the confusion matrix of two class maps.  The trainers call these after
+// boundary map, the Rand F-score and the information score (VInfo) of two such labellings, and the confusion matrix of two class maps.  The trainers call these after
 // every optimizer step; nothing is read back until the accuracies are asked for.
 //
 // These kernels are bound by latency and atomics, not by arithmetic.  Three rules hold throughout:
@@ -292,15 +292,22 @@ __global__ __launch_bounds__(256) void sg_rand_count_kernel(const int32_t* __res
     }
 }
 
-__global__ void sg_rand_final_kernel(const unsigned long long* sums, double* acc, int64_t* sums_out, double* f_out) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const unsigned long long A2 = sums[0], B2 = sums[1], AB2 = sums[2], aux = sums[3];
+// The F-score from the four integers; one expression for every kernel that reports it, so the same integers give the same bits.
+__device__ __forceinline__ double sg_rand_f_from_sums(unsigned long long A2, unsigned long long B2, unsigned long long AB2,
+                                                      unsigned long long aux) {
     double f = __builtin_nan("");
     if (A2 != 0 && B2 + aux != 0) {
         const double num = (double)(AB2 + aux);
         const double prec = num / (double)(B2 + aux), rec = num / (double)A2;
         f = 2.0 / (1.0 / prec + 1.0 / rec);
     }
+    return f;
+}
+
+__global__ void sg_rand_final_kernel(const unsigned long long* sums, double* acc, int64_t* sums_out, double* f_out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const unsigned long long A2 = sums[0], B2 = sums[1], AB2 = sums[2], aux = sums[3];
+    const double f = sg_rand_f_from_sums(A2, B2, AB2, aux);
     acc[0] += f;
     acc[1] += 1.0;
     if (sums_out) {
@@ -317,6 +324,27 @@ extern "C" int64_t sgan_rand_f_workspace(int32_t H, int32_t W) {
     return sg_rand_layout(H, W).bytes;
 }
 
+// The launches both scores share: zero `zero_bytes` of the workspace (the Rand layout, and whatever the caller keeps behind it), then
+// count.  Afterwards the workspace holds A2, B2, AB2, aux and every a_i, b_j, c_ij.
+static int sg_rand_count_launch(const int32_t* t_labels, const int32_t* s_labels, int32_t H, int32_t W, void* workspace,
+                                const SgRandLayout& l, int64_t zero_bytes, int32_t* dev_err, hipStream_t st) {
+    unsigned long long* sums = (unsigned long long*)workspace;
+    unsigned long long* keys = sums + 4;
+    int* cnt_a = (int*)(keys + l.slots);
+    int* cnt_b = cnt_a + l.np;
+    int* cnt_ab = cnt_b + l.np;
+    const int64_t n16 = zero_bytes / 16;
+    hipLaunchKernelGGL(sg_zero16_kernel, dim3((unsigned)((n16 + 255) / 256 < 2048 ? (n16 + 255) / 256 : 2048)), dim3(256), 0, st,
+                       (uint4*)workspace, n16);
+    SGAN_LAUNCH_CHECK();
+    const int64_t waves = (int64_t)H * ((W + 63) / 64);
+    SGAN_CHECK((waves + 3) / 4 < (1ll << 31), "too many rows");
+    hipLaunchKernelGGL(sg_rand_count_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, t_labels, s_labels, H, W, sums, keys,
+                       cnt_a, cnt_b, cnt_ab, l.log2_slots, dev_err);
+    SGAN_LAUNCH_CHECK();
+    return SGAN_OK;
+}
+
 extern "C" int sgan_rand_f_accumulate(const int32_t* t_labels, const int32_t* s_labels, int32_t H, int32_t W, void* workspace,
                                       int64_t workspace_bytes, double* acc, int64_t* sums_out, double* f_out, int32_t* dev_err,
                                       void* stream) {
@@ -327,23 +355,169 @@ extern "C" int sgan_rand_f_accumulate(const int32_t* t_labels, const int32_t* s_
                (long long)workspace_bytes, (long long)l.bytes, H, W);
     SGAN_CHECK(((uintptr_t)workspace & 15) == 0, "workspace not 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long* sums = (unsigned long long*)workspace;
-    unsigned long long* keys = sums + 4;
-    int* cnt_a = (int*)(keys + l.slots);
-    int* cnt_b = cnt_a + l.np;
-    int* cnt_ab = cnt_b + l.np;
-    const int64_t n16 = l.bytes / 16;
-    hipLaunchKernelGGL(sg_zero16_kernel, dim3((unsigned)((n16 + 255) / 256 < 2048 ? (n16 + 255) / 256 : 2048)), dim3(256), 0, st,
-                       (uint4*)workspace, n16);
-    SGAN_LAUNCH_CHECK();
-    const int64_t waves = (int64_t)H * ((W + 63) / 64);
-    SGAN_CHECK((waves + 3) / 4 < (1ll << 31), "too many rows");
-    hipLaunchKernelGGL(sg_rand_count_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, t_labels, s_labels, H, W, sums, keys,
-                       cnt_a, cnt_b, cnt_ab, l.log2_slots, dev_err);
-    SGAN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sg_rand_final_kernel, dim3(1), dim3(64), 0, st, sums, acc, sums_out, f_out);
+    const int rc = sg_rand_count_launch(t_labels, s_labels, H, W, workspace, l, l.bytes, dev_err, st);
+    if (rc != SGAN_OK) return rc;
+    hipLaunchKernelGGL(sg_rand_final_kernel, dim3(1), dim3(64), 0, st, (const unsigned long long*)workspace, acc, sums_out, f_out);
     SGAN_LAUNCH_CHECK();
     g_sgan_last_kernel = "sg_rand_count_kernel";
+    return SGAN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Information score (VInfo) from the counters the Rand count leaves behind.  Workspace: the Rand layout, then
+// [SA, SB, SAB: 3 double][m: 1 uint64] (SG_VINFO_TAIL bytes), zeroed with it.
+//   SA = sum_i a_i ln a_i,  SB = sum_j b_j ln b_j,  SAB = sum_ij c_ij ln c_ij,  m = sum_i a_i  (natural log, counts > 0)
+// cnt_a, cnt_b and cnt_ab follow each other in the workspace (np, np and slots int32; np is even and slots a multiple of 64, so the
+// three together are a whole number of 16-byte words starting on one): the reduce kernel reads them as ONE array of uint4 and tells
+// by its index which sum a counter belongs to.  cnt_a[0] and cnt_b[0] (wall) are never written and stay 0.
+// ------------------------------------------------------------------------------------------------------------------------------
+#define SG_VINFO_TAIL 32
+#define SG_VINFO_PARTS 11
+
+__device__ __forceinline__ void sg_vinfo_term(unsigned c, int64_t e, int64_t np, double& sa, double& sb, double& sab, long long& m) {
+    if (c == 0) return;
+    const double term = c > 1 ? (double)c * log((double)c) : 0.0;
+    if (e < np) {
+        sa += term;
+        m += c;
+    } else if (e < 2 * np) {
+        sb += term;
+    } else {
+        sab += term;
+    }
+}
+
+__device__ __forceinline__ double sg_wave_sum_f64(double v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// Latency-bound: ~4 H W counters, most of them 0, one 16-byte load per lane and trip; a word of four zeros costs nothing more.
+// The fp64 sums arrive in an order that depends on scheduling: SA, SB, SAB are reproducible to rounding (~H W 2^-53 relative), m exactly.
+__global__ __launch_bounds__(256) void sg_vinfo_reduce_kernel(const uint4* __restrict__ cnt, int64_t n16, int64_t np, double* vsum,
+                                                              unsigned long long* m_out) {
+    __shared__ double part[4][3];
+    __shared__ long long part_m[4];
+    double sa = 0.0, sb = 0.0, sab = 0.0;
+    long long m = 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (int64_t)gridDim.x * 256) {
+        const uint4 v = cnt[i];
+        if ((v.x | v.y | v.z | v.w) == 0) continue;
+        sg_vinfo_term(v.x, 4 * i, np, sa, sb, sab, m);
+        sg_vinfo_term(v.y, 4 * i + 1, np, sa, sb, sab, m);
+        sg_vinfo_term(v.z, 4 * i + 2, np, sa, sb, sab, m);
+        sg_vinfo_term(v.w, 4 * i + 3, np, sa, sb, sab, m);
+    }
+    sa = sg_wave_sum_f64(sa);
+    sb = sg_wave_sum_f64(sb);
+    sab = sg_wave_sum_f64(sab);
+    m = sg_wave_sum_i64(m);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        part[wave][0] = sa;
+        part[wave][1] = sb;
+        part[wave][2] = sab;
+        part_m[wave] = m;
+    }
+    SG_SYNC();      // the four waves' partial sums
+    if (threadIdx.x == 0) {
+        sa = (part[0][0] + part[1][0]) + (part[2][0] + part[3][0]);
+        sb = (part[0][1] + part[1][1]) + (part[2][1] + part[3][1]);
+        sab = (part[0][2] + part[1][2]) + (part[2][2] + part[3][2]);
+        m = part_m[0] + part_m[1] + part_m[2] + part_m[3];
+        if (sa != 0.0) atomicAdd(&vsum[0], sa);
+        if (sb != 0.0) atomicAdd(&vsum[1], sb);
+        if (sab != 0.0) atomicAdd(&vsum[2], sab);
+        if (m) atomicAdd(m_out, (unsigned long long)m);
+    }
+}
+
+// Which entropies are zero is decided from the integers: H_T = 0 iff truth is one region (A2 == m^2); H_S = 0 iff the prediction is
+// one region over all of it (no pixel on prediction wall and B2 == m^2) or there is one pixel.  m < 2^30, so m^2 is exact.
+__global__ void sg_vinfo_final_kernel(const unsigned long long* sums, const double* vsum, const unsigned long long* m_in, double* acc,
+                                      double* acc_rand, double* parts_out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const unsigned long long A2 = sums[0], B2 = sums[1], AB2 = sums[2], aux = sums[3], m = *m_in;
+    const double SA = vsum[0], SB = vsum[1], SAB = vsum[2], nan = __builtin_nan("");
+    double hs = nan, ht = nan, mi = nan, v = nan, split = nan, merge = nan;
+    if (m != 0) {
+        const double dm = (double)m, lnm = log(dm);
+        const bool ht_zero = A2 == m * m, hs_zero = (aux == 0 && B2 == m * m) || m == 1;
+        ht = ht_zero ? 0.0 : lnm - SA / dm;
+        hs = hs_zero ? 0.0 : lnm - SB / dm;
+        const double hst = lnm - SAB / dm, lim = hs < ht ? hs : ht;
+        mi = hs + ht - hst;
+        mi = mi < 0.0 ? 0.0 : mi;
+        mi = mi > lim ? lim : mi;
+        if (ht_zero && hs_zero) v = 1.0;
+        else if (ht_zero || hs_zero) v = 0.0;
+        else v = 2.0 * mi / (hs + ht);
+        if (!hs_zero) split = mi / hs;
+        if (!ht_zero) merge = mi / ht;
+    }
+    acc[0] += v;
+    acc[1] += 1.0;
+    if (acc_rand) {
+        acc_rand[0] += sg_rand_f_from_sums(A2, B2, AB2, aux);
+        acc_rand[1] += 1.0;
+    }
+    if (parts_out) {
+        parts_out[0] = SA;
+        parts_out[1] = SB;
+        parts_out[2] = SAB;
+        parts_out[3] = (double)aux;
+        parts_out[4] = (double)m;
+        parts_out[5] = hs;
+        parts_out[6] = ht;
+        parts_out[7] = mi;
+        parts_out[8] = v;
+        parts_out[9] = split;
+        parts_out[10] = merge;
+    }
+}
+
+extern "C" int64_t sgan_vinfo_workspace(int32_t H, int32_t W) {
+    if (H < 1 || W < 1 || (int64_t)H * W >= (1ll << 30)) return sgan_fail(SGAN_ERR_INVALID, "bad shape %d x %d", H, W);
+    return sg_rand_layout(H, W).bytes + SG_VINFO_TAIL;
+}
+
+// workgroups of the reduce kernel: enough to fill the device's CUs four deep, never more than the data has 16-byte words for
+static int64_t sg_vinfo_grid(int64_t n16) {
+    static int cus = 0;
+    if (cus == 0) {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
+            n = 256;
+        cus = n;
+    }
+    const int64_t want = (n16 + 255) / 256, cap = 4ll * cus;
+    return want < cap ? want : cap;
+}
+
+extern "C" int sgan_vinfo_accumulate(const int32_t* t_labels, const int32_t* s_labels, int32_t H, int32_t W, void* workspace,
+                                     int64_t workspace_bytes, double* acc, double* acc_rand, double* parts_out, int32_t* dev_err,
+                                     void* stream) {
+    SGAN_CHECK(t_labels && s_labels && workspace && acc && dev_err, "null pointer");
+    SGAN_CHECK(H >= 1 && W >= 1 && (int64_t)H * W < (1ll << 30), "bad shape %d x %d", H, W);
+    const SgRandLayout l = sg_rand_layout(H, W);
+    const int64_t need = l.bytes + SG_VINFO_TAIL;
+    SGAN_CHECK(workspace_bytes >= need, "workspace of %lld bytes, %lld needed for %d x %d (sgan_vinfo_workspace); nothing was launched",
+               (long long)workspace_bytes, (long long)need, H, W);
+    SGAN_CHECK(((uintptr_t)workspace & 15) == 0, "workspace not 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = sg_rand_count_launch(t_labels, s_labels, H, W, workspace, l, need, dev_err, st);
+    if (rc != SGAN_OK) return rc;
+    const unsigned long long* sums = (const unsigned long long*)workspace;
+    const uint4* cnt = (const uint4*)((const char*)workspace + 32 + 8 * l.slots);
+    double* vsum = (double*)((char*)workspace + l.bytes);
+    unsigned long long* m_sum = (unsigned long long*)(vsum + 3);
+    const int64_t n16 = (2 * l.np + l.slots) / 4;
+    hipLaunchKernelGGL(sg_vinfo_reduce_kernel, dim3((unsigned)sg_vinfo_grid(n16)), dim3(256), 0, st, cnt, n16, l.np, vsum, m_sum);
+    SGAN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sg_vinfo_final_kernel, dim3(1), dim3(64), 0, st, sums, (const double*)vsum, (const unsigned long long*)m_sum, acc,
+                       acc_rand, parts_out);
+    SGAN_LAUNCH_CHECK();
+    g_sgan_last_kernel = "sg_vinfo_reduce_kernel";
     return SGAN_OK;
 }
 

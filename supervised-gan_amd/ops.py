@@ -893,11 +893,13 @@ def as_nhwc(t: torch.Tensor) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------------
-# Segmentation metrics (sgan_metrics.hip): labelling, Rand F-score sums, confusion matrix.  All three
-# only enqueue; `metric_err` is the one word the kernels raise when they had to give up on a pixel.
+# Segmentation metrics (sgan_metrics.hip): labelling, Rand F-score sums, VInfo, confusion matrix.  All
+# of them only enqueue; `metric_err` is the one word the kernels raise when they had to give up on a pixel.
 # ------------------------------------------------------------------------------------------------
 _metric_err = {}
 _rand_ws = {}
+_vinfo_ws = {}
+VINFO_PARTS = ('SA', 'SB', 'SAB', 'aux', 'm', 'H_S', 'H_T', 'I', 'VInfo', 'split', 'merge')      # parts_out of vinfo_accumulate
 
 
 def metric_err(device):
@@ -970,6 +972,38 @@ def rand_f_accumulate(t_labels, s_labels, acc, sums_out=None, f_out=None, worksp
     ws = rand_f_workspace(H, W, dev) if workspace is None else workspace
     L.check(L.lib().sgan_rand_f_accumulate(_ptr(t_labels), _ptr(s_labels), H, W, _ptr(ws), ws.numel() * ws.element_size(), _ptr(acc),
                                            _ptr(sums_out), _ptr(f_out), _ptr(metric_err(dev)), _stream()), "sgan_rand_f_accumulate")
+
+
+def vinfo_workspace(H, W, device):
+    """The scratch of vinfo_accumulate for H x W maps (the Rand layout and the VInfo sums behind it), cached per (H, W, device)."""
+    key = (H, W, device.index)
+    ws = _vinfo_ws.get(key)
+    if ws is None:
+        nbytes = L.lib().sgan_vinfo_workspace(H, W)
+        if nbytes < 0:
+            raise L.SganError(f"sgan_vinfo_workspace({H}, {W}): {L.lib().sgan_last_error().decode()}")
+        ws = _vinfo_ws[key] = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
+    return ws
+
+
+def vinfo_accumulate(t_labels, s_labels, acc, acc_rand=None, parts_out=None, workspace=None):
+    """acc[0] += VInfo (the ISBI information score, include/sgan_hip.h) of the labelling s_labels (prediction) against t_labels
+    (truth), acc[1] += 1 (sgan_vinfo_accumulate); acc: float64[2] on the device.  acc_rand (float64[2]) receives what
+    rand_f_accumulate would add for the same pair, from the same counting pass; parts_out (float64[11], VINFO_PARTS) this pair's
+    values."""
+    H, W = t_labels.shape
+    dev = t_labels.device
+    require_gpu(t_labels, "vinfo_accumulate")
+    for t in (t_labels, s_labels):
+        assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (H, W) and t.device == dev, (t.shape, t.dtype)
+    for a in (acc, acc_rand):
+        assert a is None or (a.dtype == torch.float64 and a.is_contiguous() and a.numel() == 2 and a.device == dev)
+    assert acc is not None
+    assert parts_out is None or (parts_out.dtype == torch.float64 and parts_out.is_contiguous() and parts_out.numel() == len(VINFO_PARTS)
+                                 and parts_out.device == dev)
+    ws = vinfo_workspace(H, W, dev) if workspace is None else workspace
+    L.check(L.lib().sgan_vinfo_accumulate(_ptr(t_labels), _ptr(s_labels), H, W, _ptr(ws), ws.numel() * ws.element_size(), _ptr(acc),
+                                          _ptr(acc_rand), _ptr(parts_out), _ptr(metric_err(dev)), _stream()), "sgan_vinfo_accumulate")
 
 
 def confusion_accumulate(x, C, conf, label=None, y=None, add_background=False):

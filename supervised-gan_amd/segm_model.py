@@ -119,8 +119,8 @@ class SegmentationModel(CGANModel):
     # that accumulates after every step never waits for the GPU; get_current_accs() is the one place that synchronises and reads.
     def reset_accs(self):
         self.confusion, self.numAveragedPixels, self.numAveragedImages = 0, 0, 0
-        self.pixelAcc = self.meanAcc = self.meanIU = self.RandScore = 0
-        for t in (getattr(self, '_acc_rand', None), getattr(self, '_acc_conf', None)):
+        self.pixelAcc = self.meanAcc = self.meanIU = self.RandScore = self.VInfo = 0
+        for t in (getattr(self, '_acc_rand', None), getattr(self, '_acc_conf', None), getattr(self, '_acc_vinfo', None)):
             if t is not None:
                 t.zero_()
 
@@ -128,12 +128,15 @@ class SegmentationModel(CGANModel):
         if getattr(self, '_acc_rand', None) is None:
             k = self.num_classes + 1 if self.opt.add_background_onehot_acc else self.num_classes
             self._acc_rand = torch.zeros(2, dtype=torch.float64, device=self.device)          # sum of F, images
+            self._acc_vinfo = torch.zeros(2, dtype=torch.float64, device=self.device)         # sum of VInfo, images
             self._acc_conf = torch.zeros((k, k), dtype=torch.int64, device=self.device)       # [label, prediction]
             self._acc_labels = None
         return self._acc_rand, self._acc_conf
 
     def accum_accs(self):
-        if 'RandScore' in self.opt.which_metric:
+        if 'VInfo' in self.opt.which_metric:          # one labelling and one counting pass feed both scores
+            self.compute_current_VInfo(with_rand='RandScore' in self.opt.which_metric)
+        elif 'RandScore' in self.opt.which_metric:
             self.compute_current_Rand_score()
         if 'meanIU' in self.opt.which_metric:
             self.compute_current_accuracy()
@@ -149,15 +152,29 @@ class SegmentationModel(CGANModel):
 
         Batch 1, like every kernel of this path.  An image whose truth map has no free pixel scores NaN, and the NaN stays in the
         running sum until reset_accs(), as in the reference's running mean; nothing on the host sees it before get_current_accs()."""
+        acc, _ = self._acc_buffers()
+        t_labels, s_labels = self._label_boundary_maps()
+        ops.rand_f_accumulate(t_labels, s_labels, acc)
+
+    def _label_boundary_maps(self):
+        """Labels the regions of channel 0 of real_B and fake_B (truth, prediction) into the trainer's own label buffer."""
         assert self.num_classes == 2      # binary segmentation only, as in the reference
         assert self.fake_B.shape[0] == 1, "the device metrics take batch 1, like every kernel of this path"
-        acc, _ = self._acc_buffers()
+        self._acc_buffers()
         s, t = self.fake_B.detach()[0, 0], self.real_B.detach()[0, 0]
         if self._acc_labels is None or self._acc_labels.shape[1:] != t.shape:
             self._acc_labels = torch.empty((2,) + tuple(t.shape), dtype=torch.int32, device=self.device)
         ops.ccl_label(t, self._acc_labels[0])
         ops.ccl_label(s, self._acc_labels[1])
-        ops.rand_f_accumulate(self._acc_labels[0], self._acc_labels[1], acc)
+        return self._acc_labels[0], self._acc_labels[1]
+
+    def compute_current_VInfo(self, with_rand=False):
+        """Adds the information score (util.compute_VInfo_scores) of the same pair of maps, under the conventions of
+        compute_current_Rand_score, to its running sum on the device.  with_rand: the Rand F-score of the pair goes to ITS running
+        sum from the same call -- the counting pass is the expensive launch and both scores are functions of its counters, so asking
+        for both costs one labelling and one count; the value added is rand_f_accumulate's, bit for bit."""
+        t_labels, s_labels = self._label_boundary_maps()
+        ops.vinfo_accumulate(t_labels, s_labels, self._acc_vinfo, acc_rand=self._acc_rand if with_rand else None)
 
     def compute_current_accuracy(self):
         """conf[label, prediction] += 1 for every pixel, on the device (segm_model.py:309-331; the ratios are taken when the
@@ -171,17 +188,20 @@ class SegmentationModel(CGANModel):
             ops.confusion_accumulate(ops.as_nhwc(self.logit.detach()), self.num_classes, conf, label=self.label)
 
     def get_current_accs(self):
-        """Reads the device accumulators (the only synchronisation of the metric path) and derives RandScore, pixelAcc, meanAcc and
-        meanIU from them."""
+        """Reads the device accumulators (the only synchronisation of the metric path) and derives RandScore, VInfo, pixelAcc,
+        meanAcc and meanIU from them."""
         if getattr(self, '_acc_rand', None) is not None:
             ops.check_metric_err(self.device)
             rand, conf = self._acc_rand.cpu().numpy(), self._acc_conf.cpu().numpy().astype(np.float64)
-            self.numAveragedImages = int(rand[1])
+            vinfo = self._acc_vinfo.cpu().numpy()
+            self.numAveragedImages = int(max(rand[1], vinfo[1]))
             self.RandScore = rand[0] / rand[1] if rand[1] else 0
+            self.VInfo = vinfo[0] / vinfo[1] if vinfo[1] else 0
             self.confusion, self.numAveragedPixels = conf, int(conf.sum())
             rel, sel, tp = conf.sum(axis=1), conf.sum(axis=0), np.diag(conf)
             self.pixelAcc = tp.sum() / max(1, self.numAveragedPixels)
             self.meanAcc = float(np.mean(tp / np.maximum(1, rel)))
             self.meanIU = float(np.mean(tp / np.maximum(1, rel + sel - tp)))
         return OrderedDict(([('RandScore', self.RandScore)] if 'RandScore' in self.opt.which_metric else [])
+                           + ([('VInfo', self.VInfo)] if 'VInfo' in self.opt.which_metric else [])
                            + ([('meanIU', self.meanIU)] if 'meanIU' in self.opt.which_metric else []))

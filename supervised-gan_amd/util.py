@@ -1,5 +1,5 @@
 """Image and metric helpers of the drivers (util/util.py:15-28, :41-43, :86-128 of the reference): tensor -> uint8 image -> PNG,
-the Rand F-score of a binary segmentation."""
+the Rand F-score of a binary segmentation, and the information score (VInfo) that goes with it."""
 import os
 
 import numpy as np
@@ -58,3 +58,59 @@ def compute_Rand_F_scores(S, T, do_thin=False):
         prec, rec = sumAB2 / sumB2, sumAB2 / sumA2
         scores[k] = 2 / (1 / prec + 1 / rec)
     return scores
+
+
+def _xlogx_sum(counts):
+    """sum of c ln c over the nonzero entries of an integer array (fp64)."""
+    c = np.asarray(counts, dtype=np.float64).ravel()
+    c = c[c > 0]
+    return float((c * np.log(c)).sum())
+
+
+def compute_VInfo_parts(s, t):
+    """The terms of compute_VInfo_scores for one [H, W] pair, as a dict: SA, SB, SAB, aux, m, H_S, H_T, I, VInfo, split, merge."""
+    t_label = _label_false_regions(np.asarray(t) > 0.5).astype(np.int64)
+    s_label = _label_false_regions(np.asarray(s) > 0.5).astype(np.int64)
+    t_max, s_max = int(t_label.max()), int(s_label.max())
+    p = np.bincount((t_label * (s_max + 1) + s_label).ravel(), minlength=(t_max + 1) * (s_max + 1)).reshape(t_max + 1, s_max + 1)
+    p = p[1:, :]                                        # without the ground-truth wall row
+    a, b, c, aux = p.sum(axis=1), p[:, 1:].sum(axis=0), p[:, 1:], int(p[:, 0].sum())
+    m = int(a.sum())
+    nan = float('nan')
+    out = dict(SA=_xlogx_sum(a), SB=_xlogx_sum(b), SAB=_xlogx_sum(c), aux=float(aux), m=float(m), H_S=nan, H_T=nan, I=nan, VInfo=nan,
+               split=nan, merge=nan)
+    if m == 0:
+        return out
+    A2, B2 = int((a.astype(object) ** 2).sum()), int((b.astype(object) ** 2).sum())
+    ht_zero, hs_zero = A2 == m * m, (aux == 0 and B2 == m * m) or m == 1
+    ln_m = float(np.log(float(m)))
+    h_t = 0.0 if ht_zero else ln_m - out['SA'] / m
+    h_s = 0.0 if hs_zero else ln_m - out['SB'] / m
+    h_st = ln_m - out['SAB'] / m
+    info = min(max(h_s + h_t - h_st, 0.0), min(h_s, h_t))
+    if ht_zero and hs_zero:
+        v = 1.0
+    elif ht_zero or hs_zero:
+        v = 0.0
+    else:
+        v = 2.0 * info / (h_s + h_t)
+    out.update(H_S=h_s, H_T=h_t, I=info, VInfo=v, split=nan if hs_zero else info / h_s, merge=nan if ht_zero else info / h_t)
+    return out
+
+
+def compute_VInfo_scores(S, T, do_thin=False):
+    """Information-theoretic F-score (V^Info of the ISBI-2012 segmentation challenge) of prediction S against ground truth T per
+    image, under the conventions of compute_Rand_F_scores: both thresholded at 0.5, regions = 8-connected non-wall components, the
+    pixels on truth wall left out, a pixel of a truth region on prediction wall a segment of its own.  With a_i, b_j, c_ij the pixel
+    counts of truth region i, prediction region j (inside some truth region) and their intersection, and m = sum_i a_i:
+        H_T = ln m - sum_i a_i ln a_i / m,  H_S = ln m - sum_j b_j ln b_j / m,  H_ST = ln m - sum_ij c_ij ln c_ij / m
+    (singletons add 1 ln 1 = 0),  I = H_S + H_T - H_ST clamped to [0, min(H_S, H_T)],  VInfo = 2 I / (H_S + H_T).
+    Whether an entropy is exactly 0 is decided from the integer counts: m == 0 scores NaN, two single regions 1, one single region
+    against a split 0.  S, T: [N, 1, H, W] (or a single [H, W] pair).  The host yardstick of the device path
+    (sgan_vinfo_accumulate); the trainers do not call it."""
+    S, T = np.asarray(S), np.asarray(T)
+    if S.ndim == 2:
+        S, T = S.reshape((1, 1) + S.shape), T.reshape((1, 1) + T.shape)
+    if do_thin:
+        raise NotImplementedError("do_thin needs skimage.morphology.thin, which this image does not carry")
+    return np.array([compute_VInfo_parts(S[k].squeeze(axis=0), T[k].squeeze(axis=0))['VInfo'] for k in range(T.shape[0])])

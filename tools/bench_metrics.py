@@ -5,7 +5,10 @@ util.compute_Rand_F_scores on channel 0 + a bincount confusion matrix read back)
 step loop without accuracies, with the device path and with the host path after every step.
 
     python tools/bench_metrics.py [--steps 300] [--warmup 10] [--repeats 3] [--out profiles/r07_metrics.json]
-    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_metrics.py --metric_only 50
+    python tools/bench_metrics.py --metrics RandScore VInfo meanIU --compare RandScore meanIU --out profiles/r08_metrics.json
+        (`--metrics`: what accum_accs is asked for; `--compare`: a second metric set timed on the same tensors in the same run --
+        the cost of adding VInfo to RandScore is the difference of the two)
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_metrics.py --metric_only 50 [--metrics ...]
         (only the metric launches, on per-pixel noise maps: the per-kernel split of one accum_accs)
 
 Kernel time is taken with events around the queued kernels after a synchronise (warm-up excluded); the loops are wall time between
@@ -30,7 +33,7 @@ from supervised_gan_amd.graph_step import GraphedStep  # noqa: E402
 from supervised_gan_amd.models import create_model  # noqa: E402
 from supervised_gan_amd.options import TrainOptions  # noqa: E402
 from supervised_gan_amd.synthetic_data import SyntheticDataset  # noqa: E402
-from supervised_gan_amd.util import compute_Rand_F_scores  # noqa: E402
+from supervised_gan_amd.util import compute_Rand_F_scores, compute_VInfo_scores  # noqa: E402
 
 
 def host_accum(model, state):
@@ -51,22 +54,28 @@ def clocks():
         return ["rocm-smi not usable: %r" % (e,)]
 
 
-def metric_only(n_iter, n, dev):
-    """n_iter x (two labellings, the Rand sums, the confusion matrix) on per-pixel noise at wall density 0.5, nothing else: run
-    under a kernel trace for the per-launch split."""
+def metric_only(n_iter, n, dev, metrics=("RandScore", "meanIU")):
+    """n_iter x (two labellings, the Rand sums -- with VInfo among `metrics` the one call that feeds both scores --, the confusion
+    matrix) on per-pixel noise at wall density 0.5, nothing else: run under a kernel trace for the per-launch split."""
     g = torch.Generator().manual_seed(1)
     fb, rb = torch.rand(n, n, 4, generator=g).to(dev), torch.rand(n, n, 4, generator=g).to(dev)
     label = (rb[:, :, 0] < rb[:, :, 1]).long().reshape(-1).contiguous()
     labels = torch.empty((2, n, n), dtype=torch.int32, device=dev)
     acc, conf = torch.zeros(2, dtype=torch.float64, device=dev), torch.zeros((2, 2), dtype=torch.int64, device=dev)
+    acc_v = torch.zeros(2, dtype=torch.float64, device=dev)
     for _ in range(n_iter):
-        ops.ccl_label(rb[:, :, 0], labels[0])
-        ops.ccl_label(fb[:, :, 0], labels[1])
-        ops.rand_f_accumulate(labels[0], labels[1], acc)
-        ops.confusion_accumulate(fb, 2, conf, label=label)
+        if "RandScore" in metrics or "VInfo" in metrics:
+            ops.ccl_label(rb[:, :, 0], labels[0])
+            ops.ccl_label(fb[:, :, 0], labels[1])
+        if "VInfo" in metrics:
+            ops.vinfo_accumulate(labels[0], labels[1], acc_v, acc_rand=acc if "RandScore" in metrics else None)
+        elif "RandScore" in metrics:
+            ops.rand_f_accumulate(labels[0], labels[1], acc)
+        if "meanIU" in metrics:
+            ops.confusion_accumulate(fb, 2, conf, label=label)
     torch.cuda.synchronize()
     ops.check_metric_err(dev)
-    print("metric_only: %d iterations, mean F %.6f" % (n_iter, float(acc[0] / acc[1])))
+    print("metric_only: %d iterations, mean F %.6f, mean VInfo %.6f" % (n_iter, float(acc[0] / acc[1]), float(acc_v[0] / acc_v[1])))
 
 
 def stats(ms):
@@ -94,15 +103,17 @@ def main(argv=None):
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r07_metrics.json"))
+    ap.add_argument("--metrics", nargs="+", default=["RandScore", "meanIU"], help="--which_metric of the trainer")
+    ap.add_argument("--compare", nargs="+", default=None, help="a second metric set, timed on the same tensors (device kernels only)")
     a = ap.parse_args(argv)
     n = a.size
     if a.metric_only:
-        return metric_only(a.metric_only, n, torch.device("cuda", 0))
+        return metric_only(a.metric_only, n, torch.device("cuda", 0), a.metrics)
     with tempfile.TemporaryDirectory() as tmp:
         argv_m = ("--name bench_metrics --model segmentation --which_direction AtoB --dataset_mode aligned --fineSize %d "
                   "--which_model_netG unet_256 --ngf 32 --norm instance --which_channel b_rg --gpu_ids 0 --no_dropout --dataroot synthetic "
-                  "--manualSeed 4 --which_metric RandScore meanIU --which_model_netD n_layers --n_layers_D 3 --ndf 32 --scale_factor 1 "
-                  "--lambda_D 1.0 --weights 1 2 --no_lsgan --checkpoints_dir %s" % (n, tmp)).split()
+                  "--manualSeed 4 --which_metric %s --which_model_netD n_layers --n_layers_D 3 --ndf 32 --scale_factor 1 "
+                  "--lambda_D 1.0 --weights 1 2 --no_lsgan --checkpoints_dir %s" % (n, " ".join(a.metrics), tmp)).split()
         opt = TrainOptions().parse(argv_m, save=False, verbose=False)
         model = create_model(opt)
         data = list(SyntheticDataset(opt, 4))
@@ -114,14 +125,15 @@ def main(argv=None):
         torch.cuda.synchronize()
         dev = model.device
         out = {"clocks_before": clocks(), "size": n, "steps": a.steps, "warmup": a.warmup, "device": torch.cuda.get_device_name(0),
+               "metrics": a.metrics,
                "baseline": "parent commit's accum_accs (host): .cpu() + util.compute_Rand_F_scores on channel 0 + bincount confusion"}
 
         # ---- the metric alone, on the trainer's tensors and on a cell-like boundary map ------------------------------------------
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         trainer_maps = (model.fake_B, model.real_B)
-        for name, (fb, rb) in (("trainer_tensors_synthetic_noise", trainer_maps), ("cell_map", cell_maps(n, dev))):
-            model.fake_B, model.real_B = fb, rb
-            dev_ms, enq_ms, host_ms = [], [], []
+
+        def device_times():
+            dev_ms, enq_ms = [], []
             for i in range(a.warmup + a.steps):
                 torch.cuda.synchronize()
                 w0 = time.perf_counter()
@@ -133,6 +145,17 @@ def main(argv=None):
                 if i >= a.warmup:
                     dev_ms.append(e0.elapsed_time(e1))
                     enq_ms.append((w1 - w0) * 1e3)
+            return dev_ms, enq_ms
+
+        for name, (fb, rb) in (("trainer_tensors_synthetic_noise", trainer_maps), ("cell_map", cell_maps(n, dev))):
+            model.fake_B, model.real_B = fb, rb
+            host_ms = []
+            dev_ms, enq_ms = device_times()
+            compare = None
+            if a.compare:          # the same trainer asked for the other metric set, on the same tensors, back to back
+                model.opt.which_metric = a.compare
+                compare = {"metrics": a.compare, "device_kernels": stats(device_times()[0])}
+                model.opt.which_metric = a.metrics
             state = {"rand": [], "conf": np.zeros((2, 2))}
             for i in range(a.warmup + a.steps):
                 torch.cuda.synchronize()
@@ -143,9 +166,16 @@ def main(argv=None):
             model.reset_accs()
             model.accum_accs()
             got = model.get_current_accs()
-            assert abs(got["RandScore"] - state["rand"][-1]) < 1e-9, (got, state["rand"][-1])
+            if "RandScore" in got:
+                assert abs(got["RandScore"] - state["rand"][-1]) < 1e-9, (got, state["rand"][-1])
             out[name] = {"device_kernels": stats(dev_ms), "device_enqueue_host_side": stats(enq_ms), "host_path": stats(host_ms),
-                         "regions_truth": int(torch.unique(model._acc_labels[0]).numel()), "RandScore": float(got["RandScore"])}
+                         "regions_truth": int(torch.unique(model._acc_labels[0]).numel())}
+            out[name].update({k: float(v) for k, v in got.items()})
+            if "VInfo" in got:
+                want = float(compute_VInfo_scores(model.fake_B.detach()[0, 0].cpu().numpy(), model.real_B.detach()[0, 0].cpu().numpy())[0])
+                assert abs(got["VInfo"] - want) < 1e-9, (got, want)
+            if compare is not None:
+                out[name]["compare"] = compare
             print(name, json.dumps(out[name]))
         model.fake_B, model.real_B = trainer_maps
 

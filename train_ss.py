@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Training driver of the segmentation trainers (`--model segmentation`, `segmentation_cycle`) with the loop of the reference's
-train_ss.py: like train.py, plus the running accuracies (`--which_metric RandScore meanIU`) accumulated after EVERY optimizer step,
+train_ss.py: like train.py, plus the running accuracies (`--which_metric RandScore VInfo meanIU`) accumulated after EVERY optimizer step,
 a validation pass over `<dataroot>/val` after every epoch, and a `best` checkpoint kept by `--best_metric`.
 
     python train_ss.py --dataroot synthetic --name sgan_ss --model segmentation --which_direction AtoB --dataset_mode aligned \
