@@ -26,6 +26,15 @@ class BaseModel:
     def Tensor(self, *size):
         return torch.empty(*size, dtype=torch.float32, device=self.device)
 
+    def _own_rng_streams(self, *nets):
+        """Every network of a trainer with more than one generator draws from Philox keys of its own: the trainer's seed in the
+        low word, the net's position (1, 2, ...) in the high word.  The nets add small integers (level, block, stage) to their
+        key and each counts its own offset from 0, so without this two generators of equal shape would draw the same dropout
+        masks and noise on every step; the trainer's own latent keys (seed + small integer, high word 0) stay clear of all of them."""
+        for i, net in enumerate(nets, 1):
+            if net is not None:
+                net._rng_seed = ops.net_stream_seed(self._rng_seed, i)
+
     def _backward(self, loss):
         """loss.backward() with a cached unit gradient (autograd would launch a fill kernel for it on every call)."""
         one = getattr(self, '_grad_one', None)

@@ -51,6 +51,7 @@ class CGANCycleModel(BaseModel):
                                        n_layers_CRN_block=opt.n_layers_CRN_block2,
                                        share_label_weights=not opt.no_share_label_block_weights2,
                                        n_layers_G_skip=opt.n_layers_G2_skip, gpu_ids=self.gpu_ids)
+        self._own_rng_streams(self.netG1, self.netG2)
         if self.isTrain:
             assert (len(opt.scale_factor1) == len(opt.lambda_D1) == len(opt.n_layers_D1))
             # the reference's sample_noise (:140-146) does not regenerate fake_A: its second backward_G of a step walks a freed

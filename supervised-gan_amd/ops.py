@@ -518,6 +518,12 @@ def dropout_mask(mask, p, seed, offset_dev=None, advance=True):
                                       int(bool(advance)), _stream()), "sgan_dropout_mask")
 
 
+def net_stream_seed(seed, index):
+    """Philox key of the index-th network of a trainer seeded `seed`: the index goes into the high key word (k1), which the
+    `seed + small integer` keys of the trainer itself and of the tensors inside one network never reach."""
+    return (int(seed) + (int(index) << 32)) & (2 ** 64 - 1)
+
+
 def rng_advance(offset_dev, by):
     L.check(L.lib().sgan_rng_advance(_ptr(offset_dev), C.c_uint64(int(by)), _stream()), "sgan_rng_advance")
 

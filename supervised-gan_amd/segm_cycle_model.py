@@ -53,6 +53,7 @@ class SegmentationCycleModel(CGANCycleModel):
                                      n_layers_G_skip=getattr(opt, 'n_layers_G%s_skip' % k), gpu_ids=self.gpu_ids)
         self.netG1 = G(opt.input_nc, self.num_classes, '1')             # :63-69
         self.netG2 = G(self.num_classes, opt.input_nc, '2')             # :70-76
+        self._own_rng_streams(self.netG1, self.netG2)
         if self.isTrain:
             assert (len(opt.scale_factor2) == len(opt.lambda_D2) == len(opt.n_layers_D2))
             self.n_netD2 = len(opt.scale_factor2)

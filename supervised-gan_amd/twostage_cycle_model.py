@@ -68,6 +68,7 @@ class TwoStageCycleModel(BaseModel):
                                            gaussian_sigma=opt.gaussian_sigma, upsample_mode=opt.upsample_mode2,
                                            n_layers_CRN_block=opt.n_layers_CRN_block2,
                                            share_label_weights=not opt.no_share_label_block_weights2, gpu_ids=self.gpu_ids)
+        self._own_rng_streams(self.netG1, self.netG2, self.netF2)
         if 'bilinear' in opt.transform_1to2:
             sc = int(opt.transform_1to2.split('_')[1])
             if sc != 2:
