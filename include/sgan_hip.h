@@ -255,6 +255,22 @@ int sgan_softmax_fwd(const float* z, int32_t ld, int32_t npix, int32_t C, float*
 int sgan_softmax_bwd(const float* dp, int32_t dpld, const float* p, int32_t pld, int32_t npix, int32_t C, float* dz, int32_t dzld,
                      void* stream);
 
+/* ---- sigmoid over channels and weighted BCE (`--use_sigmoid_ss`, models/segm_model.py:155-160,216-236; <= 16 channels) --------
+ * sgan_sigmoid_nhwc_fwd / _bwd: p = sigmoid(z) over the C logical channels (padding channels of p: zeros); dz = dp * p (1 - p).
+ * sgan_bce_weighted_fwd: loss = mean over pixels and channels of w(pix) * BCE(p_c, t_c) (torch's log clamp at -100), with
+ *               w = 1 + sum_{i < nw} t_i * (class_w[i] - 1); nw = 0: unweighted.  `workspace`: SGAN_BCE_WEIGHTED_WS_BYTES of 8-byte
+ *               aligned device scratch, ZERO on first use; the ticket at its end is left at zero (no fill per call).
+ * sgan_bce_weighted_bwd: dp = gout[0] * w * (p - t) / max(p (1 - p), 1e-12) / (C * npix)   (padding channels of dp: zeros).
+ * Replaces torch.sigmoid, the narrow / mul / add loop that builds the weight map, and F.binary_cross_entropy(weight=). */
+#define SGAN_BCE_WEIGHTED_WS_BYTES 1024
+int sgan_sigmoid_nhwc_fwd(const float* z, int32_t ld, int32_t npix, int32_t C, float* p, int32_t pld, void* stream);
+int sgan_sigmoid_nhwc_bwd(const float* dp, int32_t dpld, const float* p, int32_t pld, int32_t npix, int32_t C, float* dz, int32_t dzld,
+                          void* stream);
+int sgan_bce_weighted_fwd(const float* p, int32_t pld, const float* t, int32_t tld, int32_t npix, int32_t C, const float* class_w,
+                          int32_t nw, float* loss_out, void* workspace, int64_t workspace_bytes, void* stream);
+int sgan_bce_weighted_bwd(const float* p, int32_t pld, const float* t, int32_t tld, int32_t npix, int32_t C, const float* class_w,
+                          int32_t nw, const float* gout, float* dp, int32_t dpld, void* stream);
+
 /* ---- backward pass of a one-channel stride-1 head (the PatchGAN logits conv, models/networks.py:832-835) in one launch: the job
  * lists of sgan_conv_dgrad_grouped and sgan_conv_wgrad_grouped for the SAME pass (wjobs may be NULL: input gradient only).  Returns 1
  * when the layer is not of that type (Conv2d, stride 1, k <= 4, stored Cout 4 / logical 1, Cin >= 64, no `accumulate`): the caller
@@ -385,6 +401,39 @@ typedef struct sgan_gan_loss_job {
 int sgan_gan_loss_multi_fwd(const sgan_gan_loss_job* jobs, int32_t n, int32_t mode, float* each_out, float* total_out,
                             void* workspace, int64_t workspace_bytes, void* stream);
 int sgan_gan_loss_multi_bwd(const sgan_gan_loss_job* jobs, int32_t n, int32_t mode, const float* gout, void* stream);
+
+/* ---- every factored-discriminator GAN-loss term of one backward pass at once -----------------------------
+ * Term i multiplies two discriminator maps before the criterion (models/twostage_factD_model.py:256-296,352-383, util.mul):
+ *   a1 = SIG1 ? sigmoid(l1) : l1  [h1, w1]      a2 = SIG2 ? sigmoid(l2) : l2  [H2, W2]      (channel 0 of NHWC maps)
+ *   u  = up == 2 ? bilinear x2 of a1 (align_corners = False, the taps of sgan_bilinear_up2_fwd) : a1          [hu, wu]
+ *   q  = u reflection-padded to [H2, W2] with left = floor(dW / 2), right = dW - left, bottom = floor(dH / 2), top = dH - bottom
+ *   p  = q * a2;  loss_i = mean(MSE ? (p - target_i)^2 : BCE(p, target_i) with torch's log clamp at -100)
+ *   total = sum_i weight_i * loss_i;  each_out[i] = loss_i.
+ * A forward job with a `dl1` and / or `dl2` buffer also gets d total / d l1, d total / d l2 for an upstream gradient of 1 (other
+ * stored channels 0); the backward entry point writes them for gout[0].  Either buffer may be NULL (a detached side).  The
+ * gradients are gathered, without float atomics: the same inputs give the same bits.
+ * Returns 1 and writes nothing ("not covered": the caller keeps its own composition) unless n <= 8, up is 1 or 2, hu <= H2,
+ * wu <= W2, every pad is smaller than the padded dimension of u (torch's reflect rule), and BCE comes with SIG1 and SIG2 both
+ * set (a raw score times a probability can leave [0, 1]).
+ * Replaces, per term: two nn.Sigmoid, nn.Upsample, F.pad(reflect), the product, the target fill, nn.BCELoss / nn.MSELoss and
+ * the sums and lambda factors around them, forward and backward. */
+#define SGAN_FACTD_SIG1 1
+#define SGAN_FACTD_SIG2 2
+#define SGAN_FACTD_MSE 4
+typedef struct sgan_factd_loss_job {
+    const float* l1; int32_t ld1; int32_t h1; int32_t w1;
+    const float* l2; int32_t ld2; int32_t H2; int32_t W2;
+    int32_t up;
+    float target; float weight;
+    float* dl1; int32_t dld1;      /* optional, forward and backward */
+    float* dl2; int32_t dld2;
+} sgan_factd_loss_job;
+/* `workspace`: SGAN_FACTD_LOSS_WS_BYTES of 8-byte aligned device scratch, ZERO on first use and owned by one stream at a time;
+ * the ticket counter at its end is left at zero, as with SGAN_GAN_LOSS_WS_BYTES -- one launch, no fill per call. */
+#define SGAN_FACTD_LOSS_WS_BYTES 2048
+int sgan_factd_loss_multi_fwd(const sgan_factd_loss_job* jobs, int32_t n, int32_t mode, float* each_out, float* total_out,
+                              void* workspace, int64_t workspace_bytes, void* stream);
+int sgan_factd_loss_multi_bwd(const sgan_factd_loss_job* jobs, int32_t n, int32_t mode, const float* gout, void* stream);
 
 /* ---- standalone nn.Sigmoid on channel 0 of a logits map (models/networks.py:836-837) --------
  * Only needed when a caller wants the probability map itself; the GAN loss above consumes logits. */

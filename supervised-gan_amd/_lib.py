@@ -9,6 +9,7 @@ LIB_PATH = os.environ.get("SGAN_HIP_LIB") or os.path.join(_HERE, "csrc", "libsga
 
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
 MATH_F32, MATH_BF16X3, MATH_BF16X1 = 0, 1, 2
+FACTD_SIG1, FACTD_SIG2, FACTD_MSE = 1, 2, 4
 CONV, CONVT = 0, 1
 
 
@@ -65,6 +66,13 @@ class GanLossJob(C.Structure):
                 ("dlogits", C.c_void_p), ("dld", C.c_int32)]
 
 
+class FactdLossJob(C.Structure):
+    _fields_ = [("l1", C.c_void_p), ("ld1", C.c_int32), ("h1", C.c_int32), ("w1", C.c_int32),
+                ("l2", C.c_void_p), ("ld2", C.c_int32), ("H2", C.c_int32), ("W2", C.c_int32),
+                ("up", C.c_int32), ("target", C.c_float), ("weight", C.c_float),
+                ("dl1", C.c_void_p), ("dld1", C.c_int32), ("dl2", C.c_void_p), ("dld2", C.c_int32)]
+
+
 class BnRunningDesc(C.Structure):
     _fields_ = [("stats", C.c_void_p), ("running_mean", C.c_void_p), ("running_var", C.c_void_p),
                 ("num_batches_tracked", C.c_void_p), ("C", C.c_int32), ("count", C.c_int32), ("sq_stride", C.c_int32),
@@ -116,6 +124,8 @@ SIGNATURES = {
     "sgan_gan_loss_bwd": [_P, _I, _I, _F, _I, _P, _P, _I, _P],
     "sgan_gan_loss_multi_fwd": [C.POINTER(GanLossJob), _I, _I, _P, _P, _P, C.c_int64, _P],
     "sgan_gan_loss_multi_bwd": [C.POINTER(GanLossJob), _I, _I, _P, _P],
+    "sgan_factd_loss_multi_fwd": [C.POINTER(FactdLossJob), _I, _I, _P, _P, _P, C.c_int64, _P],
+    "sgan_factd_loss_multi_bwd": [C.POINTER(FactdLossJob), _I, _I, _P, _P],
     "sgan_sigmoid_fwd": [_P, _I, _I, _P, _I, _P],
     "sgan_sigmoid_bwd": [_P, _I, _P, _I, _I, _P, _I, _P],
     "sgan_tanh_bwd": [_P, _P, _P, _L, _P],
@@ -135,6 +145,10 @@ SIGNATURES = {
     "sgan_ce_bwd": [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P],
     "sgan_softmax_fwd": [_P, _I, _I, _I, _P, _I, _P],
     "sgan_softmax_bwd": [_P, _I, _P, _I, _I, _I, _P, _I, _P],
+    "sgan_sigmoid_nhwc_fwd": [_P, _I, _I, _I, _P, _I, _P],
+    "sgan_sigmoid_nhwc_bwd": [_P, _I, _P, _I, _I, _I, _P, _I, _P],
+    "sgan_bce_weighted_fwd": [_P, _I, _P, _I, _I, _I, _P, _I, _P, _P, C.c_int64, _P],
+    "sgan_bce_weighted_bwd": [_P, _I, _P, _I, _I, _I, _P, _I, _P, _P, _I, _P],
     "sgan_normal_fill": [_P, _L, C.c_uint64, _P, _I, _P],
     "sgan_normal_fill_nhwc": [_P, _I, _I, _I, _I, C.c_uint64, _P, _I, _P],
     "sgan_normal_fill_nhwc_pair": [_P, _P, _I, _I, _I, _I, C.c_uint64, _P, _P, C.c_int64, _P],

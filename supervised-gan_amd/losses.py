@@ -1,5 +1,6 @@
 """Losses and small differentiable ops of the trainers on the MI355X path (models/networks.py:152-214 GANLoss / GANLossMultiClass /
-WeightedL1Loss; the (label, image) pair concat, BCE on rescaled tanh outputs, bilinear x2 upsampling): one kernel forward, one backward."""
+WeightedL1Loss; the (label, image) pair concat, BCE on rescaled tanh outputs, bilinear x2 upsampling, the factored-discriminator loss,
+the channel sigmoid and weighted BCE of `--use_sigmoid_ss`): one kernel forward, one backward."""
 from __future__ import annotations
 
 import math
@@ -131,6 +132,122 @@ class GANLoss(nn.Module):
                                      *[self._logits_of(i) for i in inputs])
 
 
+# ------------------------------------------------------------------------------------------------
+# factored discriminators (`--model twostage_factd`): D2_i's map times D1_i's, upsampled and reflection-padded (util.mul)
+# ------------------------------------------------------------------------------------------------
+def factd_pad_split(dH, dW):
+    """(left, right, top, bottom) of util.mul (util/util.py:140-144) for a map that is dH rows and dW columns short: the left and
+    the bottom take the floor of the half, the right and the top the remainder."""
+    pl, pb = int(dW / 2), int(dH / 2)
+    return pl, dW - pl, dH - pb, pb
+
+
+def factored_product(in1, in2):
+    """util.mul (util/util.py:131-145): in1 reflection-padded up to in2's size, times in2; the reference returns None when in1 is
+    the larger one."""
+    if in1.shape == in2.shape:
+        return in1 * in2
+    if not (in1.shape[2] <= in2.shape[2] and in1.shape[3] <= in2.shape[3]):
+        raise ValueError("twostage_factd: the upsampled D1 map %s is larger than D2's %s (the reference's util.mul returns None here); "
+                         "choose --n_layers_D1 / --n_layers_D2 so that it is not" % (tuple(in1.shape[2:]), tuple(in2.shape[2:])))
+    return F.pad(in1, factd_pad_split(in2.shape[2] - in1.shape[2], in2.shape[3] - in1.shape[3]), mode='reflect') * in2
+
+
+def factored_gan_loss_composed(l1s, l2s, targets, weights, up, sig1, sig2, mse):
+    """The factored terms as a composition of torch calls -- what the trainer ran before sgan_factd_loss_multi_fwd and what
+    factored_gan_loss still runs for a call the kernel does not cover: (total, each)."""
+    each = []
+    for l1, l2, t in zip(l1s, l2s, targets):
+        a1 = torch.sigmoid(l1) if sig1 else l1
+        a2 = torch.sigmoid(l2) if sig2 else l2
+        if up == 2:
+            a1 = F.interpolate(a1, scale_factor=2, mode='bilinear', align_corners=False)
+        pred = factored_product(a1, a2)
+        tgt = torch.full_like(pred, float(t))
+        each.append(F.mse_loss(pred, tgt) if mse else F.binary_cross_entropy(pred, tgt))
+    total = sum(e * float(w) for e, w in zip(each, weights))
+    return total, torch.stack([e.detach() for e in each])
+
+
+class _FactdNotCovered(Exception):
+    pass
+
+
+class _FactdLossMultiFn(torch.autograd.Function):
+    """total = sum_i w_i * crit(mul(transform(act(l1_i)), act(l2_i)), target_i) -- ONE kernel for all terms (<= 8), their finish and,
+    for every logits map that needs one, d total / d l for an upstream gradient of 1 (_GanLossMultiFn's contract).  backward()
+    hands those out as they are under the trainers' cached unit gradient and has the kernel's second entry point write them again
+    for any other upstream gradient.  `logits`: l1_0 .. l1_{n-1}, l2_0 .. l2_{n-1}."""
+
+    @staticmethod
+    def forward(ctx, targets, weights, mode, up, *logits):
+        n = len(logits) // 2
+        lbs = [ops.as_nhwc(l) for l in logits]
+        dev = logits[0].device
+        each = torch.empty(n, dtype=torch.float32, device=dev)
+        total = torch.empty((), dtype=torch.float32, device=dev)
+        ds = [torch.empty_like(lb) if need else None for lb, need in zip(lbs, ctx.needs_input_grad[4:])]
+        ctx.args = (lbs[:n], lbs[n:], [up] * n, targets, weights, mode)
+        if not ops.factd_loss_multi_fwd(*ctx.args, each, total, ds[:n], ds[n:]):
+            raise _FactdNotCovered()
+        ctx.ds = ds
+        ctx.mark_non_differentiable(each)
+        ctx.set_materialize_grads(False)      # or autograd zero-fills a gradient for `each` on every backward (one more launch)
+        return total, each
+
+    @staticmethod
+    def backward(ctx, gtotal, _geach):
+        ds = ctx.ds
+        if gtotal is None:
+            return (None,) * (4 + len(ds))
+        if not ops.is_unit_grad(gtotal) and any(d is not None for d in ds):
+            n = len(ds) // 2
+            ds = [torch.empty_like(d) if d is not None else None for d in ds]
+            ops.factd_loss_multi_bwd(*ctx.args, gtotal.contiguous().float(), ds[:n], ds[n:])
+        return (None, None, None, None) + tuple(ops.logical_view(d, 1) if d is not None else None for d in ds)
+
+
+def _factd_logits(out, use_lsgan):
+    """The logits behind a discriminator output: the output itself for lsgan, the tagged logits otherwise (GANLoss._logits_of)."""
+    if use_lsgan:
+        return out
+    logits = getattr(out, "_sgan_logits", None)
+    if logits is None and getattr(out, "_sgan_pending_sigmoid", False):
+        logits = out
+    if logits is None:
+        raise SganError("factored_gan_loss(use_lsgan=False) needs the output of a supervised_gan_amd discriminator built with "
+                        "use_sigmoid=True (it carries its logits); got a plain tensor")
+    return logits
+
+
+def factored_gan_loss(d1_outs, d2_outs, targets_are_real, weights, up=2, use_lsgan1=False, use_lsgan2=False):
+    """sum_i weights[i] * crit(util.mul(transform(D1 output i), D2 output i), target i) of the factored discriminators as ONE
+    autograd node and one launch (<= 8 terms): returns (total, each), `each` the unweighted terms for logging.
+
+    d1_outs / d2_outs: what the discriminators return under `fuse_sigmoid_into_loss` (tagged logits with use_sigmoid, raw scores
+    without); no stand-alone sigmoid is launched.  up: 1 or 2, the `--transform_1to2` step.  crit is BCE without lsgan2, MSE with
+    it.  A call the kernel does not cover (more than 8 terms, a pad as large as the map, BCE on anything but two probabilities,
+    tensors that are not batch-1 fp32 on the device) runs as the composition of torch calls; an upsampled D1 map larger than D2's
+    raises the ValueError of util.mul's None."""
+    l1s = [_factd_logits(o, use_lsgan1) for o in d1_outs]
+    l2s = [_factd_logits(o, use_lsgan2) for o in d2_outs]
+    assert len(l1s) == len(l2s) == len(targets_are_real) == len(weights) and len(l1s) >= 1
+    assert up in (1, 2), "--transform_1to2: None or bilinear_2"
+    for a, b in zip(l1s, l2s):
+        if a.shape[2] * up > b.shape[2] or a.shape[3] * up > b.shape[3]:
+            factored_product(a.new_empty((1, 1, a.shape[2] * up, a.shape[3] * up), device="meta"), b)       # raises
+    ts = [1.0 if r else 0.0 for r in targets_are_real]
+    ws = [float(w) for w in weights]
+    sig1, sig2, mse = not use_lsgan1, not use_lsgan2, bool(use_lsgan2)
+    on_dev = all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.shape[0] == 1 and t.shape[1] == 1 for t in l1s + l2s)
+    if on_dev:
+        try:
+            return _FactdLossMultiFn.apply(ts, ws, ops.factd_mode(sig1, sig2, mse), int(up), *l1s, *l2s)
+        except _FactdNotCovered:
+            pass
+    return factored_gan_loss_composed(l1s, l2s, ts, ws, up, sig1, sig2, mse)
+
+
 class _CEFn(torch.autograd.Function):
     """Class-weighted cross-entropy of a [1, C, H, W] logits map against an int64 label map [1, H, W] (or one class for every
     pixel): sgan_ce_fwd / sgan_ce_bwd.  The forward keeps nothing but the two fp64 sums; the backward recomputes the softmax."""
@@ -181,6 +298,69 @@ def softmax_channels(logits):
     no layout copy)."""
     assert logits.dim() == 4 and logits.shape[0] == 1 and logits.shape[1] <= 16, logits.shape
     return _SoftmaxFn.apply(logits)
+
+
+class _SigmoidChannelsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits):
+        zb = ops.as_nhwc(logits)
+        pb = torch.empty_like(zb)
+        ops.sigmoid_nhwc_fwd(zb, logits.shape[1], pb)
+        ctx.pb, ctx.C = pb, logits.shape[1]
+        return ops.logical_view(pb, logits.shape[1])
+
+    @staticmethod
+    def backward(ctx, g):
+        dz = torch.empty_like(ctx.pb)
+        ops.sigmoid_nhwc_bwd(ops.as_nhwc(g), ctx.pb, ctx.C, dz)
+        return ops.logical_view(dz, ctx.C)
+
+
+def _bce_envelope(t):
+    return t.is_cuda and t.dim() == 4 and t.shape[0] == 1 and t.shape[1] <= 16 and t.dtype == torch.float32
+
+
+def sigmoid_channels(logits):
+    """torch.sigmoid(logits) of a [1, C, H, W] map on the HIP kernel (`--use_sigmoid_ss`; NHWC-backed like softmax_channels, so
+    cat_pair reads it with no layout copy).  Anything else (a batch, C > 16, not fp32 on the device) goes to torch.sigmoid."""
+    if not _bce_envelope(logits):
+        return torch.sigmoid(logits)
+    return _SigmoidChannelsFn.apply(logits)
+
+
+class _WeightedBceFn(torch.autograd.Function):
+    """mean(w * BCE(p, t)) with w = 1 + sum_{i < nw} t_i (cw_i - 1) built inside the kernel; gradient w.r.t. p only."""
+
+    @staticmethod
+    def forward(ctx, p, t, cw, nw):
+        pb, tb = ops.as_nhwc(p), ops.as_nhwc(t)
+        loss = torch.empty((), dtype=torch.float32, device=p.device)
+        ops.bce_weighted_fwd(pb, tb, p.shape[1], cw, nw, loss)
+        ctx.pb, ctx.tb, ctx.cw, ctx.nw, ctx.C = pb, tb, cw, nw, p.shape[1]
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        dp = torch.empty_like(ctx.pb)
+        ops.bce_weighted_bwd(ctx.pb, ctx.tb, ctx.C, ctx.cw, ctx.nw, gout.contiguous().float(), dp)
+        return ops.logical_view(dp, ctx.C), None, None, None
+
+
+def weighted_bce(p, t, class_weights=None):
+    """F.binary_cross_entropy(p, t, weight=wm) with the weight map wm = 1 + sum_i t[:, i] * (class_weights[i] - 1) of the
+    segmentation trainers (models/segm_model.py:216-225) on the HIP kernel; class_weights None: unweighted.  `t` is a constant.
+    Outside the kernel's envelope (a batch, C > 16, not fp32 on the device) the torch calls run."""
+    t = t.detach()
+    nw = 0 if class_weights is None else int(class_weights.numel())
+    if not (_bce_envelope(p) and _bce_envelope(t) and p.shape == t.shape and nw <= p.shape[1]):
+        wm = None
+        if nw:
+            wm = torch.ones_like(t[:, :1])
+            for i in range(nw):
+                wm = wm + t.narrow(1, i, 1) * (class_weights[i] - 1.0)
+        return F.binary_cross_entropy(p, t, weight=wm)
+    cw = class_weights.detach().float().contiguous() if nw else None
+    return _WeightedBceFn.apply(p, t, cw, nw)
 
 
 class GANLossMultiClass(nn.Module):

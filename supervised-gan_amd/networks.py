@@ -26,8 +26,9 @@ from .discriminators import (DCGANDiscriminator, NLayerDiscriminator, NLayerDisc
                              matlab_style_gauss2D)
 from .generators import (AutoEncoder, CascadedRefinementNetwork, DCGANGenerator, FCGANGenerator, FCGANGeneratorStar,      # noqa: F401
                          ResnetGenerator, UnetGenerator)
-from .losses import (GANLoss, GANLossMultiClass, WeightedL1Loss, _CatPairFn, _GanLossFn, _GanLossMultiFn, bce_on_rescaled,      # noqa: F401
-                     bilinear_upsample2x, cat_pair)
+from .losses import (GANLoss, GANLossMultiClass, WeightedL1Loss, _CatPairFn, _FactdLossMultiFn, _GanLossFn, _GanLossMultiFn,      # noqa: F401
+                     bce_on_rescaled, bilinear_upsample2x, cat_pair, factored_gan_loss, factored_product, sigmoid_channels,
+                     weighted_bce)
 
 
 def weights_init(m):

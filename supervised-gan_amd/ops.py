@@ -711,6 +711,96 @@ def gan_loss_multi_bwd(logits, targets, weights, mode, gout, dlogits):
     L.check(L.lib().sgan_gan_loss_multi_bwd(arr, len(logits), mode, _ptr(gout), _stream()), "sgan_gan_loss_multi_bwd")
 
 
+FACTD_LOSS_WS_BYTES = 2048   # SGAN_FACTD_LOSS_WS_BYTES
+_factd_ws = {}
+
+
+def _factd_loss_workspace(device):
+    """Zero-initialised once per device and left zeroed by the kernel, like _gan_loss_workspace (main stream only)."""
+    ws = _factd_ws.get(device.index)
+    if ws is None:
+        ws = _factd_ws[device.index] = torch.zeros(FACTD_LOSS_WS_BYTES // 8, dtype=torch.float64, device=device)
+    return ws
+
+
+def factd_mode(sig1, sig2, mse):
+    return (L.FACTD_SIG1 if sig1 else 0) | (L.FACTD_SIG2 if sig2 else 0) | (L.FACTD_MSE if mse else 0)
+
+
+def _factd_jobs(l1s, l2s, ups, targets, weights, dl1s, dl2s):
+    """The C ABI sees raw pointers: every map is checked against its storage here, before anything is launched."""
+    n = len(l1s)
+    arr = (L.FactdLossJob * n)()
+    for i in range(n):
+        a, b = l1s[i], l2s[i]
+        d1 = dl1s[i] if dl1s is not None else None
+        d2 = dl2s[i] if dl2s is not None else None
+        _fits(a, a.shape[0], a.shape[1], 1, "factd_loss l1")
+        _fits(b, b.shape[0], b.shape[1], 1, "factd_loss l2")
+        if d1 is not None:
+            _fits(d1, a.shape[0], a.shape[1], d1.shape[2], "factd_loss dl1")
+            assert d1.shape[:2] == a.shape[:2] and d1.is_contiguous()
+        if d2 is not None:
+            _fits(d2, b.shape[0], b.shape[1], d2.shape[2], "factd_loss dl2")
+            assert d2.shape[:2] == b.shape[:2] and d2.is_contiguous()
+        arr[i] = L.FactdLossJob(_ptr(a).value, a.stride(1), a.shape[0], a.shape[1], _ptr(b).value, b.stride(1), b.shape[0], b.shape[1],
+                                int(ups[i]), float(targets[i]), float(weights[i]),
+                                _ptr(d1).value if d1 is not None else None, d1.stride(1) if d1 is not None else 0,
+                                _ptr(d2).value if d2 is not None else None, d2.stride(1) if d2 is not None else 0)
+    return arr
+
+
+def factd_loss_multi_fwd(l1s, l2s, ups, targets, weights, mode, each_out, total_out, dl1s=None, dl2s=None):
+    """sgan_factd_loss_multi_fwd on lists of NHWC logits buffers [h, w, Cs] (channel 0 is read).  dl1s / dl2s: optional lists whose
+    entries (buffers or None) receive d total / d l for an upstream gradient of 1.  Returns False, having launched nothing, when
+    the library reports the call as not covered."""
+    arr = _factd_jobs(l1s, l2s, ups, targets, weights, dl1s, dl2s)
+    ws = _factd_loss_workspace(each_out.device)
+    rc = L.lib().sgan_factd_loss_multi_fwd(arr, len(l1s), int(mode), _ptr(each_out), _ptr(total_out), _ptr(ws), FACTD_LOSS_WS_BYTES, _stream())
+    if rc == 1:
+        return False
+    L.check(rc, "sgan_factd_loss_multi_fwd")
+    return True
+
+
+def factd_loss_multi_bwd(l1s, l2s, ups, targets, weights, mode, gout, dl1s, dl2s):
+    arr = _factd_jobs(l1s, l2s, ups, targets, weights, dl1s, dl2s)
+    L.check(L.lib().sgan_factd_loss_multi_bwd(arr, len(l1s), int(mode), _ptr(gout), _stream()), "sgan_factd_loss_multi_bwd")
+
+
+def sigmoid_nhwc_fwd(z, Creal, p):
+    H, W, _ = z.shape
+    L.check(L.lib().sgan_sigmoid_nhwc_fwd(_ptr(_act(z)), z.stride(1), H * W, Creal, _ptr(_act(p)), p.stride(1), _stream()), "sgan_sigmoid_nhwc_fwd")
+
+
+def sigmoid_nhwc_bwd(dp, p, Creal, dz):
+    H, W, _ = p.shape
+    L.check(L.lib().sgan_sigmoid_nhwc_bwd(_ptr(_act(dp)), dp.stride(1), _ptr(_act(p)), p.stride(1), H * W, Creal, _ptr(_act(dz)),
+                                          dz.stride(1), _stream()), "sgan_sigmoid_nhwc_bwd")
+
+
+BCE_WEIGHTED_WS_BYTES = 1024   # SGAN_BCE_WEIGHTED_WS_BYTES
+_bcew_ws = {}
+
+
+def bce_weighted_fwd(p, t, Creal, class_w, nw, loss_out):
+    """Weighted BCE of two [H, W, Cs] buffers (sgan_bce_weighted_fwd); class_w: device float vector of >= nw entries, or None."""
+    H, W, _ = p.shape
+    assert t.shape[:2] == (H, W) and (nw == 0 or class_w.numel() >= nw)
+    ws = _bcew_ws.get(p.device.index)
+    if ws is None:      # zero once; the kernel leaves its ticket at zero
+        ws = _bcew_ws[p.device.index] = torch.zeros(BCE_WEIGHTED_WS_BYTES // 8, dtype=torch.float64, device=p.device)
+    L.check(L.lib().sgan_bce_weighted_fwd(_ptr(_act(p)), p.stride(1), _ptr(_act(t)), t.stride(1), H * W, Creal, _ptr(class_w), int(nw),
+                                          _ptr(loss_out), _ptr(ws), BCE_WEIGHTED_WS_BYTES, _stream()), "sgan_bce_weighted_fwd")
+
+
+def bce_weighted_bwd(p, t, Creal, class_w, nw, gout, dp):
+    H, W, _ = p.shape
+    assert t.shape[:2] == (H, W) and dp.shape[:2] == (H, W)
+    L.check(L.lib().sgan_bce_weighted_bwd(_ptr(_act(p)), p.stride(1), _ptr(_act(t)), t.stride(1), H * W, Creal, _ptr(class_w), int(nw),
+                                          _ptr(gout), _ptr(_act(dp)), dp.stride(1), _stream()), "sgan_bce_weighted_bwd")
+
+
 def sigmoid_fwd(x, p):
     H, W, _ = x.shape
     L.check(L.lib().sgan_sigmoid_fwd(_ptr(_act(x)), x.stride(1), H * W, _ptr(_act(p)), p.stride(1), _stream()), "sgan_sigmoid_fwd")

@@ -3,17 +3,16 @@ real_A -> U-Net -> logits -> softmax (or `--use_sigmoid_ss` sigmoid) = the "fake
 cat(real_A, .); generator loss = sum_i lambda_i GAN(D_i(fake), 1) + (class-weighted) cross-entropy against the label.
 
 Built on CGANModel: discriminator step, pooling, optimizers, checkpoints and the hipGraph step are inherited; the generator runs
-with the caller's `activation=` (identity) so the conv chain ends raw, and softmax / cross-entropy are PyTorch's own kernels on
-the num_classes x H x W maps (models/loss.py:6-12 is NLLLoss2d(log_softmax))."""
+with the caller's `activation=` (identity) so the conv chain ends raw; softmax / cross-entropy (models/loss.py:6-12 is
+NLLLoss2d(log_softmax)) and the sigmoid / weighted BCE of `--use_sigmoid_ss` are kernels of losses.py on the num_classes x H x W maps."""
 from collections import OrderedDict
 
 import numpy as np
 import torch
-import torch.nn.functional as F
 
 from . import networks, ops
 from .cgan_model import CGANModel
-from .losses import cross_entropy_logits, softmax_channels
+from .losses import cross_entropy_logits, sigmoid_channels, softmax_channels, weighted_bce
 
 
 def _identity(x):
@@ -62,7 +61,7 @@ class SegmentationModel(CGANModel):
         self.real_B = self.input_B
         self.noise = self._draw_noise_val() if val_mode else self._draw_noise()
         self.logit = self.netG.forward(self.real_A, self.noise, activation=_identity)                 # :155
-        self.fake_B = torch.sigmoid(self.logit) if self.use_sigmoid_ss else softmax_channels(self.logit)
+        self.fake_B = sigmoid_channels(self.logit) if self.use_sigmoid_ss else softmax_channels(self.logit)
 
     sample_noise = forward
 
@@ -82,12 +81,7 @@ class SegmentationModel(CGANModel):
     # ---- losses -------------------------------------------------------------------------------
     def compute_cross_entropy_loss(self, weighted=False):
         if self.use_sigmoid_ss:                                                                           # :216-225, :235-236
-            wm = None
-            if weighted and self.class_weights is not None:
-                wm = torch.ones_like(self.real_B[:, :1])
-                for i in range(self.class_weights.numel()):
-                    wm = wm + self.real_B.narrow(1, i, 1) * (self.class_weights[i] - 1.0)
-            self.loss_G_CE = F.binary_cross_entropy(self.fake_B, self.real_B, weight=wm)
+            self.loss_G_CE = weighted_bce(self.fake_B, self.real_B, self.class_weights if weighted else None)      # sgan_bce_weighted_*
         else:
             w = self.class_weights if (weighted or self.isTrain) else None
             self.loss_G_CE = cross_entropy_logits(self.logit, self.label, 0, w)      # models/loss.py:6-12 on the HIP kernel

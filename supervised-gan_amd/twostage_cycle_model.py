@@ -411,8 +411,9 @@ class TwoStageFactDModel(TwoStageModel):
     """TwoStageModel of models/twostage_factD_model.py (`--model twostage_factd`): the image discriminators are factored -- every D2_i
     prediction is multiplied by the prediction of D1_i on the half-size label, upsampled x2 (`transform`) and reflection-padded to
     D2_i's map size (util.mul, util/util.py:131-145) -- in the D2 step (:256-296) and in the generators' GAN term (:352-383).
-    The products are formed on probabilities (or raw lsgan scores), so these terms run un-fused: one discriminator call each, the
-    upsample / pad / product / loss on PyTorch's kernels over the 35 x 35-sized maps."""
+    All terms of a backward pass go through networks.factored_gan_loss: the D1 calls and the D2 calls run grouped
+    (networks.multi_forward) and hand their logits to one launch of sgan_factd_loss_multi_fwd, which forms the products, the
+    criterion, the weighted sum and the gradients towards both discriminators."""
 
     def name(self):
         return 'TwoStageFactDModel'
@@ -423,37 +424,18 @@ class TwoStageFactDModel(TwoStageModel):
         if self.isTrain:
             assert self.n_netD1 == self.n_netD2, "factored discriminators come in (D1_i, D2_i) pairs"
 
-    @staticmethod
-    def _mul(in1, in2):
-        """util.mul (util/util.py:131-145): in1 reflection-padded up to in2's size; the reference returns None when in1 is larger."""
-        if in1.shape == in2.shape:
-            return in1 * in2
-        if not (in1.shape[2] <= in2.shape[2] and in1.shape[3] <= in2.shape[3]):
-            raise ValueError("twostage_factd: the upsampled D1 map %s is larger than D2's %s (the reference's util.mul returns None here); "
-                             "choose --n_layers_D1 / --n_layers_D2 so that it is not" % (tuple(in1.shape[2:]), tuple(in2.shape[2:])))
-        pl, pb = int((in2.shape[3] - in1.shape[3]) / 2), int((in2.shape[2] - in1.shape[2]) / 2)
-        pr, pt = in2.shape[3] - in1.shape[3] - pl, in2.shape[2] - in1.shape[2] - pb
-        return F.pad(in1, (pl, pr, pt, pb), mode='reflect') * in2
-
-    def _plain(self, netD, x):
-        """One discriminator call returning probabilities (--no_lsgan) or raw scores, never the logits-tagged fused form."""
-        fused, netD.fuse_sigmoid_into_loss = netD.fuse_sigmoid_into_loss, False
-        try:
-            return netD.forward(x)
-        finally:
-            netD.fuse_sigmoid_into_loss = fused
-
-    def _factored(self, i, label, pair):
-        p1 = F.interpolate(self._plain(self.netD1[i], label), scale_factor=2, mode='bilinear', align_corners=False)      # self.transform
-        return self._mul(p1, self._plain(self.netD2[i], pair))
-
-    def _crit(self, pred, real):
-        if self.opt.no_lsgan2:
-            return F.binary_cross_entropy(pred, torch.full_like(pred, 1.0 if real else 0.0))
-        return F.mse_loss(pred, torch.full_like(pred, 1.0 if real else 0.0))
+    def _factd_loss(self, terms, weights):
+        """terms: [(i, label, pair, target_is_real)] -> (sum_k weights[k] * crit(mul(transform(D1_i(label)), D2_i(pair)), target), each)
+        for <= 8 terms: two grouped discriminator walks and one loss launch."""
+        o = self.opt
+        d1 = networks.multi_forward([(self.netD1[i], lab) for i, lab, _, _ in terms])
+        d2 = networks.multi_forward([(self.netD2[i], pair) for i, _, pair, _ in terms])
+        return networks.factored_gan_loss(d1, d2, [r for _, _, _, r in terms], weights, up=2 if 'bilinear' in o.transform_1to2 else 1,
+                                          use_lsgan1=not o.no_lsgan1, use_lsgan2=not o.no_lsgan2)
 
     def backward_D2_binary(self):
-        """(twostage_factD_model.py:256-296): the label half of every (pooled) pair goes through transform_inverse to its D1."""
+        """(twostage_factD_model.py:256-296): the label half of every (pooled) pair goes through transform_inverse to its D1;
+        loss_D2 = (sum over fake pairs / their number + real) * 0.5 as one weighted sum, in chunks of <= 8 terms."""
         o = self.opt
         n, nc = self.n_netD2, o.input_nc
         fakes = []
@@ -462,21 +444,28 @@ class TwoStageFactDModel(TwoStageModel):
         if 'fake_fake' in o.GAN_losses_D2:
             fakes.append(self._query(1 + len(fakes), self.fake_pool2,
                                      lambda: self._pair(self.transform(self.fake_A), self.fake_B_from_fake_A)).detach())
-        self.loss_D2_fake = 0
+        num_fake_pairs = len(fakes)
+        terms = []
         for f in fakes:
             lab = self.transform_inverse(f.narrow(1, 0, nc)).detach()
-            self.loss_D2_fake = self.loss_D2_fake + sum(self._crit(self._factored(i, lab, f), False) for i in range(n))
-        self.loss_D2_fake = self.loss_D2_fake / len(fakes)
+            terms += [(i, lab, f, False) for i in range(n)]
         real = self._pair(self.real_A, self.real_B)
         lab = self.transform_inverse(self.real_A)
-        self.loss_D2_real = sum(self._crit(self._factored(i, lab, real), True) for i in range(n))
-        self.loss_D2 = (self.loss_D2_fake + self.loss_D2_real) * 0.5
+        terms += [(i, lab, real, True) for i in range(n)]
+        weights = [0.5 / num_fake_pairs] * (n * num_fake_pairs) + [0.5] * n
+        total, each = None, []
+        for i0 in range(0, len(terms), 8):           # the fused loss node takes <= 8 terms
+            t, e = self._factd_loss(terms[i0:i0 + 8], weights[i0:i0 + 8])
+            total = t if total is None else total + t
+            each.append(e)
+        each = each[0] if len(each) == 1 else torch.cat(each)
+        self.loss_D2_fake = each[:n * num_fake_pairs].sum() / num_fake_pairs
+        self.loss_D2_real = each[n * num_fake_pairs:].sum()
+        self.loss_D2 = total
         self._backward(self.loss_D2)
 
     def _g2_gan_term(self, fake, label, trick):
+        """sum_i lambda_D2[i] * crit(factored prediction i of the pair, real) (:352-383), -lambda and `fake` without the log-D trick."""
         lab = label()
-        t = 0
-        for i, lam in enumerate(self.opt.lambda_D2):
-            pred = self._factored(i, lab, fake)
-            t = t + (self._crit(pred, True) * lam if trick else -self._crit(pred, False) * lam)
+        t, _ = self._factd_loss([(i, lab, fake, trick) for i in range(self.n_netD2)], [l if trick else -l for l in self.opt.lambda_D2])
         return t
