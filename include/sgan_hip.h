@@ -271,6 +271,30 @@ int sgan_bce_weighted_fwd(const float* p, int32_t pld, const float* t, int32_t t
 int sgan_bce_weighted_bwd(const float* p, int32_t pld, const float* t, int32_t tld, int32_t npix, int32_t C, const float* class_w,
                           int32_t nw, const float* gout, float* dp, int32_t dpld, void* stream);
 
+/* ---- the loss section of a segmentation step with no discriminator (`--which_model_netD None`, models/segm_model.py:203-228) ----
+ * sgan_seg_head: ONE pass over the [npix][ld] logits (C <= 16 logical channels) writes the prediction p, the loss and, unless
+ *               `dlogits` is NULL, d loss / d logits for an upstream gradient of 1 (padding channels of p and dlogits: zeros).
+ *   SGAN_SEGHEAD_SOFTMAX: `label_or_target` is the int64 label map; p = softmax(z);
+ *               loss = sum_p w[y_p] (logsumexp(z_p) - z_p[y_p]) / norm[0];  dlogits = w[y_p] (p - onehot(y_p)) / norm[0]
+ *               (sgan_softmax_fwd + sgan_ce_fwd + sgan_ce_bwd with gout = 1).  class_w NULL = unit weights, else nw >= C of them;
+ *               labels outside [0, C) contribute nothing.  `norm`: device float, sum_p w[y_p] (sgan_label_weight_sum); 0 -> loss 0.
+ *   SGAN_SEGHEAD_SIGMOID: `label_or_target` is the float target map [npix][tld]; p = sigmoid(z);  w = 1 + sum_{i < nw} t_i (class_w[i] - 1);
+ *               loss = mean over pixels and channels of w * BCE(p, t) (torch's log clamp at -100);
+ *               dlogits = w (p - t) / max(p (1 - p), 1e-12) * p (1 - p) / (C * npix)
+ *               (sgan_sigmoid_nhwc_fwd + sgan_bce_weighted_fwd + sgan_bce_weighted_bwd + sgan_sigmoid_nhwc_bwd with gout = 1); `norm` unused.
+ *   Valid only while the loss is the one consumer of p: a gradient that arrives at p from elsewhere is not in dlogits.
+ * sgan_label_weight_sum: out[0] = sum_p class_w[label_p] (fp64 accumulation) over the labels in [0, C); class_w NULL: their count.
+ * `workspace` (both): SGAN_SEGHEAD_WS_BYTES of 8-byte aligned device scratch, ZERO on first use, owned by one stream at a time and
+ * left zeroed by every call (no fill per call).  The sums are taken in a fixed order: equal inputs give equal bits.
+ * Both return 1 (not covered, nothing launched) for C > 16 or a NULL required pointer. */
+#define SGAN_SEGHEAD_WS_BYTES 8192
+#define SGAN_SEGHEAD_SOFTMAX 0
+#define SGAN_SEGHEAD_SIGMOID 1
+int sgan_label_weight_sum(const int64_t* label, int32_t npix, int32_t C, const float* class_w, float* out, void* workspace, void* stream);
+int sgan_seg_head(const float* logits, int32_t ld, int32_t npix, int32_t C, int32_t mode, const void* label_or_target, int32_t tld,
+                  const float* class_w, int32_t nw, const float* norm, float* p_out, int32_t pld, float* dlogits, int32_t dld,
+                  float* loss_out, void* workspace, void* stream);
+
 /* ---- backward pass of a one-channel stride-1 head (the PatchGAN logits conv, models/networks.py:832-835) in one launch: the job
  * lists of sgan_conv_dgrad_grouped and sgan_conv_wgrad_grouped for the SAME pass (wjobs may be NULL: input gradient only).  Returns 1
  * when the layer is not of that type (Conv2d, stride 1, k <= 4, stored Cout 4 / logical 1, Cin >= 64, no `accumulate`): the caller

@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get("SGAN_HIP_LIB") or os.path.join(_HERE, "csrc", "libsga
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
 MATH_F32, MATH_BF16X3, MATH_BF16X1 = 0, 1, 2
 FACTD_SIG1, FACTD_SIG2, FACTD_MSE = 1, 2, 4
+SEGHEAD_SOFTMAX, SEGHEAD_SIGMOID = 0, 1
 CONV, CONVT = 0, 1
 
 
@@ -149,6 +150,8 @@ SIGNATURES = {
     "sgan_sigmoid_nhwc_bwd": [_P, _I, _P, _I, _I, _I, _P, _I, _P],
     "sgan_bce_weighted_fwd": [_P, _I, _P, _I, _I, _I, _P, _I, _P, _P, C.c_int64, _P],
     "sgan_bce_weighted_bwd": [_P, _I, _P, _I, _I, _I, _P, _I, _P, _P, _I, _P],
+    "sgan_label_weight_sum": [_P, _I, _I, _P, _P, _P, _P],
+    "sgan_seg_head": [_P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P],
     "sgan_normal_fill": [_P, _L, C.c_uint64, _P, _I, _P],
     "sgan_normal_fill_nhwc": [_P, _I, _I, _I, _I, C.c_uint64, _P, _I, _P],
     "sgan_normal_fill_nhwc_pair": [_P, _P, _I, _I, _I, _I, C.c_uint64, _P, _P, C.c_int64, _P],

@@ -52,7 +52,8 @@ class CGANModel(BaseModel):
                                       n_layers_G_skip=opt.n_layers_G_skip, gpu_ids=self.gpu_ids)
         if hasattr(self.netG, '_rng_seed'):
             self.netG._rng_seed = 0 if opt.manualSeed is None else int(opt.manualSeed)
-        if self.isTrain:
+        self.has_netD = self.isTrain and self._builds_netD(opt)
+        if self.has_netD:
             use_sigmoid = opt.no_lsgan
             assert (len(opt.scale_factor) == len(opt.lambda_D) == len(opt.n_layers_D))
             self.n_netD = len(opt.scale_factor)
@@ -67,22 +68,30 @@ class CGANModel(BaseModel):
                 networks.pack_flat(self.netD)
         if not self.isTrain or opt.continue_train:
             self.load_network(self.netG, 'G', opt.which_epoch)
-            if self.isTrain:
+            if self.has_netD:
                 for netD, n in zip(self.netD, range(self.n_netD)):
                     self.load_network(netD, 'D_%d' % n, opt.which_epoch)
 
         if self.isTrain:
-            self.fake_pool = ImagePool(opt.pool_size)
+            if self.has_netD:
+                self.fake_pool = ImagePool(opt.pool_size)
             self.old_lr = opt.lr
-            self.criterionGAN = networks.GANLoss(use_lsgan=not opt.no_lsgan)
+            if self.has_netD:
+                self.criterionGAN = networks.GANLoss(use_lsgan=not opt.no_lsgan)
             self.criterionL1 = networks.WeightedL1Loss()
             self.optimizer_G = FusedAdam(self.netG.parameters(), lr=opt.lr, betas=(opt.beta1, 0.999), zero_grads_in_step=True)
-            params = []
-            for netD in self.netD:
-                params += list(netD.model.parameters())
-            self.optimizer_D = FusedAdam(params, lr=opt.lr, betas=(opt.beta1, 0.999))
+            if self.has_netD:
+                params = []
+                for netD in self.netD:
+                    params += list(netD.model.parameters())
+                self.optimizer_D = FusedAdam(params, lr=opt.lr, betas=(opt.beta1, 0.999))
             self.grad_sync = None
             self._pool_override = None
+
+    def _builds_netD(self, opt):
+        """False: a trainer without discriminators (SegmentationModel under `--which_model_netD None`), which then has no netD,
+        optimizer_D, fake_pool or criterionGAN and reads none of the discriminator options."""
+        return True
 
     def _output_channels(self, opt):
         """Channels the generator emits / the discriminators see beside real_A (the segmentation trainer emits class scores)."""

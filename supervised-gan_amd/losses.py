@@ -363,6 +363,81 @@ def weighted_bce(p, t, class_weights=None):
     return _WeightedBceFn.apply(p, t, cw, nw)
 
 
+class _SegHeadNotCovered(Exception):
+    pass
+
+
+class _SegHeadFn(torch.autograd.Function):
+    """(p, loss) of a segmentation step whose loss is the ONE consumer of the prediction: softmax (or sigmoid) over the channels, the
+    class-weighted cross-entropy (or weighted BCE) and d loss / d logits in one launch (sgan_seg_head).  A gradient arriving at p
+    has no way into the dlogits the forward wrote, so the backward refuses one."""
+
+    @staticmethod
+    def forward(ctx, logits, lt, cw, nw, norm, mode):
+        zb = ops.as_nhwc(logits)
+        C_ = logits.shape[1]
+        if mode == ops.SEGHEAD_SOFTMAX:
+            lt = lt.reshape(-1).contiguous()
+        else:
+            lt = ops.as_nhwc(lt)
+        pb = torch.empty_like(zb)
+        dz = torch.empty_like(zb) if ctx.needs_input_grad[0] else None
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        if not ops.seg_head(zb, C_, mode, lt, cw, nw, norm, pb, dz, loss):
+            raise _SegHeadNotCovered()
+        ctx.dz, ctx.C = dz, C_
+        ctx.pb = pb      # the buffer object outlives this call: the detached alias autograd hands out maps back to it (as _CatPairFn)
+        ctx.set_materialize_grads(False)      # no gradient for p is the rule: None, not a zero fill, is what backward sees then
+        return ops.logical_view(pb, C_), loss
+
+    @staticmethod
+    def backward(ctx, gp, gout):
+        assert gp is None, "seg_head: a gradient arrived at p -- the fused head is valid only while the loss is p's one consumer"
+        if gout is None or ctx.dz is None:
+            return None, None, None, None, None, None
+        dz = ctx.dz
+        if not ops.is_unit_grad(gout):
+            dz = torch.empty_like(ctx.dz)
+            ops.scale(gout.contiguous().float(), ctx.dz, dz)
+        return ops.logical_view(dz, ctx.C), None, None, None, None, None
+
+
+def seg_head(logits, label_or_target, class_weights=None, norm=None, mode=0):
+    """The loss section of a segmentation step with no discriminator: returns (p, loss).
+
+    mode ops.SEGHEAD_SOFTMAX: p = F.softmax(logits, 1), loss = sum_p w[y_p] nll_p / norm with `label_or_target` the int64 label map
+    [1, H, W] on the logits' device and `norm` the device scalar sum_p w[y_p] (ops.label_weight_sum; None: computed here) -- that is
+    F.cross_entropy(logits, label, weight=class_weights).  mode ops.SEGHEAD_SIGMOID: p = torch.sigmoid(logits), loss =
+    F.binary_cross_entropy(p, target, weight=wm) with wm = 1 + sum_i target[:, i] (class_weights[i] - 1); `norm` is not read.
+
+    One launch (sgan_seg_head) writes p, the loss and d loss / d logits; the backward hands the last out times the upstream gradient.
+    p comes back NHWC-backed, like softmax_channels': it must have no consumer that sends a gradient back (the backward asserts it;
+    read it through .detach(), as the metrics and the visuals do).  Under torch.no_grad() no gradient is written.  Outside the kernel's envelope (a batch, more than 16 channels, not
+    fp32 on the device) the existing functions are composed: softmax_channels + cross_entropy_logits on the device, torch calls off it."""
+    softmax = mode == ops.SEGHEAD_SOFTMAX
+    lt = label_or_target.detach()
+    nw = 0 if class_weights is None else int(class_weights.numel())
+    if softmax:
+        assert lt.dtype == torch.int64 and lt.device == logits.device, "seg_head: the label map is torch.int64 on the logits' device"
+    if _bce_envelope(logits) and (softmax or (_bce_envelope(lt) and lt.shape == logits.shape and nw <= logits.shape[1])):
+        cw = class_weights.detach().float().contiguous() if nw else None
+        if softmax:
+            assert lt.numel() == logits.shape[2] * logits.shape[3] and (cw is None or nw == logits.shape[1])
+            if norm is None:
+                norm = torch.empty((), dtype=torch.float32, device=logits.device)
+                ops.label_weight_sum(lt.reshape(-1).contiguous(), logits.shape[1], cw, norm)
+        try:
+            return _SegHeadFn.apply(logits, lt, cw, nw, norm, int(mode))
+        except _SegHeadNotCovered:
+            pass
+    if softmax:
+        if logits.is_cuda and logits.dim() == 4 and logits.shape[0] == 1 and logits.shape[1] <= 16 and logits.dtype == torch.float32:
+            return softmax_channels(logits), cross_entropy_logits(logits, lt, 0, class_weights)
+        return F.softmax(logits, dim=1), F.cross_entropy(logits, lt, weight=class_weights)
+    p = sigmoid_channels(logits)
+    return p, weighted_bce(p, lt, class_weights)
+
+
 class GANLossMultiClass(nn.Module):
     """GANLossMultiClass (models/networks.py:188-202): CrossEntropyLoss over the class channel of every pixel of a
     discriminator map against one class: one forward and one backward launch (sgan_ce_fwd / sgan_ce_bwd)."""

@@ -27,7 +27,7 @@ from .discriminators import (DCGANDiscriminator, NLayerDiscriminator, NLayerDisc
 from .generators import (AutoEncoder, CascadedRefinementNetwork, DCGANGenerator, FCGANGenerator, FCGANGeneratorStar,      # noqa: F401
                          ResnetGenerator, UnetGenerator)
 from .losses import (GANLoss, GANLossMultiClass, WeightedL1Loss, _CatPairFn, _FactdLossMultiFn, _GanLossFn, _GanLossMultiFn,      # noqa: F401
-                     bce_on_rescaled, bilinear_upsample2x, cat_pair, factored_gan_loss, factored_product, sigmoid_channels,
+                     bce_on_rescaled, bilinear_upsample2x, cat_pair, factored_gan_loss, factored_product, seg_head, sigmoid_channels,
                      weighted_bce)
 
 

@@ -801,6 +801,71 @@ def bce_weighted_bwd(p, t, Creal, class_w, nw, gout, dp):
                                           _ptr(gout), _ptr(_act(dp)), dp.stride(1), _stream()), "sgan_bce_weighted_bwd")
 
 
+SEGHEAD_WS_BYTES = 8192   # SGAN_SEGHEAD_WS_BYTES
+SEGHEAD_SOFTMAX, SEGHEAD_SIGMOID = L.SEGHEAD_SOFTMAX, L.SEGHEAD_SIGMOID
+_seghead_ws = {}
+
+
+def _seghead_workspace(device, which):
+    """Zero-initialised once per device and entry point, left zeroed by the kernels (main stream only, like _gan_loss_workspace)."""
+    ws = _seghead_ws.get((device.index, which))
+    if ws is None:
+        ws = _seghead_ws[(device.index, which)] = torch.zeros(SEGHEAD_WS_BYTES // 8, dtype=torch.float64, device=device)
+    return ws
+
+
+def label_weight_sum(label, Creal, class_w, out):
+    """out[0] = sum over the pixels of class_w[label] (class_w None: the count of labels in [0, Creal)): sgan_label_weight_sum on an
+    int64 device label map; `out` a float32 device scalar."""
+    require_gpu(label, "label_weight_sum")
+    assert label.dtype == torch.int64 and label.is_contiguous() and out.dtype == torch.float32 and out.numel() == 1 and out.device == label.device
+    assert class_w is None or (class_w.dtype == torch.float32 and class_w.is_contiguous() and class_w.numel() >= Creal and class_w.device == label.device)
+    rc = L.lib().sgan_label_weight_sum(_ptr(label), label.numel(), int(Creal), _ptr(class_w), _ptr(out),
+                                       _ptr(_seghead_workspace(label.device, "norm")), _stream())
+    if rc == 1:
+        raise L.SganError("sgan_label_weight_sum: not covered (more than 16 classes)")
+    L.check(rc, "sgan_label_weight_sum")
+
+
+def seg_head(z, Creal, mode, label_or_target, class_w, nw, norm, p, dz, loss_out):
+    """sgan_seg_head on an [H, W, Cs] logits buffer: p (and dz unless None) are [H, W, Cs'] buffers, `label_or_target` the int64 label
+    map of H * W entries (softmax) or the [H, W, Cs''] target buffer (sigmoid), `norm` the float32 device scalar of label_weight_sum
+    (softmax).  Every operand is checked against its storage here, before anything is launched.  Returns False, having launched
+    nothing, when the library reports the call as not covered."""
+    H, W, _ = z.shape
+
+    def rows_fit(t, what, written):
+        # the kernel moves whole stored rows (16-byte accesses) where the pixel stride is 4, 8, 12 or 16, and writes the padding channels
+        _act(t)
+        row = t.stride(1) if (written or t.stride(1) in (4, 8, 12, 16)) else Creal
+        if t.shape[0] * t.shape[1] != H * W or t.shape[2] < Creal or t.stride(1) < Creal or (H * W - 1) * t.stride(1) + row > _avail(t):
+            raise L.SganError(f"seg_head {what}: tensor {tuple(t.shape)} (pixel stride {t.stride(1)}, {_avail(t)} elements of storage) does "
+                              f"not hold {H}x{W} rows of {row}; nothing was launched")
+
+    rows_fit(z, "logits", False)
+    rows_fit(p, "p", True)
+    assert loss_out.dtype == torch.float32 and loss_out.numel() == 1 and loss_out.is_cuda
+    if dz is not None:
+        rows_fit(dz, "dlogits", True)
+    tld = 0
+    if mode == SEGHEAD_SOFTMAX:
+        assert label_or_target.dtype == torch.int64 and label_or_target.is_cuda and label_or_target.is_contiguous() and label_or_target.numel() == H * W
+        assert norm is not None and norm.dtype == torch.float32 and norm.is_cuda and norm.numel() == 1
+        assert class_w is None or nw >= Creal
+    else:
+        rows_fit(label_or_target, "target", False)
+        tld = label_or_target.stride(1)
+        assert nw <= Creal
+    assert class_w is None or (class_w.dtype == torch.float32 and class_w.is_cuda and class_w.is_contiguous() and class_w.numel() >= nw)
+    rc = L.lib().sgan_seg_head(_ptr(z), z.stride(1), H * W, int(Creal), int(mode), _ptr(label_or_target), tld, _ptr(class_w),
+                               int(nw) if class_w is not None else 0, _ptr(norm), _ptr(p), p.stride(1), _ptr(dz),
+                               dz.stride(1) if dz is not None else 0, _ptr(loss_out), _ptr(_seghead_workspace(z.device, "head")), _stream())
+    if rc == 1:
+        return False
+    L.check(rc, "sgan_seg_head")
+    return True
+
+
 def sigmoid_fwd(x, p):
     H, W, _ = x.shape
     L.check(L.lib().sgan_sigmoid_fwd(_ptr(_act(x)), x.stride(1), H * W, _ptr(_act(p)), p.stride(1), _stream()), "sgan_sigmoid_fwd")

@@ -2,6 +2,10 @@
 real_A -> U-Net -> logits -> softmax (or `--use_sigmoid_ss` sigmoid) = the "fake" one-hot label the PatchGAN discriminators see on
 cat(real_A, .); generator loss = sum_i lambda_i GAN(D_i(fake), 1) + (class-weighted) cross-entropy against the label.
 
+`--which_model_netD None` is the supervised baseline (segm_model.py:76,91,103,115,203,239,255,267,274): no discriminators, the
+generator trained on the (class-weighted) cross-entropy alone.  With no second consumer of the prediction the loss section of the
+step -- softmax / sigmoid, the loss, d loss / d logits -- is one launch (losses.seg_head, sgan_seg_head).
+
 Built on CGANModel: discriminator step, pooling, optimizers, checkpoints and the hipGraph step are inherited; the generator runs
 with the caller's `activation=` (identity) so the conv chain ends raw; softmax / cross-entropy (models/loss.py:6-12 is
 NLLLoss2d(log_softmax)) and the sigmoid / weighted BCE of `--use_sigmoid_ss` are kernels of losses.py on the num_classes x H x W maps."""
@@ -12,7 +16,7 @@ import torch
 
 from . import networks, ops
 from .cgan_model import CGANModel
-from .losses import cross_entropy_logits, sigmoid_channels, softmax_channels, weighted_bce
+from .losses import cross_entropy_logits, seg_head, sigmoid_channels, softmax_channels, weighted_bce
 
 
 def _identity(x):
@@ -29,12 +33,20 @@ class SegmentationModel(CGANModel):
         assert len(picks) == 2
         self.label_nc = len(picks[1])
         self.num_classes = self.label_nc + 1 if opt.add_background_onehot else self.label_nc          # segm_model.py:45
-        if getattr(opt, 'which_model_netD', 'None') == 'None' and opt.isTrain:
-            raise NotImplementedError("--which_model_netD None (cross-entropy only) is not on the MI355X path")
         CGANModel.initialize(self, opt)
         self.class_weights = None if opt.weights is None else torch.tensor(opt.weights, dtype=torch.float32, device=self.device)
         self.use_sigmoid_ss = opt.use_sigmoid_ss
+        self.no_netD = self.isTrain and not self.has_netD
+        if self.no_netD:
+            assert opt.weights is None or self.use_sigmoid_ss or len(opt.weights) == self.num_classes, \
+                "--weights: one per class (%d) for the softmax cross-entropy" % self.num_classes
+            self.loss_G_GAN = 0
+            self.norm = None      # sum_p w[label_p], a persistent device scalar refreshed with the label (softmax mode)
+            self.graph_spec = self._graph_spec_no_netD      # an attribute of THIS trainer only: GraphedStep looks for it
         self.reset_accs()
+
+    def _builds_netD(self, opt):
+        return getattr(opt, 'which_model_netD', 'None') != 'None'
 
     def _output_channels(self, opt):
         return self.num_classes          # generator output and discriminator input are sized by the class count (:69,83-86)
@@ -54,6 +66,10 @@ class SegmentationModel(CGANModel):
         if getattr(self, 'label', None) is None or self.label.shape != lab.shape:
             self.label = torch.empty_like(lab)        # persistent: a captured hipGraph keeps reading this buffer (label_, :61,138-139)
         self.label.copy_(lab)
+        if getattr(self, 'no_netD', False) and not self.use_sigmoid_ss and self.device.type == 'cuda':
+            if self.norm is None:
+                self.norm = torch.zeros((), dtype=torch.float32, device=self.device)
+            ops.label_weight_sum(self.label.reshape(-1), self.num_classes, self.class_weights, self.norm)
 
     def forward(self, val_mode=False):
         """val_mode: the validation pass of train_ss.py draws its latent at --noiseSizeVal (segm_model.py:145-155)."""
@@ -61,6 +77,12 @@ class SegmentationModel(CGANModel):
         self.real_B = self.input_B
         self.noise = self._draw_noise_val() if val_mode else self._draw_noise()
         self.logit = self.netG.forward(self.real_A, self.noise, activation=_identity)                 # :155
+        if getattr(self, 'no_netD', False):      # the loss is fake_B's one consumer: prediction, loss and d loss / d logit in one launch
+            if self.use_sigmoid_ss:
+                self.fake_B, self._head_loss = seg_head(self.logit, self.real_B, self.class_weights, None, ops.SEGHEAD_SIGMOID)
+            else:
+                self.fake_B, self._head_loss = seg_head(self.logit, self.label, self.class_weights, self.norm, ops.SEGHEAD_SOFTMAX)
+            return      # backward_G names it loss_G_CE: the re-draw that ends an update (n_update_G > 1) must not replace the logged loss
         self.fake_B = sigmoid_channels(self.logit) if self.use_sigmoid_ss else softmax_channels(self.logit)
 
     sample_noise = forward
@@ -89,6 +111,11 @@ class SegmentationModel(CGANModel):
 
     def backward_G(self):
         """loss_G = sum_i lambda_i * GAN(D_i(cat(A, fake_B)), 1) + CE   (segm_model.py:203-232)"""
+        if self.no_netD:      # :202-203,227: loss_G_GAN = 0, the cross-entropy forward() left behind is the whole loss
+            self.loss_G_GAN = 0
+            self.loss_G = self.loss_G_CE = self._head_loss
+            self._backward(self.loss_G)
+            return
         skip = getattr(self.opt, 'skip_wasted_D_wgrad', False)
         for netD in self.netD:
             netD.compute_param_grads = not skip
@@ -99,7 +126,47 @@ class SegmentationModel(CGANModel):
         self.loss_G = self.loss_G_GAN + self.compute_cross_entropy_loss(weighted=True)
         self._backward(self.loss_G)
 
+    def optimize_parameters(self):
+        if not self.no_netD:
+            return CGANModel.optimize_parameters(self)
+        ops.begin_step(())                                   # segm_model.py:237-251 without the discriminator loop
+        self.forward()
+        for _ in range(self.opt.n_update_G):
+            self.optimizer_G.zero_grad()
+            self.backward_G()
+            if self.grad_sync is not None:
+                self.grad_sync(self.optimizer_G)
+            self.optimizer_G.step()
+            if self.opt.n_update_G > 1:
+                self.sample_noise()
+
+    def _graph_spec_no_netD(self):
+        """The step as graph_step.GraphedStep captures it: no pool, nothing to hand to a discriminator, the generator updates."""
+        prog = []
+        for _ in range(self.opt.n_update_G):
+            prog += [[self.optimizer_G.zero_grad, self.backward_G], ("sync", self.optimizer_G), [self.optimizer_G.step]]
+            if self.opt.n_update_G > 1:
+                prog[-1].append(self.sample_noise)
+        return dict(pools=[], sources=lambda: [], set_overrides=lambda views: None, program=prog)
+
+    def save(self, label):
+        if not self.no_netD:
+            return CGANModel.save(self, label)
+        self.save_network(self.netG, 'G', label, gpu_ids=self.gpu_ids)
+
+    def update_learning_rate(self):
+        if not self.no_netD:
+            return CGANModel.update_learning_rate(self)
+        lr = self.old_lr - self.opt.lr / self.opt.niter_decay
+        for param_group in self.optimizer_G.param_groups:
+            param_group['lr'] = lr
+        self.optimizer_G.sync_lr()
+        print('update learning rate: %f -> %f' % (self.old_lr, lr))
+        self.old_lr = lr
+
     def get_current_errors(self):
+        if self.no_netD:                                     # :253-257
+            return OrderedDict([('G_CE', float(self.loss_G_CE.detach()))])
         return OrderedDict([('G_CE', float(self.loss_G_CE.detach())), ('G_GAN', float(self.loss_G_GAN.detach())),
                             ('D_real', float(self.loss_D_real)), ('D_fake', float(self.loss_D_fake))])
 
