@@ -724,7 +724,24 @@ int sgan_lbfgs_advance(sgan_lbfgs_state* state, int32_t J, int64_t n, float* x, 
  *   logical channels (C <= 16) of x at pixel stride x_ld; truth = label[p] (int64 map) when label is given, else the argmax of y in
  *   the same way.  add_background: class C = 1 - min(1, sum_c v_c) (fp32, summed in channel order) is appended to both channel
  *   maps before the argmax and k = C + 1, else k = C.  Ties go to the first maximum and a NaN counts as the maximum, as in
- *   torch.argmax. */
+ *   torch.argmax.
+ * sgan_thin_workspace: bytes of the workspace sgan_thin needs for an H x W plane (< 0: bad shape).
+ * sgan_thin: Guo-Hall thinning of the wall pixels of one plane to one-pixel lines, as skimage.morphology.thin performs it (the border
+ *   thinning of the ISBI-2012 scores: compute_Rand_F_scores(..., do_thin=True), util/util.py:99-101 of the reference; util.thin is
+ *   the host restatement the kernel is tested against).  The plane is read as sgan_ccl_label reads it (pixel stride, wall when
+ *   x > 0.5, a NaN is not wall); out is a dense float [H * W] plane of 0.0 / 1.0, so sgan_ccl_label(out, 1, ...) labels the thinned
+ *   map.  An iteration is two sub-iterations, each deciding every wall pixel from one snapshot of its 8 neighbours (outside the
+ *   image = 0); max_num_iter <= 0 means "until nothing changes".  iters_out (optional, one int32 in device memory) receives the number
+ *   of iterations that deleted something.
+ *   Nothing is read back and nothing is decided on the host: a call enqueues a sequence of launches that depends on (H, W,
+ *   max_num_iter) only -- init, ceil(iterations / 8) tile launches of up to 8 iterations each (a 32 x 32 core with a 16-pixel halo
+ *   in LDS), emit -- so it can be captured in a hipGraph and replayed on data that needs any other number of iterations.  Per-iteration
+ *   deletion counters in the workspace carry convergence: a tile launch whose predecessor deleted nothing returns at once.
+ *   "Until nothing changes" is budgeted at min(H, W) / 2 + 2 iterations (an all-wall plane needs min(H, W) / 2 + 1), and a larger
+ *   max_num_iter is cut to the budget; if the budget's last iteration still deleted something, *dev_err gets bit 16 and out holds
+ *   the state reached.  The result is integers: the same bits on every run.  Workspace, dev_err and stream as sgan_rand_f_accumulate;
+ *   the call's first launch initialises what it uses.  H * W < 2^30 and H <= 65535 * 32 (one grid row per 32 image rows); both entries
+ *   refuse any other shape. */
 #define SGAN_RAND_F_MAX_PROBE 1024
 int sgan_ccl_label(const float* plane, int64_t pix_stride, int32_t H, int32_t W, int32_t* labels, int32_t* dev_err, void* stream);
 int64_t sgan_rand_f_workspace(int32_t H, int32_t W);
@@ -735,6 +752,9 @@ int sgan_vinfo_accumulate(const int32_t* t_labels, const int32_t* s_labels, int3
                           int64_t workspace_bytes, double* acc, double* acc_rand, double* parts_out, int32_t* dev_err, void* stream);
 int sgan_confusion_accumulate(const float* x, int32_t x_ld, int32_t C, const int64_t* label, const float* y, int32_t y_ld,
                               int32_t add_background, int64_t npix, int64_t* conf, int32_t* dev_err, void* stream);
+int64_t sgan_thin_workspace(int32_t H, int32_t W);
+int sgan_thin(const float* plane, int64_t pix_stride, int32_t H, int32_t W, float* out, int32_t max_num_iter, void* workspace,
+              int64_t workspace_bytes, int32_t* iters_out, int32_t* dev_err, void* stream);
 
 #ifdef __cplusplus
 }

@@ -580,3 +580,177 @@ extern "C" int sgan_confusion_accumulate(const float* x, int32_t x_ld, int32_t C
     g_sgan_last_kernel = "sg_confusion_kernel";
     return SGAN_OK;
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Guo-Hall thinning of the wall pixels (skimage.morphology.thin; util.thin is the host restatement).  An iteration is two
+// sub-iterations; each decides every wall pixel from ONE snapshot of its eight neighbours and then deletes, so a pixel after s
+// sub-iterations depends on the pixels at most s away.  A workgroup holds a tile with a halo of SG_THIN_K pixels in LDS and runs up
+// to SG_THIN_K sub-iterations on it: after sub-iteration s the outermost s rings of the region may be wrong (their neighbours outside
+// the region were not known), the rest is exact, and the core is what it writes back.  Sub-iteration s therefore touches only the
+// rings >= s + 1, which are all the later ones read.  Two byte masks in the workspace are ping-ponged between launches, because a
+// tile's halo is its neighbours' state BEFORE the launch.
+// Nothing is decided on the host: a call enqueues init, a fixed number of step launches and emit.  Convergence is carried by
+// cnt[i] = pixels deleted in iteration i (core pixels only, so the tiles' counts add up to the image's), zeroed by init; a step
+// launch whose predecessor's last iteration deleted nothing returns at once and leaves its destination mask untouched, and emit
+// derives from the counters how many launches ran, which tells it the mask that is live.  The counters cross launch boundaries only,
+// so plain loads read them.
+// Workspace: [cnt: budget int32, rounded up to 16 bytes][mask 0: H W bytes, rounded up to 16][mask 1: likewise].
+// ------------------------------------------------------------------------------------------------------------------------------
+#define SG_THIN_K 16                                  // halo = sub-iterations per launch (even); 16 against 8 measured in DESIGN.md R11
+#define SG_THIN_TH 32                                 // core rows of a tile
+#define SG_THIN_RW 64                                 // region width: one wave holds one row of the region
+#define SG_THIN_TW (SG_THIN_RW - 2 * SG_THIN_K)       // core columns of a tile
+#define SG_THIN_RH (SG_THIN_TH + 2 * SG_THIN_K)
+#define SG_THIN_IPL (SG_THIN_K / 2)                   // iterations per launch
+#define SG_THIN_THREADS 256
+static_assert(SG_THIN_K >= 2 && SG_THIN_K % 2 == 0 && SG_THIN_TW >= 8, "SG_THIN_K: even, and a core of at least 8 columns");
+
+static int sg_thin_budget(int32_t H, int32_t W) { return (H < W ? H : W) / 2 + 2; }
+
+// c: the neighbour code, bit k = b[k], b0..b7 = E, NE, N, NW, W, SW, S, SE (counter-clockwise from E).  The conditions as util.thin_tables
+// states them, on the code rotated by one and two places: bit i of r1 is b[(i+1)%8], of r2 b[(i+2)%8], of l1 b[(i+7)%8].
+__device__ __forceinline__ bool sg_thin_deletable(unsigned c, int second) {
+    const unsigned r1 = ((c >> 1) | (c << 7)) & 255u, r2 = ((c >> 2) | (c << 6)) & 255u, l1 = ((c << 1) | (c >> 7)) & 255u;
+    if (__builtin_popcount(~c & (r1 | r2) & 0x55u) != 1) return false;                                    // G1
+    const int n1 = __builtin_popcount((c | l1) & 0xAAu), n2 = __builtin_popcount((c | r1) & 0xAAu);      // k odd: b[k] | b[k-1], b[k] | b[k+1]
+    const int m = n1 < n2 ? n1 : n2;
+    if (m != 2 && m != 3) return false;                                                                   // G2
+    if (second) return !(((c & 0x60u) || !(c & 0x08u)) && (c & 0x10u));                                   // G3': not ((b5 | b6 | !b3) & b4)
+    return !(((c & 0x06u) || !(c & 0x80u)) && (c & 0x01u));                                               // G3:  not ((b1 | b2 | !b7) & b0)
+}
+
+__global__ __launch_bounds__(256) void sg_thin_init_kernel(const float* __restrict__ plane, int64_t pix_stride, int n, uint8_t* __restrict__ mask,
+                                                           int32_t* __restrict__ cnt, int iters) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    for (int j = i; j < iters; j += gridDim.x * 256) cnt[j] = 0;
+    if (i < n) mask[i] = plane[(int64_t)i * pix_stride] > 0.5f ? 1 : 0;
+}
+
+// Iterations it0 .. it0 + nit - 1 (nit <= SG_THIN_IPL) of the tile at (blockIdx.x, blockIdx.y): src -> dst.
+__global__ __launch_bounds__(SG_THIN_THREADS) void sg_thin_step_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int H, int W,
+                                                                       int32_t* cnt, int it0, int nit) {
+    if (it0 > 0 && cnt[it0 - 1] == 0) return;      // converged before this launch (uniform over the grid): dst stays as it is
+    __shared__ uint8_t M[2][SG_THIN_RH * SG_THIN_RW];
+    __shared__ int deleted[SG_THIN_IPL];
+    const int tid = threadIdx.x;
+    const int cx0 = blockIdx.x * SG_THIN_TW, cy0 = blockIdx.y * SG_THIN_TH;
+    for (int p = tid; p < SG_THIN_RH * SG_THIN_RW; p += SG_THIN_THREADS) {
+        const int y = cy0 - SG_THIN_K + p / SG_THIN_RW, x = cx0 - SG_THIN_K + p % SG_THIN_RW;
+        M[0][p] = (y >= 0 && y < H && x >= 0 && x < W) ? src[y * W + x] : (uint8_t)0;      // outside the image: 0
+    }
+    if (tid < SG_THIN_IPL) deleted[tid] = 0;
+    SG_SYNC();      // the region and deleted[] are in place
+    const int rx = tid % SG_THIN_RW;
+    for (int s = 0; s < 2 * nit; ++s) {
+        const uint8_t* a = M[s & 1];
+        uint8_t* b = M[(s & 1) ^ 1];
+        const int lo = s + 1;      // rings 0 .. s are not needed any more
+        int del = 0;
+        if (rx >= lo && rx < SG_THIN_RW - lo) {
+            for (int ry = lo + tid / SG_THIN_RW; ry < SG_THIN_RH - lo; ry += SG_THIN_THREADS / SG_THIN_RW) {      // uniform over a wave
+                const int p = ry * SG_THIN_RW + rx;
+                uint8_t v = a[p];
+                if (v) {
+                    const unsigned c = (unsigned)a[p + 1] | (unsigned)a[p - SG_THIN_RW + 1] << 1 | (unsigned)a[p - SG_THIN_RW] << 2 |
+                                       (unsigned)a[p - SG_THIN_RW - 1] << 3 | (unsigned)a[p - 1] << 4 | (unsigned)a[p + SG_THIN_RW - 1] << 5 |
+                                       (unsigned)a[p + SG_THIN_RW] << 6 | (unsigned)a[p + SG_THIN_RW + 1] << 7;
+                    if (sg_thin_deletable(c, s & 1)) {
+                        v = 0;
+                        if (rx >= SG_THIN_K && rx < SG_THIN_RW - SG_THIN_K && ry >= SG_THIN_K && ry < SG_THIN_RH - SG_THIN_K) ++del;
+                    }
+                }
+                b[p] = v;
+            }
+        }
+        if (del) atomicAdd(&deleted[s >> 1], del);
+        SG_SYNC();      // sub-iteration s is complete in b, and nobody reads a any more: the next one overwrites it
+    }
+    const uint8_t* f = M[(2 * nit) & 1];
+    for (int p = tid; p < SG_THIN_TH * SG_THIN_TW; p += SG_THIN_THREADS) {
+        const int cy = p / SG_THIN_TW, cx = p % SG_THIN_TW, y = cy0 + cy, x = cx0 + cx;
+        if (y < H && x < W) dst[y * W + x] = f[(cy + SG_THIN_K) * SG_THIN_RW + cx + SG_THIN_K];
+    }
+    if (tid < nit && deleted[tid]) atomicAdd(&cnt[it0 + tid], deleted[tid]);
+}
+
+// Step launch j >= 1 ran iff cnt[j * SG_THIN_IPL - 1] > 0; with `ran` launches run in all the live mask is number ran & 1.
+__global__ __launch_bounds__(256) void sg_thin_emit_kernel(const uint8_t* __restrict__ m0, const uint8_t* __restrict__ m1,
+                                                           const int32_t* __restrict__ cnt, int iters, int n, float* __restrict__ out,
+                                                           int32_t* iters_out, int flag_short, int32_t* dev_err) {
+    __shared__ int ran, changing;
+    if (threadIdx.x == 0) {
+        ran = 1;
+        changing = 0;
+    }
+    SG_SYNC();      // the two counts initialised
+    for (int i = threadIdx.x; i < iters; i += 256) {
+        if (cnt[i] > 0) {
+            atomicAdd(&changing, 1);
+            if ((i + 1) % SG_THIN_IPL == 0 && i + 1 < iters) atomicAdd(&ran, 1);
+        }
+    }
+    SG_SYNC();      // the two counts complete
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (iters_out) *iters_out = changing;
+        if (flag_short && cnt[iters - 1] > 0) sg_flag(dev_err, 16);      // the budget's last iteration still deleted something
+    }
+    const uint8_t* live = (ran & 1) ? m1 : m0;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = live[i] ? 1.0f : 0.0f;
+}
+
+struct SgThinLayout {
+    int budget;
+    int64_t cnt_bytes, mask_bytes, bytes;
+};
+
+static SgThinLayout sg_thin_layout(int32_t H, int32_t W) {
+    SgThinLayout l;
+    l.budget = sg_thin_budget(H, W);
+    l.cnt_bytes = (4ll * l.budget + 15) & ~15ll;
+    l.mask_bytes = ((int64_t)H * W + 15) & ~15ll;
+    l.bytes = l.cnt_bytes + 2 * l.mask_bytes;
+    return l;
+}
+
+// the shapes both entries take: H W < 2^30, and no more tile rows than a grid has in y
+static bool sg_thin_shape_ok(int32_t H, int32_t W) {
+    return H >= 1 && W >= 1 && (int64_t)H * W < (1ll << 30) && (H + SG_THIN_TH - 1) / SG_THIN_TH <= 65535;
+}
+
+extern "C" int64_t sgan_thin_workspace(int32_t H, int32_t W) {
+    if (!sg_thin_shape_ok(H, W)) return sgan_fail(SGAN_ERR_INVALID, "bad shape %d x %d", H, W);
+    return sg_thin_layout(H, W).bytes;
+}
+
+extern "C" int sgan_thin(const float* plane, int64_t pix_stride, int32_t H, int32_t W, float* out, int32_t max_num_iter, void* workspace,
+                         int64_t workspace_bytes, int32_t* iters_out, int32_t* dev_err, void* stream) {
+    SGAN_CHECK(plane && out && workspace && dev_err, "null pointer");
+    SGAN_CHECK(sg_thin_shape_ok(H, W) && pix_stride >= 1, "bad shape %d x %d, pixel stride %lld", H, W, (long long)pix_stride);
+    const SgThinLayout l = sg_thin_layout(H, W);
+    SGAN_CHECK(workspace_bytes >= l.bytes, "workspace of %lld bytes, %lld needed for %d x %d (sgan_thin_workspace); nothing was launched",
+               (long long)workspace_bytes, (long long)l.bytes, H, W);
+    SGAN_CHECK(((uintptr_t)workspace & 15) == 0, "workspace not 16-byte aligned");
+    const dim3 tiles((W + SG_THIN_TW - 1) / SG_THIN_TW, (H + SG_THIN_TH - 1) / SG_THIN_TH);
+    // "until nothing changes" runs the budget; a max_num_iter beyond the budget is cut to it, and reported like the former if it was short
+    const int iters = (max_num_iter > 0 && max_num_iter < l.budget) ? max_num_iter : l.budget;
+    const int flag_short = (max_num_iter <= 0 || max_num_iter > l.budget) ? 1 : 0;
+    int32_t* cnt = (int32_t*)workspace;
+    uint8_t* mask[2] = {(uint8_t*)workspace + l.cnt_bytes, (uint8_t*)workspace + l.cnt_bytes + l.mask_bytes};
+    const int n = H * W, nb = (n + 255) / 256;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(sg_thin_init_kernel, dim3(nb), dim3(256), 0, st, plane, pix_stride, n, mask[0], cnt, iters);
+    SGAN_LAUNCH_CHECK();
+    int j = 0;
+    for (int it0 = 0; it0 < iters; it0 += SG_THIN_IPL, ++j) {
+        const int nit = iters - it0 < SG_THIN_IPL ? iters - it0 : SG_THIN_IPL;
+        hipLaunchKernelGGL(sg_thin_step_kernel, tiles, dim3(SG_THIN_THREADS), 0, st, (const uint8_t*)mask[j & 1], mask[(j + 1) & 1], H, W, cnt,
+                           it0, nit);
+        SGAN_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(sg_thin_emit_kernel, dim3(nb), dim3(256), 0, st, (const uint8_t*)mask[0], (const uint8_t*)mask[1], (const int32_t*)cnt,
+                       iters, n, out, iters_out, flag_short, dev_err);
+    SGAN_LAUNCH_CHECK();
+    g_sgan_last_kernel = "sg_thin_step_kernel";
+    return SGAN_OK;
+}

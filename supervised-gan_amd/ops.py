@@ -1060,6 +1060,7 @@ def as_nhwc(t: torch.Tensor) -> torch.Tensor:
 _metric_err = {}
 _rand_ws = {}
 _vinfo_ws = {}
+_thin_ws = {}
 VINFO_PARTS = ('SA', 'SB', 'SAB', 'aux', 'm', 'H_S', 'H_T', 'I', 'VInfo', 'split', 'merge')      # parts_out of vinfo_accumulate
 
 
@@ -1079,7 +1080,7 @@ def check_metric_err(device):
     if code:
         e.zero_()
         raise L.SganError(f"segmentation metric kernels gave up on part of their input (flags {code:#x}: 1 = union-find bound, "
-                          "2 = pair table full, 4 / 8 = label out of range); the accumulated values are incomplete")
+                          "2 = pair table full, 4 / 8 = label out of range, 16 = thinning budget ran out); the accumulated values are incomplete")
 
 
 def _plane(t, what):
@@ -1105,6 +1106,37 @@ def ccl_label(plane, labels=None):
     L.check(L.lib().sgan_ccl_label(_ptr(plane), plane.stride(1), H, W, _ptr(labels), _ptr(metric_err(plane.device)), _stream()),
             "sgan_ccl_label")
     return labels
+
+
+def thin_workspace(H, W, device):
+    """The scratch of thin for H x W planes (change counters and two byte masks), cached per (H, W, device) like rand_f_workspace."""
+    key = (H, W, device.index)
+    ws = _thin_ws.get(key)
+    if ws is None:
+        nbytes = L.lib().sgan_thin_workspace(H, W)
+        if nbytes < 0:
+            raise L.SganError(f"sgan_thin_workspace({H}, {W}): {L.lib().sgan_last_error().decode()}")
+        ws = _thin_ws[key] = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
+    return ws
+
+
+def thin(plane, out=None, max_num_iter=None, iters_out=None, workspace=None):
+    """Guo-Hall thinning of the pixels of `plane` [H, W] that are > 0.5 to one-pixel lines (sgan_thin; util.thin is the host
+    yardstick): float32 [H, W] of 0.0 / 1.0, which ccl_label labels as it lies.  max_num_iter None: until nothing changes.  iters_out
+    (int32[1] on the device) receives the number of iterations that deleted something.  Only enqueues -- the launch sequence depends
+    on the shape and max_num_iter alone -- and reads `plane` in place when its rows are W pixel strides apart."""
+    plane = _plane(plane, "thin")
+    assert max_num_iter is None or max_num_iter >= 1, max_num_iter
+    H, W = plane.shape
+    dev = plane.device
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.float32, device=dev)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == H * W and out.device == dev
+    assert iters_out is None or (iters_out.dtype == torch.int32 and iters_out.numel() == 1 and iters_out.device == dev)
+    ws = thin_workspace(H, W, dev) if workspace is None else workspace
+    L.check(L.lib().sgan_thin(_ptr(plane), plane.stride(1), H, W, _ptr(out), 0 if max_num_iter is None else int(max_num_iter), _ptr(ws),
+                              ws.numel() * ws.element_size(), _ptr(iters_out), _ptr(metric_err(dev)), _stream()), "sgan_thin")
+    return out
 
 
 def rand_f_workspace(H, W, device):

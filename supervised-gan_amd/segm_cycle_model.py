@@ -206,6 +206,7 @@ class SegmentationCycleModel(CGANCycleModel):
     compute_current_Rand_score = SegmentationModel.compute_current_Rand_score
     _label_boundary_maps = SegmentationModel._label_boundary_maps
     compute_current_VInfo = SegmentationModel.compute_current_VInfo
+    compute_current_thinned_scores = SegmentationModel.compute_current_thinned_scores
     compute_current_accuracy = SegmentationModel.compute_current_accuracy
     get_current_accs = SegmentationModel.get_current_accs
     compute_cross_entropy_loss = SegmentationModel.compute_cross_entropy_loss      # test_ss.py: sets loss_G_CE

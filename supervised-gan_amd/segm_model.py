@@ -180,8 +180,9 @@ class SegmentationModel(CGANModel):
     # that accumulates after every step never waits for the GPU; get_current_accs() is the one place that synchronises and reads.
     def reset_accs(self):
         self.confusion, self.numAveragedPixels, self.numAveragedImages = 0, 0, 0
-        self.pixelAcc = self.meanAcc = self.meanIU = self.RandScore = self.VInfo = 0
-        for t in (getattr(self, '_acc_rand', None), getattr(self, '_acc_conf', None), getattr(self, '_acc_vinfo', None)):
+        self.pixelAcc = self.meanAcc = self.meanIU = self.RandScore = self.VInfo = self.RandScoreThin = self.VInfoThin = 0
+        for t in (getattr(self, '_acc_rand', None), getattr(self, '_acc_conf', None), getattr(self, '_acc_vinfo', None),
+                  getattr(self, '_acc_thin', None)):
             if t is not None:
                 t.zero_()
 
@@ -199,6 +200,8 @@ class SegmentationModel(CGANModel):
             self.compute_current_VInfo(with_rand='RandScore' in self.opt.which_metric)
         elif 'RandScore' in self.opt.which_metric:
             self.compute_current_Rand_score()
+        if 'RandScoreThin' in self.opt.which_metric or 'VInfoThin' in self.opt.which_metric:
+            self.compute_current_thinned_scores(truth_labelled='VInfo' in self.opt.which_metric or 'RandScore' in self.opt.which_metric)
         if 'meanIU' in self.opt.which_metric:
             self.compute_current_accuracy()
 
@@ -237,6 +240,33 @@ class SegmentationModel(CGANModel):
         t_labels, s_labels = self._label_boundary_maps()
         ops.vinfo_accumulate(t_labels, s_labels, self._acc_vinfo, acc_rand=self._acc_rand if with_rand else None)
 
+    def compute_current_thinned_scores(self, truth_labelled=False):
+        """Adds the scores after border thinning -- util.compute_thinned_scores, the reference's do_thin=True -- to running sums of
+        their own: channel 0 of fake_B thinned to one-pixel lines (ops.thin) into a plane of the trainer's, that plane labelled into
+        a third label buffer, then one counting pass for whichever of RandScoreThin / VInfoThin is asked for.  The truth is not
+        thinned, and its labelling is the un-thinned scores' when they were taken in this accum_accs (truth_labelled)."""
+        assert self.num_classes == 2 and self.fake_B.shape[0] == 1, "binary segmentation at batch 1, like every kernel of this path"
+        self._acc_buffers()
+        s, t = self.fake_B.detach()[0, 0], self.real_B.detach()[0, 0]
+        if getattr(self, '_acc_thin', None) is None:
+            self._acc_thin = torch.zeros((2, 2), dtype=torch.float64, device=self.device)      # [Rand, VInfo] x [sum, images]
+            self._thin_plane = self._thin_labels = None
+        if self._thin_plane is None or self._thin_plane.shape != t.shape:
+            self._thin_plane = torch.empty(tuple(t.shape), dtype=torch.float32, device=self.device)
+            self._thin_labels = torch.empty(tuple(t.shape), dtype=torch.int32, device=self.device)
+        if self._acc_labels is None or self._acc_labels.shape[1:] != t.shape:
+            self._acc_labels = torch.empty((2,) + tuple(t.shape), dtype=torch.int32, device=self.device)
+            truth_labelled = False
+        if not truth_labelled:
+            ops.ccl_label(t, self._acc_labels[0])
+        ops.thin(s, out=self._thin_plane)
+        ops.ccl_label(self._thin_plane, self._thin_labels)
+        with_rand = 'RandScoreThin' in self.opt.which_metric
+        if 'VInfoThin' in self.opt.which_metric:
+            ops.vinfo_accumulate(self._acc_labels[0], self._thin_labels, self._acc_thin[1], acc_rand=self._acc_thin[0] if with_rand else None)
+        else:
+            ops.rand_f_accumulate(self._acc_labels[0], self._thin_labels, self._acc_thin[0])
+
     def compute_current_accuracy(self):
         """conf[label, prediction] += 1 for every pixel, on the device (segm_model.py:309-331; the ratios are taken when the
         accuracies are read)."""
@@ -250,12 +280,17 @@ class SegmentationModel(CGANModel):
 
     def get_current_accs(self):
         """Reads the device accumulators (the only synchronisation of the metric path) and derives RandScore, VInfo, pixelAcc,
-        meanAcc and meanIU from them."""
+        meanAcc and meanIU from them, and RandScoreThin / VInfoThin (after the existing keys) when they were asked for."""
         if getattr(self, '_acc_rand', None) is not None:
             ops.check_metric_err(self.device)
             rand, conf = self._acc_rand.cpu().numpy(), self._acc_conf.cpu().numpy().astype(np.float64)
             vinfo = self._acc_vinfo.cpu().numpy()
             self.numAveragedImages = int(max(rand[1], vinfo[1]))
+            if getattr(self, '_acc_thin', None) is not None:
+                thin = self._acc_thin.cpu().numpy()
+                self.numAveragedImages = int(max(self.numAveragedImages, thin[0, 1], thin[1, 1]))
+                self.RandScoreThin = thin[0, 0] / thin[0, 1] if thin[0, 1] else 0
+                self.VInfoThin = thin[1, 0] / thin[1, 1] if thin[1, 1] else 0
             self.RandScore = rand[0] / rand[1] if rand[1] else 0
             self.VInfo = vinfo[0] / vinfo[1] if vinfo[1] else 0
             self.confusion, self.numAveragedPixels = conf, int(conf.sum())
@@ -265,4 +300,6 @@ class SegmentationModel(CGANModel):
             self.meanIU = float(np.mean(tp / np.maximum(1, rel + sel - tp)))
         return OrderedDict(([('RandScore', self.RandScore)] if 'RandScore' in self.opt.which_metric else [])
                            + ([('VInfo', self.VInfo)] if 'VInfo' in self.opt.which_metric else [])
-                           + ([('meanIU', self.meanIU)] if 'meanIU' in self.opt.which_metric else []))
+                           + ([('meanIU', self.meanIU)] if 'meanIU' in self.opt.which_metric else [])
+                           + ([('RandScoreThin', self.RandScoreThin)] if 'RandScoreThin' in self.opt.which_metric else [])
+                           + ([('VInfoThin', self.VInfoThin)] if 'VInfoThin' in self.opt.which_metric else []))

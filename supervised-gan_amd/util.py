@@ -1,5 +1,6 @@
 """Image and metric helpers of the drivers (util/util.py:15-28, :41-43, :86-128 of the reference): tensor -> uint8 image -> PNG,
-the Rand F-score of a binary segmentation, and the information score (VInfo) that goes with it."""
+the Rand F-score of a binary segmentation, the information score (VInfo) that goes with it, and Guo-Hall thinning (the border
+thinning both scores are ranked after: `thin`, `compute_thinned_scores`)."""
 import os
 
 import numpy as np
@@ -28,6 +29,66 @@ def _label_false_regions(mask):
     from scipy import ndimage
     lab, _ = ndimage.label(~mask, structure=np.ones((3, 3), dtype=np.int32))
     return lab
+
+
+_THIN_WEIGHTS = np.array([[8, 4, 2], [16, 0, 1], [32, 64, 128]], dtype=np.uint8)      # E = 1, then counter-clockwise: NE N NW W SW S SE
+
+
+def thin_tables():
+    """The two 256-entry deletion tables of Guo-Hall thinning, indexed by the neighbour code (bit k = b[k], b0..b7 = E, NE, N, NW, W,
+    SW, S, SE): table[s][code] is True when a set pixel with these neighbours is deleted in sub-iteration s + 1.
+        G1: #{i in 0,2,4,6 : not b[i] and (b[i+1] or b[(i+2)%8])} == 1
+        G2: min(N1, N2) in {2, 3},  N1 = #{k in 1,3,5,7 : b[k] or b[k-1]},  N2 = #{k in 1,3,5,7 : b[k] or b[(k+1)%8]}
+        G3 (sub-iteration 1): not ((b1 or b2 or not b7) and b0);  G3' (sub-iteration 2): not ((b5 or b6 or not b3) and b4)"""
+    tables = np.zeros((2, 256), dtype=bool)
+    for code in range(256):
+        b = [bool((code >> k) & 1) for k in range(8)]
+        g1 = sum((not b[i]) and (b[i + 1] or b[(i + 2) % 8]) for i in (0, 2, 4, 6)) == 1
+        n1 = sum(b[k] or b[k - 1] for k in (1, 3, 5, 7))
+        n2 = sum(b[k] or b[(k + 1) % 8] for k in (1, 3, 5, 7))
+        g12 = g1 and min(n1, n2) in (2, 3)
+        tables[0, code] = g12 and not ((b[1] or b[2] or not b[7]) and b[0])
+        tables[1, code] = g12 and not ((b[5] or b[6] or not b[3]) and b[4])
+    return tables
+
+
+def thin(mask, max_num_iter=None):
+    """Guo-Hall thinning of a boolean [H, W] image to one-pixel lines, as skimage.morphology.thin performs it: an iteration is two
+    sub-iterations, each of which decides every set pixel from one snapshot of its eight neighbours (outside the image = 0) by
+    thin_tables() and then deletes; it stops after the first iteration that deletes nothing, or after max_num_iter iterations.
+    Returns (thinned bool [H, W], n_changing = the number of iterations that deleted something).
+
+    skimage is not installed where this was written, so "identical to skimage.morphology.thin" is unverified; what the tests claim
+    is that the device kernel (sgan_thin) is identical to THIS function.  The host yardstick of ops.thin; the trainers do not call it."""
+    from scipy import ndimage
+    m = (np.asarray(mask) != 0).astype(np.uint8)
+    assert m.ndim == 2, m.shape
+    tables = thin_tables()
+    n_changing, it = 0, 0
+    while max_num_iter is None or it < max_num_iter:
+        before = int(m.sum())
+        for table in tables:
+            code = ndimage.correlate(m, _THIN_WEIGHTS, mode='constant', cval=0)
+            m = m & ~table[code]
+        it += 1
+        if int(m.sum()) == before:
+            break
+        n_changing += 1
+    return m.astype(bool), n_changing
+
+
+def compute_thinned_scores(S, T):
+    """(Rand F-score [N], VInfo [N]) of the THINNED prediction against the truth: compute_Rand_F_scores and compute_VInfo_scores on
+    thin(S > 0.5)[0] and T > 0.5 -- the reference's compute_Rand_F_scores(S, T, do_thin=True) (util/util.py:99-101), which thins the
+    prediction only.  The regions are still labelled 8-connected, as in the reference, so a thinned DIAGONAL wall does not separate
+    the regions on its two sides: that is the reference's do_thin=True convention, kept as it is.
+    S, T: [N, 1, H, W] (or a single [H, W] pair)."""
+    S, T = np.asarray(S), np.asarray(T)
+    if S.ndim == 2:
+        S, T = S.reshape((1, 1) + S.shape), T.reshape((1, 1) + T.shape)
+    St = np.stack([thin(S[k].squeeze(axis=0) > 0.5)[0][None] for k in range(S.shape[0])]).astype(np.float64)
+    Tt = (T > 0.5).astype(np.float64)
+    return compute_Rand_F_scores(St, Tt), compute_VInfo_scores(St, Tt)
 
 
 def compute_Rand_F_scores(S, T, do_thin=False):

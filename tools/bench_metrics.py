@@ -10,6 +10,10 @@ step loop without accuracies, with the device path and with the host path after 
         the cost of adding VInfo to RandScore is the difference of the two)
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_metrics.py --metric_only 50 [--metrics ...]
         (only the metric launches, on per-pixel noise maps: the per-kernel split of one accum_accs)
+    python tools/bench_metrics.py --thin [--steps 100] --out profiles/r11_thin.json
+        (the thinned path on maps alone, no trainer: sgan_thin, the thinned score pair and the un-thinned pair on per-pixel noise,
+        the cell map, the cell map with its walls dilated by 3 pixels, and an already thin map -- every tile launch but the first
+        returns at once there, which is the cost of the early-exit launches)
 
 Kernel time is taken with events around the queued kernels after a synchronise (warm-up excluded); the loops are wall time between
 two synchronises, divided by the step count.  Every figure is reported per repeat so the spread is in the file, and the clocks
@@ -78,6 +82,90 @@ def metric_only(n_iter, n, dev, metrics=("RandScore", "meanIU")):
     print("metric_only: %d iterations, mean F %.6f, mean VInfo %.6f" % (n_iter, float(acc[0] / acc[1]), float(acc_v[0] / acc_v[1])))
 
 
+def thin_bench(a, dev):
+    """sgan_thin alone, the thinned score pair (thin, two labellings, one counting pass for both scores) and the un-thinned pair on
+    the same maps.  Each is timed twice: with events around one eager call after a synchronise (what a training loop that is not
+    graphed pays, host enqueue gaps included) and as the mean of 10 calls captured in one hipGraph (device time alone)."""
+    from scipy import ndimage
+    from supervised_gan_amd.util import thin as host_thin
+    n = a.size
+    g = torch.Generator().manual_seed(1)
+    noise = torch.rand(2, n, n, generator=g)
+    cs, ct = (m[0, 0].cpu() for m in cell_maps(n, dev))
+    thick = torch.from_numpy(ndimage.binary_dilation(cs.numpy() > 0.5, structure=np.ones((3, 3), bool), iterations=3).astype(np.float32))
+    thin_map = torch.from_numpy(host_thin(cs.numpy() > 0.5)[0].astype(np.float32))
+    inputs = (("per_pixel_noise", noise[0], noise[1]), ("cell_map", cs, ct), ("cell_map_walls_dilated_3", thick, ct),
+              ("already_thin_early_exit_launches", thin_map, ct))
+    out = {"clocks_before": clocks(), "size": n, "steps": a.steps, "warmup": a.warmup, "device": torch.cuda.get_device_name(0),
+           "budget_iterations": n // 2 + 2, "unit": "ms per call"}
+    labels = torch.empty((3, n, n), dtype=torch.int32, device=dev)
+    plane = torch.empty((n, n), dtype=torch.float32, device=dev)
+    acc = torch.zeros((2, 2), dtype=torch.float64, device=dev)
+    it = torch.zeros(1, dtype=torch.int32, device=dev)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def eager(fn):
+        ms = []
+        for i in range(a.warmup + a.steps):
+            torch.cuda.synchronize()
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            if i >= a.warmup:
+                ms.append(e0.elapsed_time(e1))
+        return stats(ms)
+
+    def graphed(fn, calls=10):
+        gr = torch.cuda.CUDAGraph()
+        torch.cuda.synchronize()
+        with torch.cuda.graph(gr):
+            for _ in range(calls):
+                fn()
+        ms = []
+        for i in range(3 + max(5, a.steps // calls)):
+            torch.cuda.synchronize()
+            e0.record()
+            gr.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            if i >= 3:
+                ms.append(e0.elapsed_time(e1) / calls)
+        return stats(ms)
+
+    for name, s_host, t_host in inputs:
+        s, t = s_host.to(dev).contiguous(), t_host.to(dev).contiguous()
+
+        def only_thin():
+            ops.thin(s, out=plane, iters_out=it)
+
+        def thinned_pair():
+            ops.ccl_label(t, labels[0])
+            ops.thin(s, out=plane)
+            ops.ccl_label(plane, labels[2])
+            ops.vinfo_accumulate(labels[0], labels[2], acc[1], acc_rand=acc[0])
+
+        def plain_pair():
+            ops.ccl_label(t, labels[0])
+            ops.ccl_label(s, labels[1])
+            ops.vinfo_accumulate(labels[0], labels[1], acc[1], acc_rand=acc[0])
+
+        only_thin()
+        want, n_host = host_thin(s_host.numpy() > 0.5)
+        assert np.array_equal(plane.cpu().numpy() == 1.0, want) and int(it.item()) == n_host, name
+        out[name] = {"wall_pixels": int((s_host > 0.5).sum()), "wall_pixels_thinned": int(want.sum()), "changing_iterations": n_host}
+        for key, fn in (("sgan_thin", only_thin), ("thinned_score_pair", thinned_pair), ("unthinned_score_pair", plain_pair)):
+            out[name][key] = {"eager_events": eager(fn), "graphed": graphed(fn)}
+        print(name, json.dumps(out[name]))
+    ops.check_metric_err(dev)
+    out["clocks_after"] = clocks()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return out
+
+
 def stats(ms):
     ms = sorted(ms)
     return {"median_ms": statistics.median(ms), "min_ms": ms[0], "p90_ms": ms[int(0.9 * (len(ms) - 1))], "max_ms": ms[-1], "n": len(ms)}
@@ -99,6 +187,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--metric_only", type=int, default=0, help="run only this many metric iterations on noise maps and exit")
+    ap.add_argument("--thin", action="store_true", help="time the thinned path on maps alone (no trainer) and exit")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--size", type=int, default=512)
@@ -109,6 +198,8 @@ def main(argv=None):
     n = a.size
     if a.metric_only:
         return metric_only(a.metric_only, n, torch.device("cuda", 0), a.metrics)
+    if a.thin:
+        return thin_bench(a, torch.device("cuda", 0))
     with tempfile.TemporaryDirectory() as tmp:
         argv_m = ("--name bench_metrics --model segmentation --which_direction AtoB --dataset_mode aligned --fineSize %d "
                   "--which_model_netG unet_256 --ngf 32 --norm instance --which_channel b_rg --gpu_ids 0 --no_dropout --dataroot synthetic "
