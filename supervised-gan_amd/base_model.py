@@ -1,4 +1,7 @@
-"""BaseModel (models/base_model.py:5-64): trainer protocol + checkpoint I/O.
+"""BaseModel (models/base_model.py:5-64): trainer protocol, the training step and checkpoint I/O.
+
+A trainer states its step once -- step_stages(), and where they apply step_zeroing(), step_pools(), check_graphable() -- and
+optimize_parameters() here and graph_step.GraphedStep both run the program built from that statement.
 
 Checkpoint layout is the reference's: one file per network, `<epoch>_net_<label>.pth`, holding the
 bare CPU state_dict with the reference's key names and logical shapes.  Loading tolerates old-torch
@@ -22,6 +25,8 @@ class BaseModel:
         self.device = torch.device('cuda', self.gpu_ids[0]) if self.gpu_ids else torch.device('cpu')
         self.save_dir = os.path.join(opt.checkpoints_dir, opt.name)
         self.model_dir = getattr(opt, 'pretrained_model_dir', '')
+        self.grad_sync = None            # data-parallel hook: callable(optimizer) run between backward and step
+        self._pool_overrides = None      # graphed step: one static buffer per step_pools() entry, read instead of querying the pool
 
     def Tensor(self, *size):
         return torch.empty(*size, dtype=torch.float32, device=self.device)
@@ -52,7 +57,90 @@ class BaseModel:
     def get_current_errors(self):
         return {}
 
+    # ---- the training step -------------------------------------------------------------------------
+    def step_stages(self):
+        """[(optimizer, backward method, updates per step), ...] in the order the step runs them."""
+        raise NotImplementedError
+
+    def step_zeroing(self):
+        """Gradient buffers the step's first launch (ops.begin_step) clears together with the statistics arenas."""
+        return ()
+
+    def step_pools(self):
+        """[(ImagePool, callable -> what the step hands to its query()), ...] in the reference's query order."""
+        return []
+
+    def check_graphable(self):
+        """Asserts what graph_step.GraphedStep needs of this trainer's options before it captures the step."""
+
+    def step_program(self):
+        """The step after forward(): lists of calls, with a ("sync", optimizer) item where the data-parallel gradient exchange goes."""
+        program = []
+        for optimizer, backward, n_updates in self.step_stages():
+            for _ in range(n_updates):
+                program += [[optimizer.zero_grad, backward], ("sync", optimizer), [optimizer.step]]
+                if n_updates > 1:
+                    program[-1].append(self.sample_noise)
+        return program
+
+    def run_program(self, program):
+        for item in program:
+            if isinstance(item, list):
+                for call in item:
+                    call()
+            elif self.grad_sync is not None:
+                self.grad_sync(item[1])
+
+    def optimize_parameters(self):
+        ops.begin_step(self.step_zeroing())      # one launch zeroes every statistics arena of the step
+        self.forward()
+        self.run_program(self.step_program())
+
+    def _pooled(self, i):
+        """Fake number `i` of the discriminator step: the answer of its ImagePool, or the buffer the graphed step filled with it."""
+        if self._pool_overrides is not None:
+            return self._pool_overrides[i]
+        pool, source = self.step_pools()[i]
+        return pool.query(source())
+
+    # ---- learning-rate schedules: `update_learning_rate` of a trainer is one of these -----------------
+    def decay_single_rate(self):
+        """fcgan / cgan / segmentation (fcgan_model.py:224-236): every group at old_lr - lr / niter_decay, not clamped."""
+        lr = self.old_lr - self.opt.lr / self.opt.niter_decay
+        for optimizer, _, _ in self.step_stages():
+            for group in optimizer.param_groups:
+                group['lr'] = lr
+            optimizer.sync_lr()
+        print('update learning rate: %f -> %f' % (self.old_lr, lr))
+        self.old_lr = lr
+
+    def decay_three_rates(self):
+        """The cycle and two-stage trainers (twostage_cycle_model.py:477-500): lr, lr1, lr2 each fall by their own base / niter_decay
+        down to 0; the groups named G1 / D1 follow lr1, G2 / F2 / D2 follow lr2, any other lr."""
+        new = {k: max(0, getattr(self, 'old_' + k) - getattr(self.opt, k) / self.opt.niter_decay) for k in ('lr', 'lr1', 'lr2')}
+        follows = {'G1': 'lr1', 'D1': 'lr1', 'G2': 'lr2', 'F2': 'lr2', 'D2': 'lr2'}
+        for optimizer, _, _ in self.step_stages():
+            for group in optimizer.param_groups:
+                group['lr'] = new[follows.get(group.get('name'), 'lr')]
+            optimizer.sync_lr()
+        print('update learning rate: %f -> %f, %f -> %f' % (self.old_lr1, new['lr1'], self.old_lr2, new['lr2']))
+        self.old_lr, self.old_lr1, self.old_lr2 = new['lr'], new['lr1'], new['lr2']
+
     # ---- checkpoints -----------------------------------------------------------------------------
+    def checkpoint_nets(self):
+        """[(label, network)]: every network this trainer holds, under the label of its checkpoint file."""
+        return []
+
+    def save(self, label):
+        for net_label, net in self.checkpoint_nets():
+            self.save_network(net, net_label, label, gpu_ids=self.gpu_ids)
+
+    def load(self, epoch_label, only=None, model_dir=''):
+        """Reads every network's file; `only`: the networks whose label (a discriminator's without its `_<n>`) it names."""
+        for net_label, net in self.checkpoint_nets():
+            if only is None or net_label.split('_')[0] in only:
+                self.load_network(net, net_label, epoch_label, model_dir=model_dir)
+
     def _checkpoint_path(self, network_label, epoch_label, model_dir):
         """`<epoch>_net_<label>.pth` under the run's directory, or under --pretrained_model_dir when the caller asks for the
         pretrained copy (any true `model_dir`: the reference ignores its value and reads opt.pretrained_model_dir, :46-49,56-59)."""
@@ -73,7 +161,7 @@ def _not_overridden(self, *args, **kwargs):
 
 
 # the rest of the trainer protocol: hooks a subclass overrides, no-ops here (models/base_model.py:21-39,63-64)
-for _hook in ('forward', 'test', 'get_image_paths', 'optimize_parameters', 'save', 'update_learning_rate'):
+for _hook in ('forward', 'test', 'get_image_paths', 'update_learning_rate'):
     setattr(BaseModel, _hook, _not_overridden)
 
 

@@ -69,18 +69,9 @@ class CGANCycleModel(BaseModel):
             if self.gpu_ids:
                 networks.pack_flat(self.netD1)
         if self.isTrain and opt.sequential_train:
-            for label, net in (('G1', self.netG1), ('G2', self.netG2)):
-                if label in opt.which_model_to_load:
-                    self.load_network(net, label, opt.which_epoch_sequential, model_dir=opt.pretrained_model_dir)
-            if 'D1' in opt.which_model_to_load:
-                for n, netD in enumerate(self.netD1):
-                    self.load_network(netD, 'D1_%d' % n, opt.which_epoch_sequential, model_dir=opt.pretrained_model_dir)
+            self.load(opt.which_epoch_sequential, only=opt.which_model_to_load, model_dir=opt.pretrained_model_dir)
         if not self.isTrain or opt.continue_train:
-            self.load_network(self.netG1, 'G1', opt.which_epoch)
-            self.load_network(self.netG2, 'G2', opt.which_epoch)
-            if self.isTrain:
-                for n, netD in enumerate(self.netD1):
-                    self.load_network(netD, 'D1_%d' % n, opt.which_epoch)
+            self.load(opt.which_epoch)
         if self.isTrain:
             self.fake_pool1 = ImagePool(opt.pool_size)
             self.old_lr, self.old_lr1, self.old_lr2 = opt.lr, opt.lr1, opt.lr2
@@ -90,21 +81,26 @@ class CGANCycleModel(BaseModel):
                                            {'name': 'G2', 'params': self.netG2.parameters(), 'lr': opt.lr2}],
                                           lr=opt.lr, betas=(opt.beta1, 0.999))
             self.optimizer_D1 = FusedAdam([p for d in self.netD1 for p in d.model.parameters()], lr=opt.lr1, betas=(opt.beta1, 0.999))
-            self.grad_sync = None
-            self._pool_overrides = None
+            self.optimizer_D1.param_groups[0]['name'] = 'D1'      # decay_three_rates: follows lr1
 
-    # ---- hipGraph hooks (graph_step.GraphedStep) --------------------------------------------------
+    # ---- the step (:227-244), as BaseModel.optimize_parameters and graph_step.GraphedStep run it ---------------------------------
+    def step_stages(self):
+        o = self.opt
+        return [(self.optimizer_D1, self.backward_D1, o.n_update_D1), (self.optimizer_G, self.backward_G, o.n_update_G)]
+
+    def step_pools(self):
+        return [(self.fake_pool1, self._d_fake_source)]
+
+    def check_graphable(self):
+        assert all(n == 1 for _, _, n in self.step_stages()), "graphed %s step: one update each" % self.opt.model
+
+    def checkpoint_nets(self):
+        return [('G1', self.netG1), ('G2', self.netG2)] + [('D1_%d' % n, d) for n, d in enumerate(self.netD1 if self.isTrain else [])]
+
+    update_learning_rate = BaseModel.decay_three_rates      # (:270-289): G1 / D1 follow lr1, G2 follows lr2
+
     def _pair(self, a, b):
         return b if self.opt.no_cgan else networks.cat_pair(a, b)
-
-    def graph_spec(self):
-        o = self.opt
-        assert (o.n_update_D1, o.n_update_G) == (1, 1), "graphed cgan_cycle step: one update each"
-        prog = [[self.optimizer_D1.zero_grad, self.backward_D1], ("sync", self.optimizer_D1),
-                [self.optimizer_D1.step, self.optimizer_G.zero_grad, self.backward_G], ("sync", self.optimizer_G),
-                [self.optimizer_G.step]]
-        return dict(pools=[self.fake_pool1], sources=lambda: [self._d_fake_source()],
-                    set_overrides=lambda views: setattr(self, "_pool_overrides", views), program=prog)
 
     # ---- data ---------------------------------------------------------------------------------
     def set_input(self, input):
@@ -163,11 +159,7 @@ class CGANCycleModel(BaseModel):
 
     def backward_D1(self):
         """(:162-186)"""
-        if self._pool_overrides is not None:
-            fake = self._pool_overrides[0]
-        else:
-            fake = self.fake_pool1.query(self._d_fake_source())
-        fake = fake.detach()
+        fake = self._pooled(0).detach()
         real = self._pair(self.real_A, self.real_B)
         n = self.n_netD1
         self.loss_D, each = self._gan([(d, fake, False) for d in self.netD1] + [(d, real, True) for d in self.netD1], [0.5] * (2 * n))
@@ -190,20 +182,6 @@ class CGANCycleModel(BaseModel):
         self.loss_G = self.loss_G_GAN + self.loss_G_L1 * o.lambda_A + self.loss_G_CE * o.lambda_B + self.loss_G_cycle * o.lambda_A_cycle
         self._backward(self.loss_G)
 
-    def optimize_parameters(self):
-        ops.begin_step()      # one launch zeroes every statistics arena of the step
-        o = self.opt
-        self.forward()
-        for n_up, opt_, back in ((o.n_update_D1, self.optimizer_D1, self.backward_D1), (o.n_update_G, self.optimizer_G, self.backward_G)):
-            for _ in range(n_up):
-                opt_.zero_grad()
-                back()
-                if self.grad_sync is not None:
-                    self.grad_sync(opt_)
-                opt_.step()
-                if n_up > 1:
-                    self.sample_noise()
-
     def get_current_errors(self):
         return OrderedDict([('G1', float(self.loss_G.detach())), ('G2', float(self.loss_G_cycle.detach())), ('D1', float(self.loss_D.detach()))])
 
@@ -212,24 +190,3 @@ class CGANCycleModel(BaseModel):
             return OrderedDict([('real_A', self.real_A.detach()), ('real_B', self.real_B.detach()), ('fake_B', self.fake_B.detach()),
                                 ('recon_A', self.recon_A.detach())])
         return OrderedDict([('real_A', self.real_A.detach()), ('fake_B', self.fake_B.detach())])
-
-    def save(self, label):
-        self.save_network(self.netG1, 'G1', label, gpu_ids=self.gpu_ids)
-        self.save_network(self.netG2, 'G2', label, gpu_ids=self.gpu_ids)
-        for n, netD in enumerate(self.netD1):
-            self.save_network(netD, 'D1_%d' % n, label, gpu_ids=self.gpu_ids)
-
-    def update_learning_rate(self):
-        """(:270-289): G1 / D1 follow lr1, G2 follows lr2."""
-        nd = self.opt.niter_decay
-        lr = max(0, self.old_lr - self.opt.lr / nd)
-        lr1 = max(0, self.old_lr1 - self.opt.lr1 / nd)
-        lr2 = max(0, self.old_lr2 - self.opt.lr2 / nd)
-        for g in self.optimizer_D1.param_groups:
-            g['lr'] = lr1
-        for g in self.optimizer_G.param_groups:
-            g['lr'] = lr1 if g.get('name') == 'G1' else lr2 if g.get('name') == 'G2' else lr
-        self.optimizer_D1.sync_lr()
-        self.optimizer_G.sync_lr()
-        print('update learning rate: %f -> %f, %f -> %f' % (self.old_lr1, lr1, self.old_lr2, lr2))
-        self.old_lr, self.old_lr1, self.old_lr2 = lr, lr1, lr2

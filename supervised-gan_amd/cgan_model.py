@@ -67,10 +67,7 @@ class CGANModel(BaseModel):
             if self.gpu_ids:
                 networks.pack_flat(self.netD)
         if not self.isTrain or opt.continue_train:
-            self.load_network(self.netG, 'G', opt.which_epoch)
-            if self.has_netD:
-                for netD, n in zip(self.netD, range(self.n_netD)):
-                    self.load_network(netD, 'D_%d' % n, opt.which_epoch)
+            self.load(opt.which_epoch)
 
         if self.isTrain:
             if self.has_netD:
@@ -85,8 +82,6 @@ class CGANModel(BaseModel):
                 for netD in self.netD:
                     params += list(netD.model.parameters())
                 self.optimizer_D = FusedAdam(params, lr=opt.lr, betas=(opt.beta1, 0.999))
-            self.grad_sync = None
-            self._pool_override = None
 
     def _builds_netD(self, opt):
         """False: a trainer without discriminators (SegmentationModel under `--which_model_netD None`), which then has no netD,
@@ -169,8 +164,7 @@ class CGANModel(BaseModel):
 
     def backward_D(self):
         """loss_D = 0.5 * (sum_i GAN(D_i(fake), 0) + sum_i GAN(D_i(real), 1))   (cgan_model.py:158-182)"""
-        fake = self._pool_override if self._pool_override is not None else self.fake_pool.query(self._pool_source())
-        fake = fake.detach()
+        fake = self._pooled(0).detach()
         real = self.real_B if self.opt.no_cgan else networks.cat_pair(self.real_A, self.real_B)
         n = self.n_netD
         self.loss_D, self._each_D = self._d_losses([(d, fake, False) for d in self.netD] + [(d, real, True) for d in self.netD],
@@ -200,25 +194,21 @@ class CGANModel(BaseModel):
     def loss_D_real(self):
         return self._each_D[self.n_netD:].sum()
 
-    def optimize_parameters(self):
-        ops.begin_step(self.optimizer_D.take_zeroing())      # one launch zeroes every statistics arena of the step and D's gradients
-        self.forward()
-        for _ in range(self.opt.n_update_D):
-            self.optimizer_D.zero_grad()
-            self.backward_D()
-            if self.grad_sync is not None:
-                self.grad_sync(self.optimizer_D)
-            self.optimizer_D.step()
-            if self.opt.n_update_D > 1:
-                self.sample_noise()
-        for _ in range(self.opt.n_update_G):
-            self.optimizer_G.zero_grad()
-            self.backward_G()
-            if self.grad_sync is not None:
-                self.grad_sync(self.optimizer_G)
-            self.optimizer_G.step()
-            if self.opt.n_update_G > 1:
-                self.sample_noise()
+    # ---- the step (cgan_model.py:212-226), as BaseModel.optimize_parameters and graph_step.GraphedStep run it; a trainer without
+    # discriminators (SegmentationModel) keeps the generator's stage only ----------------------------------------------------
+    def step_stages(self):
+        o = self.opt
+        d = [(self.optimizer_D, self.backward_D, o.n_update_D)] if self.has_netD else []
+        return d + [(self.optimizer_G, self.backward_G, o.n_update_G)]
+
+    def step_zeroing(self):
+        return self.optimizer_D.take_zeroing() if self.has_netD else ()      # the step's one zeroing launch clears D's gradients too
+
+    def step_pools(self):
+        return [(self.fake_pool, self._pool_source)] if self.has_netD else []
+
+    def check_graphable(self):
+        assert not self.has_netD or self.opt.n_update_D == 1, "graphed step supports n_update_D == 1 (every README recipe)"
 
     def get_current_errors(self):
         return OrderedDict([('G_GAN', float(self.loss_G.detach())), ('G_L1', float(self.loss_G_L1.detach())),
@@ -230,17 +220,7 @@ class CGANModel(BaseModel):
             out['real_B'] = self.real_B.detach()
         return out
 
-    def save(self, label):
-        self.save_network(self.netG, 'G', label, gpu_ids=self.gpu_ids)
-        for netD, n in zip(self.netD, range(self.n_netD)):
-            self.save_network(netD, 'D_%d' % n, label, self.gpu_ids)
+    def checkpoint_nets(self):
+        return [('G', self.netG)] + [('D_%d' % n, netD) for n, netD in enumerate(self.netD if self.has_netD else [])]
 
-    def update_learning_rate(self):
-        lrd = self.opt.lr / self.opt.niter_decay
-        lr = self.old_lr - lrd
-        for opt_ in (self.optimizer_D, self.optimizer_G):
-            for param_group in opt_.param_groups:
-                param_group['lr'] = lr
-            opt_.sync_lr()
-        print('update learning rate: %f -> %f' % (self.old_lr, lr))
-        self.old_lr = lr
+    update_learning_rate = BaseModel.decay_single_rate

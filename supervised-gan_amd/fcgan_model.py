@@ -75,10 +75,7 @@ class FCGANModel(BaseModel):
             if self.gpu_ids:
                 networks.pack_flat(self.netD)   # one arena: single Adam segment, single gradient all-reduce
         if not self.isTrain or opt.continue_train:
-            self.load_network(self.netG, 'G', opt.which_epoch)
-            if self.isTrain:
-                for netD, n in zip(self.netD, range(self.n_netD)):
-                    self.load_network(netD, 'D_%d' % n, opt.which_epoch)
+            self.load(opt.which_epoch)
 
         if self.isTrain:
             self.fake_pool = ImagePool(opt.pool_size)
@@ -89,8 +86,6 @@ class FCGANModel(BaseModel):
             for netD in self.netD:
                 params += list(netD.model.parameters())   # "all learnable parameters should be in netD.model"
             self.optimizer_D = FusedAdam(params, lr=opt.lr, betas=(opt.beta1, 0.999))
-            self.grad_sync = None   # data-parallel hook: callable(optimizer) run between backward and step
-            self._pool_override = None   # graphed step: static buffer the host-side ImagePool fills
             self._group = bool(self.gpu_ids) and not getattr(opt, 'no_group', False)
             n_streams = 2 * self.n_netD if (self.gpu_ids and not getattr(opt, 'no_d_streams', False)) else 0
             self._streams = [torch.cuda.Stream(device=self.device) for _ in range(n_streams)]
@@ -178,9 +173,6 @@ class FCGANModel(BaseModel):
         self.noise = self.noise_
         self.fake = self._fake_next
 
-    def _pool_source(self):
-        return self.fake
-
     def test(self):
         with torch.no_grad():
             self.noise = self._draw_noise()
@@ -235,8 +227,7 @@ class FCGANModel(BaseModel):
 
     def backward_D(self):
         """loss_D = 0.5 * (sum_i BCE(D_i(fake), 0) + sum_i BCE(D_i(real), 1))   (fcgan_model.py:146-163)"""
-        fake = self._pool_override if self._pool_override is not None else self.fake_pool.query(self.fake)
-        fake = fake.detach()
+        fake = self._pooled(0).detach()
         n = self.n_netD
         self.loss_D, self._each_D = self._d_losses([(d, fake, False) for d in self.netD] + [(d, self.real, True) for d in self.netD],
                                                    [0.5] * (2 * n))
@@ -265,25 +256,19 @@ class FCGANModel(BaseModel):
     def loss_D_real(self):
         return self._each_D[self.n_netD:].sum()
 
-    def optimize_parameters(self):
-        ops.begin_step(self.optimizer_D.take_zeroing())      # one launch zeroes every statistics arena of the step and D's gradients
-        self.forward()
-        for _ in range(self.opt.n_update_D):
-            self.optimizer_D.zero_grad()
-            self.backward_D()
-            if self.grad_sync is not None:
-                self.grad_sync(self.optimizer_D)
-            self.optimizer_D.step()
-            if self.opt.n_update_D > 1:
-                self.sample_noise()
-        for _ in range(self.opt.n_update_G):
-            self.optimizer_G.zero_grad()
-            self.backward_G()
-            if self.grad_sync is not None:
-                self.grad_sync(self.optimizer_G)
-            self.optimizer_G.step()
-            if self.opt.n_update_G > 1:
-                self.sample_noise()
+    # ---- the step (fcgan_model.py:178-193), as BaseModel.optimize_parameters and graph_step.GraphedStep run it --------------------
+    def step_stages(self):
+        o = self.opt
+        return [(self.optimizer_D, self.backward_D, o.n_update_D), (self.optimizer_G, self.backward_G, o.n_update_G)]
+
+    def step_zeroing(self):
+        return self.optimizer_D.take_zeroing()      # the step's one zeroing launch clears D's gradients too
+
+    def step_pools(self):
+        return [(self.fake_pool, lambda: self.fake)]
+
+    def check_graphable(self):
+        assert self.opt.n_update_D == 1, "graphed step supports n_update_D == 1 (every README recipe)"
 
     def get_current_errors(self):
         return OrderedDict([('G_GAN', float(self.loss_G.detach())), ('D_real', float(self.loss_D_real)),
@@ -375,17 +360,7 @@ class FCGANModel(BaseModel):
         else:
             self.fixed_noiseB = self.noise
 
-    def save(self, label):
-        self.save_network(self.netG, 'G', label, gpu_ids=self.gpu_ids)
-        for netD, n in zip(self.netD, range(self.n_netD)):
-            self.save_network(netD, 'D_%d' % n, label, self.gpu_ids)
+    def checkpoint_nets(self):
+        return [('G', self.netG)] + [('D_%d' % n, netD) for n, netD in enumerate(self.netD if self.isTrain else [])]
 
-    def update_learning_rate(self):
-        lrd = self.opt.lr / self.opt.niter_decay
-        lr = self.old_lr - lrd
-        for opt_ in (self.optimizer_D, self.optimizer_G):
-            for param_group in opt_.param_groups:
-                param_group['lr'] = lr
-            opt_.sync_lr()
-        print('update learning rate: %f -> %f' % (self.old_lr, lr))
-        self.old_lr = lr
+    update_learning_rate = BaseModel.decay_single_rate

@@ -1,17 +1,18 @@
-"""hipGraph capture of FCGANModel.optimize_parameters (models/fcgan_model.py:178-193) and
-CGANModel.optimize_parameters (models/cgan_model.py:212-226).
+"""hipGraph capture of a trainer's optimize_parameters (models/fcgan_model.py:178-193, models/cgan_model.py:212-226, ...).  Every
+trainer states its step once (BaseModel.step_stages); BaseModel.optimize_parameters runs the program built from it launch by
+launch, GraphedStep captures the very same program.
 
 A bs=1 step is a few hundred short kernels; launched eagerly from Python the host is the bottleneck.
 The step is therefore captured once into hipGraphs and replayed:
 
     graph A : forward()                      latent fill + G forward -> static `fake` (cgan: cat(real_A, fake_B))
     host    : ImagePool.query(fake)          the reference's python-random history policy, one D2D copy
-    graph B : D step, then the G step(s)     zero_grad / backward / Adam, loss scalars left on device
+    graph B : BaseModel.step_program()       D step(s), then the G step(s): zero_grad / backward / Adam, loss scalars left on device
 
 Everything that changes from step to step lives in device memory the kernels read and advance
 themselves (Adam step counter and LR, Philox offset, BatchNorm num_batches_tracked), so replays are
 faithful.  With data parallelism the gradient all-reduce is not captured: graph B is cut at the
-two/three synchronisation points and RCCL runs between the pieces on the same stream.
+program's ("sync", optimizer) items -- one per update -- and RCCL runs between the pieces on the same stream.
 
 Prefetch (fcgan with n_update_G > 1): the re-draw that ends a step and the forward() that opens the next one are two generator
 passes over the same weights, each a chain of launches too small to fill the card (~100 us for 4 GFLOP).  The graphed step runs
@@ -26,45 +27,23 @@ from . import ops
 
 
 class GraphedStep:
-    """Works on any trainer exposing optimizer_D/G, backward_D/G, forward, sample_noise, fake_pool, `_pool_source()`
-    (what the reference feeds ImagePool.query) and `_pool_override`; or, for trainers with their own step structure
-    (the two-stage models), `graph_spec()` -> dict(pools, sources, set_overrides, program)."""
+    """Captures the step a trainer declares (base_model.BaseModel): `step_program()` is what graph B runs, `step_zeroing()` what the
+    first launch clears, `step_pools()` the ImagePools the host queries between the graphs, `_pool_overrides` the static buffers
+    the discriminator step reads in their place, `check_graphable()` the trainer's own preconditions."""
 
     def __init__(self, model, warmup_steps=2):
         self.m = model
-        opt = model.opt
-        assert hasattr(model, "graph_spec") or opt.n_update_D == 1, "graphed step supports n_update_D == 1 (every README recipe)"
-        assert opt.batchSize == 1
+        model.check_graphable()
+        assert model.opt.batchSize == 1
         self._captured = False
         self._warmup_steps = warmup_steps
         self._arenas = ops.ArenaPool()      # a captured program owns the pool its arenas came from: the graphs point into its slots
-        self._prefetch = (not hasattr(model, "graph_spec") and hasattr(model, "prefetch_supported") and model.prefetch_supported()
+        self._prefetch = (hasattr(model, "prefetch_supported") and model.prefetch_supported()
                           and os.environ.get("SGAN_NO_G_PREFETCH", "0") in ("", "0"))
 
-    # the step cut into capturable segments; "sync_D"/"sync_G" are the data-parallel hand-off points
-    def _program(self):
-        m, o = self.m, self.m.opt
-        prog = [[m.optimizer_D.zero_grad, m.backward_D], "sync_D", [m.optimizer_D.step]]
-        for _ in range(o.n_update_G):
-            prog[-1] += [m.optimizer_G.zero_grad, m.backward_G]
-            prog += ["sync_G", [m.optimizer_G.step]]
-            if o.n_update_G > 1:
-                prog[-1].append(m.sample_noise)
-        if self._prefetch:
-            prog[-1][-1] = m.sample_noise_and_prefetch
-        return prog
-
     def _begin(self):
-        """Start of a step: the arenas' zeroing launch, which also clears the gradient buffers optimizer_D.zero_grad() is about to."""
-        opt_d = getattr(self.m, "optimizer_D", None)
-        ops.begin_step(opt_d.take_zeroing() if (hasattr(opt_d, "take_zeroing") and not hasattr(self.m, "graph_spec")) else ())
-
-    def _spec(self):
-        m = self.m
-        if hasattr(m, "graph_spec"):
-            return m.graph_spec()
-        return dict(pools=[m.fake_pool], sources=lambda: [m._pool_source()],
-                    set_overrides=lambda views: setattr(m, "_pool_override", views[0]), program=self._program())
+        """Start of a step: the arenas' zeroing launch, which also clears the gradient buffers the trainer folds into it."""
+        ops.begin_step(self.m.step_zeroing())
 
     def capture(self, example_input):
         """Warm-up steps, the eager run of the graph's own program and every capture draw their arenas from this step's own pool;
@@ -75,7 +54,10 @@ class GraphedStep:
     def _capture_all(self, example_input):
         m = self.m
         assert getattr(m, "noise_source", None) is None, "graphed step draws its latents on the device"
-        spec = self._spec()
+        program, pools = m.step_program(), m.step_pools()
+        if self._prefetch:
+            program[-1][-1] = m.sample_noise_and_prefetch      # the step's last re-draw also runs the next step's forward()
+        sources = lambda: [source() for _, source in pools]      # noqa: E731
         for _ in range(self._warmup_steps - (1 if self._prefetch else 0)):   # lazy state (optimizer moments, caches) must exist before capture
             m.set_input(example_input)
             m.optimize_parameters()
@@ -92,23 +74,17 @@ class GraphedStep:
             with torch.cuda.stream(self._cap_stream):
                 self._begin()
                 m.forward()
-                for item in self._program():
-                    if isinstance(item, list):
-                        for f in item:
-                            f()
-                    elif m.grad_sync is not None:
-                        m.grad_sync(m.optimizer_D if item == "sync_D" else m.optimizer_G)
+                m.run_program(program)
             torch.cuda.current_stream().wait_stream(self._cap_stream)
-        for name in ("optimizer_D", "optimizer_D1", "optimizer_D2", "optimizer_G"):
-            if hasattr(m, name):
-                getattr(m, name).sync_lr()
+        for optimizer, _, _ in m.step_stages():
+            optimizer.sync_lr()
         torch.cuda.synchronize()
         if self._prefetch:
             m.adopt_prefetched()
-        self.pools = spec["pools"]
-        shapes = [tuple(t.shape) for t in spec["sources"]()]
+        self.pools = [pool for pool, _ in pools]
+        shapes = [tuple(t.shape) for t in sources()]
         self.fake_for_D = [torch.zeros((h, w, ops.pad4(nc)), dtype=torch.float32, device=m.device) for (_, nc, h, w) in shapes]
-        spec["set_overrides"]([ops.logical_view(buf, sh[1]) for buf, sh in zip(self.fake_for_D, shapes)])
+        m._pool_overrides = [ops.logical_view(buf, sh[1]) for buf, sh in zip(self.fake_for_D, shapes)]
         # with a process group alive its watchdog thread polls CUDA events: only the capturing thread is held to the
         # capture rules then (PyTorch's recipe for graphs next to NCCL)
         dist_on = torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
@@ -118,7 +94,7 @@ class GraphedStep:
             torch.cuda.synchronize()
         if self._prefetch:
             self.gA = None
-            self._fakeA = spec["sources"]()      # the kept forward's output: every replay's two-problem pass rewrites it in place
+            self._fakeA = sources()      # the kept forward's output: every replay's two-problem pass rewrites it in place
             pool = None
             merged = [self._begin]
         else:
@@ -126,23 +102,17 @@ class GraphedStep:
             with torch.cuda.graph(self.gA, capture_error_mode=self._mode):
                 self._begin()      # the statistics arenas of the whole step (graph A and every piece of graph B), one launch
                 m.forward()
-                self._fakeA = spec["sources"]()
+                self._fakeA = sources()
             pool = self.gA.pool()
             merged = []
         self.segs = []
-        for item in spec["program"]:
-            if isinstance(item, tuple):          # ("sync", optimizer): data-parallel hand-off point
-                if m.grad_sync is not None:
-                    self.segs.append(("graph", self._capture(merged, pool, self._mode)))
-                    self.segs.append(("sync", item[1]))
-                    merged = []
-            elif isinstance(item, str):
-                if m.grad_sync is not None:
-                    self.segs.append(("graph", self._capture(merged, pool, self._mode)))
-                    self.segs.append(("sync", m.optimizer_D if item == "sync_D" else m.optimizer_G))
-                    merged = []
-            else:
+        for item in program:
+            if isinstance(item, list):
                 merged += item
+            elif m.grad_sync is not None:        # ("sync", optimizer): data-parallel hand-off point, graph B is cut here
+                self.segs.append(("graph", self._capture(merged, pool, self._mode)))
+                self.segs.append(item)
+                merged = []
         if merged:
             self.segs.append(("graph", self._capture(merged, pool, self._mode)))
         self._captured = True

@@ -67,18 +67,9 @@ class SegmentationCycleModel(CGANCycleModel):
             if self.gpu_ids:
                 networks.pack_flat(self.netD2)
         if self.isTrain and opt.sequential_train and not opt.continue_train:
-            for label, net in (('G1', self.netG1), ('G2', self.netG2)):
-                if label in opt.which_model_to_load:
-                    self.load_network(net, label, opt.which_epoch_sequential, model_dir=opt.pretrained_model_dir)
-            if 'D2' in opt.which_model_to_load:
-                for n, netD in enumerate(self.netD2):
-                    self.load_network(netD, 'D2_%d' % n, opt.which_epoch_sequential, model_dir=opt.pretrained_model_dir)
+            self.load(opt.which_epoch_sequential, only=opt.which_model_to_load, model_dir=opt.pretrained_model_dir)
         if not self.isTrain or opt.continue_train:
-            self.load_network(self.netG1, 'G1', opt.which_epoch)
-            self.load_network(self.netG2, 'G2', opt.which_epoch)
-            if self.isTrain:
-                for n, netD in enumerate(self.netD2):
-                    self.load_network(netD, 'D2_%d' % n, opt.which_epoch)
+            self.load(opt.which_epoch)
         if self.isTrain:
             self.fake_pool2 = ImagePool(opt.pool_size)
             self.old_lr, self.old_lr1, self.old_lr2 = opt.lr, opt.lr1, opt.lr2
@@ -88,17 +79,19 @@ class SegmentationCycleModel(CGANCycleModel):
                                            {'name': 'G2', 'params': self.netG2.parameters(), 'lr': opt.lr2}],
                                           lr=opt.lr, betas=(opt.beta1, 0.999))
             self.optimizer_D2 = FusedAdam([p for d in self.netD2 for p in d.model.parameters()], lr=opt.lr2, betas=(opt.beta1, 0.999))
-            self.grad_sync = None
-            self._pool_overrides = None
+            self.optimizer_D2.param_groups[0]['name'] = 'D2'      # decay_three_rates: follows lr2
         SegmentationModel.reset_accs(self)
 
-    def graph_spec(self):
+    # ---- the step (:261-278): D2, then G1 and G2 together; G1 follows lr1, G2 and D2 follow lr2 (:313-332) ------------------------
+    def step_stages(self):
         o = self.opt
-        assert (o.n_update_D2, o.n_update_G) == (1, 1), "graphed segmentation_cycle step: one update each"
-        prog = [[self.optimizer_D2.zero_grad, self.backward_D2], ("sync", self.optimizer_D2),
-                [self.optimizer_D2.step, self.optimizer_G.zero_grad, self.backward_G], ("sync", self.optimizer_G), [self.optimizer_G.step]]
-        return dict(pools=[self.fake_pool2], sources=lambda: [self._d_fake_source()],
-                    set_overrides=lambda views: setattr(self, "_pool_overrides", views), program=prog)
+        return [(self.optimizer_D2, self.backward_D2, o.n_update_D2), (self.optimizer_G, self.backward_G, o.n_update_G)]
+
+    def step_pools(self):
+        return [(self.fake_pool2, self._d_fake_source)]
+
+    def checkpoint_nets(self):
+        return [('G1', self.netG1), ('G2', self.netG2)] + [('D2_%d' % n, d) for n, d in enumerate(self.netD2 if self.isTrain else [])]
 
     # ---- data / forward ---------------------------------------------------------------------------
     def set_input(self, input):
@@ -135,8 +128,7 @@ class SegmentationCycleModel(CGANCycleModel):
 
     def backward_D2(self):
         """(:201-222)"""
-        fake = self._pool_overrides[0] if self._pool_overrides is not None else self.fake_pool2.query(self._d_fake_source())
-        fake = fake.detach()
+        fake = self._pooled(0).detach()
         real = self.real_A if self.opt.no_cgan else networks.cat_pair(self.real_B, self.real_A)
         n = self.n_netD2
         self.loss_D2, each = self._gan([(d, fake, False) for d in self.netD2] + [(d, real, True) for d in self.netD2], [0.5] * (2 * n))
@@ -157,20 +149,6 @@ class SegmentationCycleModel(CGANCycleModel):
         self.loss_G = self.loss_G1_CE * o.lambda_A + self.loss_G2_GAN + self.loss_G_L1 * o.lambda_B + self.loss_G_cycle * o.lambda_A_cycle
         self._backward(self.loss_G)
 
-    def optimize_parameters(self):
-        ops.begin_step()      # one launch zeroes every statistics arena of the step
-        o = self.opt
-        self.forward()
-        for n_up, opt_, back in ((o.n_update_D2, self.optimizer_D2, self.backward_D2), (o.n_update_G, self.optimizer_G, self.backward_G)):
-            for _ in range(n_up):
-                opt_.zero_grad()
-                back()
-                if self.grad_sync is not None:
-                    self.grad_sync(opt_)
-                opt_.step()
-                if n_up > 1:
-                    self.sample_noise()
-
     def get_current_errors(self):
         return OrderedDict([('G_CE', float(self.loss_G1_CE.detach())), ('G_GAN', float(self.loss_G2_GAN.detach())),
                             ('G_L1', float(self.loss_G_L1.detach())), ('G_cycle', float(self.loss_G_cycle.detach())),
@@ -180,25 +158,6 @@ class SegmentationCycleModel(CGANCycleModel):
         three = lambda t: t if t.shape[1] in (1, 3) else torch.cat([t, torch.zeros_like(t[:, :1])], 1)[:, :3]      # noqa: E731
         return OrderedDict([('image', self.real_A.detach()), ('label', three(self.real_B.detach() * 2 - 1)),
                             ('prediction', three(self.fake_B.detach() * 2 - 1))])
-
-    def save(self, label):
-        self.save_network(self.netG1, 'G1', label, gpu_ids=self.gpu_ids)
-        self.save_network(self.netG2, 'G2', label, gpu_ids=self.gpu_ids)
-        for n, netD in enumerate(self.netD2):
-            self.save_network(netD, 'D2_%d' % n, label, gpu_ids=self.gpu_ids)
-
-    def update_learning_rate(self):
-        """(:313-332): G1 follows lr1, G2 and D2 follow lr2."""
-        nd = self.opt.niter_decay
-        lr, lr1, lr2 = (max(0, old - base / nd) for old, base in ((self.old_lr, self.opt.lr), (self.old_lr1, self.opt.lr1), (self.old_lr2, self.opt.lr2)))
-        for g in self.optimizer_D2.param_groups:
-            g['lr'] = lr2
-        for g in self.optimizer_G.param_groups:
-            g['lr'] = lr1 if g.get('name') == 'G1' else lr2 if g.get('name') == 'G2' else lr
-        self.optimizer_D2.sync_lr()
-        self.optimizer_G.sync_lr()
-        print('update learning rate: %f -> %f, %f -> %f' % (self.old_lr1, lr1, self.old_lr2, lr2))
-        self.old_lr, self.old_lr1, self.old_lr2 = lr, lr1, lr2
 
     reset_accs = SegmentationModel.reset_accs
     _acc_buffers = SegmentationModel._acc_buffers

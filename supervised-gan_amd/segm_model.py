@@ -6,7 +6,8 @@ cat(real_A, .); generator loss = sum_i lambda_i GAN(D_i(fake), 1) + (class-weigh
 generator trained on the (class-weighted) cross-entropy alone.  With no second consumer of the prediction the loss section of the
 step -- softmax / sigmoid, the loss, d loss / d logits -- is one launch (losses.seg_head, sgan_seg_head).
 
-Built on CGANModel: discriminator step, pooling, optimizers, checkpoints and the hipGraph step are inherited; the generator runs
+Built on CGANModel: the step with or without its discriminator stage, pooling, optimizers, checkpoints and the LR schedule are
+inherited; the generator runs
 with the caller's `activation=` (identity) so the conv chain ends raw; softmax / cross-entropy (models/loss.py:6-12 is
 NLLLoss2d(log_softmax)) and the sigmoid / weighted BCE of `--use_sigmoid_ss` are kernels of losses.py on the num_classes x H x W maps."""
 from collections import OrderedDict
@@ -42,7 +43,6 @@ class SegmentationModel(CGANModel):
                 "--weights: one per class (%d) for the softmax cross-entropy" % self.num_classes
             self.loss_G_GAN = 0
             self.norm = None      # sum_p w[label_p], a persistent device scalar refreshed with the label (softmax mode)
-            self.graph_spec = self._graph_spec_no_netD      # an attribute of THIS trainer only: GraphedStep looks for it
         self.reset_accs()
 
     def _builds_netD(self, opt):
@@ -125,44 +125,6 @@ class SegmentationModel(CGANModel):
             netD.compute_param_grads = True
         self.loss_G = self.loss_G_GAN + self.compute_cross_entropy_loss(weighted=True)
         self._backward(self.loss_G)
-
-    def optimize_parameters(self):
-        if not self.no_netD:
-            return CGANModel.optimize_parameters(self)
-        ops.begin_step(())                                   # segm_model.py:237-251 without the discriminator loop
-        self.forward()
-        for _ in range(self.opt.n_update_G):
-            self.optimizer_G.zero_grad()
-            self.backward_G()
-            if self.grad_sync is not None:
-                self.grad_sync(self.optimizer_G)
-            self.optimizer_G.step()
-            if self.opt.n_update_G > 1:
-                self.sample_noise()
-
-    def _graph_spec_no_netD(self):
-        """The step as graph_step.GraphedStep captures it: no pool, nothing to hand to a discriminator, the generator updates."""
-        prog = []
-        for _ in range(self.opt.n_update_G):
-            prog += [[self.optimizer_G.zero_grad, self.backward_G], ("sync", self.optimizer_G), [self.optimizer_G.step]]
-            if self.opt.n_update_G > 1:
-                prog[-1].append(self.sample_noise)
-        return dict(pools=[], sources=lambda: [], set_overrides=lambda views: None, program=prog)
-
-    def save(self, label):
-        if not self.no_netD:
-            return CGANModel.save(self, label)
-        self.save_network(self.netG, 'G', label, gpu_ids=self.gpu_ids)
-
-    def update_learning_rate(self):
-        if not self.no_netD:
-            return CGANModel.update_learning_rate(self)
-        lr = self.old_lr - self.opt.lr / self.opt.niter_decay
-        for param_group in self.optimizer_G.param_groups:
-            param_group['lr'] = lr
-        self.optimizer_G.sync_lr()
-        print('update learning rate: %f -> %f' % (self.old_lr, lr))
-        self.old_lr = lr
 
     def get_current_errors(self):
         if self.no_netD:                                     # :253-257

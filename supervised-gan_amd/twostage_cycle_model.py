@@ -98,23 +98,10 @@ class TwoStageCycleModel(BaseModel):
             if self.gpu_ids:
                 networks.pack_flat(self.netD1)
                 networks.pack_flat(self.netD2)
-        nets = [('G1', self.netG1), ('G2', self.netG2)] + ([('F2', self.netF2)] if self.cycle else [])
-        self._gnets = nets
         if self.isTrain and opt.sequential_train:
-            for label, net in nets:
-                if label in opt.which_model_to_load:
-                    self.load_network(net, label, opt.which_epoch_sequential, model_dir=opt.pretrained_model_dir)
-            for tag, ds in (('D1', self.netD1), ('D2', self.netD2)):
-                if tag in opt.which_model_to_load:
-                    for n, netD in enumerate(ds):
-                        self.load_network(netD, '%s_%d' % (tag, n), opt.which_epoch_sequential, model_dir=opt.pretrained_model_dir)
+            self.load(opt.which_epoch_sequential, only=opt.which_model_to_load, model_dir=opt.pretrained_model_dir)
         if not self.isTrain or opt.continue_train:
-            for label, net in nets:
-                self.load_network(net, label, opt.which_epoch)
-            if self.isTrain:
-                for tag, ds in (('D1', self.netD1), ('D2', self.netD2)):
-                    for n, netD in enumerate(ds):
-                        self.load_network(netD, '%s_%d' % (tag, n), opt.which_epoch)
+            self.load(opt.which_epoch)
 
         if self.isTrain:
             self.fake_pool1 = ImagePool(opt.pool_size)
@@ -136,39 +123,40 @@ class TwoStageCycleModel(BaseModel):
             self.optimizer_G = AdamGroups(groups, lr=opt.lr, betas=(opt.beta1, 0.999))
             self.optimizer_D1 = FusedAdam([p for d in self.netD1 for p in d.model.parameters()], lr=opt.lr1, betas=(opt.beta1, 0.999))
             self.optimizer_D2 = FusedAdam([p for d in self.netD2 for p in d.model.parameters()], lr=opt.lr2, betas=(opt.beta1, 0.999))
-            self.grad_sync = None
-            self._pool_overrides = None     # graphed step: static buffers the host-side ImagePools fill
+            self.optimizer_D1.param_groups[0]['name'], self.optimizer_D2.param_groups[0]['name'] = 'D1', 'D2'      # decay_three_rates
 
-    # ---- hipGraph hooks (graph_step.GraphedStep) --------------------------------------------------
-    def _pool_sources(self):
-        """What the step feeds to ImagePool.query, in the reference's order (backward_D1, then backward_D2_binary)."""
-        o = self.opt
-        srcs = [self.fake_A]
-        if self.multi_class:
-            return srcs + [self._pair(self.real_A, self.fake_B_from_real_A), self._pair(self.transform(self.fake_A), self.fake_B_from_fake_A)]
-        if 'real_fake' in o.GAN_losses_D2:
-            srcs.append(self._pair(self.real_A, self.fake_B_from_real_A))
-        if 'fake_fake' in o.GAN_losses_D2:
-            srcs.append(self._pair(self.transform(self.fake_A), self.fake_B_from_fake_A))
-        return srcs
-
-    def _query(self, idx, pool, src):
-        if self._pool_overrides is not None:
-            return self._pool_overrides[idx]
-        return pool.query(src())
-
-    def graph_spec(self):
+    # ---- the step (:412-437; twostage_model.py:379-395: one update each), as BaseModel.optimize_parameters and GraphedStep run it ----
+    def step_stages(self):
         o = self.opt
         ups = (o.n_update_D1, o.n_update_D2, o.n_update_G) if self.cycle else (1, 1, 1)
-        assert ups == (1, 1, 1) and not o.use_fixed_noise1, "graphed two-stage step: one update each, device-drawn latents"
-        npool2 = ('real_fake' in o.GAN_losses_D2) + ('fake_fake' in o.GAN_losses_D2)
-        pools2 = [self.fake_pool2_1, self.fake_pool2_2] if self.multi_class else [self.fake_pool2] * npool2
-        prog = [[self.optimizer_D1.zero_grad, self.backward_D1], ("sync", self.optimizer_D1),
-                [self.optimizer_D1.step, self.optimizer_D2.zero_grad, self.backward_D2], ("sync", self.optimizer_D2),
-                [self.optimizer_D2.step, self.optimizer_G.zero_grad, self.backward_G], ("sync", self.optimizer_G),
-                [self.optimizer_G.step]]
-        return dict(pools=[self.fake_pool1] + pools2, sources=self._pool_sources,
-                    set_overrides=lambda views: setattr(self, "_pool_overrides", views), program=prog)
+        return [(self.optimizer_D1, self.backward_D1, ups[0]), (self.optimizer_D2, self.backward_D2, ups[1]),
+                (self.optimizer_G, self.backward_G, ups[2])]
+
+    def step_pools(self):
+        """backward_D1's fake label, then the (label, image) pairs of backward_D2 in its order."""
+        o = self.opt
+        real_fake = lambda: self._pair(self.real_A, self.fake_B_from_real_A)      # noqa: E731
+        fake_fake = lambda: self._pair(self.transform(self.fake_A), self.fake_B_from_fake_A)      # noqa: E731
+        pools = [(self.fake_pool1, lambda: self.fake_A)]
+        if self.multi_class:      # one pool per fake class (:122-124)
+            return pools + [(self.fake_pool2_1, real_fake), (self.fake_pool2_2, fake_fake)]
+        if 'real_fake' in o.GAN_losses_D2:
+            pools.append((self.fake_pool2, real_fake))
+        if 'fake_fake' in o.GAN_losses_D2:
+            pools.append((self.fake_pool2, fake_fake))
+        return pools
+
+    def check_graphable(self):
+        assert all(n == 1 for _, _, n in self.step_stages()) and not self.opt.use_fixed_noise1, \
+            "graphed two-stage step: one update each, device-drawn latents"
+
+    def checkpoint_nets(self):
+        nets = [('G1', self.netG1), ('G2', self.netG2)] + ([('F2', self.netF2)] if self.cycle else [])
+        for tag, ds in (('D1', self.netD1), ('D2', self.netD2)) if self.isTrain else ():
+            nets += [('%s_%d' % (tag, n), netD) for n, netD in enumerate(ds)]
+        return nets
+
+    update_learning_rate = BaseModel.decay_three_rates      # (:477-500)
 
     # ---- data ---------------------------------------------------------------------------------
     def set_input(self, input):
@@ -236,7 +224,7 @@ class TwoStageCycleModel(BaseModel):
 
     def backward_D1(self):
         """(:245-262)"""
-        fake = self._query(0, self.fake_pool1, lambda: self.fake_A).detach()
+        fake = self._pooled(0).detach()
         real = self.transform_inverse(self.real_A)
         n = self.n_netD1
         self.loss_D1, each = self._gan(self.criterionGAN1, [(d, fake, False) for d in self.netD1] + [(d, real, True) for d in self.netD1],
@@ -251,12 +239,7 @@ class TwoStageCycleModel(BaseModel):
         """(:264-299) -- one ImagePool serves both fake pairs, queried in the reference's order."""
         o = self.opt
         jobs, n = [], self.n_netD2
-        fakes = []
-        if 'real_fake' in o.GAN_losses_D2:
-            fakes.append(self._query(1, self.fake_pool2, lambda: self._pair(self.real_A, self.fake_B_from_real_A)).detach())
-        if 'fake_fake' in o.GAN_losses_D2:
-            fakes.append(self._query(1 + len(fakes), self.fake_pool2,
-                                     lambda: self._pair(self.transform(self.fake_A), self.fake_B_from_fake_A)).detach())
+        fakes = [self._pooled(i).detach() for i in range(1, len(self.step_pools()))]
         num_fake_pairs = len(fakes)
         for f in fakes:
             jobs += [(d, f, False) for d in self.netD2]
@@ -277,8 +260,7 @@ class TwoStageCycleModel(BaseModel):
     def backward_D2_multiclass(self):
         """(:302-335): classes 0 = (real_A, real_B), 1 = (real_A, fake_B), 2 = (fake_A, fake_B); cross-entropy; one pool per fake class."""
         real = self._pair(self.real_A, self.real_B)
-        f1 = self._query(1, self.fake_pool2_1, lambda: self._pair(self.real_A, self.fake_B_from_real_A)).detach()
-        f2 = self._query(2, self.fake_pool2_2, lambda: self._pair(self.transform(self.fake_A), self.fake_B_from_fake_A)).detach()
+        f1, f2 = self._pooled(1).detach(), self._pooled(2).detach()
         n = self.n_netD2
         preds = networks.multi_forward([(d, real) for d in self.netD2] + [(d, f1) for d in self.netD2] + [(d, f2) for d in self.netD2])
         ce = [sum(self.criterionGAN2(p, k) for p in preds[k * n:(k + 1) * n]) for k in range(3)]
@@ -338,23 +320,6 @@ class TwoStageCycleModel(BaseModel):
             + self.loss_G2_fake_cycle * o.lambda_A_cycle * o.lambda_fake_cycle
         self._backward(self.loss_G)
 
-    def optimize_parameters(self):
-        ops.begin_step()      # one launch zeroes every statistics arena of the step
-        o = self.opt
-        self.forward()
-        ups = (o.n_update_D1, o.n_update_D2, o.n_update_G) if self.cycle else (1, 1, 1)     # twostage_model.py:379-395: one each
-        for n_up, opt_, back in ((ups[0], self.optimizer_D1, self.backward_D1),
-                                 (ups[1], self.optimizer_D2, self.backward_D2),
-                                 (ups[2], self.optimizer_G, self.backward_G)):
-            for _ in range(n_up):
-                opt_.zero_grad()
-                back()
-                if self.grad_sync is not None:
-                    self.grad_sync(opt_)
-                opt_.step()
-                if n_up > 1:
-                    self.sample_noise()
-
     def get_current_errors(self):
         f = lambda v: float(v.detach()) if torch.is_tensor(v) else float(v)
         if not self.cycle:
@@ -372,30 +337,6 @@ class TwoStageCycleModel(BaseModel):
                 out.update([('fake_A_real_B', self.fake_A_from_real_B.detach()), ('recon_real_A', self.recon_real_A.detach()),
                             ('recon_fake_A', self.recon_fake_A.detach())])
         return out
-
-    def save(self, label):
-        for tag, net in self._gnets:
-            self.save_network(net, tag, label, gpu_ids=self.gpu_ids)
-        for tag, ds in (('D1', self.netD1), ('D2', self.netD2)):
-            for n, netD in enumerate(ds):
-                self.save_network(netD, '%s_%d' % (tag, n), label, gpu_ids=self.gpu_ids)
-
-    def update_learning_rate(self):
-        """(:477-500)"""
-        o = self.opt
-        lr = max(0, self.old_lr - o.lr / o.niter_decay)
-        lr1 = max(0, self.old_lr1 - o.lr1 / o.niter_decay)
-        lr2 = max(0, self.old_lr2 - o.lr2 / o.niter_decay)
-        for g in self.optimizer_D1.param_groups:
-            g['lr'] = lr1
-        for g in self.optimizer_D2.param_groups:
-            g['lr'] = lr2
-        for g in self.optimizer_G.param_groups:
-            g['lr'] = {'G1': lr1, 'G2': lr2, 'F2': lr2}.get(g.get('name'), lr)
-        for opt_ in (self.optimizer_D1, self.optimizer_D2, self.optimizer_G):
-            opt_.sync_lr()
-        print('update learning rate: %f -> %f, %f -> %f' % (self.old_lr1, lr1, self.old_lr2, lr2))
-        self.old_lr, self.old_lr1, self.old_lr2 = lr, lr1, lr2
 
 
 class TwoStageModel(TwoStageCycleModel):
@@ -438,12 +379,7 @@ class TwoStageFactDModel(TwoStageModel):
         loss_D2 = (sum over fake pairs / their number + real) * 0.5 as one weighted sum, in chunks of <= 8 terms."""
         o = self.opt
         n, nc = self.n_netD2, o.input_nc
-        fakes = []
-        if 'real_fake' in o.GAN_losses_D2:
-            fakes.append(self._query(1, self.fake_pool2, lambda: self._pair(self.real_A, self.fake_B_from_real_A)).detach())
-        if 'fake_fake' in o.GAN_losses_D2:
-            fakes.append(self._query(1 + len(fakes), self.fake_pool2,
-                                     lambda: self._pair(self.transform(self.fake_A), self.fake_B_from_fake_A)).detach())
+        fakes = [self._pooled(i).detach() for i in range(1, len(self.step_pools()))]
         num_fake_pairs = len(fakes)
         terms = []
         for f in fakes:

@@ -45,6 +45,16 @@ CGAN_CYCLE = ["--model", "cgan_cycle", "--which_direction", "AtoB", "--dataset_m
               "--weights", "2", "4"]
 
 
+# the segmentation trainers: class logits out of G (G1), one discriminator on cat(image, one-hot) / cat(one-hot, image)
+SEGM = ["--model", "segmentation", "--which_direction", "AtoB", "--dataset_mode", "aligned", "--fineSize", "128", "--which_model_netG", "unet_128",
+        "--ngf", "8", "--which_channel", "b_rg", "--no_dropout", "--which_model_netD", "n_layers", "--n_layers_D", "3", "--ndf", "8",
+        "--scale_factor", "1", "--lambda_D", "1.0", "--weights", "1", "2", "--no_lsgan"]
+SEGM_CYCLE = ["--model", "segmentation_cycle", "--which_direction", "AtoB", "--dataset_mode", "aligned", "--fineSize", "128",
+              "--which_channel", "b_rg", "--which_model_netG1", "unet_128", "--ngf1", "8", "--which_model_netG2", "unet_128", "--ngf2", "8",
+              "--no_dropout1", "--no_dropout2", "--which_model_netD2", "n_layers", "--n_layers_D2", "3", "--ndf2", "8", "--scale_factor2", "1",
+              "--lambda_D2", "1.0", "--no_lsgan2"]
+
+
 def _build(argv):
     from supervised_gan_amd.models import create_model
     from supervised_gan_amd.options import TrainOptions
@@ -61,8 +71,9 @@ def _ring(hw, n=4):
 
 
 @pytest.mark.parametrize("argv,hw,out", [(FCGAN, 128, "fake"), (CGAN, 256, "fake_B"), (TWOSTAGE, 256, "fake_B_from_fake_A"),
-                                         (CGAN_CYCLE, 256, "recon_A"), (FACTD, 256, "fake_B_from_fake_A")],
-                         ids=["fcgan", "cgan", "twostage_cycle", "cgan_cycle", "twostage_factd"])
+                                         (CGAN_CYCLE, 256, "recon_A"), (FACTD, 256, "fake_B_from_fake_A"), (SEGM, 128, "fake_B"),
+                                         (SEGM_CYCLE, 128, "recon_A")],
+                         ids=["fcgan", "cgan", "twostage_cycle", "cgan_cycle", "twostage_factd", "segmentation", "segmentation_cycle"])
 def test_graphed_step_equals_eager(argv, hw, out):
     if not torch.cuda.is_available():
         pytest.fail("-m gpu tests need an MI355X; no CUDA/HIP device is visible")

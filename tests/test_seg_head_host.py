@@ -69,10 +69,10 @@ def test_trainer_without_discriminators_builds_on_cpu(tmp_path):
     m.optimizer_G.sync_lr = lambda: None
     m.update_learning_rate()
     assert abs(m.optimizer_G.param_groups[0]["lr"] - (2e-4 - 2e-4 / 100)) < 1e-12
-    spec = m.graph_spec()
-    assert spec["pools"] == [] and spec["sources"]() == [] and spec["set_overrides"]([]) is None
-    lists = [item for item in spec["program"] if isinstance(item, list)]
-    syncs = [item for item in spec["program"] if isinstance(item, tuple)]
+    assert m.step_pools() == [] and len(m.step_zeroing()) == 0
+    program = m.step_program()
+    lists = [item for item in program if isinstance(item, list)]
+    syncs = [item for item in program if isinstance(item, tuple)]
     assert len(lists) == 4 and len(syncs) == 2 and all(s == ("sync", m.optimizer_G) for s in syncs)
     assert lists[0] == [m.optimizer_G.zero_grad, m.backward_G] and lists[1] == [m.optimizer_G.step, m.sample_noise]
     # --continue_train reads the generator's file only
@@ -81,8 +81,9 @@ def test_trainer_without_discriminators_builds_on_cpu(tmp_path):
         assert torch.equal(a, b), k
 
 
-def test_with_discriminators_the_trainer_has_no_graph_spec(tmp_path):
-    """graph_step.GraphedStep asks hasattr(model, 'graph_spec'): the step with discriminators must keep answering no."""
+def test_with_discriminators_the_step_is_the_conditional_gans(tmp_path):
+    """With discriminators the segmentation step stays CGANModel's: D then G, optimizer_D's zeroing folded into the step's first
+    launch, one ImagePool fed by _pool_source()."""
     from supervised_gan_amd.models import create_model
     from supervised_gan_amd.options import TrainOptions
     argv = _argv(tmp_path)
@@ -90,7 +91,11 @@ def test_with_discriminators_the_trainer_has_no_graph_spec(tmp_path):
     argv[i + 1] = "n_layers"
     m = create_model(TrainOptions().parse(argv + ["--ndf", "8", "--n_layers_D", "3", "--scale_factor", "1", "--lambda_D", "1.0"],
                                           save=False, verbose=False))
-    assert not hasattr(m, "graph_spec") and len(m.netD) == 1 and hasattr(m, "optimizer_D") and not m.no_netD
+    assert len(m.netD) == 1 and hasattr(m, "optimizer_D") and not m.no_netD
+    assert m.step_stages() == [(m.optimizer_D, m.backward_D, 1), (m.optimizer_G, m.backward_G, 2)]
+    m.optimizer_D.take_zeroing = lambda: "the zeroing of D"
+    assert m.step_zeroing() == "the zeroing of D"
+    assert m.step_pools() == [(m.fake_pool, m._pool_source)]
 
 
 def test_seg_head_composition_on_cpu_tensors():
