@@ -2,7 +2,7 @@
 // Gaussian pre-filter (strided, diagonal only), GAN loss on the logits map, tanh backward, layout
 // boundary copy, multi-segment Adam, Philox normal fill.  All are 16-byte-per-lane streaming
 // kernels (or tiny single-workgroup reductions); none allocates or synchronises.
-#include "sgan_common.h"
+#include "sgan_reduce.h"
 
 thread_local char g_sgan_err[512] = {0};
 thread_local const char* g_sgan_last_kernel = "";
@@ -90,8 +90,6 @@ extern "C" int sgan_profile_read(int i, const char** name, float* ms) {   // cal
     if (hipEventElapsedTime(ms, g_prof_e0[i], g_prof_e1[i]) != hipSuccess) return sgan_fail(SGAN_ERR_HIP, "hipEventElapsedTime failed");
     return SGAN_OK;
 }
-
-static inline int ew_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 // ------------------------------------------------------------------------------------------
 // InstanceNorm / BatchNorm(batch 1) backward, in place on dy
@@ -200,7 +198,7 @@ extern "C" int sgan_norm_bwd_apply_multi(const sgan_norm_bwd_job* jobs, int32_t 
         // every workgroup first turns the replica sums of ALL channels into coefficients (32 fp64 loads + a divide and a root per
         // channel): few, fat workgroups amortise that (SGAN_NBA_CHUNK 16-byte chunks per thread: tuning knob)
         static const int chunk = getenv("SGAN_NBA_CHUNK") ? atoi(getenv("SGAN_NBA_CHUNK")) : 4;
-        int blocks = ew_cdiv(total, 256 * (chunk > 0 ? chunk : 4));
+        int blocks = sg_cdiv(total, 256 * (chunk > 0 ? chunk : 4));
         if (blocks > 2048) blocks = 2048;
         if (blocks < 1) blocks = 1;
         J.blocks = blocks;
@@ -320,7 +318,7 @@ extern "C" int sgan_norm_apply_fwd(const float* u, int32_t u_ld, const sgan_norm
                                    const float* noise, float sigma, float* t, int32_t t_ld, int32_t npix, int32_t C, void* stream) {
     SGAN_CHECK(u && t && npix > 0 && C > 0 && (C & 3) == 0 && u_ld >= C && t_ld >= C && (u_ld & 3) == 0 && (t_ld & 3) == 0, "bad argument");
     const int64_t total = (int64_t)npix * (C >> 2);
-    int blocks = ew_cdiv(total, 256 * 2);
+    int blocks = sg_cdiv(total, 256 * 2);
     if (blocks > 2048) blocks = 2048;
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(sg_norm_apply_fwd_kernel, dim3(blocks), dim3(256), (size_t)3 * C * 4, (hipStream_t)stream, u, u_ld,
@@ -333,7 +331,7 @@ extern "C" int sgan_norm_apply_bwd_sums(float* dt, int32_t dt_ld, const float* m
                                         const sgan_norm_desc* u_norm, double* bwd_sums, int32_t npix, int32_t C, void* stream) {
     SGAN_CHECK(dt && u && bwd_sums && npix > 0 && C > 0 && (C & 3) == 0 && u_ld >= C && dt_ld >= C, "bad argument");
     const int64_t total = (int64_t)npix * (C >> 2);
-    int blocks = ew_cdiv(total, 256 * 8);
+    int blocks = sg_cdiv(total, 256 * 8);
     if (blocks > 512) blocks = 512;
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(sg_norm_apply_bwd_sums_kernel, dim3(blocks), dim3(256), (size_t)4 * C * 4, (hipStream_t)stream, dt, dt_ld,
@@ -392,7 +390,7 @@ extern "C" int sgan_pad_reflect_fwd(const float* x, int32_t x_ld, int32_t H, int
                "bad argument");
     SGAN_CHECK(pad >= 0 && pad < H && pad < W, "reflection padding must be smaller than the image");
     const int64_t total = (int64_t)(H + 2 * pad) * (W + 2 * pad) * (C >> 2);
-    int blocks = ew_cdiv(total, 256 * 4);
+    int blocks = sg_cdiv(total, 256 * 4);
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(sg_pad_reflect_fwd_kernel, dim3(blocks), dim3(256), (size_t)2 * C * 4, (hipStream_t)stream, x, x_ld, H, W, C,
                        sg_norm_from(x_norm), mask, pad, out, out_ld);
@@ -471,7 +469,7 @@ extern "C" int sgan_pad_reflect_bwd(const float* dout, int32_t dout_ld, int32_t 
     SGAN_CHECK(!(bwd_sums && !x), "bwd_sums needs x");
     SGAN_CHECK(!x || ((x_ld & 3) == 0 && x_ld >= C), "bad x_ld");
     const int64_t total = (int64_t)H * W * (C >> 2);
-    int blocks = ew_cdiv(total, 256 * 4);
+    int blocks = sg_cdiv(total, 256 * 4);
     if (blocks > 1024) blocks = 1024;
     hipLaunchKernelGGL(sg_pad_reflect_bwd_kernel, dim3(blocks), dim3(256), (size_t)4 * C * 4 + (size_t)2 * C * 8, (hipStream_t)stream, dout,
                        dout_ld, H, W, C, pad, x, x_ld, sg_norm_from(x ? x_norm : nullptr), mask, din, din_ld, bwd_sums, bwd_sums_sq_stride);
@@ -487,16 +485,14 @@ extern "C" int sgan_pad_reflect_bwd(const float* dout, int32_t dout_ld, int32_t 
 #define SG_IMGLOSS_BLOCKS 256
 __device__ __forceinline__ void sg_block_partial(double acc, double* part) {
     __shared__ double wsum[4];
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    SG_SYNC();
-    if (threadIdx.x == 0) part[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    const double sum = sg_block_sum<4>(acc, wsum);
+    if (threadIdx.x == 0) part[blockIdx.x] = sum;
 }
 
 __global__ __launch_bounds__(64) void sg_imgloss_fin_kernel(const double* part, int nparts, double scale, float* loss_out) {
     double acc = 0.0;
     for (int i = threadIdx.x; i < nparts; i += 64) acc += part[i];
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    acc = sg_wave_sum(acc);
     if (threadIdx.x == 0) loss_out[0] = (float)(acc * scale);
 }
 
@@ -544,9 +540,8 @@ __global__ __launch_bounds__(256) void sg_bce01_fwd_kernel(const float* x, int x
             float gv = 0.f;
             if (c < C) {
                 const float pr = (x[(int64_t)p * x_ld + c] + 1.f) * 0.5f, tg = (t[(int64_t)p * t_ld + c] + 1.f) * 0.5f;
-                const float lp = fmaxf(logf(pr), -100.f), lq = fmaxf(log1pf(-pr), -100.f);
-                acc += (double)(-(tg * lp + (1.f - tg) * lq));
-                gv = (pr - tg) / fmaxf(pr * (1.f - pr), 1e-12f) * 0.5f * (float)inv;
+                acc += (double)sg_bce_term(pr, tg);
+                gv = sg_bce_dterm(pr, tg) * 0.5f * (float)inv;
             }
             g[(int64_t)p * g_ld + c] = gv;
         }
@@ -555,7 +550,7 @@ __global__ __launch_bounds__(256) void sg_bce01_fwd_kernel(const float* x, int x
 }
 
 static int sg_imgloss_blocks(int npix) {
-    int b = ew_cdiv(npix, 256);
+    int b = sg_cdiv(npix, 256);
     return b > SG_IMGLOSS_BLOCKS ? SG_IMGLOSS_BLOCKS : b;
 }
 
@@ -594,7 +589,7 @@ extern "C" int sgan_l1w_fwd(const float* x, int32_t x_ld, const float* y, int32_
 
 extern "C" int sgan_scale(const float* gout, const float* g, float* dx, int64_t n, void* stream) {
     SGAN_CHECK(gout && g && dx && n > 0 && (n & 3) == 0, "bad argument");
-    int blocks = ew_cdiv(n / 4, 256);
+    int blocks = sg_cdiv(n / 4, 256);
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(sg_scale_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, gout, g, dx, n / 4);
     SGAN_LAUNCH_CHECK();
@@ -633,8 +628,10 @@ __global__ __launch_bounds__(256) void sg_ce_fwd_kernel(const float* logits, int
         s_num += (double)(w * (lse - zy));
         s_den += (double)w;
     }
+    // two sums behind one barrier, added w0 + w1 + w2 + w3: not sg_block_sum<4>'s pairing, and the order is part of the result
     __shared__ double red[2][4];
-    for (int o = 32; o > 0; o >>= 1) { s_num += __shfl_xor(s_num, o); s_den += __shfl_xor(s_den, o); }
+    s_num = sg_wave_sum(s_num);
+    s_den = sg_wave_sum(s_den);
     if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s_num; red[1][threadIdx.x >> 6] = s_den; }
     SG_SYNC();
     if (threadIdx.x == 0) {
@@ -667,7 +664,7 @@ __global__ __launch_bounds__(256) void sg_ce_bwd_kernel(const float* logits, int
 extern "C" int sgan_ce_fwd(const float* logits, int32_t ld, int32_t npix, int32_t C, const int64_t* label, int32_t const_label,
                            const float* class_w, double* acc, uint32_t* ticket, float* loss_out, void* stream) {
     SGAN_CHECK(logits && acc && ticket && loss_out && npix > 0 && C >= 1 && C <= SG_CE_MAXC && ld >= C, "bad argument (1..%d classes)", SG_CE_MAXC);
-    int blocks = ew_cdiv(npix, 256);
+    int blocks = sg_cdiv(npix, 256);
     if (blocks > 512) blocks = 512;
     hipLaunchKernelGGL(sg_ce_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, logits, ld, npix, C, label, const_label, class_w, acc,
                        ticket, loss_out);
@@ -678,7 +675,7 @@ extern "C" int sgan_ce_fwd(const float* logits, int32_t ld, int32_t npix, int32_
 extern "C" int sgan_ce_bwd(const float* logits, int32_t ld, int32_t npix, int32_t C, const int64_t* label, int32_t const_label,
                            const float* class_w, const double* acc, const float* gout, float* dlogits, int32_t dld, void* stream) {
     SGAN_CHECK(logits && acc && gout && dlogits && npix > 0 && C >= 1 && C <= SG_CE_MAXC && ld >= C && dld >= C, "bad argument");
-    int blocks = ew_cdiv(npix, 256);
+    int blocks = sg_cdiv(npix, 256);
     if (blocks > 1024) blocks = 1024;
     hipLaunchKernelGGL(sg_ce_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, logits, ld, npix, C, label, const_label, class_w, acc,
                        gout, dlogits, dld);
@@ -704,7 +701,7 @@ __global__ __launch_bounds__(256) void sg_softmax_bwd_kernel(const float* dp, in
 }
 extern "C" int sgan_softmax_fwd(const float* z, int32_t ld, int32_t npix, int32_t C, float* p, int32_t pld, void* stream) {
     SGAN_CHECK(z && p && npix > 0 && C >= 1 && C <= SG_CE_MAXC && ld >= C && pld >= C, "bad argument");
-    int blocks = ew_cdiv(npix, 256);
+    int blocks = sg_cdiv(npix, 256);
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(sg_softmax_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, z, ld, npix, C, p, pld);
     SGAN_LAUNCH_CHECK();
@@ -713,7 +710,7 @@ extern "C" int sgan_softmax_fwd(const float* z, int32_t ld, int32_t npix, int32_
 extern "C" int sgan_softmax_bwd(const float* dp, int32_t dpld, const float* p, int32_t pld, int32_t npix, int32_t C, float* dz, int32_t dzld,
                                 void* stream) {
     SGAN_CHECK(dp && p && dz && npix > 0 && C >= 1 && C <= SG_CE_MAXC && dpld >= C && pld >= C && dzld >= C, "bad argument");
-    int blocks = ew_cdiv(npix, 256);
+    int blocks = sg_cdiv(npix, 256);
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(sg_softmax_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dp, dpld, p, pld, npix, C, dz, dzld);
     SGAN_LAUNCH_CHECK();
@@ -939,7 +936,7 @@ extern "C" int sgan_image_prep(const unsigned char* img, int32_t H0, int32_t W0,
     SGAN_CHECK(img && dst && H0 > 0 && W0 > 0 && n > 0, "bad argument");
     SGAN_CHECK(x0 >= 0 && y0 >= 0 && x0 + n <= W0 && y0 + n <= H0, "crop window %d+%d x %d+%d outside the %d x %d image", x0, n, y0, n, W0, H0);
     SGAN_CHECK(rot >= 0 && rot <= 3 && Cstore >= 3 && dst_ld >= Cstore, "bad rot / channel count");
-    int blocks = ew_cdiv((int64_t)n * n, 256);
+    int blocks = sg_cdiv((int64_t)n * n, 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(sg_image_prep_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, img, H0, W0, x0, y0, n, flip != 0, rot, dst,
                        dst_ld, Cstore);
@@ -1052,15 +1049,15 @@ extern "C" int sgan_image_resize(const unsigned char* src, int32_t H, int32_t W,
     const unsigned char* cur = src;
     if (Wo != W) {                 // horizontal pass first (ImagingResample)
         unsigned char* out = Ho != H ? tmp : dst;
-        hipLaunchKernelGGL(sg_resample_coeffs_kernel, dim3(ew_cdiv(Wo, 256)), dim3(256), 0, st, W, Wo, bic, ksh, bh, kh);
-        int blocks = ew_cdiv((int64_t)H * Wo * C, 256);
+        hipLaunchKernelGGL(sg_resample_coeffs_kernel, dim3(sg_cdiv(Wo, 256)), dim3(256), 0, st, W, Wo, bic, ksh, bh, kh);
+        int blocks = sg_cdiv((int64_t)H * Wo * C, 256);
         if (blocks > 8192) blocks = 8192;
         hipLaunchKernelGGL((sg_resample_pass_kernel<true>), dim3(blocks), dim3(256), 0, st, cur, W, C, out, H, Wo, bh, kh, ksh);
         cur = out;
     }
     if (Ho != H) {
-        hipLaunchKernelGGL(sg_resample_coeffs_kernel, dim3(ew_cdiv(Ho, 256)), dim3(256), 0, st, H, Ho, bic, ksv, bv, kv);
-        int blocks = ew_cdiv((int64_t)Ho * Wo * C, 256);
+        hipLaunchKernelGGL(sg_resample_coeffs_kernel, dim3(sg_cdiv(Ho, 256)), dim3(256), 0, st, H, Ho, bic, ksv, bv, kv);
+        int blocks = sg_cdiv((int64_t)Ho * Wo * C, 256);
         if (blocks > 8192) blocks = 8192;
         hipLaunchKernelGGL((sg_resample_pass_kernel<false>), dim3(blocks), dim3(256), 0, st, cur, Wo, C, dst, Ho, Wo, bv, kv, ksv);
     }
@@ -1273,7 +1270,7 @@ extern "C" int sgan_gauss_down_multi_fwd(const sgan_gauss_job* jobs, int32_t n, 
     int64_t maxt = 0;
     int maxk = 0;
     for (int i = 0; i < n; ++i) { maxt = max(maxt, (int64_t)jobs[i].Ho * jobs[i].Wo * (C >> 2)); maxk = max(maxk, jobs[i].k); }
-    int blocks = ew_cdiv(maxt, 256);
+    int blocks = sg_cdiv(maxt, 256);
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(sg_gauss_multi_fwd_kernel, dim3(blocks, n), dim3(256), (size_t)maxk * maxk * C * 4, (hipStream_t)stream, T);
     SGAN_LAUNCH_CHECK();
@@ -1288,7 +1285,7 @@ extern "C" int sgan_gauss_down_multi_bwd(const sgan_gauss_job* jobs, int32_t n, 
     size_t lds = 0;
     for (int i = 0; i < n; ++i) lds += (size_t)jobs[i].k * jobs[i].k * C * 4;
     const int64_t total = (int64_t)jobs[0].H * jobs[0].W * (C >> 2);
-    int blocks = ew_cdiv(total, 256);
+    int blocks = sg_cdiv(total, 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(sg_gauss_multi_bwd_kernel, dim3(blocks), dim3(256), lds, (hipStream_t)stream, T);
     SGAN_LAUNCH_CHECK();
@@ -1302,7 +1299,7 @@ extern "C" int sgan_gauss_down_fwd(const float* in, int32_t in_ld, int32_t H, in
     SGAN_CHECK((C & 3) == 0 && (in_ld & 3) == 0 && (out_ld & 3) == 0 && in_ld >= C && out_ld >= C && k * k * C * 4 <= 60000, "bad channel layout");
     SGAN_CHECK(Ho == (H + 2 * pad - k) / s + 1 && Wo == (W + 2 * pad - k) / s + 1, "gauss geometry mismatch");
     const int64_t total = (int64_t)Ho * Wo * (C >> 2);
-    int blocks = ew_cdiv(total, 256);
+    int blocks = sg_cdiv(total, 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(sg_gauss_fwd_kernel, dim3(blocks), dim3(256), (size_t)k * k * C * 4, (hipStream_t)stream, in, in_ld, H, W, C, Creal, g,
                        g_chan_stride, k, pad, s, out, out_ld, Ho, Wo);
@@ -1317,7 +1314,7 @@ extern "C" int sgan_gauss_down_bwd(const float* dout, int32_t dout_ld, int32_t H
     SGAN_CHECK((C & 3) == 0 && (din_ld & 3) == 0 && (dout_ld & 3) == 0 && din_ld >= C && dout_ld >= C && k * k * C * 4 <= 60000, "bad channel layout");
     SGAN_CHECK(Ho == (H + 2 * pad - k) / s + 1 && Wo == (W + 2 * pad - k) / s + 1, "gauss geometry mismatch");
     const int64_t total = (int64_t)H * W * (C >> 2);
-    int blocks = ew_cdiv(total, 256);
+    int blocks = sg_cdiv(total, 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(sg_gauss_bwd_kernel, dim3(blocks), dim3(256), (size_t)k * k * C * 4, (hipStream_t)stream, dout, dout_ld, Ho, Wo, C, Creal,
                        g, g_chan_stride, k, pad, s, din, din_ld, H, W, accumulate);
@@ -1405,7 +1402,7 @@ extern "C" int sgan_bilinear_up2_fwd(const float* in, int32_t in_ld, int32_t H, 
                    (out_ld & 3) == 0, "bad argument");
     SGAN_CHECK(256 % (C >> 2) == 0, "channel count must be 4 * a divisor of 256");
     const int64_t total = (int64_t)4 * H * W * (C >> 2);
-    int blocks = ew_cdiv(total, 256 * 4);
+    int blocks = sg_cdiv(total, 256 * 4);
     if (blocks > 2048) blocks = 2048;
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(sg_bilinear_up2_fwd_kernel, dim3(blocks), dim3(256), (size_t)2 * C * 8, (hipStream_t)stream, in, in_ld, H, W,
@@ -1419,7 +1416,7 @@ extern "C" int sgan_bilinear_up2_bwd(const float* dout, int32_t dout_ld, int32_t
     SGAN_CHECK(dout && din && H > 0 && W > 0 && C > 0 && (C & 3) == 0 && din_ld >= C && dout_ld >= C && (din_ld & 3) == 0 &&
                    (dout_ld & 3) == 0, "bad argument");
     const int64_t total = (int64_t)H * W * (C >> 2);
-    int blocks = ew_cdiv(total, 256);
+    int blocks = sg_cdiv(total, 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(sg_bilinear_up2_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dout, dout_ld, H, W, C, din,
                        din_ld);
@@ -1502,7 +1499,7 @@ extern "C" int sgan_avgpool_pyramid_bwd(const float* const* dlevels, const int32
         P.l[s] = const_cast<float*>(dlevels[s]);
         P.ld[s] = level_ld[s];
     }
-    int blocks = ew_cdiv((int64_t)H * W, 256);
+    int blocks = sg_cdiv((int64_t)H * W, 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(sg_avgpool_pyramid_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, P, H, W, dlabel, ld, accumulate);
     SGAN_LAUNCH_CHECK();
@@ -1512,8 +1509,6 @@ extern "C" int sgan_avgpool_pyramid_bwd(const float* const* dlevels, const int32
 // ------------------------------------------------------------------------------------------
 // GAN loss on the logits map (one workgroup; the maps are <= 67x67)
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ float sg_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-
 __global__ __launch_bounds__(1024) void sg_gan_loss_fwd_kernel(const float* logits, int ld, int npix, float target, int mode,
                                                                float* loss_out, float* p_out) {
     __shared__ double wsum[16];
@@ -1524,23 +1519,15 @@ __global__ __launch_bounds__(1024) void sg_gan_loss_fwd_kernel(const float* logi
         if (mode == 0) {
             const float p = sg_sigmoid(x);
             if (p_out) p_out[(int64_t)i * ld] = p;
-            const float lp = fmaxf(logf(p), -100.f);
-            const float lq = fmaxf(log1pf(-p), -100.f);
-            l = -(target * lp + (1.f - target) * lq);
+            l = sg_bce_term(p, target);
         } else {
             const float d = x - target;
             l = d * d;
         }
         acc += (double)l;
     }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    SG_SYNC();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int i = 0; i < 16; ++i) t += wsum[i];
-        loss_out[0] = (float)(t / (double)npix);
-    }
+    const double t = sg_block_sum<16>(acc, wsum);
+    if (threadIdx.x == 0) loss_out[0] = (float)(t / (double)npix);
 }
 
 __global__ __launch_bounds__(256) void sg_gan_loss_bwd_kernel(const float* logits, int ld, int npix, float target, int mode,
@@ -1554,7 +1541,7 @@ __global__ __launch_bounds__(256) void sg_gan_loss_bwd_kernel(const float* logit
             // (p - t) except where p(1-p) underflows below the clamp (|x| > ~27), where it decays to 0.
             const float p = sg_sigmoid(x);
             const float pq = (1.f - p) * p;
-            d = (p - target) / fmaxf(pq, 1e-12f) * go * pq;
+            d = sg_bce_dterm(p, target) * go * pq;
         } else {
             d = 2.f * (x - target) * go;
         }
@@ -1576,7 +1563,7 @@ extern "C" int sgan_gan_loss_fwd(const float* logits, int32_t ld, int32_t npix, 
 extern "C" int sgan_gan_loss_bwd(const float* logits, int32_t ld, int32_t npix, float target, int32_t mode, const float* gout,
                                  float* dlogits, int32_t dld, void* stream) {
     SGAN_CHECK(logits && gout && dlogits && npix > 0 && dld >= 1 && (mode == 0 || mode == 1), "bad argument");
-    int blocks = ew_cdiv(npix, 256);
+    int blocks = sg_cdiv(npix, 256);
     if (blocks > 256) blocks = 256;
     hipLaunchKernelGGL(sg_gan_loss_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, logits, ld, npix, target,
                        mode, gout, dlogits, dld);
@@ -1631,11 +1618,8 @@ __global__ __launch_bounds__(256) void sg_gan_loss_multi_fwd_kernel(SgLossMulti 
             float l, d;
             if (J.mode == 0) {
                 const float p = sg_sigmoid(x);
-                const float lp = fmaxf(logf(p), -100.f);
-                const float lq = fmaxf(log1pf(-p), -100.f);
-                l = -(tg * lp + (1.f - tg) * lq);
-                const float pq = (1.f - p) * p;
-                d = (p - tg) / fmaxf(pq, 1e-12f) * go * pq;     // the same expression as sg_gan_loss_multi_bwd_kernel
+                l = sg_bce_term(p, tg);
+                d = sg_bce_dterm(p, tg) * go * ((1.f - p) * p);     // the same expression as sg_gan_loss_multi_bwd_kernel
             } else {
                 const float df = x - tg;
                 l = df * df;
@@ -1649,31 +1633,12 @@ __global__ __launch_bounds__(256) void sg_gan_loss_multi_fwd_kernel(SgLossMulti 
             }
         }
     }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    SG_SYNC();
-    if (threadIdx.x == 0) {
-        part[j * SG_LOSS_BLOCKS + b] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-        __threadfence();                                     // the partial is out before the ticket is taken
-        last = atomicAdd(counter, 1u) == (unsigned)(SG_LOSS_BLOCKS * J.n - 1);
-    }
-    SG_SYNC();
-    if (!last || threadIdx.x >= 64) return;
+    const double sum = sg_block_sum<4>(acc, wsum);
+    if (!sg_publish_last(sum, &part[j * SG_LOSS_BLOCKS + b], counter, (unsigned)(SG_LOSS_BLOCKS * J.n - 1), &last) || threadIdx.x >= 64) return;
     __threadfence();                                         // every other workgroup's partial is visible from here on
     const int t = threadIdx.x;
-    double w = 0.0;
-    if (t < J.n) {
-        double sum = 0.0;
-        for (int bb = 0; bb < SG_LOSS_BLOCKS; ++bb) sum += __builtin_nontemporal_load(&part[t * SG_LOSS_BLOCKS + bb]);
-        const float m = (float)(sum / (double)J.npix[t]);
-        each[t] = m;
-        w = (double)J.weight[t] * (double)m;
-    }
-    for (int off = 4; off > 0; off >>= 1) w += __shfl_xor(w, off);   // n <= 8 terms sit in lanes 0..7
-    if (t == 0) {
-        total[0] = (float)w;
-        counter[0] = 0u;
-    }
+    const bool has = t < J.n;
+    sg_finish_terms<SG_LOSS_BLOCKS>(part, has, has ? (double)J.npix[t] : 1.0, has ? J.weight[t] : 0.f, each, total, counter);
 }
 
 __global__ __launch_bounds__(256) void sg_gan_loss_multi_bwd_kernel(SgLossMulti J, const float* gout) {
@@ -1686,7 +1651,7 @@ __global__ __launch_bounds__(256) void sg_gan_loss_multi_bwd_kernel(SgLossMulti 
         if (J.mode == 0) {
             const float p = sg_sigmoid(x);
             const float pq = (1.f - p) * p;
-            d = (p - J.target[j]) / fmaxf(pq, 1e-12f) * go * pq;
+            d = sg_bce_dterm(p, J.target[j]) * go * pq;
         } else {
             d = 2.f * (x - J.target[j]) * go;
         }
@@ -1765,7 +1730,7 @@ __global__ __launch_bounds__(256) void sg_sigmoid_bwd_kernel(const float* dp, in
 
 extern "C" int sgan_sigmoid_fwd(const float* x, int32_t ld, int32_t npix, float* p, int32_t pld, void* stream) {
     SGAN_CHECK(x && p && npix > 0, "bad argument");
-    int blocks = ew_cdiv(npix, 256);
+    int blocks = sg_cdiv(npix, 256);
     if (blocks > 256) blocks = 256;
     hipLaunchKernelGGL(sg_sigmoid_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, ld, npix, p, pld);
     SGAN_LAUNCH_CHECK();
@@ -1775,7 +1740,7 @@ extern "C" int sgan_sigmoid_fwd(const float* x, int32_t ld, int32_t npix, float*
 extern "C" int sgan_sigmoid_bwd(const float* dp, int32_t dpld, const float* p, int32_t pld, int32_t npix, float* dx,
                                 int32_t dxld, void* stream) {
     SGAN_CHECK(dp && p && dx && npix > 0, "bad argument");
-    int blocks = ew_cdiv(npix, 256);
+    int blocks = sg_cdiv(npix, 256);
     if (blocks > 256) blocks = 256;
     hipLaunchKernelGGL(sg_sigmoid_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dp, dpld, p, pld, npix, dx, dxld);
     SGAN_LAUNCH_CHECK();
@@ -1798,7 +1763,7 @@ __global__ __launch_bounds__(256) void sg_tanh_bwd_kernel(const float* dy, const
 
 extern "C" int sgan_tanh_bwd(const float* dy, const float* y, float* dx, int64_t n, void* stream) {
     SGAN_CHECK(dy && y && dx && n > 0 && (n & 3) == 0, "bad argument");
-    int blocks = ew_cdiv(n / 4, 256);
+    int blocks = sg_cdiv(n / 4, 256);
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(sg_tanh_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dy, y, dx, n / 4);
     SGAN_LAUNCH_CHECK();
@@ -1822,7 +1787,7 @@ __global__ __launch_bounds__(256) void sg_add_act_kernel(const float* a, const f
 extern "C" int sgan_add_act_fwd(const float* a, const float* b, float* out, int64_t n, int32_t act, void* stream) {
     SGAN_CHECK(a && b && out && n > 0 && (n & 3) == 0, "bad argument");
     SGAN_CHECK(act == SGAN_ACT_NONE || act == SGAN_ACT_TANH, "act must be SGAN_ACT_NONE or SGAN_ACT_TANH");
-    int blocks = ew_cdiv(n / 4, 256);
+    int blocks = sg_cdiv(n / 4, 256);
     if (blocks > 2048) blocks = 2048;
     if (act == SGAN_ACT_TANH) hipLaunchKernelGGL(sg_add_act_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, b, out, n / 4);
     else hipLaunchKernelGGL(sg_add_act_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, b, out, n / 4);
@@ -1876,14 +1841,14 @@ extern "C" int sgan_to_nhwc(const float* src, int64_t sc, int64_t sh, int64_t sw
                             float* dst, int32_t dst_ld, int32_t Cstore, void* stream) {
     SGAN_CHECK(src && dst && H > 0 && W > 0 && Creal <= Cstore && dst_ld >= Cstore, "bad argument");
     if (sw == 1 && Cstore == 4 && (dst_ld & 3) == 0 && ((uintptr_t)dst & 15) == 0) {
-        int blocks = ew_cdiv((int64_t)H * W, 256);
+        int blocks = sg_cdiv((int64_t)H * W, 256);
         if (blocks > 2048) blocks = 2048;
         hipLaunchKernelGGL(sg_planes_to_nhwc4_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, src, sc, sh, H, W, Creal, dst, dst_ld);
         SGAN_LAUNCH_CHECK();
         return SGAN_OK;
     }
     const int64_t total = (int64_t)H * W * Cstore;
-    int blocks = ew_cdiv(total, 256);
+    int blocks = sg_cdiv(total, 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(sg_to_nhwc_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, src, sc, sh, sw, H, W, Creal, dst,
                        dst_ld, Cstore);
@@ -1918,7 +1883,7 @@ __global__ __launch_bounds__(256) void sg_slice_nhwc_kernel(const float* src, in
 extern "C" int sgan_concat_nhwc(const float* a, int32_t a_ld, int32_t Ca, const float* b, int32_t b_ld, int32_t Cb, int64_t npix,
                                 float* dst, int32_t dst_ld, int32_t Cstore, void* stream) {
     SGAN_CHECK(a && b && dst && npix > 0 && Ca > 0 && Cb > 0 && a_ld >= Ca && b_ld >= Cb && Cstore >= Ca + Cb && dst_ld >= Cstore, "bad argument");
-    int blocks = ew_cdiv(npix, 256);
+    int blocks = sg_cdiv(npix, 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(sg_concat_nhwc_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a, a_ld, Ca, b, b_ld, Cb, npix, dst, dst_ld, Cstore);
     SGAN_LAUNCH_CHECK();
@@ -1928,7 +1893,7 @@ extern "C" int sgan_concat_nhwc(const float* a, int32_t a_ld, int32_t Ca, const 
 extern "C" int sgan_slice_nhwc(const float* src, int32_t src_ld, int32_t c0, int32_t C, int64_t npix, float* dst, int32_t dst_ld,
                                int32_t Cstore, void* stream) {
     SGAN_CHECK(src && dst && npix > 0 && c0 >= 0 && C > 0 && src_ld >= c0 + C && Cstore >= C && dst_ld >= Cstore, "bad argument");
-    int blocks = ew_cdiv(npix, 256);
+    int blocks = sg_cdiv(npix, 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(sg_slice_nhwc_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, src, src_ld, c0, C, npix, dst, dst_ld, Cstore);
     SGAN_LAUNCH_CHECK();
@@ -2001,7 +1966,7 @@ extern "C" int sgan_adam_multi(const sgan_adam_seg* segs, int32_t nseg, const fl
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(sg_adam_prep_kernel, dim3(1), dim3(1), 0, st, state_dev, lr_dev, beta1, beta2);
     SGAN_LAUNCH_CHECK();
-    int bx = ew_cdiv(maxn / 4 + 1, 256 * 2);
+    int bx = sg_cdiv(maxn / 4 + 1, 256 * 2);
     if (bx > 1024) bx = 1024;
     if (bx < 1) bx = 1;
     hipLaunchKernelGGL(sg_adam_kernel, dim3(bx, nseg), dim3(256), 0, st, T, state_dev, beta1, beta2, eps);
@@ -2226,7 +2191,7 @@ extern "C" int sgan_sgd_multi(const sgan_adam_seg* segs, int32_t nseg, const flo
         if (segs[i].n > maxn) maxn = segs[i].n;
     }
     T.nseg = nseg;
-    int bx = ew_cdiv(maxn, 256 * 4);
+    int bx = sg_cdiv(maxn, 256 * 4);
     if (bx > 1024) bx = 1024;
     if (bx < 1) bx = 1;
     hipLaunchKernelGGL(sg_sgd_kernel, dim3(bx, nseg), dim3(256), 0, (hipStream_t)stream, T, lr_dev, momentum);
@@ -2340,7 +2305,7 @@ extern "C" int sgan_rng_advance(uint64_t* offset_dev, uint64_t by, void* stream)
 extern "C" int sgan_dropout_mask(float* mask, int64_t n, float p, uint64_t seed, uint64_t* offset_dev, int32_t advance, void* stream) {
     SGAN_CHECK(mask && n > 0 && p >= 0.f && p < 1.f, "bad argument");
     const int64_t nq = (n + 3) >> 2;
-    int blocks = ew_cdiv(nq, 256);
+    int blocks = sg_cdiv(nq, 256);
     if (blocks > 1024) blocks = 1024;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(sg_dropout_mask_kernel, dim3(blocks), dim3(256), 0, st, mask, n, p, 1.f / (1.f - p), seed, offset_dev);
@@ -2354,7 +2319,7 @@ extern "C" int sgan_dropout_mask(float* mask, int64_t n, float p, uint64_t seed,
 
 static int sg_normal_fill_launch(float* dst, int64_t n, int hw, int cs, uint64_t seed, uint64_t* offset_dev, int32_t advance, void* stream) {
     const int64_t nq = (n + 3) >> 2;
-    int blocks = ew_cdiv(nq, 256);
+    int blocks = sg_cdiv(nq, 256);
     if (blocks > 1024) blocks = 1024;
     hipStream_t st = (hipStream_t)stream;
     if (!advance) {

@@ -4,11 +4,7 @@
 //     one launch -- the counterpart of sg_gan_loss_multi_fwd_kernel (sgan_ew.hip) on products of two maps;
 //   * the channel sigmoid and the weighted BCE of `--use_sigmoid_ss` (models/segm_model.py:155-160,216-236).
 // LDS holds nothing but the per-wave partial sums of the block reductions.
-#include "sgan_common.h"
-
-static inline int fd_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
-
-__device__ __forceinline__ float fd_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }      // sg_sigmoid of sgan_ew.hip
+#include "sgan_reduce.h"
 
 // ------------------------------------------------------------------------------------------
 // Factored GAN loss.  Term j:  a1 = sig1 ? sigmoid(l1) : l1   [h1, w1]        a2 = sig2 ? sigmoid(l2) : l2   [H2, W2]
@@ -53,12 +49,12 @@ __device__ __forceinline__ FdTerm fd_term(const SgFactd& J, int j) {
 
 __device__ __forceinline__ float fd_a1(const FdTerm& T, int iy, int ix) {
     const float v = T.l1[((int64_t)iy * T.w1 + ix) * T.ld1];
-    return T.sig1 ? fd_sigmoid(v) : v;
+    return T.sig1 ? sg_sigmoid(v) : v;
 }
 
 __device__ __forceinline__ float fd_a2(const FdTerm& T, int y, int x) {
     const float v = T.l2[((int64_t)y * T.W2 + x) * T.ld2];
-    return T.sig2 ? fd_sigmoid(v) : v;
+    return T.sig2 ? sg_sigmoid(v) : v;
 }
 
 // u[uy, ux]: out[2i + a] = 0.75 in[i] + 0.25 in[clamp(i - 1 + 2a)], separable, in the order sg_bilinear_up2_fwd_kernel adds them
@@ -74,15 +70,13 @@ __device__ __forceinline__ int fd_reflect(int r, int n) { return r < 0 ? -r : (r
 
 __device__ __forceinline__ float fd_loss(const FdTerm& T, float p) {
     if (T.mse) return (p - T.tg) * (p - T.tg);
-    const float lp = fmaxf(logf(p), -100.f);
-    const float lq = fmaxf(log1pf(-p), -100.f);
-    return -(T.tg * lp + (1.f - T.tg) * lq);
+    return sg_bce_term(p, T.tg);
 }
 
 // d crit / d p times `go` (= upstream * weight / pixels), the expressions of sg_gan_loss_multi_fwd_kernel
 __device__ __forceinline__ float fd_dcrit(const FdTerm& T, float p, float go) {
     if (T.mse) return 2.f * (p - T.tg) * go;
-    return (p - T.tg) / fmaxf((1.f - p) * p, 1e-12f) * go;
+    return sg_bce_dterm(p, T.tg) * go;
 }
 
 // d total / d l2 of pixel (y, x), given q and a2 there
@@ -173,31 +167,12 @@ __global__ __launch_bounds__(256) void sg_factd_loss_multi_fwd_kernel(SgFactd J,
         if (dl2) fd_store(dl2, i, dld2, fd_grad_l2(T, q, a2, go));
     }
     fd_write_l1_grad(J, T, j, b, SG_FACTD_BLOCKS, go);
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    SG_SYNC();
-    if (threadIdx.x == 0) {
-        part[j * SG_FACTD_BLOCKS + b] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-        __threadfence();                                     // the partial is out before the ticket is taken
-        last = atomicAdd(counter, 1u) == (unsigned)(SG_FACTD_BLOCKS * J.n - 1);
-    }
-    SG_SYNC();
-    if (!last || threadIdx.x >= 64) return;
+    const double sum = sg_block_sum<4>(acc, wsum);
+    if (!sg_publish_last(sum, &part[j * SG_FACTD_BLOCKS + b], counter, (unsigned)(SG_FACTD_BLOCKS * J.n - 1), &last) || threadIdx.x >= 64) return;
     __threadfence();                                         // every other workgroup's partial is visible from here on
     const int t = threadIdx.x;
-    double w = 0.0;
-    if (t < J.n) {
-        double sum = 0.0;
-        for (int bb = 0; bb < SG_FACTD_BLOCKS; ++bb) sum += __builtin_nontemporal_load(&part[t * SG_FACTD_BLOCKS + bb]);
-        const float m = (float)(sum / (double)(J.H2[t] * J.W2[t]));
-        each[t] = m;
-        w = (double)J.weight[t] * (double)m;
-    }
-    for (int off = 4; off > 0; off >>= 1) w += __shfl_xor(w, off);   // n <= 8 terms sit in lanes 0..7
-    if (t == 0) {
-        total[0] = (float)w;
-        counter[0] = 0u;
-    }
+    const bool has = t < J.n;
+    sg_finish_terms<SG_FACTD_BLOCKS>(part, has, has ? (double)(J.H2[t] * J.W2[t]) : 1.0, has ? J.weight[t] : 0.f, each, total, counter);
 }
 
 // the gradients again, for an upstream gradient other than 1
@@ -281,7 +256,7 @@ extern "C" int sgan_factd_loss_multi_bwd(const sgan_factd_loss_job* jobs, int32_
 #define SG_BCEW_MAXC 16
 __global__ __launch_bounds__(256) void sg_sigmoid_nhwc_fwd_kernel(const float* z, int ld, int npix, int C, float* p, int pld) {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < npix; i += gridDim.x * 256)
-        for (int c = 0; c < pld; ++c) p[(int64_t)i * pld + c] = c < C ? fd_sigmoid(z[(int64_t)i * ld + c]) : 0.f;
+        for (int c = 0; c < pld; ++c) p[(int64_t)i * pld + c] = c < C ? sg_sigmoid(z[(int64_t)i * ld + c]) : 0.f;
 }
 
 __global__ __launch_bounds__(256) void sg_sigmoid_nhwc_bwd_kernel(const float* dp, int dpld, const float* p, int pld, int npix, int C,
@@ -311,25 +286,15 @@ __global__ __launch_bounds__(256) void sg_bce_weighted_fwd_kernel(const float* p
         float s = 0.f;
         for (int c = 0; c < C; ++c) {
             const float pv = p[(int64_t)i * pld + c], tv = tp[c];
-            const float lp = fmaxf(logf(pv), -100.f);
-            const float lq = fmaxf(log1pf(-pv), -100.f);
-            s += -(tv * lp + (1.f - tv) * lq);
+            s += sg_bce_term(pv, tv);
         }
         acc += (double)w * (double)s;
     }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    SG_SYNC();
-    if (threadIdx.x == 0) {
-        part[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-        __threadfence();
-        last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-    }
-    SG_SYNC();
-    if (!last || threadIdx.x != 0) return;
+    const double mine = sg_block_sum<4>(acc, wsum);
+    if (!sg_publish_last(mine, &part[blockIdx.x], ticket, gridDim.x - 1, &last) || threadIdx.x != 0) return;
     __threadfence();
     double sum = 0.0;
-    for (unsigned b = 0; b < gridDim.x; ++b) sum += __builtin_nontemporal_load(&part[b]);
+    for (unsigned b = 0; b < gridDim.x; ++b) sum += sg_slot_load(&part[b]);
     loss_out[0] = (float)(sum / ((double)C * (double)npix));
     ticket[0] = 0u;
 }
@@ -344,7 +309,7 @@ __global__ __launch_bounds__(256) void sg_bce_weighted_bwd_kernel(const float* p
             float d = 0.f;
             if (c < C) {
                 const float pv = p[(int64_t)i * pld + c];
-                d = w * (pv - tp[c]) / fmaxf((1.f - pv) * pv, 1e-12f);
+                d = w * (pv - tp[c]) / sg_bce_dden(pv);
             }
             dp[(int64_t)i * dpld + c] = d;
         }
@@ -353,7 +318,7 @@ __global__ __launch_bounds__(256) void sg_bce_weighted_bwd_kernel(const float* p
 
 extern "C" int sgan_sigmoid_nhwc_fwd(const float* z, int32_t ld, int32_t npix, int32_t C, float* p, int32_t pld, void* stream) {
     SGAN_CHECK(z && p && npix > 0 && C >= 1 && C <= SG_BCEW_MAXC && ld >= C && pld >= C, "bad argument (1..%d channels)", SG_BCEW_MAXC);
-    int blocks = fd_cdiv(npix, 256);
+    int blocks = sg_cdiv(npix, 256);
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(sg_sigmoid_nhwc_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, z, ld, npix, C, p, pld);
     SGAN_LAUNCH_CHECK();
@@ -363,7 +328,7 @@ extern "C" int sgan_sigmoid_nhwc_fwd(const float* z, int32_t ld, int32_t npix, i
 extern "C" int sgan_sigmoid_nhwc_bwd(const float* dp, int32_t dpld, const float* p, int32_t pld, int32_t npix, int32_t C, float* dz,
                                      int32_t dzld, void* stream) {
     SGAN_CHECK(dp && p && dz && npix > 0 && C >= 1 && C <= SG_BCEW_MAXC && dpld >= C && pld >= C && dzld >= C, "bad argument");
-    int blocks = fd_cdiv(npix, 256);
+    int blocks = sg_cdiv(npix, 256);
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(sg_sigmoid_nhwc_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dp, dpld, p, pld, npix, C, dz, dzld);
     SGAN_LAUNCH_CHECK();
@@ -382,7 +347,7 @@ extern "C" int sgan_bce_weighted_fwd(const float* p, int32_t pld, const float* t
     static_assert((SG_BCEW_BLOCKS + 1) * sizeof(double) <= SGAN_BCE_WEIGHTED_WS_BYTES, "workspace size");
     double* part = static_cast<double*>(workspace);
     unsigned* ticket = reinterpret_cast<unsigned*>(part + SG_BCEW_BLOCKS);
-    int blocks = fd_cdiv(npix, 256);
+    int blocks = sg_cdiv(npix, 256);
     if (blocks > SG_BCEW_BLOCKS) blocks = SG_BCEW_BLOCKS;
     hipLaunchKernelGGL(sg_bce_weighted_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, pld, t, tld, npix, C, class_w, nw,
                        part, ticket, loss_out);
@@ -394,7 +359,7 @@ extern "C" int sgan_bce_weighted_bwd(const float* p, int32_t pld, const float* t
                                      const float* class_w, int32_t nw, const float* gout, float* dp, int32_t dpld, void* stream) {
     SGAN_CHECK(p && t && gout && dp && npix > 0 && C >= 1 && C <= SG_BCEW_MAXC && pld >= C && tld >= C && dpld >= C, "bad argument");
     SGAN_CHECK(nw >= 0 && nw <= C && (nw == 0 || class_w), "0..C class weights");
-    int blocks = fd_cdiv(npix, 256);
+    int blocks = sg_cdiv(npix, 256);
     if (blocks > 1024) blocks = 1024;
     hipLaunchKernelGGL(sg_bce_weighted_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, pld, t, tld, npix, C, class_w, nw,
                        gout, dp, dpld);

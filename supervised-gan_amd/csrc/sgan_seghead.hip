@@ -9,15 +9,11 @@
 // bases) a pixel is one to four 16-byte loads and as many stores per output; any other layout takes the scalar form of the same
 // arithmetic.  Every workgroup leaves its fp64 partial in a slot of its own and draws a ticket (its one atomic); the last one sums the
 // slots in a fixed order -- the same bits on every run --, writes the loss, and leaves the workspace zeroed for the next call.
-#include "sgan_common.h"
+#include "sgan_reduce.h"
 
 #define SG_SH_MAXC 16
 #define SG_SH_BLOCKS 512
 static_assert((SG_SH_BLOCKS + 1) * sizeof(double) <= SGAN_SEGHEAD_WS_BYTES, "workspace size");
-
-static inline int sh_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
-
-__device__ __forceinline__ float sh_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }      // fd_sigmoid of sgan_factd.hip
 
 struct ShArgs {
     const float* z; int ld;
@@ -67,34 +63,19 @@ __device__ __forceinline__ void sh_store_row(float* base, int64_t pix, int ld, c
     }
 }
 
-// workgroup sum of `acc` in thread 0 (fixed order)
-__device__ __forceinline__ double sh_block_sum(double acc, double* red) {
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    SG_SYNC();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// slot + ticket; true in every thread of the workgroup that arrived last.  `red` is free again on return.
-__device__ __forceinline__ bool sh_publish(double sum, double* part, unsigned* ticket, int* last) {
-    if (threadIdx.x == 0) {
-        part[blockIdx.x] = sum;
-        __threadfence();
-        *last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-    }
-    SG_SYNC();
-    return *last != 0;
-}
-
-// the last workgroup: the slots summed in a fixed order and zeroed; the result in thread 0
-__device__ __forceinline__ double sh_finish(double* part, double* red) {
+// The workgroup's sum goes through the hand-off of sgan_reduce.h; false in every workgroup but the last to arrive.  There `total` is
+// the sum of all slots in a fixed order (a strided sum per thread, then the workgroup sum) and the slots are zero again.
+__device__ __forceinline__ bool sh_total(double acc, double* part, unsigned* ticket, double* red, int* last, double& total) {
+    const double sum = sg_block_sum<4>(acc, red);
+    if (!sg_publish_last(sum, &part[blockIdx.x], ticket, gridDim.x - 1, last)) return false;      // its barrier frees `red`
     __threadfence();
     double v = 0.0;
     for (unsigned b = threadIdx.x; b < gridDim.x; b += 256) {
-        v += __hip_atomic_load(&part[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        v += sg_slot_load(&part[b]);
         part[b] = 0.0;
     }
-    return sh_block_sum(v, red);
+    total = sg_block_sum<4>(v, red);
+    return true;
 }
 
 template <int CS>
@@ -152,12 +133,10 @@ __global__ __launch_bounds__(256) void sg_seg_head_kernel(const ShArgs A) {
             for (int c = 0; c < N; ++c) {
                 float pv = 0.f, dv = 0.f;
                 if (c < C) {
-                    pv = sh_sigmoid(z[c]);
+                    pv = sg_sigmoid(z[c]);
                     const float tv = t[c];
-                    const float lp = fmaxf(logf(pv), -100.f);
-                    const float lq = fmaxf(log1pf(-pv), -100.f);
-                    s += -(tv * lp + (1.f - tv) * lq);
-                    dv = ws * (pv - tv) / fmaxf((1.f - pv) * pv, 1e-12f) * pv * (1.f - pv);      // sgan_bce_weighted_bwd, then sgan_sigmoid_nhwc_bwd
+                    s += sg_bce_term(pv, tv);
+                    dv = ws * (pv - tv) / sg_bce_dden(pv) * pv * (1.f - pv);      // sgan_bce_weighted_bwd, then sgan_sigmoid_nhwc_bwd
                 }
                 p[c] = pv;
                 d[c] = dv;
@@ -167,9 +146,8 @@ __global__ __launch_bounds__(256) void sg_seg_head_kernel(const ShArgs A) {
         sh_store_row<CS>(A.p, i, A.pld, p);
         if (A.d) sh_store_row<CS>(A.d, i, A.dld, d);
     }
-    const double sum = sh_block_sum(acc, red);
-    if (!sh_publish(sum, A.part, A.ticket, &last)) return;
-    const double total = sh_finish(A.part, red);
+    double total;
+    if (!sh_total(acc, A.part, A.ticket, red, &last, total)) return;
     if (threadIdx.x == 0) {
         if (softmax) {
             const double n = (double)A.norm[0];
@@ -197,9 +175,8 @@ __global__ __launch_bounds__(256) void sg_label_weight_sum_kernel(const int64_t*
         for (int c = 0; c < SG_SH_MAXC; ++c) w = c == y ? cw[c] : w;
         acc += (double)w;
     }
-    const double sum = sh_block_sum(acc, red);
-    if (!sh_publish(sum, part, ticket, &last)) return;
-    const double total = sh_finish(part, red);
+    double total;
+    if (!sh_total(acc, part, ticket, red, &last, total)) return;
     if (threadIdx.x == 0) {
         out[0] = (float)total;
         ticket[0] = 0u;
@@ -215,7 +192,7 @@ extern "C" int sgan_label_weight_sum(const int64_t* label, int32_t npix, int32_t
     SGAN_CHECK(((uintptr_t)workspace & 7) == 0, "workspace of SGAN_SEGHEAD_WS_BYTES (8-byte aligned) required");
     double* part = static_cast<double*>(workspace);
     unsigned* ticket = reinterpret_cast<unsigned*>(part + SG_SH_BLOCKS);
-    int blocks = sh_cdiv(npix, 256);
+    int blocks = sg_cdiv(npix, 256);
     if (blocks > SG_SH_BLOCKS) blocks = SG_SH_BLOCKS;
     hipLaunchKernelGGL(sg_label_weight_sum_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, label, npix, C, class_w, out, part,
                        ticket);
@@ -243,7 +220,7 @@ extern "C" int sgan_seg_head(const float* logits, int32_t ld, int32_t npix, int3
     A.p = p_out; A.pld = pld; A.d = dlogits; A.dld = dld; A.loss = loss_out;
     A.part = static_cast<double*>(workspace);
     A.ticket = reinterpret_cast<unsigned*>(A.part + SG_SH_BLOCKS);
-    int blocks = sh_cdiv(npix, 256);
+    int blocks = sg_cdiv(npix, 256);
     if (blocks > SG_SH_BLOCKS) blocks = SG_SH_BLOCKS;
     // 16-byte rows: every operand stored with the same 4, 8, 12 or 16 channels, on aligned bases
     const bool vec = (ld == 4 || ld == 8 || ld == 12 || ld == 16) && pld == ld && (!dlogits || dld == ld) && (softmax || tld == ld) && sh_al16(logits) &&

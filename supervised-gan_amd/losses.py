@@ -97,6 +97,19 @@ class _GanLossMultiFn(torch.autograd.Function):
         return (None, None, None) + tuple(ops.logical_view(d, 1) for d in ds)
 
 
+def _logits_behind(out, use_lsgan, who):
+    """The logits behind a discriminator output: the output itself for lsgan, the tagged logits otherwise."""
+    if use_lsgan:
+        return out
+    logits = getattr(out, "_sgan_logits", None)
+    if logits is None and getattr(out, "_sgan_pending_sigmoid", False):
+        logits = out
+    if logits is None:
+        raise SganError(f"{who}(use_lsgan=False) needs the output of a supervised_gan_amd discriminator built with "
+                        "use_sigmoid=True (it carries its logits); got a plain tensor")
+    return logits
+
+
 class GANLoss(nn.Module):
     """GANLoss (models/networks.py:152-185).  With `use_lsgan=False` the reference applies BCELoss to
     the discriminator's Sigmoid output; here the loss kernel consumes the logits behind that output
@@ -110,15 +123,7 @@ class GANLoss(nn.Module):
         self.Tensor = tensor
 
     def _logits_of(self, input):
-        if self.use_lsgan:
-            return input
-        logits = getattr(input, "_sgan_logits", None)
-        if logits is None and getattr(input, "_sgan_pending_sigmoid", False):
-            logits = input
-        if logits is None:
-            raise SganError("GANLoss(use_lsgan=False) needs the output of a supervised_gan_amd discriminator built with "
-                            "use_sigmoid=True (it carries its logits); got a plain tensor")
-        return logits
+        return _logits_behind(input, self.use_lsgan, "GANLoss")
 
     def __call__(self, input, target_is_real):
         t = self.real_label if target_is_real else self.fake_label
@@ -207,19 +212,6 @@ class _FactdLossMultiFn(torch.autograd.Function):
         return (None, None, None, None) + tuple(ops.logical_view(d, 1) if d is not None else None for d in ds)
 
 
-def _factd_logits(out, use_lsgan):
-    """The logits behind a discriminator output: the output itself for lsgan, the tagged logits otherwise (GANLoss._logits_of)."""
-    if use_lsgan:
-        return out
-    logits = getattr(out, "_sgan_logits", None)
-    if logits is None and getattr(out, "_sgan_pending_sigmoid", False):
-        logits = out
-    if logits is None:
-        raise SganError("factored_gan_loss(use_lsgan=False) needs the output of a supervised_gan_amd discriminator built with "
-                        "use_sigmoid=True (it carries its logits); got a plain tensor")
-    return logits
-
-
 def factored_gan_loss(d1_outs, d2_outs, targets_are_real, weights, up=2, use_lsgan1=False, use_lsgan2=False):
     """sum_i weights[i] * crit(util.mul(transform(D1 output i), D2 output i), target i) of the factored discriminators as ONE
     autograd node and one launch (<= 8 terms): returns (total, each), `each` the unweighted terms for logging.
@@ -229,8 +221,8 @@ def factored_gan_loss(d1_outs, d2_outs, targets_are_real, weights, up=2, use_lsg
     it.  A call the kernel does not cover (more than 8 terms, a pad as large as the map, BCE on anything but two probabilities,
     tensors that are not batch-1 fp32 on the device) runs as the composition of torch calls; an upsampled D1 map larger than D2's
     raises the ValueError of util.mul's None."""
-    l1s = [_factd_logits(o, use_lsgan1) for o in d1_outs]
-    l2s = [_factd_logits(o, use_lsgan2) for o in d2_outs]
+    l1s = [_logits_behind(o, use_lsgan1, "factored_gan_loss") for o in d1_outs]
+    l2s = [_logits_behind(o, use_lsgan2, "factored_gan_loss") for o in d2_outs]
     assert len(l1s) == len(l2s) == len(targets_are_real) == len(weights) and len(l1s) >= 1
     assert up in (1, 2), "--transform_1to2: None or bilinear_2"
     for a, b in zip(l1s, l2s):
@@ -452,6 +444,13 @@ class GANLossMultiClass(nn.Module):
         return cross_entropy_logits(input, None, int(target_label))
 
 
+def _scale_saved_grad(ctx, gout):
+    """d loss / d x of _L1Fn / _Bce01Fn: the forward kernel's unit-gradient result ctx.g times the upstream scalar."""
+    dx = torch.empty_like(ctx.g)
+    ops.scale(gout.contiguous(), ctx.g, dx)
+    return ops.logical_view(dx, ctx.C)
+
+
 class _L1Fn(torch.autograd.Function):
     """lambda * mean(|x - y| * w) with w = 1 + sum_i (A_i + 1) / 2 * (weights_i - 1), or w a per-pixel map, or 1."""
 
@@ -470,9 +469,7 @@ class _L1Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        dx = torch.empty_like(ctx.g)
-        ops.scale(gout.contiguous(), ctx.g, dx)
-        return ops.logical_view(dx, ctx.C), None, None, None, None, None
+        return _scale_saved_grad(ctx, gout), None, None, None, None, None
 
 
 class _Bce01Fn(torch.autograd.Function):
@@ -489,9 +486,7 @@ class _Bce01Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        dx = torch.empty_like(ctx.g)
-        ops.scale(gout.contiguous(), ctx.g, dx)
-        return ops.logical_view(dx, ctx.C), None
+        return _scale_saved_grad(ctx, gout), None
 
 
 def bce_on_rescaled(x, t):

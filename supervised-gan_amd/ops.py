@@ -666,7 +666,7 @@ def gan_loss_bwd(logits, target, mode, gout, dlogits):
 
 
 GAN_LOSS_WS_BYTES = 2048   # SGAN_GAN_LOSS_WS_BYTES
-_loss_ws = {}
+_zeroed_ws = {}
 _unit_grads = []           # weak references to gradient tensors known to hold 1.0 (BaseModel._backward's cached root gradient)
 
 
@@ -681,14 +681,18 @@ def is_unit_grad(t) -> bool:
     return any(r() is t for r in _unit_grads)
 
 
-def _gan_loss_workspace(device):
-    """Zero-initialised once per device; the kernel leaves its ticket counter at zero.  The fused loss runs on the trainer's main
-    stream only (side-stream chains use the per-term loss)."""
-    key = device.index
-    ws = _loss_ws.get(key)
+def _zeroed_workspace(key, device, nbytes):
+    """The float64 scratch of the loss entry point `key` on `device`: zeroed once, and every kernel that uses it leaves its ticket
+    counter (the seg-head kernels: their slots too) at zero for the next call.  One buffer per entry point and device, so these
+    losses run on the trainer's main stream only (side-stream chains use the per-term loss)."""
+    ws = _zeroed_ws.get((key, device.index))
     if ws is None:
-        ws = _loss_ws[key] = torch.zeros(GAN_LOSS_WS_BYTES // 8, dtype=torch.float64, device=device)
+        ws = _zeroed_ws[(key, device.index)] = torch.zeros(nbytes // 8, dtype=torch.float64, device=device)
     return ws
+
+
+def _gan_loss_workspace(device):
+    return _zeroed_workspace("gan_loss", device, GAN_LOSS_WS_BYTES)
 
 
 def gan_loss_multi_fwd(logits, targets, weights, mode, each_out, total_out, dlogits=None):
@@ -712,15 +716,10 @@ def gan_loss_multi_bwd(logits, targets, weights, mode, gout, dlogits):
 
 
 FACTD_LOSS_WS_BYTES = 2048   # SGAN_FACTD_LOSS_WS_BYTES
-_factd_ws = {}
 
 
 def _factd_loss_workspace(device):
-    """Zero-initialised once per device and left zeroed by the kernel, like _gan_loss_workspace (main stream only)."""
-    ws = _factd_ws.get(device.index)
-    if ws is None:
-        ws = _factd_ws[device.index] = torch.zeros(FACTD_LOSS_WS_BYTES // 8, dtype=torch.float64, device=device)
-    return ws
+    return _zeroed_workspace("factd_loss", device, FACTD_LOSS_WS_BYTES)
 
 
 def factd_mode(sig1, sig2, mse):
@@ -780,16 +779,13 @@ def sigmoid_nhwc_bwd(dp, p, Creal, dz):
 
 
 BCE_WEIGHTED_WS_BYTES = 1024   # SGAN_BCE_WEIGHTED_WS_BYTES
-_bcew_ws = {}
 
 
 def bce_weighted_fwd(p, t, Creal, class_w, nw, loss_out):
     """Weighted BCE of two [H, W, Cs] buffers (sgan_bce_weighted_fwd); class_w: device float vector of >= nw entries, or None."""
     H, W, _ = p.shape
     assert t.shape[:2] == (H, W) and (nw == 0 or class_w.numel() >= nw)
-    ws = _bcew_ws.get(p.device.index)
-    if ws is None:      # zero once; the kernel leaves its ticket at zero
-        ws = _bcew_ws[p.device.index] = torch.zeros(BCE_WEIGHTED_WS_BYTES // 8, dtype=torch.float64, device=p.device)
+    ws = _zeroed_workspace("bce_weighted", p.device, BCE_WEIGHTED_WS_BYTES)
     L.check(L.lib().sgan_bce_weighted_fwd(_ptr(_act(p)), p.stride(1), _ptr(_act(t)), t.stride(1), H * W, Creal, _ptr(class_w), int(nw),
                                           _ptr(loss_out), _ptr(ws), BCE_WEIGHTED_WS_BYTES, _stream()), "sgan_bce_weighted_fwd")
 
@@ -803,15 +799,11 @@ def bce_weighted_bwd(p, t, Creal, class_w, nw, gout, dp):
 
 SEGHEAD_WS_BYTES = 8192   # SGAN_SEGHEAD_WS_BYTES
 SEGHEAD_SOFTMAX, SEGHEAD_SIGMOID = L.SEGHEAD_SOFTMAX, L.SEGHEAD_SIGMOID
-_seghead_ws = {}
 
 
 def _seghead_workspace(device, which):
-    """Zero-initialised once per device and entry point, left zeroed by the kernels (main stream only, like _gan_loss_workspace)."""
-    ws = _seghead_ws.get((device.index, which))
-    if ws is None:
-        ws = _seghead_ws[(device.index, which)] = torch.zeros(SEGHEAD_WS_BYTES // 8, dtype=torch.float64, device=device)
-    return ws
+    """which: "head" (sgan_seg_head) or "norm" (sgan_label_weight_sum) -- the two may be in flight behind one another"""
+    return _zeroed_workspace("seghead_" + which, device, SEGHEAD_WS_BYTES)
 
 
 def label_weight_sum(label, Creal, class_w, out):
