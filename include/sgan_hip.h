@@ -756,6 +756,44 @@ int64_t sgan_thin_workspace(int32_t H, int32_t W);
 int sgan_thin(const float* plane, int64_t pix_stride, int32_t H, int32_t W, float* out, int32_t max_num_iter, void* workspace,
               int64_t workspace_bytes, int32_t* iters_out, int32_t* dev_err, void* stream);
 
+/* ---- region statistics on the device (shape features of generated against real images: shape_stats.py) --------------------------
+ * The reference's paper judges a generator by shape features of its cells and mitochondria; its repository holds only MATLAB that
+ * loads precomputed features (experiments/plots).  These entries measure every region of a label map; util.region_table is the
+ * NumPy / scipy restatement they are tested against, util.region_props derives the regionprops-style features from the rows.
+ *
+ * sgan_region_stats_workspace: bytes of the workspace sgan_region_stats needs for an H x W map (< 0: bad shape).
+ * sgan_region_stats: appends one row of SGAN_REGION_COLS int64 per region of `labels` (a map in sgan_ccl_label's form: 0 = wall, else
+ *   1 + the region's smallest raster index) to `table` (caller-owned, `capacity` rows), starting at row cursor[0].  cursor is 2 int32
+ *   in device memory, {rows used, images done}, zeroed by the caller once.  Rows are in ascending order of the region's root raster
+ *   index: row cursor[0] + k - 1 is region k of scipy.ndimage.label(free, structure=np.ones((3, 3))).  The call ends by adding the
+ *   number of rows written to cursor[0] and 1 to cursor[1].  Columns, with x = column and y = row of a pixel, all exact:
+ *      0      area in pixels
+ *      1..4   xmin, xmax, ymin, ymax (inclusive)
+ *      5..9   sum x, sum y, sum x^2, sum y^2, sum x y over the region's pixels
+ *      10     boundary pixels: pixels of the region with at least one of their 4 neighbours not in it (outside the image: not in it)
+ *      11     root raster index (label - 1)
+ *      12     image ordinal (cursor[1] at entry)
+ *      13     exposed edges: the (pixel, N/S/E/W) pairs whose neighbour is not in the region
+ *      14,15  0
+ *   If the regions do not all fit into `capacity`, the lowest-ranked ones that fit are written, cursor[0] becomes capacity, *dev_err
+ *   gets bit 32 and the ordinal still advances.  A map that is not in sgan_ccl_label's form (a label outside 0 .. H W, a label whose
+ *   root does not carry it, more roots than ceil(H / 2) ceil(W / 2)) gets bit 4 and the offending pixels are left out; no access
+ *   leaves the buffers.
+ *   Nothing is read back and nothing is decided on the host: five launches whose grids depend on (H, W) only -- root flags counted
+ *   per block of 1024 pixels, one workgroup that scans the block counts and copies the cursor, the exclusive prefix sum over the
+ *   flags (a region's dense rank) with each root initialising its own staging row, the counting pass, emit -- so the call can be
+ *   captured in a hipGraph and replayed on maps with any other number of regions.  In the counting pass a workgroup holds 64 x 4
+ *   pixels: a wave merges its 64 pixels by label (a segmented reduction: counts by ballot, the coordinate sums by one butterfly),
+ *   the four waves merge in an LDS table, and the workgroup adds each region it met to the region's staging row once, in 64-bit
+ *   integer atomics -- the same integers in any order.  The staging table lives in the workspace, indexed by dense rank, so
+ *   initialisation does not depend on capacity.  Workspace, dev_err and stream as sgan_rand_f_accumulate; the call initialises what
+ *   it uses.  H * W < 2^30 as sgan_ccl_label, and H, W <= 65536 so that the second-order sums stay below 2^62; both entries refuse
+ *   any other shape.  Null pointers, capacity < 1 and a short workspace are refused before any launch. */
+#define SGAN_REGION_COLS 16
+int64_t sgan_region_stats_workspace(int32_t H, int32_t W);
+int sgan_region_stats(const int32_t* labels, int32_t H, int32_t W, int64_t* table, int32_t capacity, int32_t* cursor, void* workspace,
+                      int64_t workspace_bytes, int32_t* dev_err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

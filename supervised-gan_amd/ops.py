@@ -1053,6 +1053,8 @@ _metric_err = {}
 _rand_ws = {}
 _vinfo_ws = {}
 _thin_ws = {}
+_region_ws = {}
+REGION_COLS = 16      # int64 per row of a region table (include/sgan_hip.h, sgan_region_stats)
 VINFO_PARTS = ('SA', 'SB', 'SAB', 'aux', 'm', 'H_S', 'H_T', 'I', 'VInfo', 'split', 'merge')      # parts_out of vinfo_accumulate
 
 
@@ -1072,7 +1074,7 @@ def check_metric_err(device):
     if code:
         e.zero_()
         raise L.SganError(f"segmentation metric kernels gave up on part of their input (flags {code:#x}: 1 = union-find bound, "
-                          "2 = pair table full, 4 / 8 = label out of range, 16 = thinning budget ran out); the accumulated values are incomplete")
+                          "2 = pair table full, 4 / 8 = label out of range, 16 = thinning budget ran out, 32 = region table full); the accumulated values are incomplete")
 
 
 def _plane(t, what):
@@ -1129,6 +1131,37 @@ def thin(plane, out=None, max_num_iter=None, iters_out=None, workspace=None):
     L.check(L.lib().sgan_thin(_ptr(plane), plane.stride(1), H, W, _ptr(out), 0 if max_num_iter is None else int(max_num_iter), _ptr(ws),
                               ws.numel() * ws.element_size(), _ptr(iters_out), _ptr(metric_err(dev)), _stream()), "sgan_thin")
     return out
+
+
+def region_stats_workspace(H, W, device):
+    """The scratch of region_stats for H x W maps (block counts, ranks and the staging rows), cached per (H, W, device)."""
+    key = (H, W, device.index)
+    ws = _region_ws.get(key)
+    if ws is None:
+        nbytes = L.lib().sgan_region_stats_workspace(H, W)
+        if nbytes < 0:
+            raise L.SganError(f"sgan_region_stats_workspace({H}, {W}): {L.lib().sgan_last_error().decode()}")
+        ws = _region_ws[key] = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
+    return ws
+
+
+def region_stats(labels, table, cursor, workspace=None):
+    """Appends one row of REGION_COLS exact integers per region of `labels` (int32 [H, W] from ccl_label) to `table` (int64
+    [capacity, 16] on the device) at row cursor[0], in scipy.ndimage.label's order (sgan_region_stats; util.region_table is the host
+    yardstick and names the columns).  cursor: int32[2] on the device, {rows used, images done}, zeroed by the caller once and
+    advanced by the call.  Regions beyond the capacity are dropped and raise bit 32 of metric_err.  Only enqueues -- the launch
+    sequence depends on the shape alone -- so any number of images go into one table without a read-back."""
+    require_gpu(labels, "region_stats")
+    assert labels.dim() == 2 and labels.dtype == torch.int32 and labels.is_contiguous(), (labels.shape, labels.dtype)
+    H, W = labels.shape
+    dev = labels.device
+    assert (table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == REGION_COLS and table.shape[0] >= 1
+            and table.is_contiguous() and table.device == dev), (table.shape, table.dtype)
+    assert cursor.dtype == torch.int32 and cursor.is_contiguous() and cursor.numel() == 2 and cursor.device == dev
+    ws = region_stats_workspace(H, W, dev) if workspace is None else workspace
+    L.check(L.lib().sgan_region_stats(_ptr(labels), H, W, _ptr(table), table.shape[0], _ptr(cursor), _ptr(ws),
+                                      ws.numel() * ws.element_size(), _ptr(metric_err(dev)), _stream()), "sgan_region_stats")
+    return table
 
 
 def rand_f_workspace(H, W, device):

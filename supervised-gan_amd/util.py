@@ -1,6 +1,7 @@
 """Image and metric helpers of the drivers (util/util.py:15-28, :41-43, :86-128 of the reference): tensor -> uint8 image -> PNG,
-the Rand F-score of a binary segmentation, the information score (VInfo) that goes with it, and Guo-Hall thinning (the border
-thinning both scores are ranked after: `thin`, `compute_thinned_scores`)."""
+the Rand F-score of a binary segmentation, the information score (VInfo) that goes with it, Guo-Hall thinning (the border
+thinning both scores are ranked after: `thin`, `compute_thinned_scores`), and the shape statistics of the regions of a map
+(`region_table`, the yardstick of the device's sgan_region_stats, and `region_props`, the features derived from its rows)."""
 import os
 
 import numpy as np
@@ -75,6 +76,96 @@ def thin(mask, max_num_iter=None):
             break
         n_changing += 1
     return m.astype(bool), n_changing
+
+
+REGION_COLS = ('area', 'xmin', 'xmax', 'ymin', 'ymax', 'sum_x', 'sum_y', 'sum_xx', 'sum_yy', 'sum_xy', 'boundary', 'root', 'image',
+               'edges', 'zero14', 'zero15')
+REGION_PROPS = ('area', 'centroid_x', 'centroid_y', 'equivalent_diameter', 'extent', 'mu20', 'mu02', 'mu11', 'major_axis_length',
+                'minor_axis_length', 'eccentricity', 'orientation', 'compactness', 'touches_border')
+
+
+def region_table(free_mask, image_ordinal=0):
+    """One row of 16 exact int64 per 8-connected region of the TRUE pixels of `free_mask` [H, W], in scipy.ndimage.label's order
+    (ascending smallest raster index): the host yardstick of ops.region_stats on ops.ccl_label's map of the same pixels.
+    Columns (REGION_COLS), x = column, y = row: 0 area; 1..4 xmin, xmax, ymin, ymax (inclusive); 5..9 sum x, sum y, sum x^2,
+    sum y^2, sum x y; 10 boundary pixels (at least one 4-neighbour not in the region, outside the image counts as not in it);
+    11 root = smallest raster index; 12 image_ordinal; 13 exposed edges = (pixel, N/S/E/W) pairs whose neighbour is not in the
+    region; 14, 15 zero.  All sums are taken in int64 (np.add.reduceat over the pixels sorted by region), never through floats."""
+    from scipy import ndimage
+    free = np.asarray(free_mask) != 0
+    assert free.ndim == 2, free.shape
+    H, W = free.shape
+    lab, k = ndimage.label(free, structure=np.ones((3, 3), dtype=np.int32))
+    table = np.zeros((k, 16), dtype=np.int64)
+    if k == 0:
+        return table
+    ys, xs = np.nonzero(lab)                                   # raster order
+    region = lab[ys, xs].astype(np.int64) - 1
+    order = np.argsort(region, kind='stable')                  # within a region the raster order is kept
+    starts = np.searchsorted(region[order], np.arange(k))
+    x, y = xs[order].astype(np.int64), ys[order].astype(np.int64)
+    pad = np.zeros((H + 2, W + 2), dtype=lab.dtype)
+    pad[1:-1, 1:-1] = lab
+    mine = pad[1:-1, 1:-1]
+    exposed = sum((nb != mine).astype(np.int64) for nb in (pad[:-2, 1:-1], pad[2:, 1:-1], pad[1:-1, :-2], pad[1:-1, 2:]))
+    e = exposed[ys, xs][order]
+    table[:, 0] = np.add.reduceat(np.ones_like(x), starts)
+    table[:, 1], table[:, 2] = np.minimum.reduceat(x, starts), np.maximum.reduceat(x, starts)
+    table[:, 3], table[:, 4] = np.minimum.reduceat(y, starts), np.maximum.reduceat(y, starts)
+    for col, v in ((5, x), (6, y), (7, x * x), (8, y * y), (9, x * y), (10, (e > 0).astype(np.int64)), (13, e)):
+        table[:, col] = np.add.reduceat(v, starts)
+    table[:, 11] = (y * W + x)[starts]
+    table[:, 12] = image_ordinal
+    return table
+
+
+def region_props(table, shape):
+    """regionprops-style features in float64 from the integer rows of region_table / ops.region_stats; shape = (H, W) of the images.
+    Returns a dict of [R] arrays (REGION_PROPS).  With A = area, Sx = sum x, ... and a pixel taken as the unit square around its centre:
+      centroid_x = Sx / A, centroid_y = Sy / A
+      equivalent_diameter = sqrt(4 A / pi): the diameter of the disc of the same area
+      extent = A / ((xmax - xmin + 1) (ymax - ymin + 1))
+      mu20 = (A Sxx - Sx^2) / A^2 + 1/12, mu02 = (A Syy - Sy^2) / A^2 + 1/12, mu11 = (A Sxy - Sx Sy) / A^2: the central second
+        moments per pixel; 1/12 is the second moment of the unit square itself, so a single pixel has mu20 = mu02 = 1/12 and an
+        a x b rectangle a^2 / 12 and b^2 / 12.  The three numerators are formed in Python integers, which are exact.
+      l1 = (mu20 + mu02 + sqrt((mu20 - mu02)^2 + 4 mu11^2)) / 2 and l2 = (mu20 mu02 - mu11^2) / l1: the eigenvalues of
+        [[mu20, mu11], [mu11, mu02]] (the second from the determinant, which does not cancel)
+      major_axis_length = 4 sqrt(l1), minor_axis_length = 4 sqrt(l2): the axes of the ellipse with the same second moments
+      eccentricity = sqrt(1 - l2 / l1)
+      orientation = atan2(2 mu11, mu20 - mu02) / 2: the angle of the major axis from the +x axis towards +y (rows grow downwards),
+        in (-pi/2, pi/2]; 0 for a region with mu20 == mu02 and mu11 == 0.  skimage measures its angle from the row axis instead.
+      compactness = 4 pi A / edges^2, the exposed edges being the perimeter of the pixel polygon: pi / 4 for any square
+      touches_border = xmin == 0 or ymin == 0 or xmax == W - 1 or ymax == H - 1 (bool)"""
+    t = np.asarray(table)
+    assert t.ndim == 2 and t.shape[1] == 16 and t.dtype == np.int64, (t.shape, t.dtype)
+    H, W = shape
+    o = t.astype(object)
+    A, Sx, Sy, Sxx, Syy, Sxy = (o[:, c] for c in (0, 5, 6, 7, 8, 9))
+    exact = lambda v: np.array([float(q) for q in v], dtype=np.float64)      # noqa: E731
+    a = t[:, 0].astype(np.float64)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        mu20 = exact(A * Sxx - Sx * Sx) / (a * a) + 1.0 / 12.0
+        mu02 = exact(A * Syy - Sy * Sy) / (a * a) + 1.0 / 12.0
+        mu11 = exact(A * Sxy - Sx * Sy) / (a * a)
+        l1 = (mu20 + mu02 + np.sqrt((mu20 - mu02) ** 2 + 4.0 * mu11 ** 2)) / 2.0
+        l2 = np.maximum((mu20 * mu02 - mu11 * mu11) / l1, 0.0)
+        edges = t[:, 13].astype(np.float64)
+        props = {
+            'area': a,
+            'centroid_x': t[:, 5] / a,
+            'centroid_y': t[:, 6] / a,
+            'equivalent_diameter': np.sqrt(4.0 * a / np.pi),
+            'extent': a / ((t[:, 2] - t[:, 1] + 1) * (t[:, 4] - t[:, 3] + 1)).astype(np.float64),
+            'mu20': mu20, 'mu02': mu02, 'mu11': mu11,
+            'major_axis_length': 4.0 * np.sqrt(l1),
+            'minor_axis_length': 4.0 * np.sqrt(l2),
+            'eccentricity': np.sqrt(np.maximum(1.0 - l2 / l1, 0.0)),
+            'orientation': 0.5 * np.arctan2(2.0 * mu11, mu20 - mu02),
+            'compactness': 4.0 * np.pi * a / (edges * edges),
+            'touches_border': (t[:, 1] == 0) | (t[:, 3] == 0) | (t[:, 2] == W - 1) | (t[:, 4] == H - 1),
+        }
+    assert tuple(props) == REGION_PROPS
+    return props
 
 
 def compute_thinned_scores(S, T):
