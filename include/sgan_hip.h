@@ -286,7 +286,13 @@ int sgan_bce_weighted_bwd(const float* p, int32_t pld, const float* t, int32_t t
  * sgan_label_weight_sum: out[0] = sum_p class_w[label_p] (fp64 accumulation) over the labels in [0, C); class_w NULL: their count.
  * `workspace` (both): SGAN_SEGHEAD_WS_BYTES of 8-byte aligned device scratch, ZERO on first use, owned by one stream at a time and
  * left zeroed by every call (no fill per call).  The sums are taken in a fixed order: equal inputs give equal bits.
- * Both return 1 (not covered, nothing launched) for C > 16 or a NULL required pointer. */
+ * Both return 1 (not covered, nothing launched) for C > 16 or a NULL required pointer.
+ * sgan_seg_head_pw / sgan_pixel_weight_sum: the same two with a per-pixel term in the weight (the border term of the U-Net loss,
+ *   sgan_border_weight): w_p = (class_w ? class_w[y_p] : 1) + pixel_add[p] (one fp32 add) for labels in [0, C), `pixel_add` a dense
+ *   float [npix] map; any other label contributes nothing to either.  sgan_pixel_weight_sum: out[0] = sum_p w_p.  sgan_seg_head_pw,
+ *   softmax only: loss = sum_p w_p (logsumexp(z_p) - z_p[y_p]) / norm[0];  dlogits = w_p (p - onehot(y_p)) / norm[0];  norm 0 -> loss 0.
+ *   Workspace, fixed summation order, padding channels and the return of 1 (here also for a NULL pixel_add or norm) as above.  With
+ *   pixel_add all zero both give the bits of the entries above. */
 #define SGAN_SEGHEAD_WS_BYTES 8192
 #define SGAN_SEGHEAD_SOFTMAX 0
 #define SGAN_SEGHEAD_SIGMOID 1
@@ -294,6 +300,11 @@ int sgan_label_weight_sum(const int64_t* label, int32_t npix, int32_t C, const f
 int sgan_seg_head(const float* logits, int32_t ld, int32_t npix, int32_t C, int32_t mode, const void* label_or_target, int32_t tld,
                   const float* class_w, int32_t nw, const float* norm, float* p_out, int32_t pld, float* dlogits, int32_t dld,
                   float* loss_out, void* workspace, void* stream);
+int sgan_pixel_weight_sum(const int64_t* label, int32_t npix, int32_t C, const float* class_w, const float* pixel_add, float* out,
+                          void* workspace, void* stream);
+int sgan_seg_head_pw(const float* logits, int32_t ld, int32_t npix, int32_t C, const int64_t* label, const float* class_w, int32_t nw,
+                     const float* pixel_add, const float* norm, float* p_out, int32_t pld, float* dlogits, int32_t dld, float* loss_out,
+                     void* workspace, void* stream);
 
 /* ---- backward pass of a one-channel stride-1 head (the PatchGAN logits conv, models/networks.py:832-835) in one launch: the job
  * lists of sgan_conv_dgrad_grouped and sgan_conv_wgrad_grouped for the SAME pass (wjobs may be NULL: input gradient only).  Returns 1
@@ -793,6 +804,26 @@ int sgan_thin(const float* plane, int64_t pix_stride, int32_t H, int32_t W, floa
 int64_t sgan_region_stats_workspace(int32_t H, int32_t W);
 int sgan_region_stats(const int32_t* labels, int32_t H, int32_t W, int64_t* table, int32_t capacity, int32_t* cursor, void* workspace,
                       int64_t workspace_bytes, int32_t* dev_err, void* stream);
+
+/* ---- border weight: the per-pixel term of the U-Net loss (Ronneberger et al. 2015, eq. 2) on the device ---------------------------
+ * w(p) = w_class[y_p] + w0 exp(-(d1(p) + d2(p))^2 / (2 sigma^2)), d1 and d2 the distances from p to the nearest and the second-nearest
+ * cell: the term that makes a wall squeezed between two different cells expensive to miss.  The trainer's crops are cut, flipped and
+ * rotated on the device, so the cells of a crop exist only there; util.border_weight_map is the NumPy restatement this is tested against.
+ *
+ * sgan_border_weight: `labels` is an H x W map in sgan_ccl_label's form (0 = wall, anything else = a cell id).  For a wall pixel p and
+ *   a cell L let m_L(p) be the smallest dy^2 + dx^2 over the pixels of L inside the image with dy^2 + dx^2 <= radius^2.  d1sq(p) and
+ *   d2sq(p) are the two smallest m_L(p) over DISTINCT L (equal when two cells are equally near), -1 where fewer than one / two cells
+ *   are in range: exact integers, the same whichever order the pixels are met in.  bmap(p) = w0 expf(-(sqrtf(d1sq) + sqrtf(d2sq))^2 /
+ *   (2 sigma^2)) where both exist, else 0.0f.  A pixel that is not wall gets bmap 0 and d1sq = d2sq = -1.  The cut at `radius` is part
+ *   of the definition: with radius = ceil(4 sigma) the dropped terms are below w0 e^-8.  bmap is a dense float [H * W] plane, d1sq and
+ *   d2sq are optional (NULL) int32 [H * W] planes.
+ *   One launch, whose grid depends on (H, W) and whose LDS on radius only: a workgroup holds a 32 x 32 core and a radius-pixel halo of
+ *   labels in LDS ((32 + 2 radius)^2 int32, 36 KB at radius 32; outside the image = wall) and every wall pixel of the core scans the disc,
+ *   nearest rows first, until no further row can change its pair.  Nothing is read back, so the call captures into a hipGraph and
+ *   replays on any other map.  A label < 0 is treated as wall and sets bit 4 of *dev_err (optional; as sgan_rand_f_accumulate's).
+ *   Returns 1, having launched nothing, for NULL labels or bmap, H or W < 1, H * W >= 2^30, radius outside [1, 32] or sigma <= 0. */
+int sgan_border_weight(const int32_t* labels, int32_t H, int32_t W, int32_t radius, float w0, float sigma, float* bmap, int32_t* d1sq,
+                       int32_t* d2sq, int32_t* dev_err, void* stream);
 
 #ifdef __cplusplus
 }

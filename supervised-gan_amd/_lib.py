@@ -152,6 +152,8 @@ SIGNATURES = {
     "sgan_bce_weighted_bwd": [_P, _I, _P, _I, _I, _I, _P, _I, _P, _P, _I, _P],
     "sgan_label_weight_sum": [_P, _I, _I, _P, _P, _P, _P],
     "sgan_seg_head": [_P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P],
+    "sgan_pixel_weight_sum": [_P, _I, _I, _P, _P, _P, _P, _P],
+    "sgan_seg_head_pw": [_P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P],
     "sgan_normal_fill": [_P, _L, C.c_uint64, _P, _I, _P],
     "sgan_normal_fill_nhwc": [_P, _I, _I, _I, _I, C.c_uint64, _P, _I, _P],
     "sgan_normal_fill_nhwc_pair": [_P, _P, _I, _I, _I, _I, C.c_uint64, _P, _P, C.c_int64, _P],
@@ -166,6 +168,7 @@ SIGNATURES = {
     "sgan_thin": [_P, _L, _I, _I, _P, _I, _P, _L, _P, _P, _P],
     "sgan_region_stats_workspace": [_I, _I],
     "sgan_region_stats": [_P, _I, _I, _P, _I, _P, _P, _L, _P, _P],
+    "sgan_border_weight": [_P, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P],
     "sgan_profile_enable": [_I],
     "sgan_profile_count": [],
     "sgan_profile_mark": [_P],

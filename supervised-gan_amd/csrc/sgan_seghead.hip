@@ -21,6 +21,7 @@ struct ShArgs {
     const int64_t* label;              // SGAN_SEGHEAD_SOFTMAX
     const float* t; int tld;           // SGAN_SEGHEAD_SIGMOID
     const float* cw; int nw;
+    const float* padd;                 // PW kernels: added to the class weight of every pixel whose label is in range
     const float* norm;
     float* p; int pld;
     float* d; int dld;                 // d == nullptr: no gradient
@@ -78,7 +79,8 @@ __device__ __forceinline__ bool sh_total(double acc, double* part, unsigned* tic
     return true;
 }
 
-template <int CS>
+// PW (softmax mode only): the weight of pixel i is cw[y_i] + padd[i]
+template <int CS, bool PW>
 __global__ __launch_bounds__(256) void sg_seg_head_kernel(const ShArgs A) {
     constexpr int N = CS ? CS : SG_SH_MAXC;
     __shared__ double red[4];
@@ -114,6 +116,7 @@ __global__ __launch_bounds__(256) void sg_seg_head_kernel(const ShArgs A) {
             float zy = 0.f, w = 0.f;
 #pragma unroll
             for (int c = 0; c < N; ++c) { zy = c == y ? z[c] : zy; w = c == y ? cw[c] : w; }
+            if constexpr (PW) w = ok ? w + A.padd[i] : 0.f;
             const float ws = w * scale;
 #pragma unroll
             for (int c = 0; c < N; ++c) {
@@ -159,8 +162,9 @@ __global__ __launch_bounds__(256) void sg_seg_head_kernel(const ShArgs A) {
     }
 }
 
-__global__ __launch_bounds__(256) void sg_label_weight_sum_kernel(const int64_t* label, int npix, int C, const float* class_w, float* out,
-                                                                  double* part, unsigned* ticket) {
+template <bool PW>
+__global__ __launch_bounds__(256) void sg_label_weight_sum_kernel(const int64_t* label, int npix, int C, const float* class_w,
+                                                                  const float* pixel_add, float* out, double* part, unsigned* ticket) {
     __shared__ double red[4];
     __shared__ int last;
     float cw[SG_SH_MAXC];
@@ -173,6 +177,7 @@ __global__ __launch_bounds__(256) void sg_label_weight_sum_kernel(const int64_t*
         float w = 0.f;
 #pragma unroll
         for (int c = 0; c < SG_SH_MAXC; ++c) w = c == y ? cw[c] : w;
+        if constexpr (PW) w = y >= 0 ? w + pixel_add[i] : 0.f;      // the weight sg_seg_head_kernel<., true> gives the pixel
         acc += (double)w;
     }
     double total;
@@ -185,28 +190,52 @@ __global__ __launch_bounds__(256) void sg_label_weight_sum_kernel(const int64_t*
 
 static inline bool sh_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-extern "C" int sgan_label_weight_sum(const int64_t* label, int32_t npix, int32_t C, const float* class_w, float* out, void* workspace,
-                                     void* stream) {
-    if (!label || !out || !workspace || C > SG_SH_MAXC) return 1;
+static int sh_weight_sum(const int64_t* label, int32_t npix, int32_t C, const float* class_w, const float* pixel_add, float* out,
+                         void* workspace, void* stream) {
     SGAN_CHECK(npix > 0 && C >= 1, "bad argument (1..%d classes)", SG_SH_MAXC);
     SGAN_CHECK(((uintptr_t)workspace & 7) == 0, "workspace of SGAN_SEGHEAD_WS_BYTES (8-byte aligned) required");
     double* part = static_cast<double*>(workspace);
     unsigned* ticket = reinterpret_cast<unsigned*>(part + SG_SH_BLOCKS);
     int blocks = sg_cdiv(npix, 256);
     if (blocks > SG_SH_BLOCKS) blocks = SG_SH_BLOCKS;
-    hipLaunchKernelGGL(sg_label_weight_sum_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, label, npix, C, class_w, out, part,
-                       ticket);
+    if (pixel_add)
+        hipLaunchKernelGGL(sg_label_weight_sum_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, label, npix, C, class_w, pixel_add,
+                           out, part, ticket);
+    else
+        hipLaunchKernelGGL(sg_label_weight_sum_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, label, npix, C, class_w, pixel_add,
+                           out, part, ticket);
     SGAN_LAUNCH_CHECK();
     return SGAN_OK;
 }
 
-extern "C" int sgan_seg_head(const float* logits, int32_t ld, int32_t npix, int32_t C, int32_t mode, const void* label_or_target,
-                             int32_t tld, const float* class_w, int32_t nw, const float* norm, float* p_out, int32_t pld, float* dlogits,
-                             int32_t dld, float* loss_out, void* workspace, void* stream) {
-    if (!logits || !label_or_target || !p_out || !loss_out || !workspace || C > SG_SH_MAXC) return 1;
-    SGAN_CHECK(mode == SGAN_SEGHEAD_SOFTMAX || mode == SGAN_SEGHEAD_SIGMOID, "mode is SGAN_SEGHEAD_SOFTMAX or SGAN_SEGHEAD_SIGMOID");
+extern "C" int sgan_label_weight_sum(const int64_t* label, int32_t npix, int32_t C, const float* class_w, float* out, void* workspace,
+                                     void* stream) {
+    if (!label || !out || !workspace || C > SG_SH_MAXC) return 1;
+    return sh_weight_sum(label, npix, C, class_w, nullptr, out, workspace, stream);
+}
+
+extern "C" int sgan_pixel_weight_sum(const int64_t* label, int32_t npix, int32_t C, const float* class_w, const float* pixel_add, float* out,
+                                     void* workspace, void* stream) {
+    if (!label || !pixel_add || !out || !workspace || C > SG_SH_MAXC) return 1;
+    return sh_weight_sum(label, npix, C, class_w, pixel_add, out, workspace, stream);
+}
+
+// cs: the channels of a 16-byte row layout (4, 8, 12, 16), or 0 for the scalar form
+template <bool PW>
+static void sh_launch(int cs, int blocks, hipStream_t st, const ShArgs& A) {
+    const dim3 g(blocks), b(256);
+    if (cs == 4) hipLaunchKernelGGL((sg_seg_head_kernel<4, PW>), g, b, 0, st, A);
+    else if (cs == 8) hipLaunchKernelGGL((sg_seg_head_kernel<8, PW>), g, b, 0, st, A);
+    else if (cs == 12) hipLaunchKernelGGL((sg_seg_head_kernel<12, PW>), g, b, 0, st, A);
+    else if (cs == 16) hipLaunchKernelGGL((sg_seg_head_kernel<16, PW>), g, b, 0, st, A);
+    else hipLaunchKernelGGL((sg_seg_head_kernel<0, PW>), g, b, 0, st, A);
+}
+
+// what sgan_seg_head and sgan_seg_head_pw share: the argument checks and the launch; pixel_add != NULL selects the PW kernels
+static int sh_head(const float* logits, int32_t ld, int32_t npix, int32_t C, int32_t mode, const void* label_or_target, int32_t tld,
+                   const float* class_w, int32_t nw, const float* pixel_add, const float* norm, float* p_out, int32_t pld, float* dlogits,
+                   int32_t dld, float* loss_out, void* workspace, void* stream) {
     const bool softmax = mode == SGAN_SEGHEAD_SOFTMAX;
-    if (softmax && !norm) return 1;
     SGAN_CHECK(npix > 0 && C >= 1 && ld >= C && pld >= C && (!dlogits || dld >= C), "bad argument (1..%d channels)", SG_SH_MAXC);
     SGAN_CHECK(softmax || tld >= C, "target rows shorter than C");
     SGAN_CHECK(nw >= 0 && (!class_w || (softmax ? nw >= C : nw <= C)) && (class_w || softmax || nw == 0),
@@ -216,7 +245,7 @@ extern "C" int sgan_seg_head(const float* logits, int32_t ld, int32_t npix, int3
     A.z = logits; A.ld = ld; A.npix = npix; A.C = C; A.mode = mode;
     A.label = softmax ? static_cast<const int64_t*>(label_or_target) : nullptr;
     A.t = softmax ? nullptr : static_cast<const float*>(label_or_target);
-    A.tld = tld; A.cw = class_w; A.nw = class_w ? nw : 0; A.norm = norm;
+    A.tld = tld; A.cw = class_w; A.nw = class_w ? nw : 0; A.padd = pixel_add; A.norm = norm;
     A.p = p_out; A.pld = pld; A.d = dlogits; A.dld = dld; A.loss = loss_out;
     A.part = static_cast<double*>(workspace);
     A.ticket = reinterpret_cast<unsigned*>(A.part + SG_SH_BLOCKS);
@@ -225,13 +254,26 @@ extern "C" int sgan_seg_head(const float* logits, int32_t ld, int32_t npix, int3
     // 16-byte rows: every operand stored with the same 4, 8, 12 or 16 channels, on aligned bases
     const bool vec = (ld == 4 || ld == 8 || ld == 12 || ld == 16) && pld == ld && (!dlogits || dld == ld) && (softmax || tld == ld) && sh_al16(logits) &&
                      sh_al16(p_out) && sh_al16(dlogits) && (softmax || sh_al16(label_or_target));
-    const dim3 g(blocks), b(256);
-    hipStream_t st = (hipStream_t)stream;
-    if (vec && ld == 4) hipLaunchKernelGGL(sg_seg_head_kernel<4>, g, b, 0, st, A);
-    else if (vec && ld == 8) hipLaunchKernelGGL(sg_seg_head_kernel<8>, g, b, 0, st, A);
-    else if (vec && ld == 12) hipLaunchKernelGGL(sg_seg_head_kernel<12>, g, b, 0, st, A);
-    else if (vec && ld == 16) hipLaunchKernelGGL(sg_seg_head_kernel<16>, g, b, 0, st, A);
-    else hipLaunchKernelGGL(sg_seg_head_kernel<0>, g, b, 0, st, A);
+    if (pixel_add) sh_launch<true>(vec ? ld : 0, blocks, (hipStream_t)stream, A);
+    else sh_launch<false>(vec ? ld : 0, blocks, (hipStream_t)stream, A);
     SGAN_LAUNCH_CHECK();
     return SGAN_OK;
+}
+
+extern "C" int sgan_seg_head(const float* logits, int32_t ld, int32_t npix, int32_t C, int32_t mode, const void* label_or_target,
+                             int32_t tld, const float* class_w, int32_t nw, const float* norm, float* p_out, int32_t pld, float* dlogits,
+                             int32_t dld, float* loss_out, void* workspace, void* stream) {
+    if (!logits || !label_or_target || !p_out || !loss_out || !workspace || C > SG_SH_MAXC) return 1;
+    SGAN_CHECK(mode == SGAN_SEGHEAD_SOFTMAX || mode == SGAN_SEGHEAD_SIGMOID, "mode is SGAN_SEGHEAD_SOFTMAX or SGAN_SEGHEAD_SIGMOID");
+    if (mode == SGAN_SEGHEAD_SOFTMAX && !norm) return 1;
+    return sh_head(logits, ld, npix, C, mode, label_or_target, tld, class_w, nw, nullptr, norm, p_out, pld, dlogits, dld, loss_out, workspace,
+                   stream);
+}
+
+extern "C" int sgan_seg_head_pw(const float* logits, int32_t ld, int32_t npix, int32_t C, const int64_t* label, const float* class_w,
+                                int32_t nw, const float* pixel_add, const float* norm, float* p_out, int32_t pld, float* dlogits,
+                                int32_t dld, float* loss_out, void* workspace, void* stream) {
+    if (!logits || !label || !pixel_add || !norm || !p_out || !loss_out || !workspace || C > SG_SH_MAXC) return 1;
+    return sh_head(logits, ld, npix, C, SGAN_SEGHEAD_SOFTMAX, label, 0, class_w, nw, pixel_add, norm, p_out, pld, dlogits, dld, loss_out,
+                   workspace, stream);
 }

@@ -365,7 +365,7 @@ class _SegHeadFn(torch.autograd.Function):
     has no way into the dlogits the forward wrote, so the backward refuses one."""
 
     @staticmethod
-    def forward(ctx, logits, lt, cw, nw, norm, mode):
+    def forward(ctx, logits, lt, cw, nw, norm, mode, pixel_add=None):
         zb = ops.as_nhwc(logits)
         C_ = logits.shape[1]
         if mode == ops.SEGHEAD_SOFTMAX:
@@ -375,7 +375,7 @@ class _SegHeadFn(torch.autograd.Function):
         pb = torch.empty_like(zb)
         dz = torch.empty_like(zb) if ctx.needs_input_grad[0] else None
         loss = torch.empty((), dtype=torch.float32, device=logits.device)
-        if not ops.seg_head(zb, C_, mode, lt, cw, nw, norm, pb, dz, loss):
+        if not ops.seg_head(zb, C_, mode, lt, cw, nw, norm, pb, dz, loss, pixel_add=pixel_add):
             raise _SegHeadNotCovered()
         ctx.dz, ctx.C = dz, C_
         ctx.pb = pb      # the buffer object outlives this call: the detached alias autograd hands out maps back to it (as _CatPairFn)
@@ -386,21 +386,24 @@ class _SegHeadFn(torch.autograd.Function):
     def backward(ctx, gp, gout):
         assert gp is None, "seg_head: a gradient arrived at p -- the fused head is valid only while the loss is p's one consumer"
         if gout is None or ctx.dz is None:
-            return None, None, None, None, None, None
+            return None, None, None, None, None, None, None
         dz = ctx.dz
         if not ops.is_unit_grad(gout):
             dz = torch.empty_like(ctx.dz)
             ops.scale(gout.contiguous().float(), ctx.dz, dz)
-        return ops.logical_view(dz, ctx.C), None, None, None, None, None
+        return ops.logical_view(dz, ctx.C), None, None, None, None, None, None
 
 
-def seg_head(logits, label_or_target, class_weights=None, norm=None, mode=0):
+def seg_head(logits, label_or_target, class_weights=None, norm=None, mode=0, pixel_add=None):
     """The loss section of a segmentation step with no discriminator: returns (p, loss).
 
     mode ops.SEGHEAD_SOFTMAX: p = F.softmax(logits, 1), loss = sum_p w[y_p] nll_p / norm with `label_or_target` the int64 label map
     [1, H, W] on the logits' device and `norm` the device scalar sum_p w[y_p] (ops.label_weight_sum; None: computed here) -- that is
     F.cross_entropy(logits, label, weight=class_weights).  mode ops.SEGHEAD_SIGMOID: p = torch.sigmoid(logits), loss =
     F.binary_cross_entropy(p, target, weight=wm) with wm = 1 + sum_i target[:, i] (class_weights[i] - 1); `norm` is not read.
+    pixel_add (softmax mode, on the device): a float32 [H, W] map added to the weight of every labelled pixel, w_p = w[y_p] +
+    pixel_add[p] (ops.border_weight's map: the U-Net loss), `norm` then sum_p w_p (ops.pixel_weight_sum; None: computed here).  This
+    form has no composition to fall back on: outside the kernel's envelope it raises.
 
     One launch (sgan_seg_head) writes p, the loss and d loss / d logits; the backward hands the last out times the upstream gradient.
     p comes back NHWC-backed, like softmax_channels': it must have no consumer that sends a gradient back (the backward asserts it;
@@ -415,13 +418,22 @@ def seg_head(logits, label_or_target, class_weights=None, norm=None, mode=0):
         cw = class_weights.detach().float().contiguous() if nw else None
         if softmax:
             assert lt.numel() == logits.shape[2] * logits.shape[3] and (cw is None or nw == logits.shape[1])
+            if pixel_add is not None:
+                pixel_add = pixel_add.detach().reshape(-1).contiguous()
             if norm is None:
                 norm = torch.empty((), dtype=torch.float32, device=logits.device)
-                ops.label_weight_sum(lt.reshape(-1).contiguous(), logits.shape[1], cw, norm)
+                if pixel_add is not None:
+                    ops.pixel_weight_sum(lt.reshape(-1).contiguous(), logits.shape[1], cw, pixel_add, norm)
+                else:
+                    ops.label_weight_sum(lt.reshape(-1).contiguous(), logits.shape[1], cw, norm)
+        else:
+            assert pixel_add is None, "seg_head: pixel_add goes with the softmax cross-entropy only"
         try:
-            return _SegHeadFn.apply(logits, lt, cw, nw, norm, int(mode))
+            return _SegHeadFn.apply(logits, lt, cw, nw, norm, int(mode), pixel_add)
         except _SegHeadNotCovered:
             pass
+    if pixel_add is not None:
+        raise SganError("seg_head: the pixel-weighted head covers [1, C <= 16, H, W] fp32 logits on the device only")
     if softmax:
         if logits.is_cuda and logits.dim() == 4 and logits.shape[0] == 1 and logits.shape[1] <= 16 and logits.dtype == torch.float32:
             return softmax_channels(logits), cross_entropy_logits(logits, lt, 0, class_weights)

@@ -819,11 +819,27 @@ def label_weight_sum(label, Creal, class_w, out):
     L.check(rc, "sgan_label_weight_sum")
 
 
-def seg_head(z, Creal, mode, label_or_target, class_w, nw, norm, p, dz, loss_out):
+def pixel_weight_sum(label, Creal, class_w, pixel_add, out):
+    """out[0] = sum over the pixels with a label in [0, Creal) of class_w[label] + pixel_add (class_w None: 1 + pixel_add):
+    sgan_pixel_weight_sum, the norm of seg_head_pw.  `pixel_add`: a dense float32 map of label.numel() entries (border_weight's bmap)."""
+    require_gpu(label, "pixel_weight_sum")
+    assert label.dtype == torch.int64 and label.is_contiguous() and out.dtype == torch.float32 and out.numel() == 1 and out.device == label.device
+    assert class_w is None or (class_w.dtype == torch.float32 and class_w.is_contiguous() and class_w.numel() >= Creal and class_w.device == label.device)
+    assert (pixel_add.dtype == torch.float32 and pixel_add.is_contiguous() and pixel_add.numel() == label.numel()
+            and pixel_add.device == label.device), (pixel_add.shape, pixel_add.dtype)
+    rc = L.lib().sgan_pixel_weight_sum(_ptr(label), label.numel(), int(Creal), _ptr(class_w), _ptr(pixel_add), _ptr(out),
+                                       _ptr(_seghead_workspace(label.device, "norm")), _stream())
+    if rc == 1:
+        raise L.SganError("sgan_pixel_weight_sum: not covered (more than 16 classes)")
+    L.check(rc, "sgan_pixel_weight_sum")
+
+
+def seg_head(z, Creal, mode, label_or_target, class_w, nw, norm, p, dz, loss_out, pixel_add=None):
     """sgan_seg_head on an [H, W, Cs] logits buffer: p (and dz unless None) are [H, W, Cs'] buffers, `label_or_target` the int64 label
     map of H * W entries (softmax) or the [H, W, Cs''] target buffer (sigmoid), `norm` the float32 device scalar of label_weight_sum
-    (softmax).  Every operand is checked against its storage here, before anything is launched.  Returns False, having launched
-    nothing, when the library reports the call as not covered."""
+    (softmax).  pixel_add (softmax only): the dense float32 map of H * W per-pixel weight terms of sgan_seg_head_pw, `norm` then the
+    scalar of pixel_weight_sum.  Every operand is checked against its storage here, before anything is launched.  Returns False, having
+    launched nothing, when the library reports the call as not covered."""
     H, W, _ = z.shape
 
     def rows_fit(t, what, written):
@@ -849,13 +865,28 @@ def seg_head(z, Creal, mode, label_or_target, class_w, nw, norm, p, dz, loss_out
         tld = label_or_target.stride(1)
         assert nw <= Creal
     assert class_w is None or (class_w.dtype == torch.float32 and class_w.is_cuda and class_w.is_contiguous() and class_w.numel() >= nw)
-    rc = L.lib().sgan_seg_head(_ptr(z), z.stride(1), H * W, int(Creal), int(mode), _ptr(label_or_target), tld, _ptr(class_w),
-                               int(nw) if class_w is not None else 0, _ptr(norm), _ptr(p), p.stride(1), _ptr(dz),
-                               dz.stride(1) if dz is not None else 0, _ptr(loss_out), _ptr(_seghead_workspace(z.device, "head")), _stream())
+    if pixel_add is not None:
+        assert mode == SEGHEAD_SOFTMAX, "seg_head: a per-pixel weight goes with the softmax cross-entropy only"
+        assert pixel_add.dtype == torch.float32 and pixel_add.is_cuda and pixel_add.is_contiguous() and pixel_add.numel() == H * W
+        rc = L.lib().sgan_seg_head_pw(_ptr(z), z.stride(1), H * W, int(Creal), _ptr(label_or_target), _ptr(class_w),
+                                      int(nw) if class_w is not None else 0, _ptr(pixel_add), _ptr(norm), _ptr(p), p.stride(1), _ptr(dz),
+                                      dz.stride(1) if dz is not None else 0, _ptr(loss_out), _ptr(_seghead_workspace(z.device, "head")),
+                                      _stream())
+        name = "sgan_seg_head_pw"
+    else:
+        rc = L.lib().sgan_seg_head(_ptr(z), z.stride(1), H * W, int(Creal), int(mode), _ptr(label_or_target), tld, _ptr(class_w),
+                                   int(nw) if class_w is not None else 0, _ptr(norm), _ptr(p), p.stride(1), _ptr(dz),
+                                   dz.stride(1) if dz is not None else 0, _ptr(loss_out), _ptr(_seghead_workspace(z.device, "head")), _stream())
+        name = "sgan_seg_head"
     if rc == 1:
         return False
-    L.check(rc, "sgan_seg_head")
+    L.check(rc, name)
     return True
+
+
+def seg_head_pw(z, Creal, label, class_w, nw, pixel_add, norm, p, dz, loss_out):
+    """sgan_seg_head_pw: seg_head in softmax mode with w_p = class_w[y_p] + pixel_add[p]."""
+    return seg_head(z, Creal, SEGHEAD_SOFTMAX, label, class_w, nw, norm, p, dz, loss_out, pixel_add=pixel_add)
 
 
 def sigmoid_fwd(x, p):
@@ -1100,6 +1131,29 @@ def ccl_label(plane, labels=None):
     L.check(L.lib().sgan_ccl_label(_ptr(plane), plane.stride(1), H, W, _ptr(labels), _ptr(metric_err(plane.device)), _stream()),
             "sgan_ccl_label")
     return labels
+
+
+def border_weight(labels, radius, w0, sigma, bmap=None, d1sq=None, d2sq=None):
+    """The border term of the U-Net loss on `labels` (int32 [H, W] in ccl_label's form: 0 = wall, else a cell id), sgan_border_weight:
+    bmap [H, W] float32 = w0 exp(-(d1 + d2)^2 / (2 sigma^2)) on wall pixels with two distinct cells within `radius` (1..32), else 0.
+    d1sq / d2sq (optional int32 [H, W]) receive the squared distances to the nearest and second-nearest cell, -1 where there is none
+    (util.border_weight_map is the host yardstick).  Only enqueues -- the launch depends on the shape and the radius alone.  A label
+    < 0 counts as wall and raises bit 4 of metric_err."""
+    require_gpu(labels, "border_weight")
+    assert labels.dim() == 2 and labels.dtype == torch.int32 and labels.is_contiguous(), (labels.shape, labels.dtype)
+    H, W = labels.shape
+    dev = labels.device
+    if bmap is None:
+        bmap = torch.empty((H, W), dtype=torch.float32, device=dev)
+    assert bmap.dtype == torch.float32 and bmap.is_contiguous() and bmap.numel() == H * W and bmap.device == dev
+    for d in (d1sq, d2sq):
+        assert d is None or (d.dtype == torch.int32 and d.is_contiguous() and d.numel() == H * W and d.device == dev)
+    rc = L.lib().sgan_border_weight(_ptr(labels), H, W, int(radius), float(w0), float(sigma), _ptr(bmap), _ptr(d1sq), _ptr(d2sq),
+                                    _ptr(metric_err(dev)), _stream())
+    if rc == 1:
+        raise L.SganError(f"sgan_border_weight: refused ({H} x {W}, radius {radius} (1..32), sigma {sigma} (> 0)); nothing was launched")
+    L.check(rc, "sgan_border_weight")
+    return bmap
 
 
 def thin_workspace(H, W, device):

@@ -3,6 +3,7 @@ options/test_options.py) for the trainers on the MI355X path: same flag names, t
 `nargs='+'` list flags, same `parse()` protocol (gpu_ids string -> list, opt.txt dump).  Flags that only
 steer out-of-scope subsystems (visdom, dataset folders) are accepted and ignored."""
 import argparse
+import math
 import os
 
 import torch
@@ -127,6 +128,7 @@ class BaseOptions:
             self.initialize()
         self.opt = self.parser.parse_args(args)
         self.opt.isTrain = self.isTrain
+        check_border_options(self.opt)
         if self.opt.math is not None:
             from . import ops
             ops.set_math(self.opt.math)
@@ -149,6 +151,22 @@ class BaseOptions:
                     f.write('%s: %s\n' % (str(k), str(v)))
                 f.write('-------------- End ----------------\n')
         return self.opt
+
+
+def check_border_options(opt):
+    """--border_weight goes with the softmax cross-entropy of the discriminator-free segmentation trainer only; fills in the default
+    radius min(32, ceil(4 SIGMA)), beyond which the term is below W0 e^-8."""
+    if getattr(opt, 'border_weight', None) is None:
+        return
+    w0, sigma = opt.border_weight
+    assert sigma > 0, "--border_weight W0 SIGMA: SIGMA must be positive (got %g)" % sigma
+    assert opt.which_model_netD == 'None', \
+        "--border_weight weights the cross-entropy of the supervised baseline: it needs --which_model_netD None (got '%s')" % opt.which_model_netD
+    assert not opt.use_sigmoid_ss, "--border_weight weights the softmax cross-entropy: it cannot be combined with --use_sigmoid_ss"
+    if opt.border_radius is None:
+        opt.border_radius = min(32, int(math.ceil(4 * sigma)))
+    assert 1 <= opt.border_radius <= 32, "--border_radius: 1..32 (got %d)" % opt.border_radius
+    assert opt.border_class >= 0, "--border_class: a class index (got %d)" % opt.border_class
 
 
 class TrainOptions(BaseOptions):
@@ -204,6 +222,12 @@ class TrainOptions(BaseOptions):
         a('--use_fixed_noise1', action='store_true')
         a('--lambda_G1', type=float, default=1)
         a('--lambda_G2', type=float, default=1)
+        # the U-Net border term of the supervised segmentation baseline (not in the reference)
+        a('--border_weight', type=float, default=None, nargs=2, metavar=('W0', 'SIGMA'),
+          help='segmentation with --which_model_netD None: add the U-Net border term W0 exp(-(d1 + d2)^2 / (2 SIGMA^2)) to the '
+               'cross-entropy weight of every wall pixel between two cells (not in the reference; default off)')
+        a('--border_radius', type=int, default=None, help='search radius of --border_weight in pixels, 1..32; default min(32, ceil(4 SIGMA))')
+        a('--border_class', type=int, default=0, help='the class whose pixels form the wall between objects (--border_weight)')
         self.isTrain = True
 
 

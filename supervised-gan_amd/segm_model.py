@@ -43,6 +43,13 @@ class SegmentationModel(CGANModel):
                 "--weights: one per class (%d) for the softmax cross-entropy" % self.num_classes
             self.loss_G_GAN = 0
             self.norm = None      # sum_p w[label_p], a persistent device scalar refreshed with the label (softmax mode)
+        self.border = getattr(opt, 'border_weight', None)      # (w0, sigma) of the U-Net border term, or None
+        self.bmap = None                                       # its map of the current crop, persistent like the label
+        if self.border is not None:
+            assert self.no_netD and not self.use_sigmoid_ss, \
+                "--border_weight: softmax training with --which_model_netD None only (options.check_border_options)"
+            assert opt.border_class < self.num_classes, "--border_class %d: there are %d classes" % (opt.border_class, self.num_classes)
+            assert opt.batchSize == 1 and self.device.type == 'cuda', "--border_weight: batch 1 on the device, like every kernel of this path"
         self.reset_accs()
 
     def _builds_netD(self, opt):
@@ -69,7 +76,29 @@ class SegmentationModel(CGANModel):
         if getattr(self, 'no_netD', False) and not self.use_sigmoid_ss and self.device.type == 'cuda':
             if self.norm is None:
                 self.norm = torch.zeros((), dtype=torch.float32, device=self.device)
-            ops.label_weight_sum(self.label.reshape(-1), self.num_classes, self.class_weights, self.norm)
+            if self.border is not None:
+                self._border_weight_map()
+                ops.pixel_weight_sum(self.label.reshape(-1), self.num_classes, self.class_weights, self.bmap.reshape(-1), self.norm)
+            else:
+                ops.label_weight_sum(self.label.reshape(-1), self.num_classes, self.class_weights, self.norm)
+
+    def _border_weight_map(self):
+        """The U-Net border term of the current label into self.bmap: the pixels of --border_class are the wall, its complement is
+        labelled into cells (ops.ccl_label), and every wall pixel gets w0 exp(-(d1 + d2)^2 / (2 sigma^2)) from its two nearest cells
+        (ops.border_weight).  Enqueues into persistent buffers; nothing is read back and nothing is allocated after the first call.
+        Runs on every set_input, a validation image's included: forward() of this trainer always goes through the pixel-weighted
+        head, which reads the map of the image it is given (the validation LOSS, compute_cross_entropy_loss, does not read it)."""
+        hw = tuple(self.label.shape[1:])
+        if self.bmap is None or tuple(self.bmap.shape) != hw:
+            self._border_is_wall = torch.empty(hw, dtype=torch.bool, device=self.device)
+            self._border_wall = torch.empty(hw, dtype=torch.float32, device=self.device)
+            self._border_cells = torch.empty(hw, dtype=torch.int32, device=self.device)
+            self.bmap = torch.empty(hw, dtype=torch.float32, device=self.device)
+        w0, sigma = self.border
+        torch.eq(self.label[0], self.opt.border_class, out=self._border_is_wall)
+        self._border_wall.copy_(self._border_is_wall)      # 1.0 = wall, as ccl_label reads a plane
+        ops.ccl_label(self._border_wall, self._border_cells)
+        ops.border_weight(self._border_cells, self.opt.border_radius, w0, sigma, bmap=self.bmap)
 
     def forward(self, val_mode=False):
         """val_mode: the validation pass of train_ss.py draws its latent at --noiseSizeVal (segm_model.py:145-155)."""
@@ -81,7 +110,8 @@ class SegmentationModel(CGANModel):
             if self.use_sigmoid_ss:
                 self.fake_B, self._head_loss = seg_head(self.logit, self.real_B, self.class_weights, None, ops.SEGHEAD_SIGMOID)
             else:
-                self.fake_B, self._head_loss = seg_head(self.logit, self.label, self.class_weights, self.norm, ops.SEGHEAD_SOFTMAX)
+                self.fake_B, self._head_loss = seg_head(self.logit, self.label, self.class_weights, self.norm, ops.SEGHEAD_SOFTMAX,
+                                                        pixel_add=self.bmap)
             return      # backward_G names it loss_G_CE: the re-draw that ends an update (n_update_G > 1) must not replace the logged loss
         self.fake_B = sigmoid_channels(self.logit) if self.use_sigmoid_ss else softmax_channels(self.logit)
 

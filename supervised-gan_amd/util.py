@@ -1,7 +1,8 @@
 """Image and metric helpers of the drivers (util/util.py:15-28, :41-43, :86-128 of the reference): tensor -> uint8 image -> PNG,
 the Rand F-score of a binary segmentation, the information score (VInfo) that goes with it, Guo-Hall thinning (the border
 thinning both scores are ranked after: `thin`, `compute_thinned_scores`), and the shape statistics of the regions of a map
-(`region_table`, the yardstick of the device's sgan_region_stats, and `region_props`, the features derived from its rows)."""
+(`region_table`, the yardstick of the device's sgan_region_stats, and `region_props`, the features derived from its rows), and the
+border term of the U-Net loss (`border_weight_map`, the yardstick of the device's sgan_border_weight)."""
 import os
 
 import numpy as np
@@ -76,6 +77,48 @@ def thin(mask, max_num_iter=None):
             break
         n_changing += 1
     return m.astype(bool), n_changing
+
+
+def border_weight_map(labels, radius, w0, sigma):
+    """The border term of the U-Net loss (Ronneberger et al. 2015, eq. 2) of a label map [H, W] (0 = wall, > 0 = a cell id; a
+    negative label counts as wall): returns (d1sq, d2sq, bmap), int64, int64 and float64 [H, W].  The host yardstick of
+    ops.border_weight; the trainers do not call it.
+
+    For a wall pixel p and a cell L, m_L(p) is the smallest dy^2 + dx^2 over the pixels of L inside the image with dy^2 + dx^2 <=
+    radius^2; d1sq(p) <= d2sq(p) are the two smallest m_L(p) over distinct L, -1 where fewer than one / two cells are in range, and
+        bmap(p) = w0 exp(-(sqrt(d1sq) + sqrt(d2sq))^2 / (2 sigma^2))
+    where both exist, else 0.  Pixels that are not wall get (-1, -1, 0).
+
+    Derivation of the method: the offsets of the disc are walked in ascending d = dy^2 + dx^2, each as one shifted copy of the map
+    (padded with wall).  Because d never decreases along the walk, the first time a pixel sees a label L at all it sees it at m_L(p).
+    So the first label a pixel sees is a nearest cell, l1, with d1sq = that d; the first label != l1 it sees later is a cell of
+    the smallest m_L among the others, with d2sq = that d.  Offsets of equal d may come in any order: which of two equally near
+    cells becomes l1 changes, the two numbers do not."""
+    lab = np.asarray(labels).astype(np.int64)
+    assert lab.ndim == 2 and radius >= 1 and sigma > 0, (lab.shape, radius, sigma)
+    lab = np.where(lab < 0, 0, lab)
+    H, W = lab.shape
+    R = int(radius)
+    wall = lab == 0
+    pad = np.zeros((H + 2 * R, W + 2 * R), dtype=np.int64)
+    pad[R:R + H, R:R + W] = lab
+    offsets = sorted((dy * dy + dx * dx, dy, dx) for dy in range(-R, R + 1) for dx in range(-R, R + 1) if 0 < dy * dy + dx * dx <= R * R)
+    l1 = np.zeros((H, W), dtype=np.int64)
+    d1sq = np.full((H, W), -1, dtype=np.int64)
+    d2sq = np.full((H, W), -1, dtype=np.int64)
+    for d, dy, dx in offsets:
+        seen = pad[R + dy:R + dy + H, R + dx:R + dx + W]
+        cell = wall & (seen > 0)
+        second = cell & (d1sq >= 0) & (d2sq < 0) & (seen != l1)
+        first = cell & (d1sq < 0)
+        d2sq[second] = d
+        l1[first] = seen[first]
+        d1sq[first] = d
+    both = d2sq >= 0
+    bmap = np.zeros((H, W), dtype=np.float64)
+    dist = np.sqrt(d1sq[both].astype(np.float64)) + np.sqrt(d2sq[both].astype(np.float64))
+    bmap[both] = float(w0) * np.exp(-dist * dist / (2.0 * float(sigma) ** 2))
+    return d1sq, d2sq, bmap
 
 
 REGION_COLS = ('area', 'xmin', 'xmax', 'ymin', 'ymax', 'sum_x', 'sum_y', 'sum_xx', 'sum_yy', 'sum_xy', 'boundary', 'root', 'image',
