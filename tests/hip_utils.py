@@ -54,6 +54,37 @@ def from_master(m, k, cin, cout, transposed):
     return (m.permute(3, 2, 0, 1) if transposed else m.permute(2, 3, 0, 1)).contiguous()
 
 
+class Guarded:
+    """An [H, W, C] NHWC view `t` into storage pre-filled with NaN: `sliced` puts it into the middle third of a 3 C wide buffer (NaN
+    channels on both sides of every pixel), and `tail` NaN elements follow the last pixel either way.  `data` (numpy / torch,
+    [H, W, C]) is copied in; without it the view itself is NaN too (an output nobody has written yet).  snapshot() is taken at
+    construction: outside_intact() says everything outside the view still holds its bits, untouched() the view as well."""
+
+    def __init__(self, H, W, C, sliced=False, data=None, tail=1024, dev="cuda"):
+        ld = 3 * C if sliced else C
+        self.store = torch.full((H * W * ld + tail,), float("nan"), dtype=torch.float32, device=dev)
+        body = self.store[: H * W * ld].view(H, W, ld)
+        self.t = body[..., C: 2 * C] if sliced else body
+        if data is not None:
+            self.t.copy_(torch.as_tensor(data, dtype=torch.float32).reshape(H, W, C))
+        self.inside = torch.zeros_like(self.store, dtype=torch.bool)
+        self.inside.as_strided(self.t.shape, self.t.stride(), self.t.storage_offset()).fill_(True)
+        self.snap = self.store.view(torch.int32).clone()
+
+    def outside_intact(self):
+        out = ~self.inside
+        return torch.equal(self.store.view(torch.int32)[out], self.snap[out])
+
+    def untouched(self):
+        return torch.equal(self.store.view(torch.int32), self.snap)
+
+    def finite_inside(self):
+        return bool(torch.isfinite(self.store[self.inside]).all())
+
+    def numpy(self):
+        return self.t.detach().cpu().numpy().copy()
+
+
 def pad_vec(v, dev="cuda"):
     out = torch.zeros(pad4(v.numel()), dtype=torch.float32)
     out[: v.numel()] = v
