@@ -570,6 +570,28 @@ int sgan_slice_nhwc(const float* src, int32_t src_ld, int32_t c0, int32_t C, int
 int sgan_image_prep(const unsigned char* img, int32_t H0, int32_t W0, int32_t x0, int32_t y0, int32_t n, int32_t flip, int32_t rot,
                     float* dst, int32_t dst_ld, int32_t Cstore, void* stream);
 
+/* ---- elastic input pipeline tail (not in the reference: the random elastic deformation of the U-Net baseline, Ronneberger et al.
+ * 2015, section 3.1) ---------------------------------------------------------------------------------
+ * sgan_image_prep with the address it gathers from displaced by a smooth field; util.elastic_field / util.elastic_prep are the NumPy
+ * restatement.  `ctrl` is [G + 3][G + 3][2] fp32 in device memory, (dx, dy) in source pixels, 1 <= G <= 13; control point (r, s) sits
+ * at crop coordinate ((s - 1) n / G, (r - 1) n / G).  For crop coordinate (u, v) -- u the column, BEFORE flip and rotation -- and per
+ * axis: a = u G, cell i = a / n, t = (float)(a % n) / (float)n (integers and one correctly rounded division).  The field at (u, v) is
+ * the Catmull-Rom (a = -0.5) tensor product of control points [j .. j + 3][i .. i + 3] in fp32 (weights of the four points at t:
+ * -t (1 - t)^2 / 2, (1 - t)(1 + t - 1.5 t^2), t (0.5 + 2 t - 1.5 t^2), -t^2 (1 - t) / 2), each component clamped to +-127; `field_out`
+ * (may be NULL) receives these floats as [n][n][2] indexed (v, u).  Then q = (int)rintf(field * 256) of the very float written, X =
+ * (x0 + u) 256 + qx, Y = (y0 + v) 256 + qy, and integers only: a channel whose bit in `nearest_mask` (bit c = channel c of RGB) is
+ * clear is sampled bilinearly, ix = X >> 8, fx = X & 255 (likewise y),
+ *     ((256 - fx)(256 - fy) p00 + fx (256 - fy) p01 + (256 - fx) fy p10 + fx fy p11 + 32768) >> 16,
+ * a channel whose bit is set takes the pixel at ((X + 128) >> 8, (Y + 128) >> 8).  Every index is mirrored into the image without
+ * repeating the edge (period 2 (W0 - 1), any number of folds; W0 == 1 -> 0): the whole image is addressable, not only the window.
+ * The value then takes sgan_image_prep's /255, (v - 0.5) / 0.5, flip / rot mapping and zero padding channels.  All-zero `ctrl` is
+ * sgan_image_prep bit for bit.  Refused like sgan_image_prep, and for G outside 1..13, ctrl == NULL, or an image side above 2^22.
+ * One 16-byte store per pixel when Cstore == 4, dst_ld is a multiple of 4 and dst is 16-byte aligned.  The random draws stay with
+ * the caller. */
+int sgan_image_prep_elastic(const unsigned char* img, int32_t H0, int32_t W0, int32_t x0, int32_t y0, int32_t n, int32_t flip, int32_t rot,
+                            const float* ctrl, int32_t G, int32_t nearest_mask, float* dst, int32_t dst_ld, int32_t Cstore,
+                            float* field_out /* may be NULL */, void* stream);
+
 /* ---- Image.resize in front of the crop (data/base_dataset.py:19-21 transforms.Scale(.., BILINEAR), :43-50 __scale_width;
  * data/aligned_dataset.py:25 AB.resize((2 loadSize, loadSize), BICUBIC)) --------------------------
  * `src` [H][W][C] uint8 (C <= 4, interleaved) -> `dst` [Ho][Wo][C] uint8, both in device memory, bit-exact with Pillow's 8-bit

@@ -115,6 +115,7 @@ SIGNATURES = {
     "sgan_scale": [_P, _P, _P, _L, _P],
     "sgan_bn_running_update": [C.POINTER(BnRunningDesc), _I, _F, _P],
     "sgan_image_prep": [_P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P],
+    "sgan_image_prep_elastic": [_P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P],
     "sgan_image_resize": [_P, _I, _I, _I, _P, _I, _I, _I, _P, _L, _P],
     "sgan_image_resize_workspace": [_I, _I, _I, _I, _I, _I],
     "sgan_gauss_down_fwd": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P],

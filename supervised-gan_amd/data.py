@@ -7,7 +7,11 @@ host memory and the trainers' set_input reads a device tensor.
 Yields what the reference's DataLoader yields at batchSize 1: {'A': [1, 3, H, W] in [-1, 1], 'A_paths': [path]} (single) or
 {'A', 'B', 'A_paths', 'B_paths'} (aligned, unaligned).  Random draws use Python's `random` like the reference; the aligned feeder makes them
 in the reference's order (aligned_dataset.py:31-38), the single feeder's crop offsets are torchvision-internal there and drawn
-here as x then y."""
+here as x then y.
+
+`--elastic G SIGMA` (train options; not in the reference) deforms every training crop: the feeder draws the (G + 3)^2 control vectors
+of a smooth field after its other draws, uploads these few hundred floats, and the same single kernel gathers through the field
+(`sgan_image_prep_elastic`).  One field for both halves of an aligned pair, one per image otherwise."""
 import os
 import random
 
@@ -52,6 +56,24 @@ class _FolderDataset:
     def _to_device(self, img):
         return torch.from_numpy(np.array(img, dtype=np.uint8)).to(self.device, non_blocking=True)      # [H, W, 3], a writable copy
 
+    def _draw_elastic(self):
+        """--elastic G SIGMA on a training feeder: the 2 (G + 3)^2 control displacements of one field, random.gauss(0, SIGMA) row-major
+        with dx before dy, drawn on the calling thread AFTER the item's other draws (none of which moves) and uploaded as [G + 3,
+        G + 3, 2] fp32.  None when the option is off or the feeder does not train: then no draw is made."""
+        el = getattr(self.opt, 'elastic', None)
+        if not self.opt.isTrain or el is None:
+            return None
+        g, sigma = int(el[0]), float(el[1])
+        vals = [random.gauss(0.0, sigma) for _ in range(2 * (g + 3) * (g + 3))]
+        return torch.tensor(vals, dtype=torch.float32).view(g + 3, g + 3, 2).to(self.device, non_blocking=True)
+
+    def _image_prep(self, dev, x0, y0, n, flip, rot, ctrl):
+        """crop -> flip -> rot90 -> ToTensor -> Normalize in one kernel; through the elastic field of `ctrl` when there is one."""
+        if ctrl is None:
+            return ops.image_prep(dev, x0, y0, n, flip, rot)
+        from .options import elastic_nearest_mask
+        return ops.image_prep_elastic(dev, x0, y0, n, flip, rot, ctrl, elastic_nearest_mask(self.opt))
+
     # An item is made in two halves: _host(index) -- file read, decode, resize: no random draws, safe on worker threads (PIL drops
     # the GIL while it decodes) -- and _device(index, host) -- the random draws in the reference's order, the upload, the kernel.
     def __getitem__(self, index):
@@ -92,7 +114,9 @@ class SingleFolderDataset(_FolderDataset):
 
     def _device(self, index, img):
         path = self.paths[index]
-        return {'A': ops.logical_view(self._draw_and_prep(img, path), 3), 'A_paths': [path]}
+        draw = self._draw(img, path)
+        A = self._prep(img, draw, self._draw_elastic())        # --elastic: the field after every other draw of the item
+        return {'A': ops.logical_view(A, 3), 'A_paths': [path]}
 
     def _decode(self, path):
         from PIL import Image
@@ -112,7 +136,8 @@ class SingleFolderDataset(_FolderDataset):
             raise ValueError('--resize_or_crop %s' % opt.resize_or_crop)
         return ow, oh
 
-    def _draw_and_prep(self, img, path):
+    def _draw(self, img, path):
+        """The random draws of one image in the reference's order -> (w, h, x0, y0, flip, rot); no device work."""
         opt, n = self.opt, self.opt.fineSize
         crop = opt.resize_or_crop != 'scale_width'
         w, h = self._resized_size(*img.size)
@@ -126,10 +151,14 @@ class SingleFolderDataset(_FolderDataset):
             x0 = y0 = 0
         flip = opt.isTrain and not opt.no_flip and random.random() < 0.5
         rot = random.randint(0, 3) if (opt.isTrain and not opt.no_rotate) else 0
+        return w, h, x0, y0, flip, rot
+
+    def _prep(self, img, draw, ctrl=None):
+        w, h, x0, y0, flip, rot = draw
         dev = self._to_device(img)
         if (w, h) != img.size:
             dev = ops.image_resize(dev, w, h, "bilinear")      # Image.resize((w, h), BILINEAR), on the device
-        return ops.image_prep(dev, x0, y0, n, flip, rot)
+        return self._image_prep(dev, x0, y0, self.opt.fineSize, flip, rot, ctrl)
 
 
 class UnalignedFolderDataset(SingleFolderDataset):
@@ -152,8 +181,10 @@ class UnalignedFolderDataset(SingleFolderDataset):
 
     def _device(self, index, imgs):
         a, b = self.A_paths[index % len(self.A_paths)], self.B_paths[index % len(self.B_paths)]
-        A = self._draw_and_prep(imgs[0], a)          # A's draws first, then B's (unaligned_dataset.py:32-33)
-        B = self._draw_and_prep(imgs[1], b)
+        da = self._draw(imgs[0], a)                  # A's draws first, then B's (unaligned_dataset.py:32-33)
+        db = self._draw(imgs[1], b)
+        ca, cb = self._draw_elastic(), self._draw_elastic()      # --elastic: one field per image, after every other draw of the item
+        A, B = self._prep(imgs[0], da, ca), self._prep(imgs[1], db, cb)
         return {'A': ops.logical_view(A, 3), 'B': ops.logical_view(B, 3), 'A_paths': [a], 'B_paths': [b]}
 
 
@@ -180,8 +211,9 @@ class AlignedFolderDataset(_FolderDataset):
         dev = self._to_device(AB)
         if AB.size != (2 * w, h):
             dev = ops.image_resize(dev, 2 * w, h, "bicubic")   # AB.resize((loadSize * 2, loadSize), Image.BICUBIC), on the device
-        A = ops.image_prep(dev, w_offset, h_offset, n, flip, 0)
-        B = ops.image_prep(dev, w + w_offset, h_offset, n, flip, 0)
+        ctrl = self._draw_elastic()                            # --elastic: one field for both halves, after every other draw of the item
+        A = self._image_prep(dev, w_offset, h_offset, n, flip, 0, ctrl)
+        B = self._image_prep(dev, w + w_offset, h_offset, n, flip, 0, ctrl)
         return {'A': ops.logical_view(A, 3), 'B': ops.logical_view(B, 3), 'A_paths': [path], 'B_paths': [path]}
 
 

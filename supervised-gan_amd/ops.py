@@ -596,6 +596,29 @@ def image_prep(img_u8, x0, y0, n, flip, rot, out=None):
     return out
 
 
+def image_prep_elastic(img_u8, x0, y0, n, flip, rot, ctrl, nearest_mask, out=None, field_out=None):
+    """image_prep through an elastic deformation (sgan_image_prep_elastic; util.elastic_prep is the host yardstick).  ctrl: [G + 3,
+    G + 3, 2] fp32 device tensor of control displacements (dx, dy) in source pixels, G in 1..13; nearest_mask: bit c set = channel c
+    of RGB is sampled at the nearest pixel (labels), clear = bilinearly (image).  field_out: optional [n, n, 2] fp32 device tensor
+    that receives the clamped per-pixel field, indexed (v, u) in crop coordinates before flip and rotation."""
+    require_gpu(img_u8, "image_prep_elastic")
+    require_gpu(ctrl, "image_prep_elastic")
+    assert img_u8.dtype == torch.uint8 and img_u8.dim() == 3 and img_u8.shape[2] == 3 and img_u8.is_contiguous(), (img_u8.shape, img_u8.dtype)
+    assert ctrl.dtype == torch.float32 and ctrl.dim() == 3 and ctrl.shape[0] == ctrl.shape[1] and ctrl.shape[2] == 2 and ctrl.is_contiguous(), \
+        (ctrl.shape, ctrl.dtype)
+    n = int(n)
+    if out is None:
+        out = torch.empty((n, n, 4), dtype=torch.float32, device=img_u8.device)
+    assert out.shape[0] == n and out.shape[1] == n and out.stride(0) == n * out.stride(1), (out.shape, out.stride())
+    if field_out is not None:
+        require_gpu(field_out, "image_prep_elastic")
+        assert field_out.dtype == torch.float32 and tuple(field_out.shape) == (n, n, 2) and field_out.is_contiguous(), (field_out.shape, field_out.dtype)
+    L.check(L.lib().sgan_image_prep_elastic(_ptr(img_u8), img_u8.shape[0], img_u8.shape[1], int(x0), int(y0), n, int(bool(flip)), int(rot),
+                                            _ptr(ctrl), ctrl.shape[0] - 3, int(nearest_mask), _ptr(_act(out)), out.stride(1), out.shape[2],
+                                            _ptr(field_out), _stream()), "sgan_image_prep_elastic")
+    return out
+
+
 RESAMPLE = {"bilinear": 2, "bicubic": 3}      # Pillow's Image.BILINEAR / Image.BICUBIC
 
 

@@ -129,6 +129,7 @@ class BaseOptions:
         self.opt = self.parser.parse_args(args)
         self.opt.isTrain = self.isTrain
         check_border_options(self.opt)
+        check_elastic_options(self.opt)
         if self.opt.math is not None:
             from . import ops
             ops.set_math(self.opt.math)
@@ -167,6 +168,26 @@ def check_border_options(opt):
         opt.border_radius = min(32, int(math.ceil(4 * sigma)))
     assert 1 <= opt.border_radius <= 32, "--border_radius: 1..32 (got %d)" % opt.border_radius
     assert opt.border_class >= 0, "--border_class: a class index (got %d)" % opt.border_class
+
+
+def check_elastic_options(opt):
+    """--elastic G SIGMA deforms the crops of the image-folder feeders (data.py): G cells a side, 1..13 (the device stages the (G + 3)^2
+    control vectors, at most 256); SIGMA >= 0 source pixels.  Leaves opt.elastic as (int G, float SIGMA)."""
+    if getattr(opt, 'elastic', None) is None:
+        return
+    g, sigma = opt.elastic
+    assert float(g) == int(g) and 1 <= int(g) <= 13, "--elastic G SIGMA: G is a whole number of cells a side, 1..13 (got %g)" % g
+    assert sigma >= 0, "--elastic G SIGMA: SIGMA must not be negative (got %g)" % sigma
+    assert opt.dataroot != 'synthetic', \
+        "--elastic deforms the decoded uint8 image of the image-folder feeders; the synthetic feeder has none (give --dataroot a folder)"
+    assert set(opt.elastic_label_channels) <= set('rgb'), \
+        "--elastic_label_channels: letters of r, g, b (got '%s')" % opt.elastic_label_channels
+    opt.elastic = (int(g), float(sigma))
+
+
+def elastic_nearest_mask(opt):
+    """The nearest_mask of ops.image_prep_elastic for --elastic_label_channels: bit c set = channel c of RGB holds labels."""
+    return sum(1 << 'rgb'.index(ch) for ch in set(opt.elastic_label_channels))
 
 
 class TrainOptions(BaseOptions):
@@ -228,6 +249,14 @@ class TrainOptions(BaseOptions):
                'cross-entropy weight of every wall pixel between two cells (not in the reference; default off)')
         a('--border_radius', type=int, default=None, help='search radius of --border_weight in pixels, 1..32; default min(32, ceil(4 SIGMA))')
         a('--border_class', type=int, default=0, help='the class whose pixels form the wall between objects (--border_weight)')
+        # random elastic deformation of every training crop, on the device (not in the reference, which augments with crop, flip and rot90)
+        a('--elastic', type=float, default=None, nargs=2, metavar=('G', 'SIGMA'),
+          help='image-folder feeders: deform every training crop by a smooth random field -- (G + 3)^2 displacement vectors drawn from '
+               'N(0, SIGMA^2) source pixels on a grid of G x G cells (1..13) over the crop, interpolated bicubically per pixel, fused '
+               'into the crop / flip / rot90 kernel (not in the reference; default off)')
+        a('--elastic_label_channels', type=str, default='rg',
+          help='letters of the RGB channels that hold labels and are sampled at the nearest pixel under --elastic; the others are '
+               'sampled bilinearly (default rg: the reference keeps labels in r and g and the image in b)')
         self.isTrain = True
 
 

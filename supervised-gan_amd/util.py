@@ -2,7 +2,8 @@
 the Rand F-score of a binary segmentation, the information score (VInfo) that goes with it, Guo-Hall thinning (the border
 thinning both scores are ranked after: `thin`, `compute_thinned_scores`), and the shape statistics of the regions of a map
 (`region_table`, the yardstick of the device's sgan_region_stats, and `region_props`, the features derived from its rows), and the
-border term of the U-Net loss (`border_weight_map`, the yardstick of the device's sgan_border_weight)."""
+border term of the U-Net loss (`border_weight_map`, the yardstick of the device's sgan_border_weight), and the elastic deformation of
+a training crop (`elastic_field`, `elastic_prep`, the yardsticks of the device's sgan_image_prep_elastic)."""
 import os
 
 import numpy as np
@@ -119,6 +120,118 @@ def border_weight_map(labels, radius, w0, sigma):
     dist = np.sqrt(d1sq[both].astype(np.float64)) + np.sqrt(d2sq[both].astype(np.float64))
     bmap[both] = float(w0) * np.exp(-dist * dist / (2.0 * float(sigma) ** 2))
     return d1sq, d2sq, bmap
+
+
+ELASTIC_CLAMP = 127.0      # source pixels: what a component of the elastic field is clamped to
+
+
+def _catmull_rom_weights(rem, n, dtype):
+    """[4, len(rem)] Catmull-Rom (a = -0.5) weights of the four control points around a cell at the fractional position rem / n,
+    in `dtype`, operation for operation as the device forms them (csrc/sgan_elastic.hip): t = rem / n and s = (n - rem) / n are two
+    correctly rounded divisions of exact integers, and every weight is a product of sums of positive terms:
+        w0 = -t s^2 / 2,  w1 = s (s^2 + 3 s t + t^2 / 2),  w2 = t (t^2 + 3 s t + s^2 / 2),  w3 = -t^2 s / 2."""
+    t = rem.astype(dtype) / dtype(n)
+    s = (n - rem).astype(dtype) / dtype(n)
+    ss, st, tt = s * s, s * t, t * t
+    return np.stack([(dtype(-0.5) * t) * ss, s * ((ss + dtype(3) * st) + dtype(0.5) * tt), t * ((tt + dtype(3) * st) + dtype(0.5) * ss),
+                     (dtype(-0.5) * tt) * s])
+
+
+def elastic_field(ctrl, n, G, dtype=np.float32, return_abs=False):
+    """The displacement field of the elastic deformation, [n, n, 2] in `dtype`, indexed (v, u) = (row, column) of the crop before flip
+    and rotation, components (dx, dy) in source pixels.  The host yardstick of the field sgan_image_prep_elastic computes
+    (ops.image_prep_elastic's field_out); the trainers do not call it.
+
+    ctrl: [G + 3, G + 3, 2], control point (r, s) at crop coordinate ((s - 1) n / G, (r - 1) n / G).  Per axis, for coordinate u:
+    a = u G, cell i = a // n, t = (a % n) / n -- integers and one rounded division.  The field is the Catmull-Rom tensor product of
+    control points [j .. j + 3][i .. i + 3], summed row by row (((w0 c0 + w1 c1) + w2 c2) + w3 c3 along s, then the same along r) in
+    `dtype`, each component clamped to +-ELASTIC_CLAMP.  float32 follows the device operation for operation (the device may contract
+    a product and a sum into one rounding, so the two agree to a few units in the last place, not to the bit); float64 is the
+    reference of the field test.  return_abs: also return sum_rs |w_r w_s c_rs| per pixel and component, in float64 from the
+    float64 weights -- the magnitude the rounding of the fp32 field is proportional to."""
+    dtype = np.dtype(dtype).type
+    c = np.asarray(ctrl)
+    assert 1 <= G <= 13 and c.shape == (G + 3, G + 3, 2) and n >= 1, (c.shape, G, n)
+    a = np.arange(n, dtype=np.int64) * G
+    cell, rem = a // n, a % n
+    w = _catmull_rom_weights(rem, n, dtype)                                   # [4, n], the same along both axes
+    c = c.astype(dtype)
+    field = None
+    for k in range(4):
+        rows = c[cell + k]                                                    # [n(v), G + 3, 2]
+        r = w[0][None, :, None] * rows[:, cell]                               # [n(v), n(u), 2]
+        for m in range(1, 4):
+            r = r + w[m][None, :, None] * rows[:, cell + m]
+        field = w[0][:, None, None] * r if k == 0 else field + w[k][:, None, None] * r
+    field = np.clip(field, dtype(-ELASTIC_CLAMP), dtype(ELASTIC_CLAMP))
+    if not return_abs:
+        return field
+    w64, c64 = np.abs(_catmull_rom_weights(rem, n, np.float64)), np.abs(np.asarray(ctrl, dtype=np.float64))
+    mag = np.zeros((n, n, 2))
+    for k in range(4):
+        for m in range(4):
+            mag += (w64[k][:, None] * w64[m][None, :])[..., None] * c64[cell + k][:, cell + m]
+    return field, mag
+
+
+def _mirror_index(i, N):
+    """i folded into [0, N) by reflection about the first and the last pixel, neither repeated (scipy's mode='mirror'); N == 1 -> 0."""
+    if N == 1:
+        return np.zeros_like(i)
+    P = 2 * (N - 1)
+    m = np.mod(i, P)
+    return np.where(m < N, m, P - m)
+
+
+def elastic_sample(img, X, Y, nearest_mask):
+    """The integer stage of elastic_prep: img [H0, W0, 3] uint8 sampled at the 8.8 fixed-point positions X, Y (int arrays of one
+    shape) -> uint8 of that shape + (3,).  A channel whose bit in nearest_mask is clear: bilinear,
+        ((256 - fx)(256 - fy) p00 + fx (256 - fy) p01 + (256 - fx) fy p10 + fx fy p11 + 32768) >> 16,  ix = X >> 8, fx = X & 255;
+    a channel whose bit is set: the pixel at ((X + 128) >> 8, (Y + 128) >> 8).  Indices are mirrored into the image."""
+    img = np.asarray(img)
+    H0, W0 = img.shape[:2]
+    X, Y = np.asarray(X, dtype=np.int64), np.asarray(Y, dtype=np.int64)
+    ix, iy, fx, fy = X >> 8, Y >> 8, X & 255, Y & 255
+    xa, xb, ya, yb = _mirror_index(ix, W0), _mirror_index(ix + 1, W0), _mirror_index(iy, H0), _mirror_index(iy + 1, H0)
+    num = (((256 - fx) * (256 - fy))[..., None] * img[ya, xa].astype(np.int64) + (fx * (256 - fy))[..., None] * img[ya, xb].astype(np.int64)
+           + ((256 - fx) * fy)[..., None] * img[yb, xa].astype(np.int64) + (fx * fy)[..., None] * img[yb, xb].astype(np.int64))
+    out = ((num + 32768) >> 16).astype(np.uint8)
+    near = img[_mirror_index((Y + 128) >> 8, H0), _mirror_index((X + 128) >> 8, W0)]
+    for ch in range(3):
+        if (int(nearest_mask) >> ch) & 1:
+            out[..., ch] = near[..., ch]
+    return out
+
+
+def elastic_positions(field, x0, y0):
+    """(X, Y): the 8.8 fixed-point source positions of an [n, n, 2] fp32 field over the window at (x0, y0): q = rint(field * 256)
+    (exact in fp32, ties to even as rintf), X = (x0 + u) 256 + qx, Y = (y0 + v) 256 + qy."""
+    field = np.asarray(field)
+    assert field.dtype == np.float32 and field.ndim == 3 and field.shape[0] == field.shape[1] and field.shape[2] == 2, (field.shape, field.dtype)
+    n = field.shape[0]
+    q = np.rint(field * np.float32(256.0)).astype(np.int64)
+    v, u = np.meshgrid(np.arange(n, dtype=np.int64), np.arange(n, dtype=np.int64), indexing='ij')
+    return (x0 + u) * 256 + q[..., 0], (y0 + v) * 256 + q[..., 1]
+
+
+def elastic_prep(img, x0, y0, n, flip, rot, ctrl, G, nearest_mask, field=None):
+    """img [H0, W0, 3] uint8 -> float32 [3, n, n]: the crop window at (x0, y0) seen through the elastic field of `ctrl`, then flip,
+    rot90, ToTensor and Normalize as the plain pipeline tail.  The host yardstick of ops.image_prep_elastic; the trainers do not
+    call it.  `field`: an [n, n, 2] fp32 field to use instead of elastic_field(ctrl, n, G, float32) -- the device's own field read
+    back, after which every step is integer and the two agree to the bit."""
+    img = np.asarray(img)
+    assert img.dtype == np.uint8 and img.ndim == 3 and img.shape[2] == 3, (img.shape, img.dtype)
+    assert 0 <= x0 and 0 <= y0 and x0 + n <= img.shape[1] and y0 + n <= img.shape[0], (x0, y0, n, img.shape)
+    if field is None:
+        field = elastic_field(ctrl, n, G, np.float32)
+    X, Y = elastic_positions(field, x0, y0)
+    c = elastic_sample(img, X, Y, nearest_mask)
+    if flip:
+        c = c[:, ::-1]
+    c = np.rot90(c, rot, axes=(0, 1))                                         # counter-clockwise, as PIL's ROTATE_90
+    t = c.astype(np.float32) / np.float32(255.0)                              # ToTensor
+    t = (t - np.float32(0.5)) / np.float32(0.5)                               # Normalize((.5,.5,.5), (.5,.5,.5))
+    return np.ascontiguousarray(t.transpose(2, 0, 1))
 
 
 REGION_COLS = ('area', 'xmin', 'xmax', 'ymin', 'ymax', 'sum_x', 'sum_y', 'sum_xx', 'sum_yy', 'sum_xy', 'boundary', 'root', 'image',
