@@ -789,6 +789,61 @@ int64_t sgan_thin_workspace(int32_t H, int32_t W);
 int sgan_thin(const float* plane, int64_t pix_stride, int32_t H, int32_t W, float* out, int32_t max_num_iter, void* workspace,
               int64_t workspace_bytes, int32_t* iters_out, int32_t* dev_err, void* stream);
 
+/* ---- object-level scores on the device: detection F1, average precision, SEG and panoptic quality ----------------------------------
+ * What the cell-segmentation literature reports beside Rand and VInfo: how many cells were found, at which overlap, and how well
+ * the found ones fit (F1 at IoU 0.5; the average precision over IoU 0.5 .. 0.95 of DSB-2018 / StarDist's matching_dataset; the
+ * Cell Tracking Challenge's SEG; panoptic quality).  util.object_match_counts is the NumPy / scipy restatement these entries are
+ * tested against, util.object_scores derives the four scores.
+ *
+ * Inputs: two H x W label maps in sgan_ccl_label's form, t the truth and s the prediction: 0 is wall, any other value is 1 + the
+ *   region's smallest raster index.
+ * Counts: unlike the Rand count, areas are WHOLE areas.  a_i = all pixels of truth region i, those on prediction wall included;
+ *   b_j = all pixels of prediction region j, those on truth wall included; c_ij = pixels in both; u_ij = a_i + b_j - c_ij.
+ * Small objects: min_area >= 1.  A region with area < min_area, on either side, is treated as absent: it is not counted and cannot
+ *   be matched.  No other region's area changes.  N_t = truth regions with a_i >= min_area, N_s = prediction regions with
+ *   b_j >= min_area.
+ * Matches at threshold k = 0 .. 9, tau_k = (10 + k) / 20: TP_k = number of pairs (i, j) that both pass min_area and satisfy
+ *   20 c_ij > (10 + k) u_ij.  The comparison is strict and is done in 64-bit integers; no floating-point comparison decides a match.
+ *   For an IoU above 1/2 the matching is unique (c_ij > u_ij / 2 means more than half of a_i and more than half of b_j, and two
+ *   disjoint regions cannot both hold more than half of a third), so no assignment problem is solved and every count is exact.
+ * Float sums: SIoU = sum of c_ij / u_ij (fp64) over the pairs counted in TP_0.  Over the pairs with both sides >= min_area and
+ *   2 c_ij > a_i (at most one j per i), SEGn is their number and SSEG the sum of c_ij / u_ij.
+ * Accumulators, caller-owned on the device, zeroed by the caller once, pooled over a dataset as matching_dataset pools them:
+ *   acc_i, int64[SGAN_OBJ_COUNTS]: [SGAN_OBJ_TP0 + k] += TP_k, [SGAN_OBJ_NT] += N_t, [SGAN_OBJ_NS] += N_s, [SGAN_OBJ_IMAGES] += 1,
+ *     [SGAN_OBJ_SEGN] += SEGn, [14] = [15] = 0;
+ *   acc_f, double[SGAN_OBJ_SUMS]: [SGAN_OBJ_SIOU] += SIoU, [SGAN_OBJ_SSEG] += SSEG.
+ *   counts_out (int64[16]) and sums_out (double[2]), both optional, receive this pair's contribution alone.
+ * Scores, derived on the host from the pooled numbers when the accumulators are read; a score whose denominator is 0 reads 0:
+ *   ObjF1 = 2 TP_0 / (N_t + N_s),  ObjAP = mean over k of TP_k / (N_t + N_s - TP_k),  SEG = SSEG / N_t,  PQ = SIoU / ((N_t + N_s) / 2).
+ * Exactness: the integers are identical on every run and in every scheduling order.  SIoU and SSEG are fp64 sums of at most N_t
+ *   terms in (0, 1], in an order that depends on scheduling: they repeat to rounding (N_t 2^-52 relative), not to the bit, as
+ *   VInfo's sums.
+ *
+ * sgan_object_match_workspace: bytes of the workspace sgan_object_match_accumulate needs for an H x W pair (< 0: bad shape).
+ * sgan_object_match_accumulate: four launches whose grids depend on (H, W) only, nothing read back and nothing decided on the
+ *   host, so the call captures into a hipGraph and replays on any other pair of maps (min_area is a launch argument, frozen with
+ *   the capture).  Zero; a counting pass that is sgan_rand_f_accumulate's (a wave holds 64 pixels of a row, runs collapsed, equal
+ *   keys merged across the wave, the pair table with its probe bounded at SGAN_RAND_F_MAX_PROBE) with every non-wall prediction
+ *   pixel counted and no square sums; an evaluation pass over the per-label counters and the pair-table slots (16-byte loads, the
+ *   two areas of a pair looked up through its key, ten integer comparisons, the fp64 terms reduced in the wave and the workgroup,
+ *   one set of atomics per workgroup into a staging block in the workspace); one final thread that adds the staging block to the
+ *   accumulators and writes the optional outputs.  Workspace, dev_err (bit 2 = pair table full, bit 4 = label out of range, the
+ *   offending pixel left out) and stream as sgan_rand_f_accumulate; the call initialises what it uses.  Shapes as
+ *   sgan_rand_f_accumulate.  Null required pointers, min_area < 1 and a short workspace are refused before any launch. */
+#define SGAN_OBJ_COUNTS 16
+#define SGAN_OBJ_TP0 0
+#define SGAN_OBJ_NT 10
+#define SGAN_OBJ_NS 11
+#define SGAN_OBJ_IMAGES 12
+#define SGAN_OBJ_SEGN 13
+#define SGAN_OBJ_SUMS 2
+#define SGAN_OBJ_SIOU 0
+#define SGAN_OBJ_SSEG 1
+int64_t sgan_object_match_workspace(int32_t H, int32_t W);
+int sgan_object_match_accumulate(const int32_t* t_labels, const int32_t* s_labels, int32_t H, int32_t W, int32_t min_area, void* workspace,
+                                 int64_t workspace_bytes, int64_t* acc_i, double* acc_f, int64_t* counts_out, double* sums_out,
+                                 int32_t* dev_err, void* stream);
+
 /* ---- region statistics on the device (shape features of generated against real images: shape_stats.py) --------------------------
  * The reference's paper judges a generator by shape features of its cells and mitochondria; its repository holds only MATLAB that
  * loads precomputed features (experiments/plots).  These entries measure every region of a label map; util.region_table is the

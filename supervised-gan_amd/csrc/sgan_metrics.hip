@@ -1,5 +1,6 @@
 // Segmentation metrics on the device (include/sgan_hip.h, "segmentation metrics"): connected-component labelling of a thresholded
-// boundary map, the Rand F-score and the information score (VInfo) of two such labellings, and the confusion matrix of two class maps.  The trainers call these after
+// boundary map, the Rand F-score, the information score (VInfo) and the object-level match counts of two such labellings, and the
+// confusion matrix of two class maps.  The trainers call these after
 // every optimizer step; nothing is read back until the accuracies are asked for.
 //
 // These kernels are bound by latency and atomics, not by arithmetic.  Three rules hold throughout:
@@ -11,6 +12,7 @@
 //     plain accesses); plain loads and stores carry data across launch boundaries only, or data that is valid whether old or new.
 //   * the results are integers, so they do not depend on the order the atomics arrive in.
 #include "sgan_common.h"
+#include "sgan_reduce.h"
 
 #define SG_CCL_TW 64
 #define SG_CCL_TH 16
@@ -237,15 +239,17 @@ __device__ __forceinline__ int sg_wave_merge(unsigned long long key, int len, in
     return total;
 }
 
-__global__ __launch_bounds__(256) void sg_rand_count_kernel(const int32_t* __restrict__ T, const int32_t* __restrict__ S, int H, int W,
-                                                            unsigned long long* sums, unsigned long long* keys, int* cnt_a, int* cnt_b,
-                                                            int* cnt_ab, int log2_slots, int32_t* dev_err) {
-    const int lane = threadIdx.x & 63, segs = (W + 63) / 64;
+// What the two counting passes (Rand / VInfo and the object matches) share.  A workgroup's four waves each take one 64-pixel segment of a
+// row; false, for the whole wave, when the segment lies past the image.  A lane past the row's end looks like wall in both maps and
+// adds nothing; a label outside 0 .. H W sets bit 4 and its pixel is left out.
+__device__ __forceinline__ bool sg_load_label_pair(const int32_t* __restrict__ T, const int32_t* __restrict__ S, int H, int W, int lane,
+                                                   int32_t* dev_err, int& t, int& s) {
+    const int segs = (W + 63) / 64;
     const int64_t seg = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (seg >= (int64_t)H * segs) return;      // uniform over the wave
+    t = s = 0;
+    if (seg >= (int64_t)H * segs) return false;
     const int y = (int)(seg / segs), x = (int)(seg % segs) * 64 + lane;
     const int n = H * W;
-    int t = 0, s = 0;       // a lane past the row's end looks like wall in both maps, and adds nothing
     if (x < W) {
         t = T[y * W + x];
         s = S[y * W + x];
@@ -254,6 +258,28 @@ __global__ __launch_bounds__(256) void sg_rand_count_kernel(const int32_t* __res
             t = s = 0;
         }
     }
+    return true;
+}
+
+// The slot of `key` in the open-addressing pair table, claimed if the key is new; -1, with bit 2 set, when the bounded probe ran out.
+__device__ __forceinline__ long long sg_pair_slot(unsigned long long* keys, unsigned long long key, int log2_slots, int32_t* dev_err) {
+    const unsigned long long mask = (1ull << log2_slots) - 1;
+    unsigned long long slot = (key * 0x9E3779B97F4A7C15ull) >> (64 - log2_slots);
+    for (int probe = 0; probe < SGAN_RAND_F_MAX_PROBE; ++probe) {
+        const unsigned long long seen = atomicCAS(&keys[slot], 0ull, key);      // t >= 1: a key is never 0
+        if (seen == 0ull || seen == key) return (long long)slot;
+        slot = (slot + 1) & mask;
+    }
+    sg_flag(dev_err, 2);
+    return -1;
+}
+
+__global__ __launch_bounds__(256) void sg_rand_count_kernel(const int32_t* __restrict__ T, const int32_t* __restrict__ S, int H, int W,
+                                                            unsigned long long* sums, unsigned long long* keys, int* cnt_a, int* cnt_b,
+                                                            int* cnt_ab, int log2_slots, int32_t* dev_err) {
+    const int lane = threadIdx.x & 63;
+    int t, s;
+    if (!sg_load_label_pair(T, S, H, W, lane, dev_err, t, s)) return;      // uniform over the wave
     const int tl = __shfl_up(t, 1, 64), sl = __shfl_up(s, 1, 64);
     const bool first = lane == 0;
     long long dA = 0, dB = 0, dAB = 0, aux = (t != 0 && s == 0) ? 1 : 0;
@@ -269,16 +295,8 @@ __global__ __launch_bounds__(256) void sg_rand_count_kernel(const int32_t* __res
     if (len) dB = sg_square_growth(atomicAdd(&cnt_b[s], len), len);
     len = sg_wave_merge(key, run, lane);
     if (len) {
-        const unsigned long long mask = (1ull << log2_slots) - 1;
-        unsigned long long slot = (key * 0x9E3779B97F4A7C15ull) >> (64 - log2_slots);
-        int probe = 0;
-        for (; probe < SGAN_RAND_F_MAX_PROBE; ++probe) {
-            const unsigned long long seen = atomicCAS(&keys[slot], 0ull, key);      // t >= 1: a key is never 0
-            if (seen == 0ull || seen == key) break;
-            slot = (slot + 1) & mask;
-        }
-        if (probe < SGAN_RAND_F_MAX_PROBE) dAB = sg_square_growth(atomicAdd(&cnt_ab[slot], len), len);
-        else sg_flag(dev_err, 2);
+        const long long slot = sg_pair_slot(keys, key, log2_slots, dev_err);
+        if (slot >= 0) dAB = sg_square_growth(atomicAdd(&cnt_ab[slot], len), len);
     }
     dA = sg_wave_sum_i64(dA);
     dB = sg_wave_sum_i64(dB);
@@ -518,6 +536,170 @@ extern "C" int sgan_vinfo_accumulate(const int32_t* t_labels, const int32_t* s_l
                        acc_rand, parts_out);
     SGAN_LAUNCH_CHECK();
     g_sgan_last_kernel = "sg_vinfo_reduce_kernel";
+    return SGAN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Object matching (include/sgan_hip.h, "object-level scores"): which truth region is found by which predicted region, at the ten
+// IoU thresholds 0.5 .. 0.95.  Workspace: [stage: 16 x 8 bytes][keys: slots uint64][cnt_a: np int32][cnt_b: np int32][cnt_ab: slots
+// int32] -- the Rand layout behind a staging block that is laid out as the accumulators are: stage[k] (uint64) is the pair's
+// contribution to acc_i[k] (slot SGAN_OBJ_IMAGES stays 0), stage[14] and stage[15] (double) are SIoU and SSEG.
+// Here a_i and b_j are WHOLE areas, so the count pass adds every run of a prediction label to cnt_b, not only those inside a truth
+// region, and keeps no square sums.
+// ------------------------------------------------------------------------------------------------------------------------------
+#define SG_OBJ_STAGE 128
+#define SG_OBJ_INTS 14      // the integer slots the evaluation reduces: acc_i[0 .. 13] (slot 12 is carried as 0)
+
+static int64_t sg_obj_bytes(const SgRandLayout& l) { return l.bytes - 32 + SG_OBJ_STAGE; }
+
+__global__ __launch_bounds__(256) void sg_obj_count_kernel(const int32_t* __restrict__ T, const int32_t* __restrict__ S, int H, int W,
+                                                           unsigned long long* keys, int* cnt_a, int* cnt_b, int* cnt_ab, int log2_slots,
+                                                           int32_t* dev_err) {
+    const int lane = threadIdx.x & 63;
+    int t, s;
+    if (!sg_load_label_pair(T, S, H, W, lane, dev_err, t, s)) return;      // uniform over the wave
+    const int tl = __shfl_up(t, 1, 64), sl = __shfl_up(s, 1, 64);
+    const bool first = lane == 0;
+    int len = sg_wave_merge((unsigned)t, sg_run_length(first || tl != t, t != 0, lane), lane);
+    if (len) atomicAdd(&cnt_a[t], len);
+    len = sg_wave_merge((unsigned)s, sg_run_length(first || sl != s, s != 0, lane), lane);
+    if (len) atomicAdd(&cnt_b[s], len);
+    const unsigned long long key = ((unsigned long long)(unsigned)t << 32) | (unsigned)s;
+    len = sg_wave_merge(key, sg_run_length(first || tl != t || sl != s, t != 0 && s != 0, lane), lane);
+    if (len) {
+        const long long slot = sg_pair_slot(keys, key, log2_slots, dev_err);
+        if (slot >= 0) atomicAdd(&cnt_ab[slot], len);
+    }
+}
+
+struct SgObjPart {
+    int n[SG_OBJ_INTS];      // a thread's and a wave's counts stay far below 2^31: there are fewer than 2^30 regions and pairs
+    double siou, sseg;
+};
+
+// One nonzero counter of the array [cnt_a | cnt_b | cnt_ab]: a region that counts, or a pair whose two areas are looked up through
+// the pair's key.  Every match is decided in 64-bit integers; the quotient is taken only for a pair that adds it to a sum.
+__device__ __forceinline__ void sg_obj_term(unsigned c, int64_t e, int64_t np, const unsigned long long* __restrict__ keys,
+                                            const int* __restrict__ cnt_a, const int* __restrict__ cnt_b, int min_area, SgObjPart& p) {
+    if (c == 0) return;
+    if (e < 2 * np) {
+        if ((int)c < min_area) return;
+        if (e < np) ++p.n[SGAN_OBJ_NT];
+        else ++p.n[SGAN_OBJ_NS];
+        return;
+    }
+    const unsigned long long key = keys[e - 2 * np];
+    const int a = cnt_a[(unsigned)(key >> 32)], b = cnt_b[(unsigned)key];      // both labels were range-checked by the count pass
+    if (a < min_area || b < min_area) return;
+    const long long u = (long long)a + b - c, c20 = 20ll * c;
+    const bool found = c20 > 10 * u, seg = 2ll * c > a;
+    if (!found && !seg) return;
+    const double iou = (double)c / (double)u;
+    if (found) {
+        p.siou += iou;
+#pragma unroll
+        for (int k = 0; k < 10; ++k) p.n[SGAN_OBJ_TP0 + k] += c20 > (10 + k) * u ? 1 : 0;
+    }
+    if (seg) {
+        ++p.n[SGAN_OBJ_SEGN];
+        p.sseg += iou;
+    }
+}
+
+// As sg_vinfo_reduce_kernel: one 16-byte load per lane and trip over ~4 H W counters, most of them 0.  A workgroup adds what it found
+// to the staging block once.
+__global__ __launch_bounds__(256) void sg_obj_eval_kernel(const uint4* __restrict__ cnt, int64_t n16, int64_t np,
+                                                          const unsigned long long* __restrict__ keys, int min_area,
+                                                          unsigned long long* stage) {
+    __shared__ int part_n[4][SG_OBJ_INTS];
+    __shared__ double red[2][4];
+    const int* cnt_a = (const int*)cnt;
+    const int* cnt_b = cnt_a + np;
+    SgObjPart p;
+#pragma unroll
+    for (int k = 0; k < SG_OBJ_INTS; ++k) p.n[k] = 0;
+    p.siou = p.sseg = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (int64_t)gridDim.x * 256) {
+        const uint4 v = cnt[i];
+        if ((v.x | v.y | v.z | v.w) == 0) continue;
+        sg_obj_term(v.x, 4 * i, np, keys, cnt_a, cnt_b, min_area, p);
+        sg_obj_term(v.y, 4 * i + 1, np, keys, cnt_a, cnt_b, min_area, p);
+        sg_obj_term(v.z, 4 * i + 2, np, keys, cnt_a, cnt_b, min_area, p);
+        sg_obj_term(v.w, 4 * i + 3, np, keys, cnt_a, cnt_b, min_area, p);
+    }
+    const int wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < SG_OBJ_INTS; ++k) {
+        int v = p.n[k];
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        if ((threadIdx.x & 63) == 0) part_n[wave][k] = v;
+    }
+    const double siou = sg_block_sum<4>(p.siou, red[0]);      // its barrier covers part_n[] as well
+    const double sseg = sg_block_sum<4>(p.sseg, red[1]);
+    if (threadIdx.x < SG_OBJ_INTS) {
+        const int v = part_n[0][threadIdx.x] + part_n[1][threadIdx.x] + part_n[2][threadIdx.x] + part_n[3][threadIdx.x];
+        if (v) atomicAdd(&stage[threadIdx.x], (unsigned long long)v);
+    }
+    if (threadIdx.x == 0) {
+        if (siou != 0.0) atomicAdd((double*)&stage[14], siou);
+        if (sseg != 0.0) atomicAdd((double*)&stage[15], sseg);
+    }
+}
+
+__global__ void sg_obj_final_kernel(const unsigned long long* stage, int64_t* acc_i, double* acc_f, int64_t* counts_out, double* sums_out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const double siou = ((const double*)stage)[14], sseg = ((const double*)stage)[15];
+    for (int k = 0; k < 16; ++k) {
+        const int64_t v = k == SGAN_OBJ_IMAGES ? 1 : k < SG_OBJ_INTS ? (int64_t)stage[k] : 0;
+        if (k < SG_OBJ_INTS) acc_i[k] += v;
+        else acc_i[k] = 0;
+        if (counts_out) counts_out[k] = v;
+    }
+    acc_f[SGAN_OBJ_SIOU] += siou;
+    acc_f[SGAN_OBJ_SSEG] += sseg;
+    if (sums_out) {
+        sums_out[SGAN_OBJ_SIOU] = siou;
+        sums_out[SGAN_OBJ_SSEG] = sseg;
+    }
+}
+
+extern "C" int64_t sgan_object_match_workspace(int32_t H, int32_t W) {
+    if (H < 1 || W < 1 || (int64_t)H * W >= (1ll << 30)) return sgan_fail(SGAN_ERR_INVALID, "bad shape %d x %d", H, W);
+    return sg_obj_bytes(sg_rand_layout(H, W));
+}
+
+extern "C" int sgan_object_match_accumulate(const int32_t* t_labels, const int32_t* s_labels, int32_t H, int32_t W, int32_t min_area,
+                                            void* workspace, int64_t workspace_bytes, int64_t* acc_i, double* acc_f, int64_t* counts_out,
+                                            double* sums_out, int32_t* dev_err, void* stream) {
+    SGAN_CHECK(t_labels && s_labels && workspace && acc_i && acc_f && dev_err, "null pointer");
+    SGAN_CHECK(H >= 1 && W >= 1 && (int64_t)H * W < (1ll << 30), "bad shape %d x %d", H, W);
+    SGAN_CHECK(min_area >= 1, "min_area = %d (>= 1)", min_area);
+    const SgRandLayout l = sg_rand_layout(H, W);
+    const int64_t need = sg_obj_bytes(l);
+    SGAN_CHECK(workspace_bytes >= need, "workspace of %lld bytes, %lld needed for %d x %d (sgan_object_match_workspace); nothing was launched",
+               (long long)workspace_bytes, (long long)need, H, W);
+    SGAN_CHECK(((uintptr_t)workspace & 15) == 0, "workspace not 16-byte aligned");
+    const int64_t waves = (int64_t)H * ((W + 63) / 64);
+    SGAN_CHECK((waves + 3) / 4 < (1ll << 31), "too many rows");
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* stage = (unsigned long long*)workspace;
+    unsigned long long* keys = stage + SG_OBJ_STAGE / 8;
+    int* cnt_a = (int*)(keys + l.slots);
+    int* cnt_b = cnt_a + l.np;
+    int* cnt_ab = cnt_b + l.np;
+    const int64_t z16 = need / 16, n16 = (2 * l.np + l.slots) / 4;
+    hipLaunchKernelGGL(sg_zero16_kernel, dim3((unsigned)((z16 + 255) / 256 < 2048 ? (z16 + 255) / 256 : 2048)), dim3(256), 0, st,
+                       (uint4*)workspace, z16);
+    SGAN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sg_obj_count_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, t_labels, s_labels, H, W, keys, cnt_a, cnt_b,
+                       cnt_ab, l.log2_slots, dev_err);
+    SGAN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sg_obj_eval_kernel, dim3((unsigned)sg_vinfo_grid(n16)), dim3(256), 0, st, (const uint4*)cnt_a, n16, l.np,
+                       (const unsigned long long*)keys, min_area, stage);
+    SGAN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sg_obj_final_kernel, dim3(1), dim3(64), 0, st, (const unsigned long long*)stage, acc_i, acc_f, counts_out, sums_out);
+    SGAN_LAUNCH_CHECK();
+    g_sgan_last_kernel = "sg_obj_eval_kernel";
     return SGAN_OK;
 }
 

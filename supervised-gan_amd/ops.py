@@ -1108,7 +1108,11 @@ _rand_ws = {}
 _vinfo_ws = {}
 _thin_ws = {}
 _region_ws = {}
+_object_ws = {}
 REGION_COLS = 16      # int64 per row of a region table (include/sgan_hip.h, sgan_region_stats)
+# acc_i / counts_out and acc_f / sums_out of object_match_accumulate (SGAN_OBJ_* of include/sgan_hip.h); TP_k: matches at IoU > (10 + k) / 20
+OBJECT_COUNTS = tuple('TP_%d' % k for k in range(10)) + ('N_t', 'N_s', 'images', 'SEGn', 'zero14', 'zero15')
+OBJECT_SUMS = ('SIoU', 'SSEG')
 VINFO_PARTS = ('SA', 'SB', 'SAB', 'aux', 'm', 'H_S', 'H_T', 'I', 'VInfo', 'split', 'merge')      # parts_out of vinfo_accumulate
 
 
@@ -1299,6 +1303,40 @@ def vinfo_accumulate(t_labels, s_labels, acc, acc_rand=None, parts_out=None, wor
     ws = vinfo_workspace(H, W, dev) if workspace is None else workspace
     L.check(L.lib().sgan_vinfo_accumulate(_ptr(t_labels), _ptr(s_labels), H, W, _ptr(ws), ws.numel() * ws.element_size(), _ptr(acc),
                                           _ptr(acc_rand), _ptr(parts_out), _ptr(metric_err(dev)), _stream()), "sgan_vinfo_accumulate")
+
+
+def object_match_workspace(H, W, device):
+    """The scratch of object_match_accumulate for H x W maps (a staging block, the pair table and the counters), cached per
+    (H, W, device) like vinfo_workspace; the kernels zero it themselves."""
+    key = (H, W, device.index)
+    ws = _object_ws.get(key)
+    if ws is None:
+        nbytes = L.lib().sgan_object_match_workspace(H, W)
+        if nbytes < 0:
+            raise L.SganError(f"sgan_object_match_workspace({H}, {W}): {L.lib().sgan_last_error().decode()}")
+        ws = _object_ws[key] = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
+    return ws
+
+
+def object_match_accumulate(t_labels, s_labels, acc_i, acc_f, min_area=1, counts_out=None, sums_out=None, workspace=None):
+    """Adds the object-level match counts (include/sgan_hip.h, "object-level scores") of the labelling s_labels (prediction) against
+    t_labels (truth) to acc_i (int64[16], OBJECT_COUNTS: TP at IoU > 0.5 .. 0.95, N_t, N_s, images, SEGn) and acc_f (float64[2],
+    OBJECT_SUMS: SIoU, SSEG), both on the device and zeroed by the caller once (sgan_object_match_accumulate).  Regions smaller than
+    min_area count as absent.  counts_out (int64[16]) and sums_out (float64[2]) receive this pair's contribution alone.  Only
+    enqueues; util.object_match_counts is the host yardstick and util.object_scores derives ObjF1, ObjAP, SEG and PQ."""
+    H, W = t_labels.shape
+    dev = t_labels.device
+    require_gpu(t_labels, "object_match_accumulate")
+    for t in (t_labels, s_labels):
+        assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (H, W) and t.device == dev, (t.shape, t.dtype)
+    for a, dtype, n in ((acc_i, torch.int64, len(OBJECT_COUNTS)), (acc_f, torch.float64, len(OBJECT_SUMS)),
+                        (counts_out, torch.int64, len(OBJECT_COUNTS)), (sums_out, torch.float64, len(OBJECT_SUMS))):
+        assert a is None or (a.dtype == dtype and a.is_contiguous() and a.numel() == n and a.device == dev)
+    assert acc_i is not None and acc_f is not None
+    ws = object_match_workspace(H, W, dev) if workspace is None else workspace
+    L.check(L.lib().sgan_object_match_accumulate(_ptr(t_labels), _ptr(s_labels), H, W, int(min_area), _ptr(ws),
+                                                 ws.numel() * ws.element_size(), _ptr(acc_i), _ptr(acc_f), _ptr(counts_out),
+                                                 _ptr(sums_out), _ptr(metric_err(dev)), _stream()), "sgan_object_match_accumulate")
 
 
 def confusion_accumulate(x, C, conf, label=None, y=None, add_background=False):

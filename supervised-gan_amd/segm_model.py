@@ -15,7 +15,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import networks, ops
+from . import networks, ops, util
 from .cgan_model import CGANModel
 from .losses import cross_entropy_logits, seg_head, sigmoid_channels, softmax_channels, weighted_bce
 
@@ -173,8 +173,9 @@ class SegmentationModel(CGANModel):
     def reset_accs(self):
         self.confusion, self.numAveragedPixels, self.numAveragedImages = 0, 0, 0
         self.pixelAcc = self.meanAcc = self.meanIU = self.RandScore = self.VInfo = self.RandScoreThin = self.VInfoThin = 0
+        self.ObjF1 = self.ObjAP = self.SEG = self.PQ = 0
         for t in (getattr(self, '_acc_rand', None), getattr(self, '_acc_conf', None), getattr(self, '_acc_vinfo', None),
-                  getattr(self, '_acc_thin', None)):
+                  getattr(self, '_acc_thin', None), getattr(self, '_acc_obj_i', None), getattr(self, '_acc_obj_f', None)):
             if t is not None:
                 t.zero_()
 
@@ -192,8 +193,12 @@ class SegmentationModel(CGANModel):
             self.compute_current_VInfo(with_rand='RandScore' in self.opt.which_metric)
         elif 'RandScore' in self.opt.which_metric:
             self.compute_current_Rand_score()
+        labelled = 'VInfo' in self.opt.which_metric or 'RandScore' in self.opt.which_metric
+        if any(k in self.opt.which_metric for k in util.OBJECT_METRICS):
+            self.compute_current_object_matches(labelled=labelled)
+            labelled = True
         if 'RandScoreThin' in self.opt.which_metric or 'VInfoThin' in self.opt.which_metric:
-            self.compute_current_thinned_scores(truth_labelled='VInfo' in self.opt.which_metric or 'RandScore' in self.opt.which_metric)
+            self.compute_current_thinned_scores(truth_labelled=labelled)
         if 'meanIU' in self.opt.which_metric:
             self.compute_current_accuracy()
 
@@ -231,6 +236,30 @@ class SegmentationModel(CGANModel):
         for both costs one labelling and one count; the value added is rand_f_accumulate's, bit for bit."""
         t_labels, s_labels = self._label_boundary_maps()
         ops.vinfo_accumulate(t_labels, s_labels, self._acc_vinfo, acc_rand=self._acc_rand if with_rand else None)
+
+    def compute_current_object_matches(self, labelled=False):
+        """Adds the object-level match counts of the same pair of maps (ops.object_match_accumulate: which truth cell is found by
+        which predicted cell at IoU > 0.5 .. 0.95, regions below --min_object_area left out) to pooled counters on the device;
+        ObjF1, ObjAP, SEG and PQ are derived from them when the accuracies are read.  labelled: RandScore / VInfo were taken in this
+        accum_accs, so both label maps are in place and nothing is labelled again."""
+        if getattr(self, '_acc_obj_i', None) is None:
+            self._acc_buffers()
+            self._acc_obj_i = torch.zeros(len(ops.OBJECT_COUNTS), dtype=torch.int64, device=self.device)
+            self._acc_obj_f = torch.zeros(len(ops.OBJECT_SUMS), dtype=torch.float64, device=self.device)
+        if labelled and self._acc_labels is not None and self._acc_labels.shape[1:] == self.real_B.shape[2:]:
+            t_labels, s_labels = self._acc_labels[0], self._acc_labels[1]
+        else:
+            t_labels, s_labels = self._label_boundary_maps()
+        ops.object_match_accumulate(t_labels, s_labels, self._acc_obj_i, self._acc_obj_f, min_area=self.opt.min_object_area)
+
+    def get_object_counts(self):
+        """The pooled object-match numbers since reset_accs() as a dict: the 16 integers of ops.OBJECT_COUNTS (TP_0 .. TP_9 at
+        IoU > 0.5 .. 0.95, N_t, N_s, images, SEGn) and the two sums of ops.OBJECT_SUMS.  Synchronises, like get_current_accs()."""
+        counts, sums = [0] * len(ops.OBJECT_COUNTS), [0.0] * len(ops.OBJECT_SUMS)
+        if getattr(self, '_acc_obj_i', None) is not None:
+            ops.check_metric_err(self.device)
+            counts, sums = self._acc_obj_i.cpu().tolist(), self._acc_obj_f.cpu().tolist()
+        return OrderedDict(list(zip(ops.OBJECT_COUNTS, counts)) + list(zip(ops.OBJECT_SUMS, sums)))
 
     def compute_current_thinned_scores(self, truth_labelled=False):
         """Adds the scores after border thinning -- util.compute_thinned_scores, the reference's do_thin=True -- to running sums of
@@ -272,7 +301,9 @@ class SegmentationModel(CGANModel):
 
     def get_current_accs(self):
         """Reads the device accumulators (the only synchronisation of the metric path) and derives RandScore, VInfo, pixelAcc,
-        meanAcc and meanIU from them, and RandScoreThin / VInfoThin (after the existing keys) when they were asked for."""
+        meanAcc and meanIU from them, and RandScoreThin / VInfoThin, then ObjF1 / ObjAP / SEG / PQ (util.object_scores of the pooled
+        counts), after the existing keys when they were asked for.  A trainer built for evaluation (test_ss.py) also prints the
+        pooled TP_k / N_t / N_s line when an object score was asked for."""
         if getattr(self, '_acc_rand', None) is not None:
             ops.check_metric_err(self.device)
             rand, conf = self._acc_rand.cpu().numpy(), self._acc_conf.cpu().numpy().astype(np.float64)
@@ -283,6 +314,15 @@ class SegmentationModel(CGANModel):
                 self.numAveragedImages = int(max(self.numAveragedImages, thin[0, 1], thin[1, 1]))
                 self.RandScoreThin = thin[0, 0] / thin[0, 1] if thin[0, 1] else 0
                 self.VInfoThin = thin[1, 0] / thin[1, 1] if thin[1, 1] else 0
+            if getattr(self, '_acc_obj_i', None) is not None:
+                obj_i, obj_f = self._acc_obj_i.cpu().numpy(), self._acc_obj_f.cpu().numpy()
+                self.numAveragedImages = int(max(self.numAveragedImages, obj_i[ops.OBJECT_COUNTS.index('images')]))
+                for k, v in util.object_scores(obj_i, obj_f).items():
+                    setattr(self, k, v)
+                if not self.isTrain and any(k in self.opt.which_metric for k in util.OBJECT_METRICS):
+                    # the evaluation drivers read the accuracies once, after the dataset: the per-threshold table goes beside them
+                    print('objects: TP at IoU > 0.50 .. 0.95: %s, N_t %d, N_s %d (min area %d)'
+                          % (' '.join(str(int(v)) for v in obj_i[:10]), obj_i[10], obj_i[11], self.opt.min_object_area))
             self.RandScore = rand[0] / rand[1] if rand[1] else 0
             self.VInfo = vinfo[0] / vinfo[1] if vinfo[1] else 0
             self.confusion, self.numAveragedPixels = conf, int(conf.sum())
@@ -294,4 +334,5 @@ class SegmentationModel(CGANModel):
                            + ([('VInfo', self.VInfo)] if 'VInfo' in self.opt.which_metric else [])
                            + ([('meanIU', self.meanIU)] if 'meanIU' in self.opt.which_metric else [])
                            + ([('RandScoreThin', self.RandScoreThin)] if 'RandScoreThin' in self.opt.which_metric else [])
-                           + ([('VInfoThin', self.VInfoThin)] if 'VInfoThin' in self.opt.which_metric else []))
+                           + ([('VInfoThin', self.VInfoThin)] if 'VInfoThin' in self.opt.which_metric else [])
+                           + [(k, getattr(self, k)) for k in util.OBJECT_METRICS if k in self.opt.which_metric])

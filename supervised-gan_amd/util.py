@@ -422,3 +422,52 @@ def compute_VInfo_scores(S, T, do_thin=False):
     if do_thin:
         raise NotImplementedError("do_thin needs skimage.morphology.thin, which this image does not carry")
     return np.array([compute_VInfo_parts(S[k].squeeze(axis=0), T[k].squeeze(axis=0))['VInfo'] for k in range(T.shape[0])])
+
+
+OBJECT_METRICS = ('ObjF1', 'ObjAP', 'SEG', 'PQ')      # the --which_metric names object_scores derives, in the order they are reported
+
+
+def object_match_counts(s, t, min_area=1):
+    """The object-level match counts (include/sgan_hip.h, "object-level scores") of prediction s against truth t, one [H, W] pair of
+    boundary maps thresholded at 0.5 and labelled 8-connected as region_table labels: (counts int64[16], sums float64[2]).
+    With whole areas a_i, b_j, the overlap c_ij and u_ij = a_i + b_j - c_ij, and regions smaller than min_area treated as absent:
+    counts[k] = TP_k = pairs with 20 c_ij > (10 + k) u_ij for k = 0 .. 9 (int64 arithmetic), counts[10] = N_t, counts[11] = N_s,
+    counts[12] = 1 (images), counts[13] = SEGn = pairs with 2 c_ij > a_i, counts[14] = counts[15] = 0; sums[0] = SIoU = sum of
+    c_ij / u_ij over the pairs of TP_0, sums[1] = SSEG = the same sum over the pairs of SEGn (math.fsum: correctly rounded).
+    The host yardstick of ops.object_match_accumulate; the trainers do not call it."""
+    import math
+    assert min_area >= 1, min_area
+    t_label = _label_false_regions(np.asarray(t) > 0.5).astype(np.int64)
+    s_label = _label_false_regions(np.asarray(s) > 0.5).astype(np.int64)
+    assert t_label.ndim == 2 and t_label.shape == s_label.shape, (t_label.shape, s_label.shape)
+    area_t, area_s = np.bincount(t_label.ravel()), np.bincount(s_label.ravel())
+    stride = int(s_label.max()) + 1
+    both = (t_label > 0) & (s_label > 0)
+    pair, c = np.unique(t_label[both] * stride + s_label[both], return_counts=True)      # the nonzero c_ij only
+    a, b, c = area_t[pair // stride], area_s[pair % stride], c.astype(np.int64)
+    keep = (a >= min_area) & (b >= min_area)
+    a, b, c = a[keep], b[keep], c[keep]
+    u = a + b - c
+    counts, sums = np.zeros(16, dtype=np.int64), np.zeros(2, dtype=np.float64)
+    for k in range(10):
+        counts[k] = int((20 * c > (10 + k) * u).sum())
+    counts[10], counts[11], counts[12] = int((area_t[1:] >= min_area).sum()), int((area_s[1:] >= min_area).sum()), 1
+    found, seg = 20 * c > 10 * u, 2 * c > a
+    counts[13] = int(seg.sum())
+    iou = c.astype(np.float64) / u.astype(np.float64)
+    sums[0], sums[1] = math.fsum(iou[found]), math.fsum(iou[seg])
+    return counts, sums
+
+
+def object_scores(counts, sums):
+    """ObjF1, ObjAP, SEG and PQ (an OrderedDict in that order) from pooled object_match_counts / ops.object_match_accumulate numbers:
+    ObjF1 = 2 TP_0 / (N_t + N_s); ObjAP = mean over the ten thresholds of TP_k / (N_t + N_s - TP_k); SEG = SSEG / N_t;
+    PQ = SIoU / ((N_t + N_s) / 2).  A score whose denominator is 0 reads 0.  The one place the trainers and the tests derive them."""
+    from collections import OrderedDict
+    tp, n_t, n_s = [int(v) for v in counts[:10]], int(counts[10]), int(counts[11])
+    siou, sseg = float(sums[0]), float(sums[1])
+    n = n_t + n_s
+    return OrderedDict([('ObjF1', 2.0 * tp[0] / n if n else 0.0),
+                        ('ObjAP', sum(v / (n - v) if n - v else 0.0 for v in tp) / 10.0),
+                        ('SEG', sseg / n_t if n_t else 0.0),
+                        ('PQ', siou / (n / 2.0) if n else 0.0)])
