@@ -844,6 +844,64 @@ int sgan_object_match_accumulate(const int32_t* t_labels, const int32_t* s_label
                                  int64_t workspace_bytes, int64_t* acc_i, double* acc_f, int64_t* counts_out, double* sums_out,
                                  int32_t* dev_err, void* stream);
 
+/* ---- boundary scores on the device: exact Euclidean distance transform, boundary F-measure, Hausdorff distance, ASSD ----------------
+ * Where the predicted wall lies relative to the true one, which the region scores above do not see: the boundary F-measure at a
+ * pixel tolerance (BSDS500's F in its distance-threshold form, `bfscore`; not the bipartite correspondPixels matching), the Hausdorff
+ * distance and the average symmetric surface distance (GlaS and the medical challenges).  util.edt_sq and util.boundary_counts are
+ * the NumPy restatements these entries are tested against, util.boundary_scores derives the scores.
+ *
+ * sgan_edt_workspace: bytes of the workspace sgan_edt_sq needs for an H x W plane (< 0: bad shape).
+ * sgan_edt_sq: the exact squared Euclidean distance transform.  The plane is read as sgan_ccl_label reads it, pixel (y, x) at
+ *   plane[(y * W + x) * pix_stride]; a pixel is wall when its value is > 0.5 (a NaN and an exact 0.5 are not wall).
+ *   dsq[y * W + x] = min over the wall pixels (y', x') of (y - y')^2 + (x - x')^2, an exact int32: 0 on a wall pixel, -1 everywhere
+ *   when the plane has no wall pixel (the convention of sgan_border_weight's d1sq), the same bits on every run.
+ *   Shapes: H, W <= 32768 and H W < 2^30, so that (H - 1)^2 + (W - 1)^2 < 2^31.  Anything else, a null pointer, a pixel stride < 1
+ *   and a short or misaligned (16 bytes) workspace return 1 with sgan_last_error set and nothing launched.
+ *   Four launches whose grids depend on (H, W) only, nothing read back and nothing decided on the host, so the call captures into a
+ *   hipGraph and replays on any other plane: a counter zeroed; the wall bits of every segment of 32 rows of every column as one
+ *   mask word, and the number of wall pixels added to the counter; per (column, segment) the vertical distance g to the column's
+ *   nearest wall pixel, the nearest wall row outside the segment looked up in the other segments' masks (nearest first, at most
+ *   H / 32 each way); per row dsq = min over x' of (x - x')^2 + g(y, x')^2, g^2 staged in LDS 2048 columns at a time, each thread
+ *   scanning outward from its own x until r^2 >= its best so far (exact; bounded by W), a longer row walked in chunks nearest first.
+ *   A plane without a wall is decided from the counter on the device.  The workspace may hold anything on entry.
+ *   dev_err is accepted like every metric entry's (required, not null); this entry sets no bit of it.
+ *
+ * sgan_boundary_workspace: bytes of the workspace sgan_boundary_accumulate needs for an H x W pair (< 0: bad shape).
+ * sgan_boundary_accumulate: t_dsq and s_dsq are sgan_edt_sq outputs of the truth and of the predicted plane.
+ *   Wall pixels: a pixel is a wall pixel of a map where that map's own dsq is 0.  A predicted wall pixel p has distance^2 t_dsq[p]
+ *     to the truth; a truth wall pixel has s_dsq[p] to the prediction.  -1 (the other map has no wall) is "not defined".
+ *   Bins: the bin of a distance^2 d is k = ceil(sqrt(d)), decided in integers: (k - 1)^2 < d <= k^2 for k = 0 .. 30; bin 31 holds
+ *     d > 900 and d = -1.  For an integer tolerance theta <= 30, "within theta" is therefore bin <= theta <=> d <= theta^2, exactly.
+ *   acc_i, int64[SGAN_BND_COUNTS], caller-owned on the device, zeroed by the caller once, pooled over a dataset:
+ *     [0 .. 31] += histogram of the predicted wall pixels by bin;  [32 .. 63] += histogram of the truth wall pixels by bin;
+ *     [64] += N_s, the predicted wall pixels;  [65] += N_t, the truth wall pixels;  [66] += 1 (images);
+ *     [67] += 1 when both maps have wall (Hausdorff defined);  [68] += predicted wall pixels with a defined distance;
+ *     [69] += truth wall pixels with a defined distance;  [70] = max over all images of the largest distance^2 on the predicted
+ *     side;  [71] the same on the truth side;  the remaining entries are 0.
+ *   acc_f, double[SGAN_BND_SUMS]: [0] += sum of sqrt(d) over the predicted wall pixels with a defined distance;  [1] += the same
+ *     over the truth wall pixels;  [2] += this image's Hausdorff distance sqrt(max of the two sides' largest d), when defined;  [3] = 0.
+ *   counts_out (int64[80]) and sums_out (double[4]), both optional, receive this pair's contribution alone, [70] and [71] holding
+ *     this pair's maxima.
+ *   Scores, derived on the host from the pooled numbers (util.boundary_scores); a score whose denominator is 0 reads 0:
+ *     BoundP = sum_{k <= theta} acc_i[k] / N_s,  BoundR = sum_{k <= theta} acc_i[32 + k] / N_t,  BoundF = 2 P R / (P + R),
+ *     HausD = acc_f[2] / acc_i[67],  ASSD = (acc_f[0] + acc_f[1]) / (acc_i[68] + acc_i[69]).
+ *   Exactness: the integers are exact (64-bit adds, an integer max) and identical in every scheduling order.  The fp64 sums are sums
+ *     of n correctly rounded square roots: within n 2^-52 relative of the exact sum.
+ *   Two launches whose grids depend on (H, W) only, nothing read back: a grid-stride count pass whose workgroups gather histograms
+ *   and counters in LDS and store them, with their two fp64 sums, in a slot of their own in the workspace; one workgroup that adds
+ *   the slots in slot order, decides "Hausdorff defined", adds to the accumulators and writes the optional outputs.  The workspace
+ *   may hold anything on entry.  dev_err as sgan_edt_sq: required, no bit set.  H W < 2^30.  Null required pointers, a bad shape and a
+ *   short workspace are refused before any launch: return 1, the reason in sgan_last_error. */
+#define SGAN_BND_BINS 32
+#define SGAN_BND_COUNTS 80
+#define SGAN_BND_SUMS 4
+int64_t sgan_edt_workspace(int32_t H, int32_t W);
+int sgan_edt_sq(const float* plane, int64_t pix_stride, int32_t H, int32_t W, int32_t* dsq, void* workspace, int64_t workspace_bytes,
+                int32_t* dev_err, void* stream);
+int64_t sgan_boundary_workspace(int32_t H, int32_t W);
+int sgan_boundary_accumulate(const int32_t* t_dsq, const int32_t* s_dsq, int32_t H, int32_t W, void* workspace, int64_t workspace_bytes,
+                             int64_t* acc_i, double* acc_f, int64_t* counts_out, double* sums_out, int32_t* dev_err, void* stream);
+
 /* ---- region statistics on the device (shape features of generated against real images: shape_stats.py) --------------------------
  * The reference's paper judges a generator by shape features of its cells and mitochondria; its repository holds only MATLAB that
  * loads precomputed features (experiments/plots).  These entries measure every region of a label map; util.region_table is the

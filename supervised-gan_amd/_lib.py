@@ -166,6 +166,10 @@ SIGNATURES = {
     "sgan_vinfo_accumulate": [_P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _P],
     "sgan_object_match_workspace": [_I, _I],
     "sgan_object_match_accumulate": [_P, _P, _I, _I, _I, _P, _L, _P, _P, _P, _P, _P, _P],
+    "sgan_edt_workspace": [_I, _I],
+    "sgan_edt_sq": [_P, _L, _I, _I, _P, _P, _L, _P, _P],
+    "sgan_boundary_workspace": [_I, _I],
+    "sgan_boundary_accumulate": [_P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _P, _P],
     "sgan_confusion_accumulate": [_P, _I, _I, _P, _P, _I, _I, _L, _P, _P, _P],
     "sgan_thin_workspace": [_I, _I],
     "sgan_thin": [_P, _L, _I, _I, _P, _I, _P, _L, _P, _P, _P],
@@ -180,7 +184,8 @@ SIGNATURES = {
 
 RESTYPES = {"sgan_image_resize_workspace": C.c_int64, "sgan_rand_f_workspace": C.c_int64,
             "sgan_vinfo_workspace": C.c_int64, "sgan_thin_workspace": C.c_int64,
-            "sgan_region_stats_workspace": C.c_int64, "sgan_object_match_workspace": C.c_int64}      # everything else returns an int status
+            "sgan_region_stats_workspace": C.c_int64, "sgan_object_match_workspace": C.c_int64,
+            "sgan_edt_workspace": C.c_int64, "sgan_boundary_workspace": C.c_int64}      # everything else returns an int status
 _lib = None
 
 

@@ -1109,10 +1109,19 @@ _vinfo_ws = {}
 _thin_ws = {}
 _region_ws = {}
 _object_ws = {}
+_edt_ws = {}
+_boundary_ws = {}
 REGION_COLS = 16      # int64 per row of a region table (include/sgan_hip.h, sgan_region_stats)
 # acc_i / counts_out and acc_f / sums_out of object_match_accumulate (SGAN_OBJ_* of include/sgan_hip.h); TP_k: matches at IoU > (10 + k) / 20
 OBJECT_COUNTS = tuple('TP_%d' % k for k in range(10)) + ('N_t', 'N_s', 'images', 'SEGn', 'zero14', 'zero15')
 OBJECT_SUMS = ('SIoU', 'SSEG')
+# acc_i / counts_out and acc_f / sums_out of boundary_accumulate (SGAN_BND_* of include/sgan_hip.h); bin k: (k - 1)^2 < distance^2 <= k^2,
+# bin 31: farther than 30 pixels, or the other map has no wall
+BOUNDARY_BINS = 32
+BOUNDARY_COUNTS = (tuple('hist_s_%d' % k for k in range(BOUNDARY_BINS)) + tuple('hist_t_%d' % k for k in range(BOUNDARY_BINS))
+                   + ('N_s', 'N_t', 'images', 'haus_images', 'defined_s', 'defined_t', 'max_dsq_s', 'max_dsq_t')
+                   + tuple('zero%d' % k for k in range(72, 80)))
+BOUNDARY_SUMS = ('sum_d_s', 'sum_d_t', 'sum_haus', 'zero3')
 VINFO_PARTS = ('SA', 'SB', 'SAB', 'aux', 'm', 'H_S', 'H_T', 'I', 'VInfo', 'split', 'merge')      # parts_out of vinfo_accumulate
 
 
@@ -1337,6 +1346,70 @@ def object_match_accumulate(t_labels, s_labels, acc_i, acc_f, min_area=1, counts
     L.check(L.lib().sgan_object_match_accumulate(_ptr(t_labels), _ptr(s_labels), H, W, int(min_area), _ptr(ws),
                                                  ws.numel() * ws.element_size(), _ptr(acc_i), _ptr(acc_f), _ptr(counts_out),
                                                  _ptr(sums_out), _ptr(metric_err(dev)), _stream()), "sgan_object_match_accumulate")
+
+
+def edt_workspace(H, W, device):
+    """The scratch of edt_sq for H x W planes (the wall counter, the column masks and the g^2 plane), cached per (H, W, device) like
+    thin_workspace; the kernels initialise what they use."""
+    key = (H, W, device.index)
+    ws = _edt_ws.get(key)
+    if ws is None:
+        nbytes = L.lib().sgan_edt_workspace(H, W)
+        if nbytes < 0:
+            raise L.SganError(f"sgan_edt_workspace({H}, {W}): {L.lib().sgan_last_error().decode()}")
+        ws = _edt_ws[key] = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
+    return ws
+
+
+def edt_sq(plane, out=None, workspace=None):
+    """The exact squared Euclidean distance transform of the pixels of `plane` [H, W] that are > 0.5 (sgan_edt_sq; util.edt_sq is the
+    host yardstick): int32 [H, W], the smallest dy^2 + dx^2 to a wall pixel, 0 on the wall, -1 everywhere when there is no wall.
+    Only enqueues -- the launch sequence depends on the shape alone -- and reads `plane` in place when its rows are W pixel strides
+    apart."""
+    plane = _plane(plane, "edt_sq")
+    H, W = plane.shape
+    dev = plane.device
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.int32, device=dev)
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() == H * W and out.device == dev
+    ws = edt_workspace(H, W, dev) if workspace is None else workspace
+    L.check(L.lib().sgan_edt_sq(_ptr(plane), plane.stride(1), H, W, _ptr(out), _ptr(ws), ws.numel() * ws.element_size(),
+                                _ptr(metric_err(dev)), _stream()), "sgan_edt_sq")
+    return out
+
+
+def boundary_workspace(H, W, device):
+    """The scratch of boundary_accumulate for H x W maps (one slot of partial counts per workgroup), cached per (H, W, device)."""
+    key = (H, W, device.index)
+    ws = _boundary_ws.get(key)
+    if ws is None:
+        nbytes = L.lib().sgan_boundary_workspace(H, W)
+        if nbytes < 0:
+            raise L.SganError(f"sgan_boundary_workspace({H}, {W}): {L.lib().sgan_last_error().decode()}")
+        ws = _boundary_ws[key] = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
+    return ws
+
+
+def boundary_accumulate(t_dsq, s_dsq, acc_i, acc_f, counts_out=None, sums_out=None, workspace=None):
+    """Adds the boundary counts (include/sgan_hip.h, "boundary scores") of the prediction against the truth, given as their edt_sq
+    planes s_dsq and t_dsq, to acc_i (int64[80], BOUNDARY_COUNTS: the two histograms of wall pixels by distance bin, N_s, N_t, images,
+    images with both walls, pixels with a defined distance, the two largest distance^2) and acc_f (float64[4], BOUNDARY_SUMS), both
+    on the device and zeroed by the caller once (sgan_boundary_accumulate).  counts_out (int64[80]) and sums_out (float64[4]) receive
+    this pair's contribution alone.  Only enqueues; util.boundary_counts is the host yardstick and util.boundary_scores derives
+    BoundF, HausD and ASSD."""
+    H, W = t_dsq.shape
+    dev = t_dsq.device
+    require_gpu(t_dsq, "boundary_accumulate")
+    for t in (t_dsq, s_dsq):
+        assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (H, W) and t.device == dev, (t.shape, t.dtype)
+    for a, dtype, n in ((acc_i, torch.int64, len(BOUNDARY_COUNTS)), (acc_f, torch.float64, len(BOUNDARY_SUMS)),
+                        (counts_out, torch.int64, len(BOUNDARY_COUNTS)), (sums_out, torch.float64, len(BOUNDARY_SUMS))):
+        assert a is None or (a.dtype == dtype and a.is_contiguous() and a.numel() == n and a.device == dev)
+    assert acc_i is not None and acc_f is not None
+    ws = boundary_workspace(H, W, dev) if workspace is None else workspace
+    L.check(L.lib().sgan_boundary_accumulate(_ptr(t_dsq), _ptr(s_dsq), H, W, _ptr(ws), ws.numel() * ws.element_size(), _ptr(acc_i),
+                                             _ptr(acc_f), _ptr(counts_out), _ptr(sums_out), _ptr(metric_err(dev)), _stream()),
+            "sgan_boundary_accumulate")
 
 
 def confusion_accumulate(x, C, conf, label=None, y=None, add_background=False):

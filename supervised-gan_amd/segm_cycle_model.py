@@ -167,6 +167,8 @@ class SegmentationCycleModel(CGANCycleModel):
     compute_current_VInfo = SegmentationModel.compute_current_VInfo
     compute_current_object_matches = SegmentationModel.compute_current_object_matches
     get_object_counts = SegmentationModel.get_object_counts
+    compute_current_boundary = SegmentationModel.compute_current_boundary
+    get_boundary_counts = SegmentationModel.get_boundary_counts
     compute_current_thinned_scores = SegmentationModel.compute_current_thinned_scores
     compute_current_accuracy = SegmentationModel.compute_current_accuracy
     get_current_accs = SegmentationModel.get_current_accs

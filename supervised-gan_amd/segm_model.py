@@ -174,8 +174,10 @@ class SegmentationModel(CGANModel):
         self.confusion, self.numAveragedPixels, self.numAveragedImages = 0, 0, 0
         self.pixelAcc = self.meanAcc = self.meanIU = self.RandScore = self.VInfo = self.RandScoreThin = self.VInfoThin = 0
         self.ObjF1 = self.ObjAP = self.SEG = self.PQ = 0
+        self.BoundF = self.HausD = self.ASSD = 0
         for t in (getattr(self, '_acc_rand', None), getattr(self, '_acc_conf', None), getattr(self, '_acc_vinfo', None),
-                  getattr(self, '_acc_thin', None), getattr(self, '_acc_obj_i', None), getattr(self, '_acc_obj_f', None)):
+                  getattr(self, '_acc_thin', None), getattr(self, '_acc_obj_i', None), getattr(self, '_acc_obj_f', None),
+                  getattr(self, '_acc_bnd_i', None), getattr(self, '_acc_bnd_f', None)):
             if t is not None:
                 t.zero_()
 
@@ -201,6 +203,8 @@ class SegmentationModel(CGANModel):
             self.compute_current_thinned_scores(truth_labelled=labelled)
         if 'meanIU' in self.opt.which_metric:
             self.compute_current_accuracy()
+        if any(k in self.opt.which_metric for k in util.BOUNDARY_METRICS):
+            self.compute_current_boundary(thinned='RandScoreThin' in self.opt.which_metric or 'VInfoThin' in self.opt.which_metric)
 
     def compute_current_Rand_score(self):
         """Adds the Rand F-score (util.compute_Rand_F_scores, do_thin=False) of the predicted against the true boundary map to the
@@ -288,6 +292,42 @@ class SegmentationModel(CGANModel):
         else:
             ops.rand_f_accumulate(self._acc_labels[0], self._thin_labels, self._acc_thin[0])
 
+    def compute_current_boundary(self, thinned=False):
+        """Adds the boundary counts of the same pair of maps (ops.boundary_accumulate: how far every predicted wall pixel lies from
+        the true wall and every true wall pixel from the predicted one) to pooled counters on the device: two exact distance
+        transforms (ops.edt_sq) of channel 0 of real_B and fake_B, one counting call.  BoundF, HausD and ASSD are derived from the
+        counters when the accuracies are read.  With --boundary_thin the predicted wall is thinned to one-pixel lines first
+        (ops.thin), the truth is not; thinned: RandScoreThin / VInfoThin were taken in this accum_accs, so the thinned plane is in
+        place and is not thinned again."""
+        assert self.num_classes == 2 and self.fake_B.shape[0] == 1, "binary segmentation at batch 1, like every kernel of this path"
+        self._acc_buffers()
+        s, t = self.fake_B.detach()[0, 0], self.real_B.detach()[0, 0]
+        if getattr(self, '_acc_bnd_i', None) is None:
+            self._acc_bnd_i = torch.zeros(len(ops.BOUNDARY_COUNTS), dtype=torch.int64, device=self.device)
+            self._acc_bnd_f = torch.zeros(len(ops.BOUNDARY_SUMS), dtype=torch.float64, device=self.device)
+            self._bnd_dsq = self._bnd_thin_plane = None
+        if self._bnd_dsq is None or self._bnd_dsq.shape[1:] != t.shape:
+            self._bnd_dsq = torch.empty((2,) + tuple(t.shape), dtype=torch.int32, device=self.device)
+        if self.opt.boundary_thin:
+            if thinned and getattr(self, '_thin_plane', None) is not None and self._thin_plane.shape == t.shape:
+                s = self._thin_plane
+            else:
+                if self._bnd_thin_plane is None or self._bnd_thin_plane.shape != t.shape:
+                    self._bnd_thin_plane = torch.empty(tuple(t.shape), dtype=torch.float32, device=self.device)
+                s = ops.thin(s, out=self._bnd_thin_plane)
+        ops.edt_sq(t, out=self._bnd_dsq[0])
+        ops.edt_sq(s, out=self._bnd_dsq[1])
+        ops.boundary_accumulate(self._bnd_dsq[0], self._bnd_dsq[1], self._acc_bnd_i, self._acc_bnd_f)
+
+    def get_boundary_counts(self):
+        """The pooled boundary numbers since reset_accs() as a dict: the 80 integers of ops.BOUNDARY_COUNTS (the two histograms by
+        distance bin, N_s, N_t, images, ...) and the four sums of ops.BOUNDARY_SUMS.  Synchronises, like get_current_accs()."""
+        counts, sums = [0] * len(ops.BOUNDARY_COUNTS), [0.0] * len(ops.BOUNDARY_SUMS)
+        if getattr(self, '_acc_bnd_i', None) is not None:
+            ops.check_metric_err(self.device)
+            counts, sums = self._acc_bnd_i.cpu().tolist(), self._acc_bnd_f.cpu().tolist()
+        return OrderedDict(list(zip(ops.BOUNDARY_COUNTS, counts)) + list(zip(ops.BOUNDARY_SUMS, sums)))
+
     def compute_current_accuracy(self):
         """conf[label, prediction] += 1 for every pixel, on the device (segm_model.py:309-331; the ratios are taken when the
         accuracies are read)."""
@@ -302,8 +342,10 @@ class SegmentationModel(CGANModel):
     def get_current_accs(self):
         """Reads the device accumulators (the only synchronisation of the metric path) and derives RandScore, VInfo, pixelAcc,
         meanAcc and meanIU from them, and RandScoreThin / VInfoThin, then ObjF1 / ObjAP / SEG / PQ (util.object_scores of the pooled
-        counts), after the existing keys when they were asked for.  A trainer built for evaluation (test_ss.py) also prints the
-        pooled TP_k / N_t / N_s line when an object score was asked for."""
+        counts), then BoundF / HausD / ASSD (util.boundary_scores of the pooled counts at --boundary_tolerance), after the existing
+        keys when they were asked for.  A trainer built for evaluation (test_ss.py) also prints the pooled TP_k / N_t / N_s line when
+        an object score was asked for, and the boundary precision / recall / F at the tolerances 0 .. 5 with the dataset's worst
+        distance when a boundary score was."""
         if getattr(self, '_acc_rand', None) is not None:
             ops.check_metric_err(self.device)
             rand, conf = self._acc_rand.cpu().numpy(), self._acc_conf.cpu().numpy().astype(np.float64)
@@ -323,6 +365,16 @@ class SegmentationModel(CGANModel):
                     # the evaluation drivers read the accuracies once, after the dataset: the per-threshold table goes beside them
                     print('objects: TP at IoU > 0.50 .. 0.95: %s, N_t %d, N_s %d (min area %d)'
                           % (' '.join(str(int(v)) for v in obj_i[:10]), obj_i[10], obj_i[11], self.opt.min_object_area))
+            if getattr(self, '_acc_bnd_i', None) is not None:
+                bnd_i, bnd_f = self._acc_bnd_i.cpu().numpy(), self._acc_bnd_f.cpu().numpy()
+                self.numAveragedImages = int(max(self.numAveragedImages, bnd_i[ops.BOUNDARY_COUNTS.index('images')]))
+                for k, v in util.boundary_scores(bnd_i, bnd_f, self.opt.boundary_tolerance).items():
+                    setattr(self, k, v)
+                if not self.isTrain and any(k in self.opt.which_metric for k in util.BOUNDARY_METRICS):
+                    print('boundary: P/R/F at tolerance 0 .. 5: %s, worst distance %.3f (N_s %d, N_t %d%s)'
+                          % (' '.join('%.4f/%.4f/%.4f' % util.boundary_pr(bnd_i, k) for k in range(6)),
+                             float(np.sqrt(float(max(bnd_i[70], bnd_i[71])))), bnd_i[64], bnd_i[65],
+                             ', prediction thinned' if self.opt.boundary_thin else ''))
             self.RandScore = rand[0] / rand[1] if rand[1] else 0
             self.VInfo = vinfo[0] / vinfo[1] if vinfo[1] else 0
             self.confusion, self.numAveragedPixels = conf, int(conf.sum())
@@ -335,4 +387,5 @@ class SegmentationModel(CGANModel):
                            + ([('meanIU', self.meanIU)] if 'meanIU' in self.opt.which_metric else [])
                            + ([('RandScoreThin', self.RandScoreThin)] if 'RandScoreThin' in self.opt.which_metric else [])
                            + ([('VInfoThin', self.VInfoThin)] if 'VInfoThin' in self.opt.which_metric else [])
-                           + [(k, getattr(self, k)) for k in util.OBJECT_METRICS if k in self.opt.which_metric])
+                           + [(k, getattr(self, k)) for k in util.OBJECT_METRICS if k in self.opt.which_metric]
+                           + [(k, getattr(self, k)) for k in util.BOUNDARY_METRICS if k in self.opt.which_metric])

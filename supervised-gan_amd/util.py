@@ -471,3 +471,100 @@ def object_scores(counts, sums):
                         ('ObjAP', sum(v / (n - v) if n - v else 0.0 for v in tp) / 10.0),
                         ('SEG', sseg / n_t if n_t else 0.0),
                         ('PQ', siou / (n / 2.0) if n else 0.0)])
+
+
+BOUNDARY_METRICS = ('BoundF', 'HausD', 'ASSD')      # the --which_metric names boundary_scores derives, in the order they are reported
+BOUNDARY_BINS = 32
+
+
+def _wall_mask(m):
+    m = np.asarray(m)
+    return m if m.dtype == np.bool_ else m > 0.5      # a NaN and an exact 0.5 are not wall
+
+
+def edt_sq(mask):
+    """The exact squared Euclidean distance transform of a [H, W] wall mask (bool, or a map thresholded at > 0.5): int32 [H, W], the
+    smallest dy^2 + dx^2 to a wall pixel, 0 on the wall, -1 everywhere when the mask is empty.  Two 1-D passes in integers: the
+    distance to the nearest wall pixel of the column from two running "last wall row seen" sweeps, then per row the minimum over
+    all columns of dx^2 + g^2.  The host yardstick of ops.edt_sq; O(H W^2), the trainers do not call it."""
+    wall = _wall_mask(mask)
+    assert wall.ndim == 2, wall.shape
+    H, W = wall.shape
+    if not wall.any():
+        return np.full((H, W), -1, dtype=np.int32)
+    far = np.int64(4 * (H + W))      # farther than any pixel of the plane: "no wall in this column"
+    rows = np.arange(H, dtype=np.int64)[:, None]
+    above = np.maximum.accumulate(np.where(wall, rows, -far), axis=0)                         # the last wall row at or above y
+    below = np.minimum.accumulate(np.where(wall, rows, far)[::-1], axis=0)[::-1]              # the first wall row at or below y
+    g = np.minimum(rows - above, below - rows)
+    has = wall.any(axis=0)
+    gsq = np.where(has[None, :], g * g, np.int64(1) << 40)
+    cols = np.arange(W, dtype=np.int64)
+    dxsq = (cols[:, None] - cols[None, :]) ** 2                                               # [x, x']
+    out = np.empty((H, W), dtype=np.int64)
+    for y in range(H):
+        out[y] = (dxsq + gsq[y][None, :]).min(axis=1)
+    return out.astype(np.int32)
+
+
+def boundary_bin(d):
+    """The bin of a distance^2 (include/sgan_hip.h, "boundary scores"): k = ceil(sqrt(d)) in integers for 0 <= d <= 900, 31 beyond
+    and for -1 (the other map has no wall)."""
+    import math
+    d = int(d)
+    if d < 0 or d > 900:
+        return BOUNDARY_BINS - 1
+    k = math.isqrt(d)
+    return k if k * k == d else k + 1
+
+
+def boundary_counts(s_wall, t_wall):
+    """The boundary counts (include/sgan_hip.h, "boundary scores") of the predicted wall s_wall against the true wall t_wall, two
+    [H, W] masks (bool, or maps thresholded at > 0.5): (counts int64[80], sums float64[4]).  counts[0:32] / counts[32:64]: the
+    predicted / truth wall pixels by the bin of their distance^2 to the other map's wall; [64] N_s, [65] N_t, [66] 1 (images),
+    [67] 1 when both maps have wall, [68] / [69] the predicted / truth wall pixels with a defined distance, [70] / [71] the largest
+    distance^2 on either side, the rest 0.  sums[0] / sums[1]: the sums of the distances over the predicted / truth wall pixels with
+    a defined distance, sums[2] the Hausdorff distance of the pair when both have wall (math.fsum of math.sqrt: correctly rounded).
+    The host yardstick of ops.boundary_accumulate; the trainers do not call it."""
+    import math
+    s_wall, t_wall = _wall_mask(s_wall), _wall_mask(t_wall)
+    assert s_wall.ndim == 2 and s_wall.shape == t_wall.shape, (s_wall.shape, t_wall.shape)
+    s_dsq, t_dsq = edt_sq(s_wall), edt_sq(t_wall)
+    counts, sums = np.zeros(80, dtype=np.int64), np.zeros(4, dtype=np.float64)
+    for side, (own, other) in enumerate(((s_wall, t_dsq), (t_wall, s_dsq))):
+        d = other[own].astype(np.int64)
+        for v, n in zip(*np.unique(d, return_counts=True)):
+            counts[32 * side + boundary_bin(v)] += n
+        counts[64 + side] = d.size
+        defined = d[d >= 0]
+        counts[68 + side] = defined.size
+        counts[70 + side] = int(defined.max()) if defined.size else 0
+        sums[side] = math.fsum(math.sqrt(int(v)) for v in defined)
+    counts[66] = 1
+    if counts[64] and counts[65]:
+        counts[67] = 1
+        sums[2] = math.sqrt(int(max(counts[70], counts[71])))
+    return counts, sums
+
+
+def boundary_pr(counts, tolerance):
+    """(BoundP, BoundR, BoundF) at an integer pixel tolerance 0 .. 30 from pooled boundary counts: the share of the predicted / truth
+    wall pixels within `tolerance` of the other map's wall, and their harmonic mean.  A zero denominator reads 0."""
+    assert 0 <= int(tolerance) <= 30, tolerance
+    k = int(tolerance) + 1
+    n_s, n_t = int(counts[64]), int(counts[65])
+    p = int(np.sum(counts[0:k])) / n_s if n_s else 0.0
+    r = int(np.sum(counts[32:32 + k])) / n_t if n_t else 0.0
+    return p, r, (2.0 * p * r / (p + r) if p + r else 0.0)
+
+
+def boundary_scores(counts, sums, tolerance):
+    """BoundF, HausD and ASSD (an OrderedDict in that order) from pooled boundary_counts / ops.boundary_accumulate numbers: BoundF at
+    `tolerance` pixels (boundary_pr); HausD = the mean over the images where both maps have wall of their Hausdorff distances,
+    sums[2] / counts[67]; ASSD = (sums[0] + sums[1]) / (counts[68] + counts[69]).  A score whose denominator is 0 reads 0.  The one
+    place the trainers and the tests derive them."""
+    from collections import OrderedDict
+    n_h, n_d = int(counts[67]), int(counts[68]) + int(counts[69])
+    return OrderedDict([('BoundF', boundary_pr(counts, tolerance)[2]),
+                        ('HausD', float(sums[2]) / n_h if n_h else 0.0),
+                        ('ASSD', (float(sums[0]) + float(sums[1])) / n_d if n_d else 0.0)])

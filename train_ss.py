@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Training driver of the segmentation trainers (`--model segmentation`, `segmentation_cycle`) with the loop of the reference's
-train_ss.py: like train.py, plus the running accuracies (`--which_metric RandScore VInfo meanIU`) accumulated after EVERY optimizer step,
+train_ss.py: like train.py, plus the running accuracies (`--which_metric RandScore VInfo meanIU`, and the thinned,
+object-level and boundary scores of the README) accumulated after EVERY optimizer step,
 a validation pass over `<dataroot>/val` after every epoch, and a `best` checkpoint kept by `--best_metric`.
 
     python train_ss.py --dataroot synthetic --name sgan_ss --model segmentation --which_direction AtoB --dataset_mode aligned \
@@ -27,6 +28,9 @@ from supervised_gan_amd.options import TrainOptions  # noqa: E402
 from supervised_gan_amd.synthetic_data import SyntheticDataset  # noqa: E402
 from supervised_gan_amd.util import save_image, tensor2im  # noqa: E402
 from supervised_gan_amd.visualizer import Visualizer  # noqa: E402
+
+
+LOWER_IS_BETTER = ('HausD', 'ASSD')      # distances in pixels: reported, never the --best_metric
 
 
 def improves(value, best):
@@ -95,6 +99,9 @@ def main(argv=None):
     if opt.graph and opt_val.valSize != opt.fineSize:
         raise ValueError("--graph: the captured step owns the trainer's input buffers, so --valSize (%d) must equal --fineSize (%d)"
                          % (opt_val.valSize, opt.fineSize))
+    if opt.best_metric in LOWER_IS_BETTER:
+        raise ValueError("--best_metric %s: a distance, lower is better, and the `best` checkpoint is kept by the highest value; "
+                         "choose a score among --which_metric (BoundF is the boundary score that rises)" % opt.best_metric)
     if opt.best_metric != 'None' and opt.best_metric not in opt.which_metric:
         raise ValueError("--best_metric %s is not among --which_metric %s" % (opt.best_metric, ' '.join(opt.which_metric)))
     model = create_model(opt)
