@@ -1300,6 +1300,7 @@ extern "C" int sgan_gauss_down_fwd(const float* in, int32_t in_ld, int32_t H, in
     SGAN_CHECK((C & 3) == 0 && (in_ld & 3) == 0 && (out_ld & 3) == 0 && in_ld >= C && out_ld >= C && k * k * C * 4 <= 60000, "bad channel layout");
     SGAN_CHECK(Ho == (H + 2 * pad - k) / s + 1 && Wo == (W + 2 * pad - k) / s + 1, "gauss geometry mismatch");
     const int64_t total = (int64_t)Ho * Wo * (C >> 2);
+    if (total >= (1ll << 31)) return sgan_fail(SGAN_ERR_UNSUPPORTED, "gauss image too large");      // the kernel indexes in 32 bits
     int blocks = sg_cdiv(total, 256);
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(sg_gauss_fwd_kernel, dim3(blocks), dim3(256), (size_t)k * k * C * 4, (hipStream_t)stream, in, in_ld, H, W, C, Creal, g,

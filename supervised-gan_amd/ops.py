@@ -481,19 +481,42 @@ def pad_reflect_bwd(dout, pad, din, x=None, x_norm=None, mask=None, bwd_sums=Non
             "sgan_pad_reflect_bwd")
 
 
+def _fits_exact(t, H, W, Cs, what):
+    """_fits, and the two sides on their own: an [H][W][>= Cs] view (H * W alone would let a transposed map through)."""
+    _act(t)
+    if tuple(t.shape[:2]) != (H, W):
+        raise L.SganError(f"{what}: tensor {tuple(t.shape)} is not the {H}x{W}x(>= {Cs}) map this call addresses; nothing was launched")
+    return _fits(t, H, W, Cs, what)
+
+
 def bilinear_up2_fwd(x, out, out_stats=None, stats_sq=0):
+    """out [2H, 2W, >= Cs] = x2 bilinear interpolation (align_corners=False) of x [H, W, Cs]; out_stats += its (sum, sum of squares)."""
     H, W, Cs = x.shape
-    L.check(L.lib().sgan_bilinear_up2_fwd(_ptr(_act(x)), x.stride(1), H, W, Cs, _ptr(_act(out)), out.stride(1), _ptr(out_stats),
+    _fits_exact(x, H, W, Cs, "bilinear_up2_fwd x")
+    _fits_exact(out, 2 * H, 2 * W, Cs, "bilinear_up2_fwd out")
+    L.check(L.lib().sgan_bilinear_up2_fwd(_ptr(x), x.stride(1), H, W, Cs, _ptr(out), out.stride(1), _ptr(out_stats),
                                           int(stats_sq), _stream()), "sgan_bilinear_up2_fwd")
 
 
 def bilinear_up2_bwd(dout, din):
+    """din [H, W, Cs] = the transpose of bilinear_up2_fwd applied to dout [2H, 2W, >= Cs]."""
     H, W, Cs = din.shape
-    L.check(L.lib().sgan_bilinear_up2_bwd(_ptr(_act(dout)), dout.stride(1), H, W, Cs, _ptr(_act(din)), din.stride(1), _stream()),
+    _fits_exact(din, H, W, Cs, "bilinear_up2_bwd din")
+    _fits_exact(dout, 2 * H, 2 * W, Cs, "bilinear_up2_bwd dout")
+    L.check(L.lib().sgan_bilinear_up2_bwd(_ptr(dout), dout.stride(1), H, W, Cs, _ptr(din), din.stride(1), _stream()),
             "sgan_bilinear_up2_bwd")
 
 
-def _level_table(levels):
+def _level_table(levels, H, W, what):
+    """Pointers and pixel strides of the six levels; every level present is checked as [H >> (s+1), W >> (s+1), >= 4] inside its storage."""
+    if len(levels) != 6:
+        raise L.SganError(f"{what}: six levels expected, got {len(levels)}; nothing was launched")
+    for s, t in enumerate(levels):
+        if t is not None:
+            if t.dim() != 3 or t.dtype != torch.float32 or t.stride(2) != 1:
+                raise L.SganError(f"{what}: level {s} {tuple(t.shape)} ({t.dtype}, strides {t.stride()}) is not a float32 NHWC map with "
+                                  "unit channel stride; nothing was launched")
+            _fits_exact(t, H >> (s + 1), W >> (s + 1), 4, f"{what} level {s}")
     ptrs = (C.c_void_p * 6)(*[t.data_ptr() if t is not None else None for t in levels])
     lds = (C.c_int32 * 6)(*[t.stride(1) if t is not None else 4 for t in levels])
     return ptrs, lds
@@ -502,14 +525,19 @@ def _level_table(levels):
 def avgpool_pyramid_fwd(label, levels):
     """levels[s]: [H >> (s+1), W >> (s+1), 4] buffers (or channel slices), s = 0..5."""
     H, W, _ = label.shape
-    ptrs, lds = _level_table(levels)
-    L.check(L.lib().sgan_avgpool_pyramid_fwd(_ptr(_act(label)), label.stride(1), H, W, ptrs, lds, _stream()), "sgan_avgpool_pyramid_fwd")
+    _fits_exact(label, H, W, 4, "avgpool_pyramid_fwd label")
+    if any(t is None for t in levels):
+        raise L.SganError("avgpool_pyramid_fwd: the forward writes all six levels; nothing was launched")
+    ptrs, lds = _level_table(levels, H, W, "avgpool_pyramid_fwd")
+    L.check(L.lib().sgan_avgpool_pyramid_fwd(_ptr(label), label.stride(1), H, W, ptrs, lds, _stream()), "sgan_avgpool_pyramid_fwd")
 
 
 def avgpool_pyramid_bwd(dlevels, dlabel, accumulate=False):
+    """dlabel [H, W, 4] (+)= sum over the levels present (None: absent) of dlevels[s][y >> (s+1), x >> (s+1)] / 4^(s+1)."""
     H, W, _ = dlabel.shape
-    ptrs, lds = _level_table(dlevels)
-    L.check(L.lib().sgan_avgpool_pyramid_bwd(ptrs, lds, H, W, _ptr(_act(dlabel)), dlabel.stride(1), int(accumulate), _stream()),
+    _fits_exact(dlabel, H, W, 4, "avgpool_pyramid_bwd dlabel")
+    ptrs, lds = _level_table(dlevels, H, W, "avgpool_pyramid_bwd")
+    L.check(L.lib().sgan_avgpool_pyramid_bwd(ptrs, lds, H, W, _ptr(dlabel), dlabel.stride(1), int(accumulate), _stream()),
             "sgan_avgpool_pyramid_bwd")
 
 

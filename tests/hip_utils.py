@@ -58,13 +58,16 @@ class Guarded:
     """An [H, W, C] NHWC view `t` into storage pre-filled with NaN: `sliced` puts it into the middle third of a 3 C wide buffer (NaN
     channels on both sides of every pixel), and `tail` NaN elements follow the last pixel either way.  `data` (numpy / torch,
     [H, W, C]) is copied in; without it the view itself is NaN too (an output nobody has written yet).  snapshot() is taken at
-    construction: outside_intact() says everything outside the view still holds its bits, untouched() the view as well."""
+    construction: outside_intact() says everything outside the view still holds its bits, untouched() the view as well.  `ld`, `off`:
+    any other pixel stride and channel offset of the view."""
 
-    def __init__(self, H, W, C, sliced=False, data=None, tail=1024, dev="cuda"):
-        ld = 3 * C if sliced else C
+    def __init__(self, H, W, C, sliced=False, data=None, tail=1024, dev="cuda", ld=None, off=0):
+        if ld is None:
+            ld, off = (3 * C, C) if sliced else (C, 0)
+        assert off + C <= ld
         self.store = torch.full((H * W * ld + tail,), float("nan"), dtype=torch.float32, device=dev)
         body = self.store[: H * W * ld].view(H, W, ld)
-        self.t = body[..., C: 2 * C] if sliced else body
+        self.t = body[..., off: off + C]
         if data is not None:
             self.t.copy_(torch.as_tensor(data, dtype=torch.float32).reshape(H, W, C))
         self.inside = torch.zeros_like(self.store, dtype=torch.bool)
