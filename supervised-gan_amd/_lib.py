@@ -176,13 +176,14 @@ SIGNATURES = {
     "sgan_region_stats_workspace": [_I, _I],
     "sgan_region_stats": [_P, _I, _I, _P, _I, _P, _P, _L, _P, _P],
     "sgan_border_weight": [_P, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P],
+    "sgan_last_variant": [],
     "sgan_profile_enable": [_I],
     "sgan_profile_count": [],
     "sgan_profile_mark": [_P],
     "sgan_profile_read": [_I, C.POINTER(C.c_char_p), C.POINTER(C.c_float)],
 }
 
-RESTYPES = {"sgan_image_resize_workspace": C.c_int64, "sgan_rand_f_workspace": C.c_int64,
+RESTYPES = {"sgan_last_variant": C.c_char_p, "sgan_image_resize_workspace": C.c_int64, "sgan_rand_f_workspace": C.c_int64,
             "sgan_vinfo_workspace": C.c_int64, "sgan_thin_workspace": C.c_int64,
             "sgan_region_stats_workspace": C.c_int64, "sgan_object_match_workspace": C.c_int64,
             "sgan_edt_workspace": C.c_int64, "sgan_boundary_workspace": C.c_int64}      # everything else returns an int status

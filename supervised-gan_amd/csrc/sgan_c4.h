@@ -370,6 +370,8 @@ static int sg_launch_c4(SgIgemmParams& P, hipStream_t st) {
     else sg_launch_c4_rb<4>(P, tiles, st);
     SGAN_LAUNCH_CHECK();
     g_sgan_last_kernel = "sg_conv_c4_kernel";
+    if (sg_c4_needs_epi(P)) snprintf(g_sgan_last_variant, sizeof(g_sgan_last_variant), "NB2 RB%d EPI gy%d", RB, (P.N + 31) / 32);
+    else snprintf(g_sgan_last_variant, sizeof(g_sgan_last_variant), "NB%d RB%d", P.N <= 32 ? 2 : P.N <= 48 ? 3 : 4, RB);
     sg_prof_end(st, g_sgan_last_kernel);
     return SGAN_OK;
 }
@@ -408,6 +410,7 @@ static int sg_launch_scatter4(SgIgemmParams& P, hipStream_t st) {
     hipLaunchKernelGGL(sg_conv_scatter4_kernel, dim3(t), dim3(256), lds, st, P);
     SGAN_LAUNCH_CHECK();
     g_sgan_last_kernel = "sg_conv_scatter4_kernel";
+    snprintf(g_sgan_last_variant, sizeof(g_sgan_last_variant), "tiles %d", t);
     sg_prof_end(st, g_sgan_last_kernel);
     return SGAN_OK;
 }

@@ -6,6 +6,7 @@
 
 thread_local char g_sgan_err[512] = {0};
 thread_local const char* g_sgan_last_kernel = "";
+thread_local char g_sgan_last_variant[96] = {0};
 
 int sgan_fail(int code, const char* fmt, ...) {
     va_list ap;
@@ -18,6 +19,7 @@ int sgan_fail(int code, const char* fmt, ...) {
 extern "C" const char* sgan_version(void) { return "sgan_hip 0.2 (gfx950; fp32 MFMA 16x16x4 + split-bf16 MFMA 32x32x16)"; }
 extern "C" const char* sgan_last_error(void) { return g_sgan_err; }
 extern "C" const char* sgan_last_kernel(void) { return g_sgan_last_kernel; }
+extern "C" const char* sgan_last_variant(void) { return g_sgan_last_variant; }
 extern "C" int sgan_stat_replicas(void) { return SGAN_STAT_REPLICAS; }      // what this build was compiled with (callers size their arenas by it)
 // The explicit device of the boundary: kernels go to the device the stream belongs to, and HIP wants the calling thread's
 // current device to be that one.  A host thread that has not chosen a device itself (an autograd worker of a non-torch host, a

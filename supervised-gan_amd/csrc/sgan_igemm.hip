@@ -867,6 +867,7 @@ static int sg_launch_small_n_nr(SgIgemmParams& P, hipStream_t st) {
     else hipLaunchKernelGGL((sg_conv_small_n_kernel<LPP, R, U, NR, false>), grid, dim3(256), lds, st, P);
     SGAN_LAUNCH_CHECK();
     g_sgan_last_kernel = LPP == 64 ? "sg_conv_small_n_kernel<64>" : LPP == 16 ? "sg_conv_small_n_kernel<16>" : "sg_conv_small_n_kernel<8>";
+    snprintf(g_sgan_last_variant, sizeof(g_sgan_last_variant), "NR%d BKC%d", NR, P.w_ks == 1 ? 1 : 0);
     sg_prof_end(st, g_sgan_last_kernel);
     return SGAN_OK;
 }

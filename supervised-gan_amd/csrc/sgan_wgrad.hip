@@ -701,6 +701,13 @@ static bool sg_thin_plan(SgWgradParams& P, double want_wgs, SgThinPlan* out) {
     return true;
 }
 
+// sgan_last_variant(): "<prefix>nsplit a,b,.." -- the pixel split of every problem
+static void sg_thin_variant(const SgWgradParams& P, const char* prefix) {
+    int n = snprintf(g_sgan_last_variant, sizeof(g_sgan_last_variant), "%snsplit ", prefix);
+    for (int g = 0; g < P.nprob && n < (int)sizeof(g_sgan_last_variant) - 8; ++g)
+        n += snprintf(g_sgan_last_variant + n, sizeof(g_sgan_last_variant) - n, g ? ",%d" : "%d", P.q[g].nsplit);
+}
+
 template <int MB, bool SWAP>
 static int sg_launch_wgrad_thin(SgWgradParams& P, hipStream_t st, const char* name, void* workspace, int64_t workspace_bytes) {
     (void)workspace;
@@ -715,6 +722,7 @@ static int sg_launch_wgrad_thin(SgWgradParams& P, hipStream_t st, const char* na
     else hipLaunchKernelGGL((sg_wgrad_thin_kernel<MB, false, SWAP>), grid, dim3(64 * SG_THIN_NW), pl.lds, st, P, pl.z);
     SGAN_LAUNCH_CHECK();
     g_sgan_last_kernel = name;
+    sg_thin_variant(P, "");
     sg_prof_end(st, g_sgan_last_kernel);
     return SGAN_OK;
 }
@@ -916,6 +924,11 @@ extern "C" int sgan_conv_bwd_thin_pair(const sgan_conv_dgrad_job* djobs, int32_t
     }
     SGAN_LAUNCH_CHECK();
     g_sgan_last_kernel = "sg_bwd_thin_pair_kernel";
+    {
+        char pre[24];
+        snprintf(pre, sizeof(pre), "DK%d RB%d ", dk, dk == 0 ? RB : 0);
+        sg_thin_variant(W, pre);
+    }
     sg_prof_end(st, g_sgan_last_kernel);
     return SGAN_OK;
 }

@@ -88,6 +88,21 @@ class Guarded:
         return self.t.detach().cpu().numpy().copy()
 
 
+GUARD = 4096      # fp32 elements of sentinel behind every operand (16 KB: more than any vector over-read)
+
+
+def _guarded(t, fill=float("nan")):
+    """A copy of `t` whose storage ends in GUARD sentinel elements (NaN: an over-READ that is used turns the result NaN; an
+    over-WRITE changes the sentinel's bit pattern).  Returns (view shaped like t, the guard)."""
+    flat = torch.full((t.numel() + GUARD,), fill, dtype=t.dtype, device="cuda")
+    flat[: t.numel()] = t.reshape(-1)
+    return flat[: t.numel()].view(t.shape), flat[t.numel():]
+
+
+def _guard_intact(g):
+    return bool(torch.isnan(g).all())
+
+
 def pad_vec(v, dev="cuda"):
     out = torch.zeros(pad4(v.numel()), dtype=torch.float32)
     out[: v.numel()] = v

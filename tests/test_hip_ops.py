@@ -1032,21 +1032,6 @@ def test_cross_entropy_and_softmax_kernels(hip, C, H, W, weighted):
     assert float((z3c.grad.cpu() - z3.grad).abs().max()) < 2e-6 * float(z3.grad.abs().max()) + 1e-9
 
 
-GUARD = 4096      # fp32 elements of sentinel behind every operand (16 KB: more than any vector over-read)
-
-
-def _guarded(t, fill=float("nan")):
-    """A copy of `t` whose storage ends in GUARD sentinel elements (NaN: an over-READ that is used turns the result NaN; an
-    over-WRITE changes the sentinel's bit pattern).  Returns (view shaped like t, the guard)."""
-    flat = torch.full((t.numel() + GUARD,), fill, dtype=t.dtype, device="cuda")
-    flat[: t.numel()] = t.reshape(-1)
-    return flat[: t.numel()].view(t.shape), flat[t.numel():]
-
-
-def _guard_intact(g):
-    return bool(torch.isnan(g).all())
-
-
 @pytest.mark.parametrize("case", [
     ("conv", 7, 1, 3, 8, 8, 16, 16),        # the layer round 2's fault ran on undersized buffers (k7, 49 taps)
     ("conv", 7, 1, 0, 8, 64, 22, 22),       # resnet head after the reflection pad (49 taps, p0)
@@ -1059,7 +1044,7 @@ def test_conv_operands_with_guarded_tails(hip, case, math_mode):
     """Every operand of forward / backward-data / backward-weight is placed so that its storage ends in a NaN guard: results match
     torch (an over-read that reaches a product would make them NaN) and every guard keeps its bit pattern (no store past an end).
     Regression shapes for the round-2 fault: the 49-tap layers, ConvT output padding, the 4-channel kernels."""
-    from hip_utils import from_buf, from_master, master_weight, pad_vec, rel, to_buf
+    from hip_utils import _guard_intact, _guarded, from_buf, from_master, master_weight, pad_vec, rel, to_buf
     from supervised_gan_amd.ops import pad4
     ops = hip
     kind, k, s, p, cin, cout, H, W = case

@@ -1,0 +1,282 @@
+"""float64 reference of the conv layers with a 4-stored-channel side (sg_conv_scatter4_kernel, sg_conv_c4_kernel,
+sg_conv_small_n_kernel, sg_wgrad_thin_kernel, sg_bwd_thin_pair_kernel), CPU only.
+
+A layer joins input pixel i and output pixel o through tap kk along each axis: conv  i = o s + kk - p,  ConvT  o = i s + kk - p
+(output_padding only lengthens the output).  forward / dgrad / wgrad below are that one relation written three times as a loop over
+the k x k taps, in float64; tests/test_thin_conv_ref_host.py holds them to torch's conv2d / conv_transpose2d and autograd.
+
+The normalise-on-load prologue is applied in fp32 the way the kernels do (plane_model._prologue: mean / rstd from the fp64 sums,
+sh = beta - mean sc, y = x sc + sh, max(y, slope y)), so reference and kernel differ by rounding alone, and every operation has
+    M_a the same sum over magnitudes, sum |a| |w| (+ |bias|, + |previous value| when accumulating),
+    M_A the same sum with A in the place of |a| (below; M_A = M_a for a plain read), and
+    L   the number of products summed into the element (taps in bounds x STORED channels; pixels for backward-weight),
+with the a-priori bound, valid for any order of summation (MFMA internals, LDS partials, fp32 atomics)
+
+    |kernel - ref| <= (L + c_a) u M_a + c_A u M_A,      u = 2^-24,
+
+which is the issue's (L + c0) u M with c0 = c_a + c_A, except that the c_A roundings of the prologue and the second-order term are
+taken relative to what they are relative to.  With statistics A = f (|x sc| + |sh| + |mean sc|), f = 1 where y > 0, else the negative
+slope (0 for ReLU): the kernel may contract x sc + sh and beta - mean sc into one FMA each, the restatement rounds twice, and those
+differences are relative to |x sc| and |mean sc|, not to |y| (|y| <= |x sc| + |sh|, so A >= |a|).  Without statistics A = |a|.
+
+The constants, derived (every term an upper bound, none measured):
+  prologue     c_A 6  sh: two roundings against one, |sh2 - sh1| <= u |mean sc| + 2 u |sh|;  y: the same way, u |x sc| + 2 u |y|, plus
+                      the difference of sh: together 3 u |x sc| + 4 u |sh| + u |mean sc| <= 4 u A';  slope y rounds once on either
+                      side, 2 u more.  The sign of y cannot differ: MASK_MARGIN, and 4 u A' < |y| / 2 element by element, are
+                      asserted for every case (test_thin_conv_ref_host.py).
+  second order c_A 2  (L + c)^2 u^2 M <= 2 u M while L + c <= 5792 (asserted); it stands on the larger magnitude.
+  sum          L      L - 1 additions and one rounding per product (none when fused), in any order: the classic L u sum |terms|.
+  bias 1, accumulate 1 (|previous| joins both magnitudes), act' 1 (the multiply by the negative slope, backward-data): c_a.
+  => forward (L + 1) u M_a + 8 u M_A;  backward-weight (L + 1) u M_a + 8 u M_A;  backward-data reads dY plain: (L + 4) u M;
+     bias gradient (L + 3) u M.
+tanh: |tanh'| <= 1 passes the bound through; tanhf itself is allowed 2 ulp = 4 u |tanh| on top.
+Statistics and norm-backward sums are fp64 sums of the kernel's fp32 values: the element bounds summed, plus N 2^-53 sum |v| for the
+order of the N fp64 additions (bound_sum); the fp32 product v xhat of the second norm sum adds u |v xhat| per pixel."""
+import numpy as np
+import torch
+
+import plane_model as PM
+
+U = 2.0 ** -24
+CA_FWD, CA_WGRAD, C_PRO = 1, 1, 8      # c_a of forward / backward-weight; c_A (prologue 6 + second order 2)
+C0_DGRAD, C0_DBIAS = 4, 3
+L_MAX = 5792
+MASK_MARGIN = 1e-5
+SLOPE = 0.2
+NEG = {0: 1.0, 1: 0.0, 2: SLOPE}
+
+
+def pad4(c):
+    return (c + 3) // 4 * 4
+
+
+class Layer:
+    """kind "conv" / "convT"; op = output_padding; cin / cout logical channels; weights in torch's layout."""
+
+    def __init__(self, kind, k, s, p, cin, cout, op=0):
+        self.kind, self.k, self.s, self.p, self.cin, self.cout, self.op = kind, k, s, p, cin, cout, op
+        self.tr = kind == "convT"
+
+    def out_hw(self, H, W):
+        k, s, p = self.k, self.s, self.p
+        if self.tr:
+            return (H - 1) * s - 2 * p + k + self.op, (W - 1) * s - 2 * p + k + self.op
+        return (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+
+    def wshape(self, cin=None, cout=None):
+        cin, cout = cin or self.cin, cout or self.cout
+        return (cin, cout, self.k, self.k) if self.tr else (cout, cin, self.k, self.k)
+
+    def tap(self, w, ky, kx):
+        """[cout, cin] matrix of a tap."""
+        return w[:, :, ky, kx].t() if self.tr else w[:, :, ky, kx]
+
+    def pairs(self, kk, n_in, n_out):
+        """(input slice, output slice) tap kk joins along one axis, or None."""
+        s, p = self.s, self.p
+        lo = max(0, -((kk - p) // s))
+        hi = min((n_in if self.tr else n_out) - 1, ((n_out if self.tr else n_in) - 1 + p - kk) // s)
+        if hi < lo:
+            return None
+        a, b = slice(lo, hi + 1), slice(lo * s + kk - p, hi * s + kk - p + 1, s)
+        return (a, b) if self.tr else (b, a)
+
+    def taps(self, H, W):
+        Ho, Wo = self.out_hw(H, W)
+        for ky in range(self.k):
+            py = self.pairs(ky, H, Ho)
+            for kx in range(self.k):
+                px = self.pairs(kx, W, Wo)
+                if py is not None and px is not None:
+                    yield ky, kx, (py[0], px[0]), (py[1], px[1])
+
+
+def forward(L, a, w, only=None):
+    """a [cin, H, W], w torch layout, float64 -> [cout, Ho, Wo] without bias.  only = (ky, kx): that tap's contribution alone."""
+    H, W = a.shape[1:]
+    out = torch.zeros((w.shape[1] if L.tr else w.shape[0],) + L.out_hw(H, W), dtype=torch.float64)
+    for ky, kx, i, o in L.taps(H, W):
+        if only is None or only == (ky, kx):
+            out[:, o[0], o[1]] += torch.einsum("oc,chw->ohw", L.tap(w, ky, kx), a[:, i[0], i[1]])
+    return out
+
+
+def dgrad(L, dy, w, H, W, only=None):
+    """dy [cout, Ho, Wo] -> the gradient of forward() with respect to a, [cin, H, W]."""
+    din = torch.zeros((w.shape[0] if L.tr else w.shape[1], H, W), dtype=torch.float64)
+    for ky, kx, i, o in L.taps(H, W):
+        if only is None or only == (ky, kx):
+            din[:, i[0], i[1]] += torch.einsum("oc,ohw->chw", L.tap(w, ky, kx), dy[:, o[0], o[1]])
+    return din
+
+
+def wgrad(L, a, dy):
+    """-> the gradient of forward() with respect to w, torch layout."""
+    H, W = a.shape[1:]
+    dw = torch.zeros(L.wshape(a.shape[0], dy.shape[0]), dtype=torch.float64)
+    for ky, kx, i, o in L.taps(H, W):
+        m = torch.einsum("ohw,chw->oc", dy[:, o[0], o[1]], a[:, i[0], i[1]])
+        dw[:, :, ky, kx] = m.t() if L.tr else m
+    return dw
+
+
+def _ones(*shape):
+    return torch.ones(shape, dtype=torch.float64)
+
+
+def count_fwd(L, H, W):
+    """taps in bounds x stored input channels, per output pixel [1, Ho, Wo]."""
+    one = Layer(L.kind, L.k, L.s, L.p, 1, 1, L.op)
+    return forward(one, _ones(1, H, W), _ones(1, 1, L.k, L.k)) * pad4(L.cin)
+
+
+def count_dgrad(L, H, W):
+    one = Layer(L.kind, L.k, L.s, L.p, 1, 1, L.op)
+    return dgrad(one, _ones(1, *L.out_hw(H, W)), _ones(1, 1, L.k, L.k), H, W) * pad4(L.cout)
+
+
+def count_wgrad(L, H, W):
+    """pixels per tap, [1, 1, k, k]."""
+    one = Layer(L.kind, L.k, L.s, L.p, 1, 1, L.op)
+    return wgrad(one, _ones(1, H, W), _ones(1, *L.out_hw(H, W)))
+
+
+# ---- the prologue ---------------------------------------------------------------------------------------------------------------------
+def stats_of(x):
+    """double[2 Cs]: sums, then sums of squares, of an fp32 [C, H, W] tensor as the kernels read them."""
+    C, Cs = x.shape[0], pad4(x.shape[0])
+    st = torch.zeros(2 * Cs, dtype=torch.float64)
+    xd = x.double()
+    st[:C], st[Cs: Cs + C] = xd.sum((1, 2)), (xd * xd).sum((1, 2))
+    return st
+
+
+def scale_shift(x, st, gamma, beta):
+    """(mean, rstd, sc, sh) in fp32 as sg_mean_rstd and the kernels' prologues form them."""
+    C, Cs = x.shape[0], st.numel() // 2
+    n = x.shape[1] * x.shape[2]
+    m = st[:C] / n
+    var = (st[Cs: Cs + C] / n - m * m).clamp_min(0.0)
+    mean, rstd = m.float(), (1.0 / torch.sqrt(var + float(np.float32(1e-5)))).float()
+    g = gamma.float() if gamma is not None else torch.ones(C)
+    b = beta.float() if beta is not None else torch.zeros(C)
+    sc = g * rstd
+    return mean, rstd, sc, b - mean * sc
+
+
+def prologue_terms(x, st, gamma, beta):
+    """A' = |x sc| + |sh| + |mean sc|: what the roundings of the prologue are relative to."""
+    mean, _, sc, sh = scale_shift(x, st, gamma, beta)
+    return (x.double() * sc.double().view(-1, 1, 1)).abs() + (sh.double().abs() + (mean.double() * sc.double()).abs()).view(-1, 1, 1)
+
+
+def prologue(x, norm, act, gamma=None, beta=None):
+    """x fp32 [C, H, W] -> (a, A, y): the fp32 prologue output and its magnitude companion as float64, and the fp32 pre-activation
+    value whose sign the activation reads."""
+    st = stats_of(x) if norm else None
+    n = x.shape[1] * x.shape[2]
+    a = PM._prologue(x[None], st, gamma, beta, bool(norm), act, n)[0]
+    y = PM._prologue(x[None], st, gamma, beta, bool(norm), 0, n)[0]
+    if not norm:
+        return a.double(), a.double().abs(), y
+    A = prologue_terms(x, st, gamma, beta)
+    f = torch.where(y > 0, torch.ones_like(A), torch.full_like(A, NEG[act]))
+    return a.double(), A * f, y
+
+
+def act_grad(x, norm, act, gamma=None, beta=None):
+    """(f, xhat, y) of the backward-data epilogue: f = act'(y), y = gamma xhat + beta, xhat = (x - mean) rstd, all fp32 as in
+    sg_conv_c4_body; without statistics xhat = y = x."""
+    if norm:
+        mean, rstd, _, _ = scale_shift(x, stats_of(x), gamma, beta)
+        xhat = (x.float() - mean.view(-1, 1, 1)) * rstd.view(-1, 1, 1)
+        g = gamma.float() if gamma is not None else torch.ones(x.shape[0])
+        b = beta.float() if beta is not None else torch.zeros(x.shape[0])
+        y = g.view(-1, 1, 1) * xhat + b.view(-1, 1, 1)
+    else:
+        xhat = y = x.float()
+    f = torch.where(y > 0, torch.ones_like(y), torch.full_like(y, NEG[act])).double()
+    return f, xhat.double(), y
+
+
+def margin(y):
+    """min |y| / max |y|: the activation's sign is safe from rounding while this stays above MASK_MARGIN."""
+    y = y.double().abs()
+    return float(y.min() / y.max())
+
+
+# ---- the operations: (ref, M, L) --------------------------------------------------------------------------------------------------------
+def _bound(Lc, c_a, M_a, c_A=0, M_A=0.0):
+    """(L + c_a) u M_a + c_A u M_A"""
+    n = float(torch.as_tensor(Lc).max()) + c_a + c_A
+    assert n <= L_MAX, n
+    return (Lc + c_a) * U * M_a + c_A * U * M_A
+
+
+def op_forward(L, x, w, bias=None, norm=None, act=0, gamma=None, beta=None, tanh=False):
+    """-> dict(ref, bound, pre, pre_bound, y): ref = [tanh](conv(prologue(x)) + bias); pre = before tanh (what the statistics sum)."""
+    a, A, y = prologue(x, norm, act, gamma, beta)
+    pre, M, MA = forward(L, a, w.double()), forward(L, a.abs(), w.double().abs()), forward(L, A, w.double().abs())
+    if bias is not None:
+        ab = bias.double().abs().view(-1, 1, 1)
+        pre, M, MA = pre + bias.double().view(-1, 1, 1), M + ab, MA + ab
+    b = _bound(count_fwd(L, *x.shape[1:]), CA_FWD, M, C_PRO, MA)
+    r = dict(pre=pre, pre_bound=b, ref=pre, bound=b, M=M, MA=MA, y=y, a=a)
+    if tanh:
+        r["ref"] = torch.tanh(pre)
+        r["bound"] = b + 4 * U * r["ref"].abs()
+    return r
+
+
+def op_dgrad(L, dy, w, H, W, x=None, norm=None, act=0, gamma=None, beta=None, prev=None):
+    """-> dict(ref, bound, xhat, y): ref = act'(norm(x)) * conv^T(dy) [+ prev]."""
+    ref, M = dgrad(L, dy.double(), w.double(), H, W), dgrad(L, dy.double().abs(), w.double().abs(), H, W)
+    r = dict(y=None, xhat=None)
+    if x is not None:
+        f, r["xhat"], r["y"] = act_grad(x, norm, act, gamma, beta)
+        ref, M = ref * f, M * f
+    r["own"], r["own_bound"] = ref, _bound(count_dgrad(L, H, W), C0_DGRAD, M)      # what the norm-backward sums add up
+    if prev is not None:
+        ref, M = ref + prev.double(), M + prev.double().abs()
+    r["ref"], r["bound"], r["M"] = ref, _bound(count_dgrad(L, H, W), C0_DGRAD, M), M
+    return r
+
+
+def op_wgrad(L, probs, prev_w=None, prev_b=None):
+    """probs: [(x, dy, norm, act, gamma, beta)] sharing one dw / dbias -> dict(dw, dw_bound, db, db_bound, ys)."""
+    dw = M = MA = Lw = db = Mb = Lb = 0
+    ys = []
+    for x, dy, norm, act, gamma, beta in probs:
+        a, A, y = prologue(x, norm, act, gamma, beta)
+        ys.append(y)
+        dw, M, Lw = dw + wgrad(L, a, dy.double()), M + wgrad(L, a.abs(), dy.double().abs()), Lw + count_wgrad(L, *x.shape[1:])
+        MA = MA + wgrad(L, A, dy.double().abs())
+        db, Mb, Lb = db + dy.double().sum((1, 2)), Mb + dy.double().abs().sum((1, 2)), Lb + dy.shape[1] * dy.shape[2]
+    if prev_w is not None:
+        dw, M, MA = dw + prev_w.double(), M + prev_w.double().abs(), MA + prev_w.double().abs()
+    if prev_b is not None:
+        db, Mb = db + prev_b.double(), Mb + prev_b.double().abs()
+    return dict(dw=dw, dw_bound=_bound(Lw, CA_WGRAD, M, C_PRO, MA), db=db, db_bound=_bound(float(Lb), C0_DBIAS, Mb), ys=ys, M=M, MA=MA, L=Lw)
+
+
+def bound_sum(v, b, w=None):
+    """Bound on |fp64 sum of the kernel's values - sum of the reference's| over the pixels of each channel ([C, H, W] inputs): the
+    element bounds summed and N 2^-53 sum |v| for the additions; w (xhat): the summed quantity is fl32(v w)."""
+    N = v.shape[1] * v.shape[2]
+    if w is None:
+        return b.sum((1, 2)) + N * 2.0 ** -53 * (v.abs() + b).sum((1, 2))
+    t = (v.abs() + b) * w.abs()
+    return (b * w.abs() + U * t).sum((1, 2)) + N * 2.0 ** -53 * t.sum((1, 2))
+
+
+def bound_sumsq(v, b):
+    N = v.shape[1] * v.shape[2]
+    return (2 * v.abs() * b + b * b).sum((1, 2)) + N * 2.0 ** -53 * ((v.abs() + b) ** 2).sum((1, 2))
+
+
+def ring2(H, W):
+    """mask of the outermost two rows and columns."""
+    m = np.ones((H, W), dtype=bool)
+    if H > 4 and W > 4:
+        m[2:-2, 2:-2] = False
+    return m
