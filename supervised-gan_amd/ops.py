@@ -1132,13 +1132,7 @@ def as_nhwc(t: torch.Tensor) -> torch.Tensor:
 # of them only enqueue; `metric_err` is the one word the kernels raise when they had to give up on a pixel.
 # ------------------------------------------------------------------------------------------------
 _metric_err = {}
-_rand_ws = {}
-_vinfo_ws = {}
-_thin_ws = {}
-_region_ws = {}
-_object_ws = {}
-_edt_ws = {}
-_boundary_ws = {}
+_metric_ws = {}       # (C symbol of the size query, H, W, device index) -> the int64 scratch of that size
 REGION_COLS = 16      # int64 per row of a region table (include/sgan_hip.h, sgan_region_stats)
 # acc_i / counts_out and acc_f / sums_out of object_match_accumulate (SGAN_OBJ_* of include/sgan_hip.h); TP_k: matches at IoU > (10 + k) / 20
 OBJECT_COUNTS = tuple('TP_%d' % k for k in range(10)) + ('N_t', 'N_s', 'images', 'SEGn', 'zero14', 'zero15')
@@ -1170,6 +1164,33 @@ def check_metric_err(device):
         e.zero_()
         raise L.SganError(f"segmentation metric kernels gave up on part of their input (flags {code:#x}: 1 = union-find bound, "
                           "2 = pair table full, 4 / 8 = label out of range, 16 = thinning budget ran out, 32 = region table full); the accumulated values are incomplete")
+
+
+def _metric_workspace(symbol, H, W, device):
+    """The scratch whose byte count the C function `symbol` reports for H x W maps, made once per (symbol, H, W, device)."""
+    key = (symbol, H, W, device.index)
+    ws = _metric_ws.get(key)
+    if ws is None:
+        nbytes = getattr(L.lib(), symbol)(H, W)
+        if nbytes < 0:
+            raise L.SganError(f"{symbol}({H}, {W}): {L.lib().sgan_last_error().decode()}")
+        ws = _metric_ws[key] = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
+    return ws
+
+
+def _label_pair(t_maps, s_maps, what):
+    """The check every counting call makes of its two int32 [H, W] maps on one device; returns (H, W, device)."""
+    H, W = t_maps.shape
+    dev = t_maps.device
+    require_gpu(t_maps, what)
+    for t in (t_maps, s_maps):
+        assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (H, W) and t.device == dev, (t.shape, t.dtype)
+    return H, W, dev
+
+
+def _is_acc(a, dtype, n, dev):
+    """An optional accumulator / output of a metric call: None, or n contiguous elements of dtype on dev."""
+    return a is None or (a.dtype == dtype and a.is_contiguous() and a.numel() == n and a.device == dev)
 
 
 def _plane(t, what):
@@ -1222,14 +1243,7 @@ def border_weight(labels, radius, w0, sigma, bmap=None, d1sq=None, d2sq=None):
 
 def thin_workspace(H, W, device):
     """The scratch of thin for H x W planes (change counters and two byte masks), cached per (H, W, device) like rand_f_workspace."""
-    key = (H, W, device.index)
-    ws = _thin_ws.get(key)
-    if ws is None:
-        nbytes = L.lib().sgan_thin_workspace(H, W)
-        if nbytes < 0:
-            raise L.SganError(f"sgan_thin_workspace({H}, {W}): {L.lib().sgan_last_error().decode()}")
-        ws = _thin_ws[key] = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
-    return ws
+    return _metric_workspace("sgan_thin_workspace", H, W, device)
 
 
 def thin(plane, out=None, max_num_iter=None, iters_out=None, workspace=None):
@@ -1244,7 +1258,7 @@ def thin(plane, out=None, max_num_iter=None, iters_out=None, workspace=None):
     if out is None:
         out = torch.empty((H, W), dtype=torch.float32, device=dev)
     assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == H * W and out.device == dev
-    assert iters_out is None or (iters_out.dtype == torch.int32 and iters_out.numel() == 1 and iters_out.device == dev)
+    assert _is_acc(iters_out, torch.int32, 1, dev)
     ws = thin_workspace(H, W, dev) if workspace is None else workspace
     L.check(L.lib().sgan_thin(_ptr(plane), plane.stride(1), H, W, _ptr(out), 0 if max_num_iter is None else int(max_num_iter), _ptr(ws),
                               ws.numel() * ws.element_size(), _ptr(iters_out), _ptr(metric_err(dev)), _stream()), "sgan_thin")
@@ -1253,14 +1267,7 @@ def thin(plane, out=None, max_num_iter=None, iters_out=None, workspace=None):
 
 def region_stats_workspace(H, W, device):
     """The scratch of region_stats for H x W maps (block counts, ranks and the staging rows), cached per (H, W, device)."""
-    key = (H, W, device.index)
-    ws = _region_ws.get(key)
-    if ws is None:
-        nbytes = L.lib().sgan_region_stats_workspace(H, W)
-        if nbytes < 0:
-            raise L.SganError(f"sgan_region_stats_workspace({H}, {W}): {L.lib().sgan_last_error().decode()}")
-        ws = _region_ws[key] = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
-    return ws
+    return _metric_workspace("sgan_region_stats_workspace", H, W, device)
 
 
 def region_stats(labels, table, cursor, workspace=None):
@@ -1284,27 +1291,15 @@ def region_stats(labels, table, cursor, workspace=None):
 
 def rand_f_workspace(H, W, device):
     """The scratch of rand_f_accumulate for H x W maps, cached per (H, W, device); the kernels zero it themselves."""
-    key = (H, W, device.index)
-    ws = _rand_ws.get(key)
-    if ws is None:
-        nbytes = L.lib().sgan_rand_f_workspace(H, W)
-        if nbytes < 0:
-            raise L.SganError(f"sgan_rand_f_workspace({H}, {W}): {L.lib().sgan_last_error().decode()}")
-        ws = _rand_ws[key] = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
-    return ws
+    return _metric_workspace("sgan_rand_f_workspace", H, W, device)
 
 
 def rand_f_accumulate(t_labels, s_labels, acc, sums_out=None, f_out=None, workspace=None):
     """acc[0] += Rand F-score of the labelling s_labels (prediction) against t_labels (truth), acc[1] += 1 (sgan_rand_f_accumulate);
     acc: float64[2] on the device.  sums_out (int64[4]: A2, B2, AB2, aux) and f_out (float64[1]) receive this pair's values."""
-    H, W = t_labels.shape
-    dev = t_labels.device
-    require_gpu(t_labels, "rand_f_accumulate")
-    for t in (t_labels, s_labels):
-        assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (H, W) and t.device == dev, (t.shape, t.dtype)
-    assert acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() == 2 and acc.device == dev
-    assert sums_out is None or (sums_out.dtype == torch.int64 and sums_out.is_contiguous() and sums_out.numel() == 4 and sums_out.device == dev)
-    assert f_out is None or (f_out.dtype == torch.float64 and f_out.numel() == 1 and f_out.device == dev)
+    H, W, dev = _label_pair(t_labels, s_labels, "rand_f_accumulate")
+    assert acc is not None and _is_acc(acc, torch.float64, 2, dev)
+    assert _is_acc(sums_out, torch.int64, 4, dev) and _is_acc(f_out, torch.float64, 1, dev)
     ws = rand_f_workspace(H, W, dev) if workspace is None else workspace
     L.check(L.lib().sgan_rand_f_accumulate(_ptr(t_labels), _ptr(s_labels), H, W, _ptr(ws), ws.numel() * ws.element_size(), _ptr(acc),
                                            _ptr(sums_out), _ptr(f_out), _ptr(metric_err(dev)), _stream()), "sgan_rand_f_accumulate")
@@ -1312,14 +1307,7 @@ def rand_f_accumulate(t_labels, s_labels, acc, sums_out=None, f_out=None, worksp
 
 def vinfo_workspace(H, W, device):
     """The scratch of vinfo_accumulate for H x W maps (the Rand layout and the VInfo sums behind it), cached per (H, W, device)."""
-    key = (H, W, device.index)
-    ws = _vinfo_ws.get(key)
-    if ws is None:
-        nbytes = L.lib().sgan_vinfo_workspace(H, W)
-        if nbytes < 0:
-            raise L.SganError(f"sgan_vinfo_workspace({H}, {W}): {L.lib().sgan_last_error().decode()}")
-        ws = _vinfo_ws[key] = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
-    return ws
+    return _metric_workspace("sgan_vinfo_workspace", H, W, device)
 
 
 def vinfo_accumulate(t_labels, s_labels, acc, acc_rand=None, parts_out=None, workspace=None):
@@ -1327,16 +1315,9 @@ def vinfo_accumulate(t_labels, s_labels, acc, acc_rand=None, parts_out=None, wor
     (truth), acc[1] += 1 (sgan_vinfo_accumulate); acc: float64[2] on the device.  acc_rand (float64[2]) receives what
     rand_f_accumulate would add for the same pair, from the same counting pass; parts_out (float64[11], VINFO_PARTS) this pair's
     values."""
-    H, W = t_labels.shape
-    dev = t_labels.device
-    require_gpu(t_labels, "vinfo_accumulate")
-    for t in (t_labels, s_labels):
-        assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (H, W) and t.device == dev, (t.shape, t.dtype)
-    for a in (acc, acc_rand):
-        assert a is None or (a.dtype == torch.float64 and a.is_contiguous() and a.numel() == 2 and a.device == dev)
-    assert acc is not None
-    assert parts_out is None or (parts_out.dtype == torch.float64 and parts_out.is_contiguous() and parts_out.numel() == len(VINFO_PARTS)
-                                 and parts_out.device == dev)
+    H, W, dev = _label_pair(t_labels, s_labels, "vinfo_accumulate")
+    assert acc is not None and _is_acc(acc, torch.float64, 2, dev) and _is_acc(acc_rand, torch.float64, 2, dev)
+    assert _is_acc(parts_out, torch.float64, len(VINFO_PARTS), dev)
     ws = vinfo_workspace(H, W, dev) if workspace is None else workspace
     L.check(L.lib().sgan_vinfo_accumulate(_ptr(t_labels), _ptr(s_labels), H, W, _ptr(ws), ws.numel() * ws.element_size(), _ptr(acc),
                                           _ptr(acc_rand), _ptr(parts_out), _ptr(metric_err(dev)), _stream()), "sgan_vinfo_accumulate")
@@ -1345,14 +1326,7 @@ def vinfo_accumulate(t_labels, s_labels, acc, acc_rand=None, parts_out=None, wor
 def object_match_workspace(H, W, device):
     """The scratch of object_match_accumulate for H x W maps (a staging block, the pair table and the counters), cached per
     (H, W, device) like vinfo_workspace; the kernels zero it themselves."""
-    key = (H, W, device.index)
-    ws = _object_ws.get(key)
-    if ws is None:
-        nbytes = L.lib().sgan_object_match_workspace(H, W)
-        if nbytes < 0:
-            raise L.SganError(f"sgan_object_match_workspace({H}, {W}): {L.lib().sgan_last_error().decode()}")
-        ws = _object_ws[key] = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
-    return ws
+    return _metric_workspace("sgan_object_match_workspace", H, W, device)
 
 
 def object_match_accumulate(t_labels, s_labels, acc_i, acc_f, min_area=1, counts_out=None, sums_out=None, workspace=None):
@@ -1361,15 +1335,10 @@ def object_match_accumulate(t_labels, s_labels, acc_i, acc_f, min_area=1, counts
     OBJECT_SUMS: SIoU, SSEG), both on the device and zeroed by the caller once (sgan_object_match_accumulate).  Regions smaller than
     min_area count as absent.  counts_out (int64[16]) and sums_out (float64[2]) receive this pair's contribution alone.  Only
     enqueues; util.object_match_counts is the host yardstick and util.object_scores derives ObjF1, ObjAP, SEG and PQ."""
-    H, W = t_labels.shape
-    dev = t_labels.device
-    require_gpu(t_labels, "object_match_accumulate")
-    for t in (t_labels, s_labels):
-        assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (H, W) and t.device == dev, (t.shape, t.dtype)
-    for a, dtype, n in ((acc_i, torch.int64, len(OBJECT_COUNTS)), (acc_f, torch.float64, len(OBJECT_SUMS)),
-                        (counts_out, torch.int64, len(OBJECT_COUNTS)), (sums_out, torch.float64, len(OBJECT_SUMS))):
-        assert a is None or (a.dtype == dtype and a.is_contiguous() and a.numel() == n and a.device == dev)
+    H, W, dev = _label_pair(t_labels, s_labels, "object_match_accumulate")
     assert acc_i is not None and acc_f is not None
+    assert all(_is_acc(a, torch.int64, len(OBJECT_COUNTS), dev) for a in (acc_i, counts_out))
+    assert all(_is_acc(a, torch.float64, len(OBJECT_SUMS), dev) for a in (acc_f, sums_out))
     ws = object_match_workspace(H, W, dev) if workspace is None else workspace
     L.check(L.lib().sgan_object_match_accumulate(_ptr(t_labels), _ptr(s_labels), H, W, int(min_area), _ptr(ws),
                                                  ws.numel() * ws.element_size(), _ptr(acc_i), _ptr(acc_f), _ptr(counts_out),
@@ -1379,14 +1348,7 @@ def object_match_accumulate(t_labels, s_labels, acc_i, acc_f, min_area=1, counts
 def edt_workspace(H, W, device):
     """The scratch of edt_sq for H x W planes (the wall counter, the column masks and the g^2 plane), cached per (H, W, device) like
     thin_workspace; the kernels initialise what they use."""
-    key = (H, W, device.index)
-    ws = _edt_ws.get(key)
-    if ws is None:
-        nbytes = L.lib().sgan_edt_workspace(H, W)
-        if nbytes < 0:
-            raise L.SganError(f"sgan_edt_workspace({H}, {W}): {L.lib().sgan_last_error().decode()}")
-        ws = _edt_ws[key] = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
-    return ws
+    return _metric_workspace("sgan_edt_workspace", H, W, device)
 
 
 def edt_sq(plane, out=None, workspace=None):
@@ -1408,14 +1370,7 @@ def edt_sq(plane, out=None, workspace=None):
 
 def boundary_workspace(H, W, device):
     """The scratch of boundary_accumulate for H x W maps (one slot of partial counts per workgroup), cached per (H, W, device)."""
-    key = (H, W, device.index)
-    ws = _boundary_ws.get(key)
-    if ws is None:
-        nbytes = L.lib().sgan_boundary_workspace(H, W)
-        if nbytes < 0:
-            raise L.SganError(f"sgan_boundary_workspace({H}, {W}): {L.lib().sgan_last_error().decode()}")
-        ws = _boundary_ws[key] = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
-    return ws
+    return _metric_workspace("sgan_boundary_workspace", H, W, device)
 
 
 def boundary_accumulate(t_dsq, s_dsq, acc_i, acc_f, counts_out=None, sums_out=None, workspace=None):
@@ -1425,15 +1380,10 @@ def boundary_accumulate(t_dsq, s_dsq, acc_i, acc_f, counts_out=None, sums_out=No
     on the device and zeroed by the caller once (sgan_boundary_accumulate).  counts_out (int64[80]) and sums_out (float64[4]) receive
     this pair's contribution alone.  Only enqueues; util.boundary_counts is the host yardstick and util.boundary_scores derives
     BoundF, HausD and ASSD."""
-    H, W = t_dsq.shape
-    dev = t_dsq.device
-    require_gpu(t_dsq, "boundary_accumulate")
-    for t in (t_dsq, s_dsq):
-        assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (H, W) and t.device == dev, (t.shape, t.dtype)
-    for a, dtype, n in ((acc_i, torch.int64, len(BOUNDARY_COUNTS)), (acc_f, torch.float64, len(BOUNDARY_SUMS)),
-                        (counts_out, torch.int64, len(BOUNDARY_COUNTS)), (sums_out, torch.float64, len(BOUNDARY_SUMS))):
-        assert a is None or (a.dtype == dtype and a.is_contiguous() and a.numel() == n and a.device == dev)
+    H, W, dev = _label_pair(t_dsq, s_dsq, "boundary_accumulate")
     assert acc_i is not None and acc_f is not None
+    assert all(_is_acc(a, torch.int64, len(BOUNDARY_COUNTS), dev) for a in (acc_i, counts_out))
+    assert all(_is_acc(a, torch.float64, len(BOUNDARY_SUMS), dev) for a in (acc_f, sums_out))
     ws = boundary_workspace(H, W, dev) if workspace is None else workspace
     L.check(L.lib().sgan_boundary_accumulate(_ptr(t_dsq), _ptr(s_dsq), H, W, _ptr(ws), ws.numel() * ws.element_size(), _ptr(acc_i),
                                              _ptr(acc_f), _ptr(counts_out), _ptr(sums_out), _ptr(metric_err(dev)), _stream()),

@@ -62,7 +62,7 @@ class BaseOptions:
         a('--n_layers_G_skip', type=int, default=-1)
         a('--weights', type=float, default=None, nargs='+')
         a('--use_sigmoid_ss', action='store_true')            # segmentation: sigmoid instead of softmax (base_options.py:55)
-        a('--which_metric', default=['None'], nargs='+')      # any of RandScore, VInfo, meanIU, RandScoreThin, VInfoThin, ObjF1, ObjAP, SEG, PQ, BoundF, HausD, ASSD (device accumulators, segm_model.py)
+        a('--which_metric', default=['None'], nargs='+')      # any of RandScore, VInfo, meanIU, RandScoreThin, VInfoThin, ObjF1, ObjAP, SEG, PQ, BoundF, HausD, ASSD (device accumulators, seg_metrics.py)
         a('--min_object_area', type=int, default=1)           # ObjF1 / ObjAP / SEG / PQ: regions with fewer pixels count as absent, on both sides
         a('--boundary_tolerance', type=int, default=2, choices=range(31), metavar='0..30')      # BoundF: a wall pixel within this many pixels of the other map's wall is matched
         a('--boundary_thin', action='store_true')             # BoundF / HausD / ASSD: thin the predicted wall to one-pixel lines first, as BSDS does; the truth is not thinned

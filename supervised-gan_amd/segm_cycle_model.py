@@ -4,7 +4,7 @@ prediction (recon_A, the cycle); generator loss = lambda_A CE(fake_B) + GAN(D2(f
 lambda_A_cycle L1(recon_A, real_A) with G1 stepped at lr1, G2 and D2 at lr2.
 
 Built on CGANCycleModel's plumbing (channel picking, latents, AdamGroups, checkpoints); the segmentation-specific pieces come from
-SegmentationModel's restatement (one-hot label, cross-entropy)."""
+SegmentationModel's restatement (one-hot label, cross-entropy) and the accuracies from the same SegMetricsMixin."""
 from collections import OrderedDict
 
 import torch
@@ -16,10 +16,11 @@ from .cgan_cycle_model import CGANCycleModel
 from .image_pool import ImagePool
 from .optim import AdamGroups, FusedAdam
 from .losses import sigmoid_channels, softmax_channels
+from .seg_metrics import SegMetrics, SegMetricsMixin
 from .segm_model import SegmentationModel, _identity
 
 
-class SegmentationCycleModel(CGANCycleModel):
+class SegmentationCycleModel(SegMetricsMixin, CGANCycleModel):
     def name(self):
         return 'SegmentationCycleModel'
 
@@ -80,7 +81,8 @@ class SegmentationCycleModel(CGANCycleModel):
                                           lr=opt.lr, betas=(opt.beta1, 0.999))
             self.optimizer_D2 = FusedAdam([p for d in self.netD2 for p in d.model.parameters()], lr=opt.lr2, betas=(opt.beta1, 0.999))
             self.optimizer_D2.param_groups[0]['name'] = 'D2'      # decay_three_rates: follows lr2
-        SegmentationModel.reset_accs(self)
+        self.seg_metrics = SegMetrics(opt, self.device, self.num_classes)
+        self.reset_accs()
 
     # ---- the step (:261-278): D2, then G1 and G2 together; G1 follows lr1, G2 and D2 follow lr2 (:313-332) ------------------------
     def step_stages(self):
@@ -159,17 +161,4 @@ class SegmentationCycleModel(CGANCycleModel):
         return OrderedDict([('image', self.real_A.detach()), ('label', three(self.real_B.detach() * 2 - 1)),
                             ('prediction', three(self.fake_B.detach() * 2 - 1))])
 
-    reset_accs = SegmentationModel.reset_accs
-    _acc_buffers = SegmentationModel._acc_buffers
-    accum_accs = SegmentationModel.accum_accs
-    compute_current_Rand_score = SegmentationModel.compute_current_Rand_score
-    _label_boundary_maps = SegmentationModel._label_boundary_maps
-    compute_current_VInfo = SegmentationModel.compute_current_VInfo
-    compute_current_object_matches = SegmentationModel.compute_current_object_matches
-    get_object_counts = SegmentationModel.get_object_counts
-    compute_current_boundary = SegmentationModel.compute_current_boundary
-    get_boundary_counts = SegmentationModel.get_boundary_counts
-    compute_current_thinned_scores = SegmentationModel.compute_current_thinned_scores
-    compute_current_accuracy = SegmentationModel.compute_current_accuracy
-    get_current_accs = SegmentationModel.get_current_accs
     compute_cross_entropy_loss = SegmentationModel.compute_cross_entropy_loss      # test_ss.py: sets loss_G_CE

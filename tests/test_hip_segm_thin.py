@@ -125,10 +125,13 @@ def test_without_the_new_names_nothing_is_added(tmp_path):
     for data in SyntheticDataset(opt, 1):
         model.set_input(data)
         model.optimize_parameters()
-    ops._thin_ws.clear()
+    thin_ws = lambda: [k for k in ops._metric_ws if k[0] == "sgan_thin_workspace"]      # noqa: E731
+    for k in thin_ws():
+        del ops._metric_ws[k]
     model.accum_accs()
     assert list(model.get_current_accs()) == ["RandScore", "VInfo", "meanIU"]
-    assert getattr(model, "_acc_thin", None) is None and getattr(model, "_thin_plane", None) is None and not ops._thin_ws
+    m = model.seg_metrics
+    assert sorted(m.acc) == ["conf", "rand", "vinfo"] and sorted(m.planes) == ["pred_labels", "truth_labels"] and not thin_ws()
 
 
 def test_segmentation_cycle_borrows_the_thinned_scores(tmp_path):
@@ -157,3 +160,55 @@ def test_segmentation_cycle_borrows_the_thinned_scores(tmp_path):
     print("cycle: RandScoreThin %r host %r, VInfoThin %r host %r" % (float(accs["RandScoreThin"]), float(r[0]), float(accs["VInfoThin"]), float(v[0])))
     assert math.isfinite(float(r[0])) and abs(float(accs["RandScoreThin"]) - float(r[0])) <= 1e-12
     assert _close(float(accs["VInfoThin"]), float(v[0]))
+
+
+def test_a_map_size_that_changes_between_calls(tmp_path):
+    """train_ss.py validates at --valSize: one trainer with all twelve names and --boundary_thin takes a 64 x 64 pair, a 32 x 32 pair
+    and the 64 x 64 pair again.  The pooled integers equal the sums of the host yardsticks over the three pairs, the Rand scores
+    agree to 1e-12 and the information scores to REL."""
+    from supervised_gan_amd import ops, util
+    from supervised_gan_amd.models import create_model
+    from supervised_gan_amd.options import TrainOptions
+    from supervised_gan_amd.synthetic_data import SyntheticDataset
+    _need_gpu()
+    names = ALL + list(util.OBJECT_METRICS) + list(util.BOUNDARY_METRICS)
+    assert len(names) == 12
+    opt = TrainOptions().parse(_net_argv(tmp_path, names, "resize") + _TRAIN + ["--boundary_thin"], save=False, verbose=False)
+    model = create_model(opt)
+    for data in SyntheticDataset(opt, 1):
+        model.set_input(data)
+        model.optimize_parameters()
+    big = [model.fake_B.detach().clone(), model.real_B.detach().clone(), model.logit.detach().clone(), model.label.clone()]
+    small = [t[..., 16:48, 16:48].contiguous() for t in big]
+    pairs = [big, small, big]
+    for model.fake_B, model.real_B, model.logit, model.label in pairs:
+        model.accum_accs()
+    accs = model.get_current_accs()
+    assert list(accs) == ["RandScore", "VInfo", "meanIU", "RandScoreThin", "VInfoThin"] + list(util.OBJECT_METRICS) + list(util.BOUNDARY_METRICS)
+    assert model.numAveragedImages == 3 and model.numAveragedPixels == 2 * 64 * 64 + 32 * 32
+    obj, bnd, conf = np.zeros(16, dtype=np.int64), np.zeros(80, dtype=np.int64), np.zeros((2, 2), dtype=np.int64)
+    host = {k: [] for k in ("RandScore", "VInfo", "RandScoreThin", "VInfoThin")}
+    for fb, rb, logit, label in pairs:
+        s, t = fb[0, 0].cpu().numpy(), rb[0, 0].cpu().numpy()
+        obj += util.object_match_counts(s, t, opt.min_object_area)[0]
+        c = util.boundary_counts(util.thin(s > 0.5)[0], t)[0]
+        bnd[:70] += c[:70]
+        bnd[70:72] = np.maximum(bnd[70:72], c[70:72])            # the two largest distances are kept, not summed
+        pred = logit[0].cpu().numpy().argmax(axis=0)
+        conf += np.bincount(label[0].cpu().numpy().ravel() * 2 + pred.ravel(), minlength=4).reshape(2, 2)
+        host["RandScore"].append(float(util.compute_Rand_F_scores(s, t)[0]))
+        host["VInfo"].append(float(util.compute_VInfo_scores(s, t)[0]))
+        r, v = util.compute_thinned_scores(s, t)
+        host["RandScoreThin"].append(float(r[0]))
+        host["VInfoThin"].append(float(v[0]))
+    for k, vals in host.items():
+        print("%s device %r host %r (%r)" % (k, float(accs[k]), float(np.mean(vals)), vals))
+    assert all(math.isfinite(v) for vals in host.values() for v in vals)
+    pooled_obj, pooled_bnd = model.get_object_counts(), model.get_boundary_counts()
+    assert [pooled_obj[k] for k in ops.OBJECT_COUNTS] == obj.tolist() and obj[12] == 3 and obj[10] > 0
+    assert [pooled_bnd[k] for k in ops.BOUNDARY_COUNTS] == bnd.tolist() and bnd[66] == 3 and bnd[65] > 0
+    assert np.array_equal(model.confusion, conf)
+    for k in ("RandScore", "RandScoreThin"):
+        assert abs(float(accs[k]) - float(np.mean(host[k]))) <= 1e-12, k
+    for k in ("VInfo", "VInfoThin"):
+        assert _close(float(accs[k]), float(np.mean(host[k]))), k

@@ -260,7 +260,7 @@ def main(argv=None):
             if "RandScore" in got:
                 assert abs(got["RandScore"] - state["rand"][-1]) < 1e-9, (got, state["rand"][-1])
             out[name] = {"device_kernels": stats(dev_ms), "device_enqueue_host_side": stats(enq_ms), "host_path": stats(host_ms),
-                         "regions_truth": int(torch.unique(model._acc_labels[0]).numel())}
+                         "regions_truth": int(torch.unique(model.seg_metrics.truth_labels).numel())}
             out[name].update({k: float(v) for k, v in got.items()})
             if "VInfo" in got:
                 want = float(compute_VInfo_scores(model.fake_B.detach()[0, 0].cpu().numpy(), model.real_B.detach()[0, 0].cpu().numpy())[0])
