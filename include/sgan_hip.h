@@ -119,9 +119,12 @@ const char* sgan_last_error(void);
 /* name of the kernel template instantiation the calling thread's last sgan_conv_* call launched
  * (matches the name rocprofv3 reports) -- lets a benchmark attribute time and flops per kernel */
 const char* sgan_last_kernel(void);
-/* what that name leaves out, for the kernels of the layers with a 4-stored-channel side; other launches leave it as it was, so read
+/* what that name leaves out, for the kernels of the layers with a 4-stored-channel side and the exact-fp32 MFMA kernels; other launches leave it as it was, so read
  * it right after the call it belongs to: "NB2 RB4 EPI gy1" (sg_conv_c4_kernel), "NR2 BKC1" (sg_conv_small_n_kernel),
- * "nsplit 3,1" per problem (sg_wgrad_thin_kernel), "DK0 RB4 nsplit 1" (sg_bwd_thin_pair_kernel), "tiles 12" (sg_conv_scatter4_kernel) */
+ * "nsplit 3,1" per problem (sg_wgrad_thin_kernel), "DK0 RB4 nsplit 1" (sg_bwd_thin_pair_kernel), "tiles 12" (sg_conv_scatter4_kernel);
+ * and for the exact-fp32 MFMA kernels: "ks8 KW2 PRO1" (sg_igemm_kernel: the K split that ran, wave groups per workgroup, prologue;
+ * " noslab" appended when a planned split found no workspace and ran unsplit), "PRO0 per4 nsplit 13,4,1" (sg_wgrad_kernel: prologue,
+ * 32-pixel chunks per workgroup the split aims at, pixel split per problem) */
 const char* sgan_last_variant(void);
 int sgan_stat_replicas(void);     /* SGAN_STAT_REPLICAS of the built library: statistics arenas must hold this many copies */
 /* The explicit device of the boundary (SURVEY 8b "Threading": backward is called from autograd worker threads that did not

@@ -1142,7 +1142,8 @@ static int sg_launch_igemm(SgIgemmParams& P, hipStream_t st, float* ws, int64_t 
     if (tiles == 0) return SGAN_OK;
     int ks = sg_plan_ksplit(P, BM, BN);
     const int64_t slab = (int64_t)P.q[0].Hout * P.q[0].Wout * P.N;
-    if (ks > 1 && (!ws || ws_bytes < (int64_t)ks * slab * 4)) ks = 1;   // no workspace: unsplit (still correct)
+    const bool noslab = ks > 1 && (!ws || ws_bytes < (int64_t)ks * slab * 4);
+    if (noslab) ks = 1;   // no workspace: unsplit (still correct)
     P.ksplit = ks;
     P.slab = ks > 1 ? ws : nullptr;
     P.slab_stride = slab;
@@ -1174,6 +1175,8 @@ static int sg_launch_igemm(SgIgemmParams& P, hipStream_t st, float* ws, int64_t 
     else
         g_sgan_last_kernel = (BM == 64 && BN == 32) ? "sg_igemm_kernel<64,32,2,2,false>" : BM == 64 ? "sg_igemm_kernel<64,64,2,2,false>" : BN == 64 ? "sg_igemm_kernel<128,64,2,2,false>"
                              : BN == 32 ? "sg_igemm_kernel<128,32,4,1,false>" : "sg_igemm_kernel<128,16,4,1,false>";
+    // sgan_last_variant(): what the name does not tell -- the K split, the wave groups, the prologue, a split that found no workspace
+    snprintf(g_sgan_last_variant, sizeof(g_sgan_last_variant), "ks%d KW%d PRO%d%s", ks, kw, pro ? 1 : 0, noslab ? " noslab" : "");
     sg_prof_end(st, g_sgan_last_kernel);
     if (ks > 1) return sg_launch_splitk_epilogue(P, st);
     return SGAN_OK;

@@ -318,6 +318,7 @@ __global__ __launch_bounds__(256) void sg_wgrad_kernel(const SgWgradParams G) {
 }
 
 static inline int sgw_cdiv(int a, int b) { return (a + b - 1) / b; }
+static void sg_thin_variant(const SgWgradParams& P, const char* prefix);      // "<prefix>nsplit a,b,.." (below)
 
 template <int BCO, int BKC, int WGC, int WGK>
 static int sg_launch_wgrad(SgWgradParams& P, hipStream_t st) {
@@ -361,6 +362,11 @@ static int sg_launch_wgrad(SgWgradParams& P, hipStream_t st) {
     SGAN_LAUNCH_CHECK();
     g_sgan_last_kernel = BCO == 64 ? "sg_wgrad_kernel<64,64,2,2>" : BCO == 32 ? "sg_wgrad_kernel<32,64,1,4>"
                                                                             : "sg_wgrad_kernel<16,128,1,4>";
+    {   // sgan_last_variant(): the prologue, the chunks per workgroup the split aims at, the pixel split of every problem
+        char prefix[32];
+        snprintf(prefix, sizeof(prefix), "PRO%d per%d ", pro ? 1 : 0, per);
+        sg_thin_variant(P, prefix);
+    }
     sg_prof_end(st, g_sgan_last_kernel);
     return SGAN_OK;
 }

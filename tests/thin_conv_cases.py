@@ -28,13 +28,14 @@ def THIN(mb, form):
 class Case:
     """op: fwd / dgrad / wgrad.  norm, act: the prologue (fwd, wgrad) or the forward tensor's norm of the backward-data epilogue
     (dgrad, with x=True); stats: result statistics (fwd) or the two norm-backward sums (dgrad); accum: pre-filled output (dgrad) /
-    pre-filled dw and dbias (wgrad); wt: backward-data reads the transposed weight copy; env: per-call knobs."""
+    pre-filled dw and dbias (wgrad); wt: backward-data reads the transposed weight copy; env: per-call knobs; math: the arithmetic
+    mode the row is launched in (None: whatever is current -- the kernels of this table do not read it)."""
 
     def __init__(self, name, op, kernel, layer, sizes, norm=None, act=0, bias=False, tanh=False, stats=False, accum=False, x=False,
-                 wt=True, env=None, variant=None):
+                 wt=True, env=None, variant=None, math=None):
         self.name, self.op, self.kernel, self.layer, self.sizes = name, op, kernel, layer, sizes
         self.norm, self.act, self.bias, self.tanh, self.stats, self.accum, self.x, self.wt = norm, act, bias, tanh, stats, accum, x, wt
-        self.env, self.variant = env or {}, variant
+        self.env, self.variant, self.math = env or {}, variant, math
 
     def __repr__(self):
         return self.name

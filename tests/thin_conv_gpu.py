@@ -1,5 +1,6 @@
-"""What tests/test_hip_thin_conv.py and tests/test_hip_thin_wgrad.py share: the rows of tests/thin_conv_cases.py turned into job lists
-in NaN-guarded storage, and the checks of what a launch left behind against tests/thin_conv_ref.py."""
+"""What tests/test_hip_thin_conv.py, tests/test_hip_thin_wgrad.py, tests/test_hip_wide_conv.py and tests/test_hip_wide_wgrad.py share:
+the rows of tests/thin_conv_cases.py and tests/wide_conv_cases.py turned into job lists in NaN-guarded storage, and the checks of what a
+launch left behind against tests/thin_conv_ref.py."""
 import numpy as np
 import torch
 
@@ -92,8 +93,9 @@ def sums_held(st, C, refs, bounds, what, key):
 
 
 # ---- forward --------------------------------------------------------------------------------------------------------------------------
-def build_fwd(ops, case, G):
-    d, L = K.data(case), case.layer
+def build_fwd(ops, case, G, key=None):
+    """key: what the worst ratios are filed under (default: the row's kernel)."""
+    d, L, key = K.data(case), case.layer, key or case.kernel
     wm, _ = weights(ops, d["w"], L.tr, G)
     bb = G(pad_vec(d["b"])) if case.bias else None
     gam, bet = _affine(case, d, G)
@@ -106,19 +108,19 @@ def build_fwd(ops, case, G):
 
     def check():
         for i, ((ob, ost), ref) in enumerate(zip(outs, K.reference(case))):
-            held(from_buf(ob, L.cout)[0], ref["ref"], ref["bound"], f"{case.name}[{i}] forward", case.kernel)
+            held(from_buf(ob, L.cout)[0], ref["ref"], ref["bound"], f"{case.name}[{i}] forward", key)
             assert pad4(L.cout) == L.cout or float(ob[..., L.cout:].abs().max()) == 0.0, "padded channels must stay exactly zero"
             if ost is not None:
                 v, b = ref["pre"], ref["pre_bound"]
                 sums_held(ost, L.cout, (v.sum((1, 2)), (v * v).sum((1, 2))), (R.bound_sum(v, b), R.bound_sumsq(v, b)), f"{case.name}[{i}] statistics",
-                          case.kernel)
+                          key)
     return jobs, check
 
 
 # ---- backward-data --------------------------------------------------------------------------------------------------------------------
-def build_dgrad(ops, case, G, accum=None):
+def build_dgrad(ops, case, G, accum=None, key=None):
     """accum=False: the same jobs without accumulate into NaN-filled outputs (the accumulate rows run both)."""
-    d, L = K.data(case), case.layer
+    d, L, key = K.data(case), case.layer, key or case.kernel
     acc = case.accum if accum is None else accum
     wm, wt = weights(ops, d["w"], L.tr, G)
     gam, bet = _affine(case, d, G) if case.x else (None, None)
@@ -134,17 +136,17 @@ def build_dgrad(ops, case, G, accum=None):
     def check():
         for i, ((din, sums), ref) in enumerate(zip(outs, K.reference(case))):
             r, b = (ref["ref"], ref["bound"]) if acc else (ref["own"], ref["own_bound"])
-            held(from_buf(din, L.cin)[0], r, b, f"{case.name}[{i}] backward-data" + ("" if acc == case.accum else " (no accumulate)"), case.kernel)
+            held(from_buf(din, L.cin)[0], r, b, f"{case.name}[{i}] backward-data" + ("" if acc == case.accum else " (no accumulate)"), key)
             assert pad4(L.cin) == L.cin or float(din[..., L.cin:].abs().max()) == 0.0, "padded channels must stay exactly zero"
             if sums is not None:
                 v, vb, xh = ref["own"], ref["own_bound"], ref["xhat"]
                 sums_held(sums, L.cin, (v.sum((1, 2)), (v * xh).sum((1, 2))), (R.bound_sum(v, vb), R.bound_sum(v, vb, xh)),
-                          f"{case.name}[{i}] norm-backward", case.kernel)
+                          f"{case.name}[{i}] norm-backward", key)
     return jobs, check, outs
 
 
 # ---- backward-weight ------------------------------------------------------------------------------------------------------------------
-def build_wgrad(ops, case, G):
+def build_wgrad(ops, case, G, key=None):
     d, L = K.data(case), case.layer
     zero_w = torch.zeros(L.wshape())
     dw = G(master_weight(d["prev_w"] if case.accum else zero_w, L.tr).clone())
@@ -153,13 +155,13 @@ def build_wgrad(ops, case, G):
     jobs = [(_desc(ops, L, p), G(to_buf(p["x"][None])), _norm(ops, case, d, p, G, gam, bet), G(to_buf(p["dy"][None])), dw, db) for p in d["probs"]]
 
     def check():
-        ref, key = K.reference(case), case.kernel or K.PAIR + " dw"
+        ref, key_ = K.reference(case), key or case.kernel or K.PAIR + " dw"
         assert bool(torch.isfinite(dw).all())
-        held(from_master(dw, L.k, L.cin, L.cout, L.tr).double(), ref["dw"], ref["dw_bound"], f"{case.name} backward-weight", key)
+        held(from_master(dw, L.k, L.cin, L.cout, L.tr).double(), ref["dw"], ref["dw_bound"], f"{case.name} backward-weight", key_)
         m = dw.detach().cpu().view(L.k, L.k, pad4(L.cout), pad4(L.cin))
         assert float(m[:, :, L.cout:].abs().max() if pad4(L.cout) > L.cout else 0.0) == 0.0, "padded rows of dw must stay exactly zero"
         assert float(m[..., L.cin:].abs().max() if pad4(L.cin) > L.cin else 0.0) == 0.0, "padded columns of dw must stay exactly zero"
         if db is not None:
-            held(db.cpu()[: L.cout].double(), ref["db"], ref["db_bound"], f"{case.name} bias gradient", key + " dbias")
+            held(db.cpu()[: L.cout].double(), ref["db"], ref["db_bound"], f"{case.name} bias gradient", key_ + " dbias")
             assert pad4(L.cout) == L.cout or float(db[L.cout:].abs().max()) == 0.0
     return jobs, check
