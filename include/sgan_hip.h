@@ -909,6 +909,45 @@ int64_t sgan_boundary_workspace(int32_t H, int32_t W);
 int sgan_boundary_accumulate(const int32_t* t_dsq, const int32_t* s_dsq, int32_t H, int32_t W, void* workspace, int64_t workspace_bytes,
                              int64_t* acc_i, double* acc_f, int64_t* counts_out, double* sums_out, int32_t* dev_err, void* stream);
 
+/* ---- cleaning the prediction: disk closing, speck removal and small-cell filling of a wall map before it is scored ----------------
+ * What every pipeline that reports the scores above does to its thresholded wall map first: close pin-hole gaps in the membrane
+ * (one missing wall pixel merges two cells), drop wall specks inside cells, fill regions too small to be a cell.
+ * util.clean_wall is the NumPy / scipy restatement these entries are tested against.
+ *
+ * The plane is read as sgan_ccl_label reads it: pixel (y, x) at plane[(y * W + x) * pix_stride], wall when x > 0.5 (a NaN and an
+ * exact 0.5 are not wall).  Three stages in this order, each skipped when its parameter is 0, all in integers:
+ *   1. close, close_rsq >= 1 (a squared Euclidean radius):  D = {p : 0 <= edt_sq(wall)(p) <= close_rsq};
+ *      wall1 = {p : edt_sq(~D)(p) > close_rsq, or ~D is empty}.  Only pixels inside the image take part: the dilation counts the
+ *      outside as free and the erosion counts it as wall, so the closing never eats the wall at the image border and wall1 contains
+ *      wall; an empty wall stays empty.  With the disk {dy^2 + dx^2 <= close_rsq} this is scipy.ndimage.binary_dilation(border_value
+ *      = 0) followed by binary_erosion(border_value = 1).
+ *   2. specks, min_wall >= 1:  the 8-connected components of wall1 with fewer than min_wall pixels become free: wall2.
+ *   3. small cells, min_cell >= 1:  the 8-connected components of ~wall2 with fewer than min_cell pixels become wall: out.
+ *   out is a dense float [H * W] plane of 0.0 / 1.0, which sgan_ccl_label, sgan_thin and sgan_edt_sq read as it lies; it may not
+ *   alias the plane.  With all three parameters 0 it is the thresholded plane.
+ *   acc (optional, int64[SGAN_CLEAN_COUNTS], caller-owned on the device, zeroed by the caller once, pooled over a dataset):
+ *     [0] += pixels set by the closing;  [1] += wall components removed;  [2] += wall pixels removed;  [3] += cells filled;
+ *     [4] += cell pixels filled;  [5] += 1 (images).  Exact integers, identical in every scheduling order.
+ *
+ * sgan_clean_workspace: bytes of the workspace sgan_clean_wall needs for an H x W plane (< 0: bad shape).
+ * sgan_clean_wall: the launch sequence depends on (H, W) and on which of the three parameters are nonzero, on nothing else; nothing
+ *   is read back and nothing is decided on the host, so the call captures into a hipGraph and replays on any other plane.
+ *   Closing: sgan_edt_sq, a threshold pass that writes the complement of D, sgan_edt_sq of that, a threshold pass that writes wall1
+ *   (and its complement when stage 2 follows) and counts the pixels the input did not have.  Each area filter: sgan_ccl_label (of
+ *   the complement plane for the specks, whose free components are the wall's), the count table zeroed, a count pass that adds
+ *   every pixel to count[label - 1] -- the label IS 1 + the component's smallest raster index, so it indexes an int32 [H W] table
+ *   directly; a wave merges its 64 pixels by label with ballots and issues one atomic per distinct label -- and an apply pass that
+ *   writes the filtered plane and counts the components (at their root pixel) and pixels that changed side.  Without a stage, one
+ *   pass copies the thresholded plane.
+ *   The workspace (16-byte aligned) may hold anything on entry.  dev_err as sgan_ccl_label: required; bit 1 from the labelling, bit 4
+ *   for a label out of range.  Shapes as sgan_edt_sq: H, W <= 32768 and H W < 2^30.  Returns 1, the reason in sgan_last_error and
+ *   nothing launched, for a null required pointer (acc alone is optional), a bad shape, a pixel stride < 1, a negative parameter,
+ *   close_rsq > 4096, out == plane, and a short or misaligned workspace. */
+#define SGAN_CLEAN_COUNTS 6
+int64_t sgan_clean_workspace(int32_t H, int32_t W);
+int sgan_clean_wall(const float* plane, int64_t pix_stride, int32_t H, int32_t W, int32_t close_rsq, int32_t min_wall, int32_t min_cell,
+                    float* out, int64_t* acc, void* workspace, int64_t workspace_bytes, int32_t* dev_err, void* stream);
+
 /* ---- region statistics on the device (shape features of generated against real images: shape_stats.py) --------------------------
  * The reference's paper judges a generator by shape features of its cells and mitochondria; its repository holds only MATLAB that
  * loads precomputed features (experiments/plots).  These entries measure every region of a label map; util.region_table is the

@@ -170,6 +170,8 @@ SIGNATURES = {
     "sgan_edt_sq": [_P, _L, _I, _I, _P, _P, _L, _P, _P],
     "sgan_boundary_workspace": [_I, _I],
     "sgan_boundary_accumulate": [_P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _P, _P],
+    "sgan_clean_workspace": [_I, _I],
+    "sgan_clean_wall": [_P, _L, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P],
     "sgan_confusion_accumulate": [_P, _I, _I, _P, _P, _I, _I, _L, _P, _P, _P],
     "sgan_thin_workspace": [_I, _I],
     "sgan_thin": [_P, _L, _I, _I, _P, _I, _P, _L, _P, _P, _P],
@@ -186,7 +188,7 @@ SIGNATURES = {
 RESTYPES = {"sgan_last_variant": C.c_char_p, "sgan_image_resize_workspace": C.c_int64, "sgan_rand_f_workspace": C.c_int64,
             "sgan_vinfo_workspace": C.c_int64, "sgan_thin_workspace": C.c_int64,
             "sgan_region_stats_workspace": C.c_int64, "sgan_object_match_workspace": C.c_int64,
-            "sgan_edt_workspace": C.c_int64, "sgan_boundary_workspace": C.c_int64}      # everything else returns an int status
+            "sgan_edt_workspace": C.c_int64, "sgan_boundary_workspace": C.c_int64, "sgan_clean_workspace": C.c_int64}      # everything else returns an int status
 _lib = None
 
 

@@ -1144,6 +1144,7 @@ BOUNDARY_COUNTS = (tuple('hist_s_%d' % k for k in range(BOUNDARY_BINS)) + tuple(
                    + ('N_s', 'N_t', 'images', 'haus_images', 'defined_s', 'defined_t', 'max_dsq_s', 'max_dsq_t')
                    + tuple('zero%d' % k for k in range(72, 80)))
 BOUNDARY_SUMS = ('sum_d_s', 'sum_d_t', 'sum_haus', 'zero3')
+CLEAN_COUNTS = ('closed_pixels', 'wall_components_removed', 'wall_pixels_removed', 'cells_filled', 'cell_pixels_filled', 'images')      # acc of clean_wall (SGAN_CLEAN_COUNTS)
 VINFO_PARTS = ('SA', 'SB', 'SAB', 'aux', 'm', 'H_S', 'H_T', 'I', 'VInfo', 'split', 'merge')      # parts_out of vinfo_accumulate
 
 
@@ -1388,6 +1389,31 @@ def boundary_accumulate(t_dsq, s_dsq, acc_i, acc_f, counts_out=None, sums_out=No
     L.check(L.lib().sgan_boundary_accumulate(_ptr(t_dsq), _ptr(s_dsq), H, W, _ptr(ws), ws.numel() * ws.element_size(), _ptr(acc_i),
                                              _ptr(acc_f), _ptr(counts_out), _ptr(sums_out), _ptr(metric_err(dev)), _stream()),
             "sgan_boundary_accumulate")
+
+
+def clean_workspace(H, W, device):
+    """The scratch of clean_wall for H x W planes (edt_sq's workspace, one int32 plane for dsq / labels, the area table and the
+    complement plane), cached per (H, W, device) like edt_workspace; the kernels initialise what they use."""
+    return _metric_workspace("sgan_clean_workspace", H, W, device)
+
+
+def clean_wall(plane, close_rsq=0, min_wall=0, min_cell=0, out=None, acc=None, workspace=None):
+    """The cleaned wall map of the pixels of `plane` [H, W] that are > 0.5 (sgan_clean_wall; util.clean_wall is the host yardstick):
+    closed with the disk dy^2 + dx^2 <= close_rsq, wall components below min_wall pixels dropped, regions below min_cell pixels
+    filled, each stage skipped at 0.  float32 [H, W] of 0.0 / 1.0, which ccl_label, thin and edt_sq read as it lies.  acc (int64[6]
+    on the device, CLEAN_COUNTS) is added to.  Only enqueues -- the launch sequence depends on the shape and on which parameters are
+    nonzero alone -- and reads `plane` in place when its rows are W pixel strides apart."""
+    plane = _plane(plane, "clean_wall")
+    H, W = plane.shape
+    dev = plane.device
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.float32, device=dev)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == H * W and out.device == dev
+    assert _is_acc(acc, torch.int64, len(CLEAN_COUNTS), dev)
+    ws = clean_workspace(H, W, dev) if workspace is None else workspace
+    L.check(L.lib().sgan_clean_wall(_ptr(plane), plane.stride(1), H, W, int(close_rsq), int(min_wall), int(min_cell), _ptr(out), _ptr(acc),
+                                    _ptr(ws), ws.numel() * ws.element_size(), _ptr(metric_err(dev)), _stream()), "sgan_clean_wall")
+    return out
 
 
 def confusion_accumulate(x, C, conf, label=None, y=None, add_background=False):

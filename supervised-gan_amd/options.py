@@ -64,6 +64,9 @@ class BaseOptions:
         a('--use_sigmoid_ss', action='store_true')            # segmentation: sigmoid instead of softmax (base_options.py:55)
         a('--which_metric', default=['None'], nargs='+')      # any of RandScore, VInfo, meanIU, RandScoreThin, VInfoThin, ObjF1, ObjAP, SEG, PQ, BoundF, HausD, ASSD (device accumulators, seg_metrics.py)
         a('--min_object_area', type=int, default=1)           # ObjF1 / ObjAP / SEG / PQ: regions with fewer pixels count as absent, on both sides
+        a('--clean_close', type=float, default=0.0)           # clean the predicted wall before the label-based scores: close gaps with a disk of this radius, close_rsq = floor(R * R); 1 = the 4-neighbour plus, 1.5 = the 3 x 3 box; at most 64
+        a('--clean_min_wall', type=int, default=0)            # ... then drop 8-connected wall components with fewer pixels than this
+        a('--clean_min_cell', type=int, default=0)            # ... then fill 8-connected regions with fewer pixels than this (seg_metrics.py; all three off: the raw thresholded map)
         a('--boundary_tolerance', type=int, default=2, choices=range(31), metavar='0..30')      # BoundF: a wall pixel within this many pixels of the other map's wall is matched
         a('--boundary_thin', action='store_true')             # BoundF / HausD / ASSD: thin the predicted wall to one-pixel lines first, as BSDS does; the truth is not thinned
         a('--add_background_onehot', action='store_true')
@@ -132,6 +135,7 @@ class BaseOptions:
         self.opt = self.parser.parse_args(args)
         self.opt.isTrain = self.isTrain
         check_border_options(self.opt)
+        check_clean_options(self.opt, self.parser)
         check_elastic_options(self.opt)
         if self.opt.math is not None:
             from . import ops
@@ -171,6 +175,26 @@ def check_border_options(opt):
         opt.border_radius = min(32, int(math.ceil(4 * sigma)))
     assert 1 <= opt.border_radius <= 32, "--border_radius: 1..32 (got %d)" % opt.border_radius
     assert opt.border_class >= 0, "--border_class: a class index (got %d)" % opt.border_class
+
+
+def check_clean_options(opt, parser=None):
+    """--clean_close R, --clean_min_wall N, --clean_min_cell N: none negative, R at most 64 (close_rsq = floor(R R) <= 4096, the
+    library's limit); refused at parse time."""
+    bad = None
+    if not 0.0 <= opt.clean_close <= 64.0:      # a NaN fails both comparisons
+        bad = "--clean_close: a radius of 0 .. 64 pixels (got %g)" % opt.clean_close
+    elif opt.clean_min_wall < 0 or opt.clean_min_cell < 0:
+        bad = "--clean_min_wall / --clean_min_cell: a pixel count, not negative (got %d / %d)" % (opt.clean_min_wall, opt.clean_min_cell)
+    if bad is not None:
+        if parser is not None:
+            parser.error(bad)
+        raise ValueError(bad)
+
+
+def clean_params(opt):
+    """(close_rsq, min_wall, min_cell) of ops.clean_wall from the --clean_* options; (0, 0, 0) for an options object without them."""
+    r = float(getattr(opt, 'clean_close', 0.0))
+    return int(math.floor(r * r)), int(getattr(opt, 'clean_min_wall', 0)), int(getattr(opt, 'clean_min_cell', 0))
 
 
 def check_elastic_options(opt):

@@ -9,7 +9,11 @@ class of --add_background_onehot comes last).  The reference (segm_model.py:299-
 whole 2-channel maps to a function that squeezes a channel axis of size one, which cannot run; this is our reading of that call
 ("Segmentation metrics on the device").  Batch 1, like every kernel of this path.  An image whose truth map has no free
 pixel scores NaN, and the NaN stays in the running sum until reset(), as in the reference's running mean; nothing on the host sees
-it before read()."""
+it before read().
+
+With --clean_close / --clean_min_wall / --clean_min_cell the predicted plane of every label-based score is the CLEANED wall map
+(ops.clean_wall: gaps closed with a disk, wall specks dropped, small regions filled), made once per accumulate().  meanIU and the
+confusion matrix stay on the logits: they are per-pixel class scores, and may be multi-class."""
 from collections import OrderedDict
 from functools import cached_property
 
@@ -17,6 +21,7 @@ import numpy as np
 import torch
 
 from . import ops, util
+from .options import clean_params
 
 # Every device accumulator: name, dtype, shape (k: the classes of the confusion matrix).  Each is made the first time a score adds
 # to it; reset(), read() and counts() walk this table.
@@ -30,6 +35,10 @@ ACCUMULATORS = (
     ('obj_f', torch.float64, (len(ops.OBJECT_SUMS),)),
     ('bnd_i', torch.int64, (len(ops.BOUNDARY_COUNTS),)),          # ops.boundary_accumulate's pooled counters
     ('bnd_f', torch.float64, (len(ops.BOUNDARY_SUMS),)),
+)
+# The counters of the cleaning stage, made only when a --clean_* option is set; beside ACCUMULATORS, and walked with it.
+CLEAN_ACCUMULATORS = (
+    ('clean_i', torch.int64, (len(ops.CLEAN_COUNTS),)),           # ops.clean_wall's pooled counters
 )
 COUNTS = {'objects': ('obj_i', 'obj_f', ops.OBJECT_COUNTS, ops.OBJECT_SUMS),
           'boundary': ('bnd_i', 'bnd_f', ops.BOUNDARY_COUNTS, ops.BOUNDARY_SUMS)}
@@ -49,7 +58,11 @@ class _Planes:
 
     @cached_property
     def s(self):
-        return self.fake_B.detach()[0, 0]
+        """The predicted plane every label-based score reads: channel 0 as it lies, or its cleaned wall map with a --clean_* option."""
+        clean = clean_params(self.m.opt)
+        if not any(clean):
+            return self.fake_B.detach()[0, 0]
+        return ops.clean_wall(self.fake_B.detach()[0, 0], *clean, out=self._store('cleaned', torch.float32), acc=self.m._acc('clean_i'))
 
     @cached_property
     def t(self):
@@ -94,7 +107,7 @@ class SegMetrics:
     def _acc(self, name):
         if name not in self.acc:
             k = self.num_classes + 1 if self.opt.add_background_onehot_acc else self.num_classes
-            dtype, shape = next((d, s(k) if callable(s) else s) for n, d, s in ACCUMULATORS if n == name)
+            dtype, shape = next((d, s(k) if callable(s) else s) for n, d, s in ACCUMULATORS + CLEAN_ACCUMULATORS if n == name)
             self.acc[name] = torch.zeros(shape, dtype=dtype, device=self.device)
         return self.acc[name]
 
@@ -110,6 +123,12 @@ class SegMetrics:
         """The label map of the truth as the last accumulate() that labelled it left it (int32 [H, W]), or None.  Read only."""
         return self.planes.get('truth_labels')
 
+    @property
+    def cleaned(self):
+        """The cleaned predicted wall map as the last accumulate() left it (float32 [H, W] of 0.0 / 1.0), or None without a --clean_*
+        option.  Read only."""
+        return self.planes.get('cleaned')
+
     def accumulate(self, fake_B, real_B, logit, label, which=None):
         """Adds the scores named by --which_metric (or `which`) for one prediction / truth pair to their accumulators:
 
@@ -119,7 +138,8 @@ class SegMetrics:
         ObjF1 .. PQ: which truth cell is found by which predicted cell at IoU > 0.5 .. 0.95 (ops.object_match_accumulate), regions
         below --min_object_area left out.  meanIU: conf[label, prediction] += 1 for every pixel (segm_model.py:309-331).
         BoundF .. ASSD: how far every predicted wall pixel lies from the true wall and every true wall pixel from the predicted one
-        (ops.boundary_accumulate)."""
+        (ops.boundary_accumulate).
+        With a --clean_* option all of these but meanIU read the cleaned prediction (ops.clean_wall, once per call)."""
         o = self.opt
         which = o.which_metric if which is None else which
         if any(k in which for k in SCORES if k != 'meanIU'):      # the scores of the label maps and of the walls
@@ -151,9 +171,16 @@ class SegMetrics:
             ops.rand_f_accumulate(t_labels, s_labels, self._acc(rand))
 
     def counts(self, which):
-        """The pooled numbers of 'objects' (the 16 integers of ops.OBJECT_COUNTS: TP_0 .. TP_9 at IoU > 0.5 .. 0.95, N_t, N_s, images,
+        """'clean': the six pooled integers of ops.CLEAN_COUNTS (pixels set by the closing, wall components / pixels removed, cells /
+        cell pixels filled, images).  Otherwise the pooled numbers of 'objects' (the 16 integers of ops.OBJECT_COUNTS: TP_0 .. TP_9 at IoU > 0.5 .. 0.95, N_t, N_s, images,
         SEGn; the two sums of ops.OBJECT_SUMS) or 'boundary' (the 80 integers of ops.BOUNDARY_COUNTS: the two histograms by distance
         bin, N_s, N_t, images, ...; the four sums of ops.BOUNDARY_SUMS) since reset(), as a dict.  Synchronises, like read()."""
+        if which == 'clean':
+            ints = [0] * len(ops.CLEAN_COUNTS)
+            if 'clean_i' in self.acc:
+                ops.check_metric_err(self.device)
+                ints = self.acc['clean_i'].cpu().tolist()
+            return OrderedDict(zip(ops.CLEAN_COUNTS, ints))
         acc_i, acc_f, names_i, names_f = COUNTS[which]
         ints, sums = [0] * len(names_i), [0.0] * len(names_f)
         if acc_i in self.acc:
@@ -166,7 +193,8 @@ class SegMetrics:
         order RandScore, VInfo, meanIU, RandScoreThin, VInfoThin, then ObjF1 / ObjAP / SEG / PQ (util.object_scores of the pooled
         counts), then BoundF / HausD / ASSD (util.boundary_scores at --boundary_tolerance).  Built for evaluation (test_ss.py) it also
         prints the pooled TP_k / N_t / N_s line when an object score was taken, and the boundary precision / recall / F at the
-        tolerances 0 .. 5 with the dataset's worst distance when a boundary score was."""
+        tolerances 0 .. 5 with the dataset's worst distance when a boundary score was, and the pooled counts of the cleaning stage
+        when a --clean_* option ran it."""
         o, v = self.opt, self.values
         if self.acc:
             ops.check_metric_err(self.device)
@@ -189,6 +217,10 @@ class SegMetrics:
                       % (' '.join('%.4f/%.4f/%.4f' % util.boundary_pr(bnd_i, tol) for tol in range(6)),
                          float(np.sqrt(float(max(bnd_i[bc('max_dsq_s')], bnd_i[bc('max_dsq_t')])))), bnd_i[bc('N_s')], bnd_i[bc('N_t')],
                          ', prediction thinned' if o.boundary_thin else ''))
+            if not o.isTrain and 'clean_i' in self.acc:
+                c = self.acc['clean_i'].cpu().tolist()
+                print('clean: closed %d pixels, removed %d wall components (%d pixels), filled %d cells (%d pixels) in %d images '
+                      '(close_rsq %d, min wall %d, min cell %d)' % (tuple(c) + clean_params(o)))
             conf = a['conf'].astype(np.float64)
             v['confusion'], v['numAveragedPixels'] = conf, int(conf.sum())
             rel, sel, tp = conf.sum(axis=1), conf.sum(axis=0), np.diag(conf)
@@ -225,3 +257,14 @@ class SegMetricsMixin:
 
     def get_boundary_counts(self):
         return self.seg_metrics.counts('boundary')
+
+    def get_clean_counts(self):
+        return self.seg_metrics.counts('clean')
+
+    def with_cleaned_visual(self, visuals):
+        """Built for evaluation with a --clean_* option: adds the wall map the label-based scores of the last accum_accs() were taken
+        on to the trainer's visuals as `fake_B_clean` ([1, 1, H, W] in [-1, 1]), so that test_ss.py's result page shows it."""
+        cleaned = self.seg_metrics.cleaned
+        if not self.opt.isTrain and any(clean_params(self.opt)) and cleaned is not None:
+            visuals['fake_B_clean'] = cleaned.detach()[None, None] * 2 - 1
+        return visuals

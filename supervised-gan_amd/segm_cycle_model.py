@@ -158,7 +158,7 @@ class SegmentationCycleModel(SegMetricsMixin, CGANCycleModel):
 
     def get_current_visuals(self, save_as_single_image=False):
         three = lambda t: t if t.shape[1] in (1, 3) else torch.cat([t, torch.zeros_like(t[:, :1])], 1)[:, :3]      # noqa: E731
-        return OrderedDict([('image', self.real_A.detach()), ('label', three(self.real_B.detach() * 2 - 1)),
-                            ('prediction', three(self.fake_B.detach() * 2 - 1))])
+        return self.with_cleaned_visual(OrderedDict([('image', self.real_A.detach()), ('label', three(self.real_B.detach() * 2 - 1)),
+                                                     ('prediction', three(self.fake_B.detach() * 2 - 1))]))
 
     compute_cross_entropy_loss = SegmentationModel.compute_cross_entropy_loss      # test_ss.py: sets loss_G_CE

@@ -507,6 +507,38 @@ def edt_sq(mask):
     return out.astype(np.int32)
 
 
+CLEAN_COUNTS = ('closed_pixels', 'wall_components_removed', 'wall_pixels_removed', 'cells_filled', 'cell_pixels_filled', 'images')
+
+
+def clean_wall(mask, close_rsq=0, min_wall=0, min_cell=0):
+    """The cleaned wall map (include/sgan_hip.h, "cleaning the prediction") of a [H, W] wall mask (bool, or a map thresholded at
+    > 0.5): (bool [H, W], counts int64[6] in CLEAN_COUNTS' order).  Three stages in this order, each skipped when its parameter is 0:
+    a closing with the disk dy^2 + dx^2 <= close_rsq from two thresholds of edt_sq (the dilation counts the outside of the image as
+    free, the erosion as wall); 8-connected wall components with fewer than min_wall pixels become free; 8-connected free components
+    with fewer than min_cell pixels become wall.  The host yardstick of ops.clean_wall; the trainers do not call it."""
+    from scipy import ndimage
+    wall = np.array(_wall_mask(mask), dtype=bool)
+    assert wall.ndim == 2 and close_rsq >= 0 and min_wall >= 0 and min_cell >= 0, (wall.shape, close_rsq, min_wall, min_cell)
+    counts = np.zeros(len(CLEAN_COUNTS), dtype=np.int64)
+    counts[5] = 1
+    if close_rsq > 0:
+        d = edt_sq(wall)
+        dilated = (d >= 0) & (d <= close_rsq)
+        e = edt_sq(~dilated)
+        closed = (e < 0) | (e > close_rsq)      # e < 0: nothing is left outside the dilation
+        counts[0] = int((closed & ~wall).sum())
+        wall = closed
+    for k, (min_area, of_wall) in enumerate(((min_wall, True), (min_cell, False))):
+        if min_area > 0:
+            labels, _ = ndimage.label(wall if of_wall else ~wall, structure=np.ones((3, 3)))
+            area = np.bincount(labels.ravel())
+            small = area < min_area
+            small[0] = False                    # label 0: the other side
+            counts[1 + 2 * k], counts[2 + 2 * k] = int(small.sum()), int(area[small].sum())
+            wall = wall & ~small[labels] if of_wall else wall | small[labels]
+    return wall, counts
+
+
 def boundary_bin(d):
     """The bin of a distance^2 (include/sgan_hip.h, "boundary scores"): k = ceil(sqrt(d)) in integers for 0 <= d <= 900, 31 beyond
     and for -1 (the other map has no wall)."""
