@@ -948,6 +948,33 @@ int64_t sgan_clean_workspace(int32_t H, int32_t W);
 int sgan_clean_wall(const float* plane, int64_t pix_stride, int32_t H, int32_t W, int32_t close_rsq, int32_t min_wall, int32_t min_cell,
                     float* out, int64_t* acc, void* workspace, int64_t workspace_bytes, int32_t* dev_err, void* stream);
 
+/* ---- whole-image inference: overlap tiles with blended seams, averaged over the 8 flips and rotations (not in the reference, whose
+ * test_ss.py scores one crop; the overlap-tile strategy of Ronneberger et al. 2015, section 2) ------------------------------------
+ * util.tile_plan / tile_window / prep_tile_ref / blend_tiles_ref are the NumPy restatement.  Per axis of length L: the
+ * padded domain is -M .. L + M - 1, mirrored into the image without repeating the edge; tiles of side T start at -M, -M + S, ... and
+ * the last at L + M - T; the integer window of a tile is w(i) = clamp(min(i + 1, T - i) - M, 0, R), zero in the margin M, a ramp of R
+ * pixels, then flat; a pass has the D4 element (flip, rot) of sgan_image_prep: horizontal flip, then rot x 90 degrees counter-clockwise.
+ *
+ * sgan_image_prep_tile: sgan_image_prep whose h x w window at (x0, y0) may reach up to H0 - 1 / W0 - 1 pixels outside the image (indices
+ *   reflected) and may be rectangular (then rot == 0).  The same bits as sgan_image_prep for a square window inside the image.  One
+ *   16-byte store per pixel when Cstore == 4, dst_ld is a multiple of 4 and dst is 16-byte aligned.
+ * sgan_tile_blend: one pass.  `logits` is the generator's raw output for the tile at (x0, y0) under (flip, rot), [T][T][ld] NHWC with C <= 4
+ *   logical channels; p = softmax over the C channels (mode SGAN_SEGHEAD_SOFTMAX, sgan_softmax_fwd's expression) or the sigmoid of each
+ *   (SGAN_SEGHEAD_SIGMOID, sgan_sigmoid_nhwc_fwd's).  For every pixel (Y, X) of the H x W `canvas` that the window shows with weight
+ *   w = w(Y - y0) w(X - x0) > 0: canvas[Y][X][c] = fmaf(w, p_c at the tile pixel that shows (Y, X), canvas[Y][X][c]).  Plain loads and
+ *   stores: a canvas pixel has one writer per launch, the stream orders the launches.  The caller zeroes the canvas before the first pass.
+ * sgan_tile_finish: prob = canvas / (float)(n_tta Wy[Y] Wx[X]) and logp = logf(max(prob, FLT_MIN)), n_tta 1 or 8; Wy [H], Wx [W] int32
+ *   in device memory (util.tile_plan).  Padding channels of both outputs are written as zeros.
+ * logits, canvas, prob, logp: pixel stride a multiple of 4 floats, 16-byte aligned.  Refused (status, nothing launched): C outside 1..4,
+ *   R outside 1..64, M < 0 or 2 M >= T, M > min(H, W) - 1, T > min(H, W) + 2 M, an origin outside -M .. L + M - T, a rotated rectangle,
+ *   a window one reflection cannot fold back, a null pointer, a side above 2^22. */
+int sgan_image_prep_tile(const unsigned char* img, int32_t H0, int32_t W0, int32_t x0, int32_t y0, int32_t h, int32_t w, int32_t flip,
+                         int32_t rot, float* dst, int32_t dst_ld, int32_t Cstore, void* stream);
+int sgan_tile_blend(const float* logits, int32_t ld, int32_t C, int32_t mode, int32_t x0, int32_t y0, int32_t T, int32_t M, int32_t R,
+                    int32_t flip, int32_t rot, float* canvas, int32_t canvas_ld, int32_t H, int32_t W, void* stream);
+int sgan_tile_finish(const float* canvas, int32_t canvas_ld, int32_t H, int32_t W, int32_t C, const int32_t* Wy, const int32_t* Wx,
+                     int32_t n_tta, float* prob, int32_t prob_ld, float* logp, int32_t logp_ld, void* stream);
+
 /* ---- region statistics on the device (shape features of generated against real images: shape_stats.py) --------------------------
  * The reference's paper judges a generator by shape features of its cells and mitochondria; its repository holds only MATLAB that
  * loads precomputed features (experiments/plots).  These entries measure every region of a label map; util.region_table is the

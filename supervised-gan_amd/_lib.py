@@ -172,6 +172,9 @@ SIGNATURES = {
     "sgan_boundary_accumulate": [_P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _P, _P],
     "sgan_clean_workspace": [_I, _I],
     "sgan_clean_wall": [_P, _L, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P],
+    "sgan_image_prep_tile": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P],
+    "sgan_tile_blend": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P],
+    "sgan_tile_finish": [_P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P, _I, _P],
     "sgan_confusion_accumulate": [_P, _I, _I, _P, _P, _I, _I, _L, _P, _P, _P],
     "sgan_thin_workspace": [_I, _I],
     "sgan_thin": [_P, _L, _I, _I, _P, _I, _P, _L, _P, _P, _P],

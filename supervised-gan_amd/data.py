@@ -11,7 +11,10 @@ here as x then y.
 
 `--elastic G SIGMA` (train options; not in the reference) deforms every training crop: the feeder draws the (G + 3)^2 control vectors
 of a smooth field after its other draws, uploads these few hundred floats, and the same single kernel gathers through the field
-(`sgan_image_prep_elastic`).  One field for both halves of an aligned pair, one per image otherwise."""
+(`sgan_image_prep_elastic`).  One field for both halves of an aligned pair, one per image otherwise.
+
+`--whole_image` / `--tta d4` (test options; not in the reference): the single-image feeder also yields the uint8 device image under
+'A_u8', and under `--whole_image` 'A' is the whole resized image, not a crop (`sgan_image_prep_tile`)."""
 import os
 import random
 
@@ -114,9 +117,30 @@ class SingleFolderDataset(_FolderDataset):
 
     def _device(self, index, img):
         path = self.paths[index]
+        if getattr(self.opt, 'tiling', False):
+            return self._device_tiled(img, path)
         draw = self._draw(img, path)
         A = self._prep(img, draw, self._draw_elastic())        # --elastic: the field after every other draw of the item
         return {'A': ops.logical_view(A, 3), 'A_paths': [path]}
+
+    def _device_tiled(self, img, path):
+        """Whole-image inference (test options, options.check_tile_options): 'A' as always, and under 'A_u8' the uint8 device image it
+        was made from, out of which SegmentationModel.test() cuts its tiles.  --whole_image: the whole image after the resize -- no
+        crop, no random draw, any aspect -- through image_prep_tile over the full window.  --tta d4 alone: today's crop, and its
+        window of the uint8 image."""
+        from .options import check_tile_options
+        opt = self.opt
+        if opt.whole_image:
+            w, h = self._resized_size(*img.size)
+            check_tile_options(opt, size=(h, w))
+            dev = self._resized(img, w, h)
+            return {'A': ops.logical_view(ops.image_prep_tile(dev, 0, 0, h, w, False, 0), 3), 'A_u8': dev, 'A_paths': [path]}
+        w, h, x0, y0, flip, rot = self._draw(img, path)
+        assert not flip and rot == 0, "--tta d4 makes the flips and rotations itself: an evaluation feeder draws none"
+        n = opt.fineSize
+        dev = self._resized(img, w, h)
+        return {'A': ops.logical_view(ops.image_prep(dev, x0, y0, n, False, 0), 3), 'A_u8': dev[y0: y0 + n, x0: x0 + n].contiguous(),
+                'A_paths': [path]}
 
     def _decode(self, path):
         from PIL import Image
@@ -153,12 +177,15 @@ class SingleFolderDataset(_FolderDataset):
         rot = random.randint(0, 3) if (opt.isTrain and not opt.no_rotate) else 0
         return w, h, x0, y0, flip, rot
 
-    def _prep(self, img, draw, ctrl=None):
-        w, h, x0, y0, flip, rot = draw
+    def _resized(self, img, w, h):
         dev = self._to_device(img)
         if (w, h) != img.size:
             dev = ops.image_resize(dev, w, h, "bilinear")      # Image.resize((w, h), BILINEAR), on the device
-        return self._image_prep(dev, x0, y0, self.opt.fineSize, flip, rot, ctrl)
+        return dev
+
+    def _prep(self, img, draw, ctrl=None):
+        w, h, x0, y0, flip, rot = draw
+        return self._image_prep(self._resized(img, w, h), x0, y0, self.opt.fineSize, flip, rot, ctrl)
 
 
 class UnalignedFolderDataset(SingleFolderDataset):

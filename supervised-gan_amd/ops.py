@@ -647,6 +647,51 @@ def image_prep_elastic(img_u8, x0, y0, n, flip, rot, ctrl, nearest_mask, out=Non
     return out
 
 
+def image_prep_tile(img_u8, x0, y0, h, w, flip, rot, out=None):
+    """image_prep whose h x w window at (x0, y0) may reach outside the image (indices reflected without repeating the edge, like
+    F.pad(mode='reflect')) and may be rectangular (rot 0 only): [H0, W0, 3] uint8 device tensor -> [h, w, 4] fp32 NHWC buffer
+    (sgan_image_prep_tile; util.prep_tile_ref is the host yardstick).  The tiles of whole-image inference, and with the full window
+    the whole image itself."""
+    require_gpu(img_u8, "image_prep_tile")
+    assert img_u8.dtype == torch.uint8 and img_u8.dim() == 3 and img_u8.shape[2] == 3 and img_u8.is_contiguous(), (img_u8.shape, img_u8.dtype)
+    h, w = int(h), int(w)
+    if out is None:
+        out = torch.empty((h, w, 4), dtype=torch.float32, device=img_u8.device)
+    assert out.shape[0] == h and out.shape[1] == w and out.stride(0) == w * out.stride(1), (out.shape, out.stride())
+    L.check(L.lib().sgan_image_prep_tile(_ptr(img_u8), img_u8.shape[0], img_u8.shape[1], int(x0), int(y0), h, w, int(bool(flip)), int(rot),
+                                         _ptr(_act(out)), out.stride(1), out.shape[2], _stream()), "sgan_image_prep_tile")
+    return out
+
+
+def tile_blend(logits, Creal, mode, x0, y0, M, R, flip, rot, canvas):
+    """One pass of whole-image inference: canvas[Y, X, c] += w(Y - y0) w(X - x0) p_c, p the softmax (mode SEGHEAD_SOFTMAX) or sigmoid
+    (SEGHEAD_SIGMOID) of the [T, T, Cs] NHWC `logits` the generator left for the tile at (x0, y0) under the D4 element (flip, rot),
+    gathered through the element's inverse (sgan_tile_blend; util.blend_tiles_ref is the host yardstick).  canvas: [H, W, 4] fp32,
+    zeroed by the caller before the first pass of an image."""
+    require_gpu(logits, "tile_blend")
+    require_gpu(canvas, "tile_blend")
+    T = logits.shape[0]
+    assert logits.shape[1] == T and logits.stride(0) == T * logits.stride(1), (logits.shape, logits.stride())
+    H, W, _ = canvas.shape
+    assert canvas.stride(0) == W * canvas.stride(1), (canvas.shape, canvas.stride())
+    L.check(L.lib().sgan_tile_blend(_ptr(_act(logits)), logits.stride(1), int(Creal), int(mode), int(x0), int(y0), T, int(M), int(R),
+                                    int(bool(flip)), int(rot), _ptr(_act(canvas)), canvas.stride(1), H, W, _stream()), "sgan_tile_blend")
+
+
+def tile_finish(canvas, Creal, Wy, Wx, n_tta, prob, logp):
+    """prob = canvas / (n_tta Wy[Y] Wx[X]), logp = log max(prob, FLT_MIN) (sgan_tile_finish); Wy [H], Wx [W]: device int32 vectors of
+    util.tile_plan; prob, logp: [H, W, 4] fp32 buffers (ops.logical_view hands them out as [1, C, H, W])."""
+    H, W, _ = canvas.shape
+    for t in (prob, logp):
+        require_gpu(t, "tile_finish")
+        assert t.shape[:2] == (H, W) and t.stride(0) == W * t.stride(1), (t.shape, t.stride())
+    assert canvas.stride(0) == W * canvas.stride(1), (canvas.shape, canvas.stride())
+    assert Wy.dtype == Wx.dtype == torch.int32 and Wy.is_cuda and Wx.is_cuda and Wy.is_contiguous() and Wx.is_contiguous()
+    assert Wy.numel() == H and Wx.numel() == W, (Wy.shape, Wx.shape, H, W)
+    L.check(L.lib().sgan_tile_finish(_ptr(_act(canvas)), canvas.stride(1), H, W, int(Creal), _ptr(Wy), _ptr(Wx), int(n_tta), _ptr(_act(prob)),
+                                     prob.stride(1), _ptr(_act(logp)), logp.stride(1), _stream()), "sgan_tile_finish")
+
+
 RESAMPLE = {"bilinear": 2, "bicubic": 3}      # Pillow's Image.BILINEAR / Image.BICUBIC
 
 

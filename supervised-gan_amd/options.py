@@ -137,6 +137,7 @@ class BaseOptions:
         check_border_options(self.opt)
         check_clean_options(self.opt, self.parser)
         check_elastic_options(self.opt)
+        check_tile_options(self.opt, self.parser)
         if self.opt.math is not None:
             from . import ops
             ops.set_math(self.opt.math)
@@ -195,6 +196,45 @@ def clean_params(opt):
     """(close_rsq, min_wall, min_cell) of ops.clean_wall from the --clean_* options; (0, 0, 0) for an options object without them."""
     r = float(getattr(opt, 'clean_close', 0.0))
     return int(math.floor(r * r)), int(getattr(opt, 'clean_min_wall', 0)), int(getattr(opt, 'clean_min_cell', 0))
+
+
+def check_tile_options(opt, parser=None, size=None):
+    """--whole_image / --tile T / --tile_margin M / --tile_ramp R / --tile_stride S / --tta (test options): whole-image inference by
+    overlapping tiles, averaged over the 8 flips and rotations under --tta d4 (util.tile_plan).  Fills in the defaults
+    (T = --fineSize, S = max(1, T - 2 M - R)) and leaves opt.tiling = is any of it on.  --tta d4 without --whole_image runs the feeder's
+    T x T crop as one tile: M = 0, R = 1, S = T.  Refuses what the geometry cannot cover, at parse time as far as the image is not
+    involved and, with `size` = (H, W), for an image (the feeder asks per file).  An options object without the flags (the training
+    drivers) has no tiling."""
+    from .util import tile_geometry_error
+    if not hasattr(opt, 'whole_image'):
+        opt.tiling = False
+        return
+    opt.tiling = bool(opt.whole_image or opt.tta == 'd4')
+    bad = None
+    if opt.tiling:
+        if opt.whole_image:
+            if opt.tile is None:
+                opt.tile = opt.fineSize
+            if opt.tile_stride is None:
+                opt.tile_stride = max(1, opt.tile - 2 * opt.tile_margin - opt.tile_ramp)
+        else:
+            opt.tile, opt.tile_margin, opt.tile_ramp, opt.tile_stride = opt.fineSize, 0, 1, opt.fineSize
+        T, M, R, S = opt.tile, opt.tile_margin, opt.tile_ramp, opt.tile_stride
+        if opt.dataroot == 'synthetic':
+            bad = "--whole_image / --tta d4 cut their tiles from the decoded uint8 image of an image folder; the synthetic feeder has none"
+        elif opt.dataset_mode != 'single':
+            bad = "--whole_image / --tta d4 read the single-image feeder (--dataset_mode single), got '%s'" % opt.dataset_mode
+        elif opt.model != 'segmentation':
+            bad = ("--whole_image / --tta d4 are built into SegmentationModel.test() (--model segmentation); the test() of --model %s "
+                   "runs another forward" % opt.model)
+        else:
+            bad = tile_geometry_error(None, T, M, R, S)
+            if bad is None and size is not None:
+                bad = tile_geometry_error(size[0], T, M, R, S, 'height') or tile_geometry_error(size[1], T, M, R, S, 'width')
+    if bad is not None:
+        if parser is not None:
+            parser.error(bad)
+        raise ValueError(bad)
 
 
 def check_elastic_options(opt):
@@ -298,4 +338,14 @@ class TestOptions(BaseOptions):
         a('--which_epoch', type=str, default='latest')
         a('--how_many', type=int, default=50)
         a('--save_as_single_image', action='store_true')
+        # whole-image inference of test_ss.py (not in the reference, which scores one crop per file): check_tile_options, DESIGN.md R21
+        a('--whole_image', action='store_true',
+          help='segmentation: predict the whole image (after the resize of --resize_or_crop, no crop) from overlapping tiles of the '
+               'mirrored image, their margins dropped and their overlaps blended')
+        a('--tile', type=int, default=None, help='side T of a tile (default --fineSize)')
+        a('--tile_margin', type=int, default=16, help='M: pixels at every side of a tile that are predicted but not used')
+        a('--tile_ramp', type=int, default=16, help='R: width of the linear ramp of the blending window behind the margin, 1..64')
+        a('--tile_stride', type=int, default=None, help='S: distance between tile origins, 1 .. T - 2 M (default T - 2 M - R, at least 1)')
+        a('--tta', type=str, default='none', choices=['none', 'd4'],
+          help='d4: average the prediction over the 8 flips and rotations of every tile; without --whole_image, of the one --fineSize crop')
         self.isTrain = False

@@ -15,9 +15,10 @@ from collections import OrderedDict
 
 import torch
 
-from . import networks, ops
+from . import networks, ops, util
 from .cgan_model import CGANModel
 from .losses import cross_entropy_logits, seg_head, sigmoid_channels, softmax_channels, weighted_bce
+from .options import check_tile_options
 from .seg_metrics import SegMetrics, SegMetricsMixin
 
 
@@ -53,6 +54,11 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
             assert opt.batchSize == 1 and self.device.type == 'cuda', "--border_weight: batch 1 on the device, like every kernel of this path"
         self.seg_metrics = SegMetrics(opt, self.device, self.num_classes)
         self.reset_accs()
+        self._tiling = not self.isTrain and getattr(opt, 'tiling', False)      # test(): whole-image inference (check_tile_options)
+        self._tile_src = self._tile_st = None                                  # the uint8 image of set_input(); plan and buffers
+        if self._tiling:
+            assert self.num_classes <= 4 and opt.batchSize == 1 and self.device.type == 'cuda', \
+                "--whole_image / --tta d4: at most 4 classes, batch 1, on the device"
 
     def _builds_netD(self, opt):
         return getattr(opt, 'which_model_netD', 'None') != 'None'
@@ -65,6 +71,7 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
         """segm_model.py:120-143: label channels rescaled to [0, 1], optional background class, index label = argmax."""
         CGANModel.set_input(self, input)
         self._one_hot_label()
+        self._tile_src = input.get('A_u8') if self._tiling else None
 
     def _one_hot_label(self):
         b = (self.input_B[:, :self.label_nc] + 1) / 2.0
@@ -130,7 +137,56 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
 
     def test(self):
         with torch.no_grad():
-            self.forward()
+            if self._tiling:
+                self._test_tiled()
+            else:
+                self.forward()
+
+    # ---- whole-image inference (--whole_image / --tta d4 of the test options; util.tile_plan) --------------------
+    def _tile_state(self, H, W):
+        """Plan and buffers of an H x W image; persistent, re-made when the size changes (like SegMetrics._plane)."""
+        st = self._tile_st
+        if st is None or st['hw'] != (H, W):
+            o, dev = self.opt, self.device
+            check_tile_options(o, size=(H, W))
+            oy, ox, Wy, Wx = util.tile_plan(H, W, o.tile, o.tile_margin, o.tile_ramp, o.tile_stride)
+            st = self._tile_st = {
+                'hw': (H, W), 'passes': util.tile_passes(oy, ox, o.tta == 'd4'),
+                'Wy': torch.tensor(Wy, dtype=torch.int32, device=dev), 'Wx': torch.tensor(Wx, dtype=torch.int32, device=dev),
+                'canvas': torch.empty((H, W, 4), dtype=torch.float32, device=dev), 'prob': torch.empty((H, W, 4), dtype=torch.float32, device=dev),
+                'logp': torch.empty((H, W, 4), dtype=torch.float32, device=dev),
+                'rgb': torch.empty((o.tile, o.tile, 4), dtype=torch.float32, device=dev),
+                'tile_A': torch.empty((o.tile, o.tile, ops.pad4(len(self.chnl_idx_input[0]))), dtype=torch.float32, device=dev)}
+        return st
+
+    def _test_tiled(self):
+        """The prediction of the whole image set_input() was given: per pass (tile-row, tile-column, flip, rot) one image_prep_tile from
+        the uint8 image, the channel pick of --which_channel, the generator with the latent forward() would draw, and one tile_blend
+        into the canvas; then one tile_finish.  Leaves fake_B = P and logit = log P at full size beside real_A / real_B / label, so the
+        cross-entropy (-log P[label]), the accuracies (argmax log P = argmax P) and the visuals read the whole image unchanged."""
+        o, u8 = self.opt, self._tile_src
+        assert u8 is not None, "--whole_image / --tta d4: the feeder did not hand over the uint8 image ('A_u8'; data.SingleFolderDataset does)"
+        H, W = u8.shape[:2]
+        assert tuple(self.input_A.shape[2:]) == (H, W), (self.input_A.shape, u8.shape)
+        st = self._tile_state(H, W)
+        self.real_A, self.real_B = self.input_A, self.input_B
+        mode = ops.SEGHEAD_SIGMOID if self.use_sigmoid_ss else ops.SEGHEAD_SOFTMAX
+        idx = self.chnl_idx_input[0]
+        run = idx == list(range(idx[0], idx[0] + len(idx)))
+        st['canvas'].zero_()
+        for y0, x0, flip, rot in st['passes']:
+            ops.image_prep_tile(u8, x0, y0, o.tile, o.tile, flip, rot, out=st['rgb'])
+            if run:
+                a = ops.logical_view(ops.slice_nhwc(st['rgb'], idx[0], len(idx), out=st['tile_A']), len(idx))
+            else:
+                a = ops.logical_view(st['rgb'], 3).index_select(1, self._chnl_dev[0])
+            self.noise = self._draw_noise()
+            z = self.netG.forward(a, self.noise, activation=_identity)
+            assert z.shape == (1, self.num_classes, o.tile, o.tile), z.shape
+            ops.tile_blend(ops.as_nhwc(z), self.num_classes, mode, x0, y0, o.tile_margin, o.tile_ramp, flip, rot, st['canvas'])
+        ops.tile_finish(st['canvas'], self.num_classes, st['Wy'], st['Wx'], 8 if o.tta == 'd4' else 1, st['prob'], st['logp'])
+        self.fake_B = ops.logical_view(st['prob'], self.num_classes)
+        self.logit = ops.logical_view(st['logp'], self.num_classes)
 
     # ---- losses -------------------------------------------------------------------------------
     def compute_cross_entropy_loss(self, weighted=False):

@@ -3,7 +3,9 @@ the Rand F-score of a binary segmentation, the information score (VInfo) that go
 thinning both scores are ranked after: `thin`, `compute_thinned_scores`), and the shape statistics of the regions of a map
 (`region_table`, the yardstick of the device's sgan_region_stats, and `region_props`, the features derived from its rows), and the
 border term of the U-Net loss (`border_weight_map`, the yardstick of the device's sgan_border_weight), and the elastic deformation of
-a training crop (`elastic_field`, `elastic_prep`, the yardsticks of the device's sgan_image_prep_elastic)."""
+a training crop (`elastic_field`, `elastic_prep`, the yardsticks of the device's sgan_image_prep_elastic), and the geometry of
+whole-image inference (`tile_plan`, `tile_window`, `prep_tile_ref`, `blend_tiles_ref`, the yardsticks of sgan_image_prep_tile /
+sgan_tile_blend / sgan_tile_finish)."""
 import os
 
 import numpy as np
@@ -234,7 +236,150 @@ def elastic_prep(img, x0, y0, n, flip, rot, ctrl, G, nearest_mask, field=None):
     return np.ascontiguousarray(t.transpose(2, 0, 1))
 
 
-REGION_COLS = ('area', 'xmin', 'xmax', 'ymin', 'ymax', 'sum_x', 'sum_y', 'sum_xx', 'sum_yy', 'sum_xy', 'boundary', 'root', 'image',
+# ---- whole-image inference: overlap tiles, blended seams, D4 averaging.  The geometry every layer reads: the options
+# check, the feeder, SegmentationModel.test() and the yardsticks of sgan_image_prep_tile / sgan_tile_blend / sgan_tile_finish ----------
+TILE_MAX_RAMP = 64
+
+
+def tile_geometry_error(L, T, M, R, S, axis='image'):
+    """None, or why tiles of side T with margin M, ramp R and stride S cannot cover an axis of length L (L None: the conditions that
+    do not involve the image)."""
+    if T < 1 or M < 0:
+        return "--tile T >= 1 and --tile_margin M >= 0 (got T %d, M %d)" % (T, M)
+    if not 1 <= R <= TILE_MAX_RAMP:
+        return "--tile_ramp: 1..%d pixels (got %d)" % (TILE_MAX_RAMP, R)
+    if not 1 <= S <= T - 2 * M:
+        return ("--tile_stride S must lie in 1 .. T - 2 M = %d, so that the non-margin parts of the tiles cover the image "
+                "(got S %d with T %d, M %d)" % (T - 2 * M, S, T, M))
+    if L is not None and M > L - 1:
+        return "--tile_margin %d: a reflection reaches at most %s length - 1 = %d pixels" % (M, axis, L - 1)
+    if L is not None and L + 2 * M < T:
+        return "--tile %d does not fit the padded %s: length %d + 2 x margin %d = %d" % (T, axis, L, M, L + 2 * M)
+    return None
+
+
+def tile_window(T, M, R):
+    """w(i) = clamp(min(i + 1, T - i) - M, 0, R), i = 0 .. T - 1, int64: zero in the margin, a ramp of R pixels, then flat; symmetric,
+    so the 2-D weight w(y) w(x) is the same under all 8 flips and rotations."""
+    i = np.arange(T, dtype=np.int64)
+    return np.clip(np.minimum(i + 1, T - i) - M, 0, R)
+
+
+def tile_origins(L, T, M, S):
+    """Tile origins along an axis of length L: -M, -M + S, ... while the tile ends before L + M, then L + M - T (the last tile is
+    shifted back, not padded further); duplicates removed."""
+    err = tile_geometry_error(L, T, M, 1, S)
+    if err is not None:
+        raise ValueError(err)
+    o, k = [], -M
+    while k + T < L + M:
+        o.append(k)
+        k += S
+    if not o or o[-1] != L + M - T:
+        o.append(L + M - T)
+    return o
+
+
+def _tile_weight_sum(L, origins, win):
+    s = np.zeros(L, dtype=np.int64)
+    for o in origins:
+        lo, hi = max(0, o), min(L, o + len(win))
+        s[lo:hi] += win[lo - o: hi - o]
+    return s
+
+
+def tile_plan(H, W, T, M, R, S):
+    """(oy, ox, Wy, Wx): the tile origins of the rows and of the columns (lists) and the per-axis weight sums Wy [H], Wx [W] (int64,
+    > 0 everywhere): Wy(Y) = sum over the row origins o of w(Y - o).  The weight a pixel collects over all passes is the exact integer
+    n_tta Wy(Y) Wx(X); it must stay below 2^24, where fp32 holds every integer."""
+    err = tile_geometry_error(H, T, M, R, S, 'height') or tile_geometry_error(W, T, M, R, S, 'width')
+    if err is not None:
+        raise ValueError(err)
+    win = tile_window(T, M, R)
+    oy, ox = tile_origins(H, T, M, S), tile_origins(W, T, M, S)
+    Wy, Wx = _tile_weight_sum(H, oy, win), _tile_weight_sum(W, ox, win)
+    assert Wy.min() > 0 and Wx.min() > 0
+    if 8 * int(Wy.max()) * int(Wx.max()) >= 1 << 24:
+        raise ValueError("tiles overlap so often that a pixel's weight sum 8 x %d x %d is no exact fp32 integer: raise --tile_stride or "
+                         "lower --tile_ramp" % (Wy.max(), Wx.max()))
+    return oy, ox, Wy, Wx
+
+
+def tile_passes(oy, ox, tta):
+    """The passes of an image in the order they run: tile-row, tile-column, flip 0..1, rot 0..3 -> [(y0, x0, flip, rot)]."""
+    d4 = [(f, r) for f in (0, 1) for r in range(4)] if tta else [(0, 0)]
+    return [(y0, x0, f, r) for y0 in oy for x0 in ox for f, r in d4]
+
+
+def _reflect_index(i, L):
+    """Index of the padded domain -> the image, mirrored without repeating the edge (F.pad(mode='reflect')): one fold."""
+    i = np.asarray(i, dtype=np.int64)
+    assert i.min() > -L and i.max() <= 2 * (L - 1), "the window reaches more than length - 1 pixels outside the image"
+    i = np.abs(i)
+    return np.where(i >= L, 2 * (L - 1) - i, i)
+
+
+def d4_apply(a, flip, rot):
+    """[..., h, w] -> horizontal flip, then rot x 90 degrees counter-clockwise (sg_image_prep_kernel's convention)."""
+    if flip:
+        a = a[..., ::-1]
+    return np.rot90(a, rot, axes=(-2, -1))
+
+
+def d4_inverse(a, flip, rot):
+    """Undoes d4_apply: what a pass computed on a transformed tile, back in the orientation of the window it was cut from."""
+    a = np.rot90(a, -rot, axes=(-2, -1))
+    return a[..., ::-1] if flip else a
+
+
+def prep_tile_ref(img_u8, y0, x0, h, w, flip, rot):
+    """img [H0, W0, 3] uint8 -> float32 [3, h, w] ([3, w, h] under an odd rot): the h x w window at (y0, x0) of the reflected image,
+    the D4 element, ToTensor and Normalize in float32 with sgan_image_prep's operation order.  The host yardstick of
+    ops.image_prep_tile, to the bit."""
+    img = np.asarray(img_u8)
+    assert img.dtype == np.uint8 and img.ndim == 3 and img.shape[2] == 3, (img.shape, img.dtype)
+    ys = _reflect_index(y0 + np.arange(h), img.shape[0])
+    xs = _reflect_index(x0 + np.arange(w), img.shape[1])
+    c = d4_apply(img[ys][:, xs].transpose(2, 0, 1), flip, rot)
+    t = c.astype(np.float32) / np.float32(255.0)                              # ToTensor
+    t = (t - np.float32(0.5)) / np.float32(0.5)                               # Normalize((.5,.5,.5), (.5,.5,.5))
+    return np.ascontiguousarray(t)
+
+
+def blend_tiles_ref(logits, H, W, T, M, R, S, tta=False, sigmoid=False, return_count=False):
+    """The whole-image prediction in float64:
+
+        P[c, Y, X] = (sum over the passes of w(y) w(x) p_pass[c] at the tile pixel that shows (Y, X)) / (n_tta Wy(Y) Wx(X))
+
+    `logits`: one [C, T, T] array per pass in tile_passes' order, or a callable (index, y0, x0, flip, rot) -> that array; p_pass is
+    its softmax over the channels (sigmoid: the logistic function of each).  A pass saw its window under d4_apply, so its result goes
+    through d4_inverse back to image orientation; what lands outside the image (mirrored territory) is dropped.  return_count: also
+    the number of passes that reached each pixel with a non-zero weight, [H, W].  The host yardstick of ops.tile_blend +
+    ops.tile_finish."""
+    oy, ox, Wy, Wx = tile_plan(H, W, T, M, R, S)
+    win = tile_window(T, M, R)
+    w2 = np.outer(win, win).astype(np.float64)
+    num, count = None, np.zeros((H, W), dtype=np.int64)
+    for k, (y0, x0, flip, rot) in enumerate(tile_passes(oy, ox, tta)):
+        z = np.asarray(logits(k, y0, x0, flip, rot) if callable(logits) else logits[k], dtype=np.float64)
+        assert z.ndim == 3 and z.shape[1:] == (T, T), z.shape
+        if sigmoid:
+            p = 1.0 / (1.0 + np.exp(-z))
+        else:
+            e = np.exp(z - z.max(axis=0, keepdims=True))
+            p = e / e.sum(axis=0, keepdims=True)
+        p = d4_inverse(p, flip, rot)
+        if num is None:
+            num = np.zeros((z.shape[0], H, W), dtype=np.float64)
+        ya, yb, xa, xb = max(0, y0), min(H, y0 + T), max(0, x0), min(W, x0 + T)
+        wgt = w2[ya - y0: yb - y0, xa - x0: xb - x0]
+        num[:, ya:yb, xa:xb] += wgt * p[:, ya - y0: yb - y0, xa - x0: xb - x0]
+        count[ya:yb, xa:xb] += wgt > 0
+    P = num / ((8 if tta else 1) * np.outer(Wy, Wx).astype(np.float64))
+    return (P, count) if return_count else P
+
+
+REGION_COLS =('area', 'xmin', 'xmax', 'ymin', 'ymax', 'sum_x', 'sum_y', 'sum_xx', 'sum_yy', 'sum_xy', 'boundary', 'root', 'image',
                'edges', 'zero14', 'zero15')
 REGION_PROPS = ('area', 'centroid_x', 'centroid_y', 'equivalent_diameter', 'extent', 'mu20', 'mu02', 'mu11', 'major_axis_length',
                 'minor_axis_length', 'eccentricity', 'orientation', 'compactness', 'touches_border')
