@@ -124,7 +124,13 @@ const char* sgan_last_kernel(void);
  * "nsplit 3,1" per problem (sg_wgrad_thin_kernel), "DK0 RB4 nsplit 1" (sg_bwd_thin_pair_kernel), "tiles 12" (sg_conv_scatter4_kernel);
  * and for the exact-fp32 MFMA kernels: "ks8 KW2 PRO1" (sg_igemm_kernel: the K split that ran, wave groups per workgroup, prologue;
  * " noslab" appended when a planned split found no workspace and ran unsplit), "PRO0 per4 nsplit 13,4,1" (sg_wgrad_kernel: prologue,
- * 32-pixel chunks per workgroup the split aims at, pixel split per problem) */
+ * 32-pixel chunks per workgroup the split aims at, pixel split per problem);
+ * and for the split 16-bit-plane kernels (F16: 1 = fp16 planes, 0 = bf16 planes): "ks8 PRO1 F161" (sg_igemm3_kernel; " noslab" as
+ * above), "AIT2 KW2 PRO0 F161" (sg_igemm3p_kernel: patch form 2 / 4 / 6 = up to 128 / up to 256 patch pixels / stride-2 parity planes,
+ * wave groups per workgroup), "PRO0 F160 per4 nsplit 13,4,2" (sg_wgrad3_kernel), "DV3 WV1 ks4 F160 WPRO1 nsplit 2,3"
+ * (sg_bwd_fused_kernel: backward-data body 1 / 2 / 3 / 5 / 6 and backward-weight body 1 / 2 as in sgan_fused.hip, the K split of the
+ * backward-data half, the planes it was actually formed from -- a published maximum on a body other than 6 runs on bf16 planes and
+ * reads F160 --, the backward-weight prologue, its pixel split per problem) */
 const char* sgan_last_variant(void);
 int sgan_stat_replicas(void);     /* SGAN_STAT_REPLICAS of the built library: statistics arenas must hold this many copies */
 /* The explicit device of the boundary (SURVEY 8b "Threading": backward is called from autograd worker threads that did not

@@ -141,6 +141,12 @@ static int sg_conv_bwd_fused_impl(const sgan_conv_dgrad_job* djobs, int32_t nd, 
     }
     SGAN_LAUNCH_CHECK();
     g_sgan_last_kernel = dx1 ? "sg_bwd_fused_kernel<x1>" : (wx1 ? "sg_bwd_fused_kernel<wgrad x1>" : "sg_bwd_fused_kernel");
+    {   // sgan_last_variant(): the two bodies, the K split of the backward-data half, the planes it was ACTUALLY formed from (a published
+        // maximum on a plan other than 6 was re-planned on bf16 planes above), the backward-weight prologue and pixel splits
+        const int n = snprintf(g_sgan_last_variant, sizeof(g_sgan_last_variant), "DV%d WV%d ks%d F16%d WPRO%d ", pd.variant, pw.variant, pd.ks,
+                               (pd.variant == 6 && P.planes_f16) ? 1 : 0, pw.pro ? 1 : 0);
+        sg_nsplit_variant(W, n);
+    }
     sg_prof_end(st, g_sgan_last_kernel);
     if (pd.ks > 1) return sg_launch_splitk_epilogue(P, st);      // sum of the slabs + the backward-data epilogue (activation derivative, norm-backward sums)
     return SGAN_OK;

@@ -1007,7 +1007,8 @@ static int sg3_launch(SgIgemmParams& P, hipStream_t st, float* ws, int64_t ws_by
     if (tiles == 0) return SGAN_OK;
     int ks = sg_plan_ksplit(P, BM, BN);
     const int64_t slab = (int64_t)P.q[0].Hout * P.q[0].Wout * P.N;
-    if (ks > 1 && (!ws || ws_bytes < (int64_t)ks * slab * 4)) ks = 1;   // no workspace: unsplit (still correct)
+    const bool noslab = ks > 1 && (!ws || ws_bytes < (int64_t)ks * slab * 4);
+    if (noslab) ks = 1;   // no workspace: unsplit (still correct)
     P.ksplit = ks;
     P.slab = ks > 1 ? ws : nullptr;
     P.slab_stride = slab;
@@ -1026,6 +1027,8 @@ static int sg3_launch(SgIgemmParams& P, hipStream_t st, float* ws, int64_t ws_by
     }
     SGAN_LAUNCH_CHECK();
     g_sgan_last_kernel = name;
+    // sgan_last_variant(): what the name does not tell -- the K split that ran, the prologue, the planes, a split that found no workspace
+    snprintf(g_sgan_last_variant, sizeof(g_sgan_last_variant), "ks%d PRO%d F16%d%s", ks, pro ? 1 : 0, P.planes_f16 ? 1 : 0, noslab ? " noslab" : "");
     sg_prof_end(st, g_sgan_last_kernel);
     if (ks > 1) return sg_launch_splitk_epilogue(P, st);
     return SGAN_OK;
@@ -1139,6 +1142,8 @@ static int sg3p_launch(SgIgemmParams& P, hipStream_t st, const char* name) {   /
     }
     SGAN_LAUNCH_CHECK();
     g_sgan_last_kernel = name;
+    // sgan_last_variant(): the patch form (two-iteration / four-iteration image, stride-2 parity planes), the wave groups, the prologue, the planes
+    snprintf(g_sgan_last_variant, sizeof(g_sgan_last_variant), "AIT%d KW%d PRO%d F16%d", A_IT, KWr, pro ? 1 : 0, P.planes_f16 ? 1 : 0);
     sg_prof_end(st, g_sgan_last_kernel);
     return SGAN_OK;
 }

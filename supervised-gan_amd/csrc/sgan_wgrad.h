@@ -42,6 +42,12 @@ struct SgWgradLocal {
     SgNorm pro;
 };
 
+// sgan_last_variant(): "nsplit a,b,.." -- the pixel split of every problem -- appended at offset n
+static inline void sg_nsplit_variant(const SgWgradParams& P, int n) {
+    n += snprintf(g_sgan_last_variant + n, sizeof(g_sgan_last_variant) - n, "nsplit ");
+    for (int g = 0; g < P.nprob && n < (int)sizeof(g_sgan_last_variant) - 8; ++g)
+        n += snprintf(g_sgan_last_variant + n, sizeof(g_sgan_last_variant) - n, g ? ",%d" : "%d", P.q[g].nsplit);
+}
 
 // split-bf16 tiled kernel (sgan_wgrad3.hip): 1 = launched, 0 = layer not covered (caller runs the fp32 kernel), < 0 = error
 int sg_launch_wgrad3(SgWgradParams& P, hipStream_t st, bool x1);

@@ -426,7 +426,7 @@ __global__ __launch_bounds__(256) void sg_wgrad3_kernel(const SgWgradParams G) {
 static inline int sgw3_cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // pixel splits, z offsets, grid and LDS bytes of a launch with BCO x BKC tiles; false: nothing to do
-static bool sgw3_prepare(SgWgradParams& P, int BCO, int BKC, dim3* grid_out, size_t* lds_out, bool* pro_out) {
+static bool sgw3_prepare(SgWgradParams& P, int BCO, int BKC, dim3* grid_out, size_t* lds_out, bool* pro_out, int* per_out = nullptr) {
     int maxK = 0;
     for (int i = 0; i < P.nphase; ++i) maxK = max(maxK, P.ktot[i]);
     const int tiles = sgw3_cdiv(maxK, BKC) * sgw3_cdiv(P.Cout, BCO);
@@ -441,6 +441,7 @@ static bool sgw3_prepare(SgWgradParams& P, int BCO, int BKC, dim3* grid_out, siz
     const double want = getenv("SGAN_WGRAD3_WANT") ? atof(getenv("SGAN_WGRAD3_WANT")) : 512.0;
     int per = (int)((double)chunks_total * tiles / want + 0.999);
     if (per < 4) per = 4;
+    if (per_out) *per_out = per;
     int z = 0;
     for (int g = 0; g < P.nprob; ++g) {
         int maxM = 0;
@@ -466,7 +467,8 @@ static int sgw3_launch(SgWgradParams& P, hipStream_t st, const char* name) {
     dim3 grid;
     size_t lds;
     bool pro;
-    if (!sgw3_prepare(P, BCO, BKC, &grid, &lds, &pro)) return 1;
+    int per = 0;
+    if (!sgw3_prepare(P, BCO, BKC, &grid, &lds, &pro, &per)) return 1;
     sg_prof_begin(st);
     if (P.planes_f16) {
         if (pro) hipLaunchKernelGGL((sg_wgrad3_kernel<BCO, BKC, WGC, WGK, true, true, X1>), grid, dim3(256), lds, st, P);
@@ -478,6 +480,10 @@ static int sgw3_launch(SgWgradParams& P, hipStream_t st, const char* name) {
     hipError_t e_ = hipGetLastError();
     if (e_ != hipSuccess) return sgan_fail(SGAN_ERR_HIP, "%s:%d: %s", __FILE__, __LINE__, hipGetErrorString(e_));
     g_sgan_last_kernel = name;
+    {   // sgan_last_variant(): the prologue, the planes, the chunks per workgroup the split aims at, the pixel split of every problem
+        int n = snprintf(g_sgan_last_variant, sizeof(g_sgan_last_variant), "PRO%d F16%d per%d ", pro ? 1 : 0, P.planes_f16 ? 1 : 0, per);
+        sg_nsplit_variant(P, n);
+    }
     sg_prof_end(st, g_sgan_last_kernel);
     return 1;
 }
