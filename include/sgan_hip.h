@@ -653,6 +653,24 @@ int sgan_zero_multi(void* const* ptrs, const int64_t* bytes, int32_t n, void* st
  * is the second update rule of the boundary for callers that do read it. */
 int sgan_sgd_multi(const sgan_adam_seg* segs, int32_t nseg, const float* lr_dev, float momentum, void* stream);
 
+/* ---- Exponential moving average of parameters over up to 64 contiguous fp32 segments in one streaming launch:
+ *     shadow += (1 - d_t) * (p - shadow),   d_t = decay (warmup == 0)  or  min(decay, (1 + t) / (10 + t)) (warmup != 0)
+ * in fp32, one fmaf(1 - d_t, p - shadow, shadow) per element; `p` is only read.  `state_dev` points at 16 bytes of device memory
+ * owned by the caller, Adam's convention: state_dev[0] is the number of updates made (starts at 0); a 1-thread prep launch does
+ * t = state_dev[0] + 1, stores it (saturating at 2^30) and leaves 1 - d_t, derived in fp64, as a float in a kernel-private word;
+ * the streaming launch reads that word -- so a captured hipGraph replays with the right t.
+ * `shadow` and `p` of a segment need 4-byte alignment only and may be misaligned differently (ranges inside an arena).
+ * decay == 1 leaves shadow bit-identical; decay == 0 without warm-up makes it bit-equal to p.  nseg == 0 or every n == 0: nothing
+ * is averaged and the update still counts.  Refused, with nothing launched: nseg outside 0..64, a NULL pointer with n > 0, n < 0,
+ * decay outside [0, 1], shadow and p of a segment overlapping (shadow == p included).
+ * Replaces: nothing in the reference, which evaluates the last iterate. */
+typedef struct sgan_ema_seg {
+    float* shadow;
+    const float* p;
+    int64_t n;
+} sgan_ema_seg;
+int sgan_ema_multi(const sgan_ema_seg* segs, int32_t nseg, float decay, int32_t warmup, int32_t* state_dev, void* stream);
+
 /* ---- N(0,1) fill (Philox4x32-10 + Box-Muller), counter-based -----------------------------------
  * Replaces: noise_.normal_(0, 1) (models/fcgan_model.py:126-127).  `offset_dev` is a device uint64
  * the kernels read; with advance != 0 it is moved on by ceil(n / 4) afterwards (graph-replay safe).  Fills with different

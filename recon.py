@@ -2,7 +2,8 @@
 """Latent reconstruction driver with the reference's loop (recon.py): load `<which_epoch>_net_G.pth` of an fcgan run, fit latents to
 `how_many` images by L-BFGS (FCGANModel.reconstruction: 3 trials x 50 step() calls, lr 0.1 by default), write the best reconstruction
 and the image beside it as PNGs under results_dir/name/<phase>_<which_epoch>/images/ with an index.html, and print the summary line
-`BCE: mean .. std ..; noise: mean .. std ..; noise init: mean .. std ..`."""
+`BCE: mean .. std ..; noise: mean .. std ..; noise init: mean .. std ..`.  `--use_ema` fits against the averaged generator
+(`<which_epoch>_net_G_ema.pth` of a run with `--ema_decay`)."""
 import argparse
 import os
 import sys

@@ -84,6 +84,10 @@ class AdamSeg(C.Structure):
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64)]
 
 
+class EmaSeg(C.Structure):
+    _fields_ = [("shadow", C.c_void_p), ("p", C.c_void_p), ("n", C.c_int64)]
+
+
 # name -> argtypes; every entry returns int except the two string getters
 _P, _I, _L, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SIGNATURES = {
@@ -140,6 +144,7 @@ SIGNATURES = {
     "sgan_slice_nhwc": [_P, _I, _I, _I, _L, _P, _I, _I, _P],
     "sgan_adam_multi": [C.POINTER(AdamSeg), _I, _P, _F, _F, _F, _P, _P],
     "sgan_sgd_multi": [C.POINTER(AdamSeg), _I, _P, _F, _P],
+    "sgan_ema_multi": [C.POINTER(EmaSeg), _I, _F, _I, _P, _P],
     "sgan_adam_pack": [_P, _P, _P, _P, _L, _P, _F, _F, _F, _P, _P, _P, _P, _P, C.POINTER(WtSeg), _I, _I, _P],
     "sgan_zero_multi": [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), _I, _P],
     "sgan_conv_head_bwd": [C.POINTER(ConvDgradJob), C.POINTER(ConvWgradJob), _I, _P],

@@ -15,6 +15,9 @@ from . import ops
 
 
 class BaseModel:
+    supports_ema = True       # --ema_decay / --use_ema: the models with ONE generator `netG` (fcgan, cgan, cgan2, segmentation, test); the
+                              # cycle and two-stage trainers, which hold several, set it False
+
     def name(self):
         return 'BaseModel'
 
@@ -27,6 +30,10 @@ class BaseModel:
         self.model_dir = getattr(opt, 'pretrained_model_dir', '')
         self.grad_sync = None            # data-parallel hook: callable(optimizer) run between backward and step
         self._pool_overrides = None      # graphed step: one static buffer per step_pools() entry, read instead of querying the pool
+        self.ema = None                  # optim.WeightEMA over (netG, netG_ema) under --ema_decay (_init_ema)
+        if (getattr(opt, 'ema_decay', None) is not None or getattr(opt, 'use_ema', False)) and not self.supports_ema:
+            raise NotImplementedError("--ema_decay / --use_ema average the one generator of fcgan, cgan, cgan2 and segmentation; "
+                                      "--model %s is not among them" % getattr(opt, 'model', self.name()))
 
     def Tensor(self, *size):
         return torch.empty(*size, dtype=torch.float32, device=self.device)
@@ -57,6 +64,43 @@ class BaseModel:
     def get_current_errors(self):
         return {}
 
+    # ---- exponential moving average of the generator's weights (--ema_decay; optim.WeightEMA) ------------------------
+    def _init_ema(self, build_G):
+        """Under --ema_decay (training only): netG_ema, a second generator from the same define_G call `build_G` (a deepcopy would
+        lose the arenas and the .grad views), loaded from netG, with netG's Philox key, in no optimizer; self.ema averages netG into
+        it.  Call it once netG and the discriminators exist (the discriminators' initial weights then do not depend on the option)
+        and before load()."""
+        from .optim import WeightEMA
+        decay = getattr(self.opt, 'ema_decay', None)
+        if not self.isTrain or decay is None:
+            return
+        self.netG_ema = build_G()
+        self.netG_ema.load_state_dict(self.netG.state_dict())
+        if hasattr(self.netG, '_rng_seed'):
+            self.netG_ema._rng_seed = self.netG._rng_seed
+        self.ema = WeightEMA(self.netG, self.netG_ema, decay, getattr(self.opt, 'ema_warmup', False))
+
+    def averaged_generator(self):
+        """Under --ema_eval: netG_ema, made ready for evaluation (WeightEMA.prepare_eval(): the live buffers, and derived weight copies
+        that a replayed step cannot have kept current); None otherwise.  The preparation holds until the next training step: a pass
+        of many forwards (train_ss.validate) asks once and hands the network to each of them."""
+        if self.ema is not None and getattr(self.opt, 'ema_eval', False):
+            self.ema.prepare_eval()
+            return self.netG_ema
+        return None
+
+    def _eval_netG(self):
+        """The generator one test() or one validation forward runs: the average under --ema_eval, prepared for this call, else netG."""
+        return self.averaged_generator() or self.netG
+
+    def _ema_nets(self):
+        """checkpoint_nets() entry of the averaged generator: [('G_ema', netG_ema)] under --ema_decay, else nothing."""
+        return [('G_ema', self.netG_ema)] if self.ema is not None else []
+
+    def _file_label(self, net_label):
+        """--use_ema (test side): netG is read from `<epoch>_net_G_ema.pth`."""
+        return 'G_ema' if net_label == 'G' and not self.isTrain and getattr(self.opt, 'use_ema', False) else net_label
+
     # ---- the training step -------------------------------------------------------------------------
     def step_stages(self):
         """[(optimizer, backward method, updates per step), ...] in the order the step runs them."""
@@ -79,8 +123,13 @@ class BaseModel:
         for optimizer, backward, n_updates in self.step_stages():
             for _ in range(n_updates):
                 program += [[optimizer.zero_grad, backward], ("sync", optimizer), [optimizer.step]]
+                if self.ema is not None and optimizer is self.optimizer_G:
+                    program[-1].append(self.ema.update)      # with data parallelism every rank averages its identical weights
                 if n_updates > 1:
                     program[-1].append(self.sample_noise)
+        if self.ema is not None and hasattr(self, 'prefetch_supported') and self.prefetch_supported():
+            # graph_step.GraphedStep replaces this slot with the prefetching re-draw
+            assert program[-1][-1] == self.sample_noise, "the step's last call must be the re-draw when prefetch is supported"
         return program
 
     def run_program(self, program):
@@ -132,14 +181,30 @@ class BaseModel:
         return []
 
     def save(self, label):
+        if self.ema is not None:
+            self.ema.prepare_eval()      # the averaged generator is saved with the live buffers (BatchNorm statistics are not averaged)
         for net_label, net in self.checkpoint_nets():
             self.save_network(net, net_label, label, gpu_ids=self.gpu_ids)
 
     def load(self, epoch_label, only=None, model_dir=''):
         """Reads every network's file; `only`: the networks whose label (a discriminator's without its `_<n>`) it names."""
         for net_label, net in self.checkpoint_nets():
-            if only is None or net_label.split('_')[0] in only:
-                self.load_network(net, net_label, epoch_label, model_dir=model_dir)
+            if only is None or net_label.split('_')[0] in only:      # 'G_ema' goes with 'G'
+                if net is getattr(self, 'netG_ema', None):
+                    self._load_ema(epoch_label, model_dir)
+                else:
+                    self.load_network(net, net_label, epoch_label, model_dir=model_dir)
+
+    def _load_ema(self, epoch_label, model_dir=''):
+        """--continue_train under --ema_decay: the saved average goes on at d_t = decay (the counter is not in the checkpoint); a
+        run saved without one starts its average from the weights just loaded."""
+        path = self._checkpoint_path('G_ema', epoch_label, model_dir)
+        if os.path.exists(path):
+            self.load_network(self.netG_ema, 'G_ema', epoch_label, model_dir=model_dir)
+            self.ema.skip_warmup()
+        else:
+            print('%s not found: the average restarts from the loaded generator' % path)
+            self.ema.reset_from_live()
 
     def _checkpoint_path(self, network_label, epoch_label, model_dir):
         """`<epoch>_net_<label>.pth` under the run's directory, or under --pretrained_model_dir when the caller asks for the
@@ -153,7 +218,11 @@ class BaseModel:
         torch.save(OrderedDict((k, v.detach().to('cpu').contiguous()) for k, v in network.state_dict().items()), path)
 
     def load_network(self, network, network_label, epoch_label, model_dir=''):
-        load_state_dict_compat(network, torch.load(self._checkpoint_path(network_label, epoch_label, model_dir), map_location='cpu'))
+        network_label = self._file_label(network_label)      # --use_ema: 'G' is read from the averaged generator's file
+        path = self._checkpoint_path(network_label, epoch_label, model_dir)
+        if network_label == 'G_ema' and not os.path.exists(path):
+            raise FileNotFoundError("%s not found: --use_ema reads the averaged generator a run with --ema_decay saves" % path)
+        load_state_dict_compat(network, torch.load(path, map_location='cpu'))
 
 
 def _not_overridden(self, *args, **kwargs):

@@ -33,20 +33,22 @@ class CGAN2Model(CGANModel):
         self.input_fake_A.resize_(fa.size()).copy_(fa)
         self.image_paths = input.get('A_paths')
 
-    def forward(self):
+    def forward(self, netG=None):
+        """netG: the generator to run (test() under --ema_eval hands over the average); None = self.netG."""
+        netG = self.netG if netG is None else netG
         self.real_A = self.input_A
         self.fake_A = self.input_fake_A
         self.real_B = self.input_B
         self.noise = self._draw_noise()
-        self.fake_B_from_real_A = self.netG.forward(self.real_A, self.noise)
-        self.fake_B_from_fake_A = self.netG.forward(self.fake_A, self.noise)
+        self.fake_B_from_real_A = netG.forward(self.real_A, self.noise)
+        self.fake_B_from_fake_A = netG.forward(self.fake_A, self.noise)
         self.fake_B = self.fake_B_from_real_A
 
     sample_noise = forward
 
     def test(self):
         with torch.no_grad():
-            self.forward()
+            self.forward(self._eval_netG())
 
     def _pair(self, fake_fake):
         if fake_fake:

@@ -14,6 +14,8 @@ from .optim import AdamGroups, FusedAdam
 
 
 class CGANCycleModel(BaseModel):
+    supports_ema = False      # two generators: --ema_decay / --use_ema are refused (BaseModel.initialize)
+
     allow_multi_G_updates = False
 
     def name(self):

@@ -43,13 +43,15 @@ class CGANModel(BaseModel):
         self._rng_offset = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.noise_source = None    # optional callable() -> z tensor (tests inject latents)
 
-        self.netG = networks.define_G(opt.input_nc, opt.output_nc, opt.ngf, opt.which_model_netG, opt.norm,
-                                      not opt.no_dropout, n_layers_G=opt.n_layers_G, use_residual=opt.use_residual,
-                                      use_fcn=opt.noiseSize != 1, noise_nc=opt.noise_nc,
-                                      add_gaussian_noise=opt.add_gaussian_noise, gaussian_sigma=opt.gaussian_sigma,
-                                      upsample_mode=opt.upsample_mode, n_layers_CRN_block=opt.n_layers_CRN_block,
-                                      share_label_weights=not opt.no_share_label_block_weights,
-                                      n_layers_G_skip=opt.n_layers_G_skip, gpu_ids=self.gpu_ids)
+        def build_G():
+            return networks.define_G(opt.input_nc, opt.output_nc, opt.ngf, opt.which_model_netG, opt.norm,
+                                     not opt.no_dropout, n_layers_G=opt.n_layers_G, use_residual=opt.use_residual,
+                                     use_fcn=opt.noiseSize != 1, noise_nc=opt.noise_nc,
+                                     add_gaussian_noise=opt.add_gaussian_noise, gaussian_sigma=opt.gaussian_sigma,
+                                     upsample_mode=opt.upsample_mode, n_layers_CRN_block=opt.n_layers_CRN_block,
+                                     share_label_weights=not opt.no_share_label_block_weights,
+                                     n_layers_G_skip=opt.n_layers_G_skip, gpu_ids=self.gpu_ids)
+        self.netG = build_G()
         if hasattr(self.netG, '_rng_seed'):
             self.netG._rng_seed = 0 if opt.manualSeed is None else int(opt.manualSeed)
         self.has_netD = self.isTrain and self._builds_netD(opt)
@@ -66,6 +68,7 @@ class CGANModel(BaseModel):
                 self.netD.append(d)
             if self.gpu_ids:
                 networks.pack_flat(self.netD)
+        self._init_ema(build_G)      # after netG's Philox key is set: the shadow takes it over
         if not self.isTrain or opt.continue_train:
             self.load(opt.which_epoch)
 
@@ -152,7 +155,7 @@ class CGANModel(BaseModel):
         with torch.no_grad():
             self.real_A = self.input_A
             self.noise = self._draw_noise()
-            self.fake_B = self.netG.forward(self.real_A, self.noise)
+            self.fake_B = self._eval_netG().forward(self.real_A, self.noise)
 
     def get_image_paths(self):
         return self.image_paths
@@ -221,6 +224,6 @@ class CGANModel(BaseModel):
         return out
 
     def checkpoint_nets(self):
-        return [('G', self.netG)] + [('D_%d' % n, netD) for n, netD in enumerate(self.netD if self.has_netD else [])]
+        return [('G', self.netG)] + self._ema_nets() + [('D_%d' % n, netD) for n, netD in enumerate(self.netD if self.has_netD else [])]
 
     update_learning_rate = BaseModel.decay_single_rate

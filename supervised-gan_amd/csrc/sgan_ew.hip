@@ -2204,6 +2204,100 @@ extern "C" int sgan_sgd_multi(const sgan_adam_seg* segs, int32_t nseg, const flo
 }
 
 // ------------------------------------------------------------------------------------------
+// Exponential moving average of parameters: shadow += (1 - d_t) * (p - shadow) over up to 64 segments.  Adam's scheme: a 1-thread
+// prep launch counts the update (state[0], saturating at 2^30) and leaves 1 - d_t, derived in fp64, as a float in state[1]; the
+// streaming launch reads it, so a captured hipGraph replays with the right t.  d_t = decay, or min(decay, (1 + t) / (10 + t)) with
+// warm-up.  8 bytes read and 4 written per element; `p` is only read.
+// A segment may start at any float offset of an arena, differently for shadow and p: the body is aligned on `shadow` (16-byte loads
+// and stores) and reads `p` as four-float groups of 4-byte alignment; the <= 3 elements in front of the first aligned shadow element
+// and the <= 3 behind the last full group go one by one.
+// ------------------------------------------------------------------------------------------
+#define SG_EMA_T_MAX (1 << 30)
+
+struct SgEmaTable {
+    sgan_ema_seg s[64];
+};
+
+struct __attribute__((packed, aligned(4))) SgF32x4A4 {      // four floats behind a pointer that is only 4-byte aligned
+    float v[4];
+};
+
+__global__ void sg_ema_prep_kernel(int32_t* state, float decay, int warmup) {
+    int t = state[0];
+    t = t >= SG_EMA_T_MAX ? SG_EMA_T_MAX : t + 1;
+    state[0] = t;
+    double d = (double)decay;
+    if (warmup) {
+        const double w = (1.0 + (double)t) / (10.0 + (double)t);
+        d = w < d ? w : d;
+    }
+    reinterpret_cast<float*>(state)[1] = (float)(1.0 - d);
+}
+
+// omd == 0 (decay 1): nothing to do, and nothing is written (0 * (p - s) + s would turn a -0 into +0); omd == 1 (decay 0): s = p
+// exactly, which fl(fl(p - s) + s) is not
+__device__ __forceinline__ float sg_ema1(float s, float p, float omd, bool copy) { return copy ? p : fmaf(omd, p - s, s); }
+
+__global__ __launch_bounds__(256) void sg_ema_kernel(SgEmaTable T, const int32_t* state) {
+    const sgan_ema_seg& S = T.s[blockIdx.y];
+    const float omd = reinterpret_cast<const float*>(state)[1];
+    if (omd == 0.f) return;
+    const bool copy = omd == 1.f;
+    const int64_t n = S.n;
+    int64_t head = (int64_t)(((16u - (unsigned)((uintptr_t)S.shadow & 15u)) & 15u) >> 2);      // elements in front of the aligned body
+    if (head > n) head = n;
+    const int64_t n4 = (n - head) >> 2;
+    float* sb = S.shadow + head;
+    const float* pb = S.p + head;
+    const bool p_aligned = ((uintptr_t)pb & 15) == 0;      // the same for the whole segment
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n4; e += (int64_t)gridDim.x * 256) {
+        f32x4 s = reinterpret_cast<const f32x4*>(sb)[e];
+        f32x4 p;
+        if (p_aligned) {
+            p = reinterpret_cast<const f32x4*>(pb)[e];
+        } else {
+            const SgF32x4A4 q = reinterpret_cast<const SgF32x4A4*>(pb)[e];
+            p[0] = q.v[0]; p[1] = q.v[1]; p[2] = q.v[2]; p[3] = q.v[3];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[j] = sg_ema1(s[j], p[j], omd, copy);
+        reinterpret_cast<f32x4*>(sb)[e] = s;
+    }
+    if (blockIdx.x == 0) {      // head by lanes 0..2 of the first wave, tail by lanes 0..2 of the second: every index inside [0, n)
+        const int64_t tail0 = head + (n4 << 2);
+        int64_t e = -1;
+        if (threadIdx.x < head) e = threadIdx.x;
+        else if (threadIdx.x >= 64 && tail0 + (threadIdx.x - 64) < n) e = tail0 + (threadIdx.x - 64);
+        if (e >= 0) S.shadow[e] = sg_ema1(S.shadow[e], S.p[e], omd, copy);
+    }
+}
+
+extern "C" int sgan_ema_multi(const sgan_ema_seg* segs, int32_t nseg, float decay, int32_t warmup, int32_t* state_dev, void* stream) {
+    SGAN_CHECK(nseg >= 0 && nseg <= 64 && (segs || nseg == 0) && state_dev, "bad argument (nseg %d; 0..64 segments, a state word)", nseg);
+    SGAN_CHECK(decay >= 0.f && decay <= 1.f, "decay %g outside [0, 1]", (double)decay);      // a NaN fails both comparisons
+    SgEmaTable T;
+    int64_t maxn = 0;
+    for (int i = 0; i < nseg; ++i) {
+        const sgan_ema_seg& s = segs[i];
+        SGAN_CHECK(s.n >= 0 && (s.n == 0 || (s.shadow && s.p)), "bad segment %d", i);
+        SGAN_CHECK(((uintptr_t)s.shadow & 3) == 0 && ((uintptr_t)s.p & 3) == 0, "segment %d not 4-byte aligned", i);
+        SGAN_CHECK(s.n == 0 || (s.shadow + s.n <= s.p || s.p + s.n <= s.shadow), "segment %d: shadow and p overlap", i);
+        T.s[i] = s;
+        if (s.n > maxn) maxn = s.n;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(sg_ema_prep_kernel, dim3(1), dim3(1), 0, st, state_dev, decay, (int)warmup);
+    SGAN_LAUNCH_CHECK();
+    if (maxn == 0) return SGAN_OK;      // nothing to average: the update still counts
+    int bx = sg_cdiv(maxn / 4 + 1, 256 * 2);      // sized as sg_adam_kernel
+    if (bx > 1024) bx = 1024;
+    if (bx < 1) bx = 1;
+    hipLaunchKernelGGL(sg_ema_kernel, dim3(bx, nseg), dim3(256), 0, st, T, state_dev);
+    SGAN_LAUNCH_CHECK();
+    return SGAN_OK;
+}
+
+// ------------------------------------------------------------------------------------------
 // N(0,1) fill: Philox4x32-10, Box-Muller
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ void sg_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,

@@ -56,12 +56,14 @@ class FCGANModel(BaseModel):
             self.fixed_noiseA = torch.randn(zshape)
             self.fixed_noiseB = torch.randn(zshape)
 
-        self.netG = networks.define_G(opt.input_nc, 0, opt.ngf, opt.which_model_netG, opt.norm, not opt.no_dropout,
-                                      n_layers_G=opt.n_layers_G, use_residual=opt.use_residual,
-                                      use_fcn=opt.noiseSize != 1, noise_nc=opt.noise_nc,
-                                      add_gaussian_noise=opt.add_gaussian_noise, gaussian_sigma=opt.gaussian_sigma,
-                                      upsample_mode=opt.upsample_mode, n_layers_CRN_block=opt.n_layers_CRN_block,
-                                      share_label_weights=not opt.no_share_label_block_weights, gpu_ids=self.gpu_ids)
+        def build_G():
+            return networks.define_G(opt.input_nc, 0, opt.ngf, opt.which_model_netG, opt.norm, not opt.no_dropout,
+                                     n_layers_G=opt.n_layers_G, use_residual=opt.use_residual,
+                                     use_fcn=opt.noiseSize != 1, noise_nc=opt.noise_nc,
+                                     add_gaussian_noise=opt.add_gaussian_noise, gaussian_sigma=opt.gaussian_sigma,
+                                     upsample_mode=opt.upsample_mode, n_layers_CRN_block=opt.n_layers_CRN_block,
+                                     share_label_weights=not opt.no_share_label_block_weights, gpu_ids=self.gpu_ids)
+        self.netG = build_G()
         if self.isTrain:
             use_sigmoid = opt.no_lsgan
             assert (len(opt.scale_factor) == len(opt.lambda_D) == len(opt.n_layers_D))
@@ -74,6 +76,7 @@ class FCGANModel(BaseModel):
                 self.netD.append(d)
             if self.gpu_ids:
                 networks.pack_flat(self.netD)   # one arena: single Adam segment, single gradient all-reduce
+        self._init_ema(build_G)
         if not self.isTrain or opt.continue_train:
             self.load(opt.which_epoch)
 
@@ -176,7 +179,7 @@ class FCGANModel(BaseModel):
     def test(self):
         with torch.no_grad():
             self.noise = self._draw_noise()
-            self.fake = self.netG.forward(self.noise)
+            self.fake = self._eval_netG().forward(self.noise)
 
     def get_image_paths(self):
         return self.image_paths
@@ -361,6 +364,6 @@ class FCGANModel(BaseModel):
             self.fixed_noiseB = self.noise
 
     def checkpoint_nets(self):
-        return [('G', self.netG)] + [('D_%d' % n, netD) for n, netD in enumerate(self.netD if self.isTrain else [])]
+        return [('G', self.netG)] + self._ema_nets() + [('D_%d' % n, netD) for n, netD in enumerate(self.netD if self.isTrain else [])]
 
     update_learning_rate = BaseModel.decay_single_rate

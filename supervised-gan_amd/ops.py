@@ -1040,6 +1040,23 @@ def sgd_multi(segs, lr_dev, momentum):
     L.check(L.lib().sgan_sgd_multi(arr, len(segs), _ptr(lr_dev), float(momentum), _stream()), "sgan_sgd_multi")
 
 
+def ema_multi(segs, decay, warmup, state):
+    """One sgan_ema_multi launch: shadow += (1 - d_t) * (p - shadow) over segs = [(shadow, p)], pairs of contiguous flat fp32 device
+    tensors of equal length (4-byte alignment is enough; `p` is only read).  `state`: the 4 int32 words of the average on the device,
+    state[0] = updates made so far.  d_t = decay, or min(decay, (1 + t) / (10 + t)) with `warmup`.  Nothing is read back."""
+    arr = (L.EmaSeg * max(len(segs), 1))()
+    for i, (s, p) in enumerate(segs):
+        if (s.dtype != torch.float32 or p.dtype != torch.float32 or not s.is_contiguous() or not p.is_contiguous() or s.dim() != 1
+                or s.shape != p.shape or s.device != p.device):
+            raise L.SganError(f"ema_multi: segment {i} must be a pair of contiguous flat fp32 tensors of equal length on one device, got "
+                              f"{tuple(s.shape)} {s.dtype} / {tuple(p.shape)} {p.dtype}; nothing was launched")
+        require_gpu(s, "ema_multi")
+        arr[i] = L.EmaSeg(s.data_ptr(), p.data_ptr(), s.numel())
+    assert state.dtype == torch.int32 and state.numel() >= 4 and state.is_contiguous()
+    require_gpu(state, "ema_multi")
+    L.check(L.lib().sgan_ema_multi(arr, len(segs), float(decay), int(bool(warmup)), _ptr(state), _stream()), "sgan_ema_multi")
+
+
 def lbfgs_advance(state, J, n, x, grad, loss, d, prev_grad, hist_s, hist_y, hist_rho):
     """One sgan_lbfgs_advance launch over J problems of n unknowns (supervised_gan_amd.lbfgs.DeviceLBFGS owns the buffers).
     x, grad: [J, >= n] fp32 with unit element stride; loss: [J] fp32."""

@@ -4,7 +4,10 @@ Mirrors `torch.optim.Adam(params, lr=, betas=)` as the reference trainers use it
 (models/fcgan_model.py:98-109: beta1 = opt.beta1 = 0.5, beta2 = 0.999, eps 1e-8, no weight decay):
 same constructor call, `param_groups[i]['lr']` writable by the LR schedule, `zero_grad()`, `step()`.
 One sgan_adam_multi launch updates every parameter of the optimizer; the step counter and the LR
-live in device memory so that a captured hipGraph of the training step replays correctly."""
+live in device memory so that a captured hipGraph of the training step replays correctly.
+
+WeightEMA (--ema_decay) averages a generator's parameters into a second generator over the same kind of arena ranges, one
+sgan_ema_multi launch after the generator's optimizer step."""
 import torch
 
 import os
@@ -13,6 +16,47 @@ from . import ops
 from ._lib import SganError
 
 _NO_ADAM_PACK = os.environ.get("SGAN_NO_ADAM_PACK", "0") not in ("", "0")      # diagnostics: the three-launch optimizer step of round 2
+
+
+def arena_ranges(params, who):
+    """Every parameter's range in its arena (a network's flat storage, or the shared arena several networks were packed into), in the
+    order given: ({id(net): net}, [(param arena, grad arena, off, n)])."""
+    nets, out = {}, []
+    for p in params:
+        seg = getattr(p, "_sgan_seg", None)
+        if seg is None:
+            raise SganError("%s only handles parameters of supervised_gan_amd networks "
+                            "(use torch.optim.Adam for foreign parameters)" % who)
+        net, off, n = seg
+        nets[id(net)] = net
+        arena_p, arena_g, base = net._arena
+        out.append((arena_p, arena_g, base + off, n))
+    return nets, out
+
+
+def merge_ranges(ranges):
+    """[(off, n)] or [(off, n, off2)] -> sorted, with adjacent ranges merged (a third entry is the offset of the range's twin in a second
+    arena -- WeightEMA's shadow -- and two ranges merge only where their twins touch as well)."""
+    rs = sorted(ranges)
+    out = [list(rs[0])]
+    for r in rs[1:]:
+        last = out[-1]
+        if all(o == lo + last[1] for o, lo in zip(r[:1] + r[2:], last[:1] + last[2:])):
+            last[1] += r[1]
+        else:
+            out.append(list(r))
+    return [tuple(r) for r in out]
+
+
+def arena_segments(params, who):
+    """The contiguous segments behind `params`: ({id(net): net}, [(param arena, grad arena, off, n)]), the ranges of one arena sorted
+    and merged where they touch, the arenas in the order their first parameter appears."""
+    nets, ranges = arena_ranges(params, who)
+    by_arena = {}
+    for arena_p, arena_g, off, n in ranges:
+        by_arena.setdefault(arena_p.data_ptr(), (arena_p, arena_g, []))[2].append((off, n))
+    segs = [(arena_p, arena_g, off, n) for arena_p, arena_g, rs in by_arena.values() for off, n in merge_ranges(rs)]
+    return nets, segs
 
 
 class FusedAdam:
@@ -26,30 +70,7 @@ class FusedAdam:
         if not params:
             raise ValueError("optimizer got an empty parameter list")
         self.param_groups = [{"params": params, "lr": float(lr), "betas": tuple(betas), "eps": float(eps)}]
-        # map every parameter to its range in an arena (a network's flat storage, or the shared arena
-        # several networks were packed into) and merge adjacent ranges
-        ranges = {}
-        self._nets = {}
-        for p in params:
-            seg = getattr(p, "_sgan_seg", None)
-            if seg is None:
-                raise SganError("FusedAdam only handles parameters of supervised_gan_amd networks "
-                                "(use torch.optim.Adam for foreign parameters)")
-            net, off, n = seg
-            self._nets[id(net)] = net
-            arena_p, arena_g, base = net._arena
-            ranges.setdefault(arena_p.data_ptr(), (arena_p, arena_g, []))[2].append((base + off, n))
-        self._segs = []   # (param arena, grad arena, off, n)
-        for arena_p, arena_g, rs in ranges.values():
-            rs.sort()
-            cur_off, cur_n = rs[0]
-            for off, n in rs[1:]:
-                if off == cur_off + cur_n:
-                    cur_n += n
-                else:
-                    self._segs.append((arena_p, arena_g, cur_off, cur_n))
-                    cur_off, cur_n = off, n
-            self._segs.append((arena_p, arena_g, cur_off, cur_n))
+        self._nets, self._segs = arena_segments(params, "FusedAdam")      # _segs: (param arena, grad arena, off, n)
         self._state = None
         self._lr_host = None
 
@@ -225,3 +246,85 @@ class AdamGroups:
     @property
     def step_count(self):
         return self.optimizers[0].step_count
+
+
+EMA_T_MAX = 1 << 30      # where the update counter saturates (sgan_ema_multi)
+
+
+class WeightEMA:
+    """Exponential moving average of a generator's parameters in a second, structurally identical generator (the shadow):
+
+        shadow += (1 - d_t) * (live - shadow),   d_t = decay,  or with warm-up  min(decay, (1 + t) / (10 + t)),  t = 1, 2, ...
+
+    `update()` is ONE sgan_ema_multi launch over the paired arena ranges of the two networks; the update counter lives in device
+    memory (Adam's convention), so a captured hipGraph of the training step replays with the right t.  Only parameters are averaged:
+    BUFFERS (BatchNorm running statistics, num_batches_tracked) ARE NOT -- prepare_eval() copies the live network's into the shadow.
+
+    Under a graphed step the Python body of update() runs at capture only, so no host-side bookkeeping can follow the replays: the
+    shadow's derived weight copies (the transposed fp32 copy and the split-bf16 packs, ChainNet._wt_key / _derived_key) would look
+    current while the replays moved the weights under them.  prepare_eval() therefore invalidates them unconditionally: call it before
+    every evaluation of the shadow network."""
+
+    def __init__(self, live_net, shadow_net, decay, warmup=False):
+        decay = float(decay)
+        if not 0.0 <= decay <= 1.0:      # a NaN fails both comparisons
+            raise ValueError("WeightEMA: decay must lie in [0, 1] (got %g)" % decay)
+        self.live, self.shadow, self.decay, self.warmup = live_net, shadow_net, decay, bool(warmup)
+        lp, sp = list(live_net.named_parameters()), list(shadow_net.named_parameters())
+        if [k for k, _ in lp] != [k for k, _ in sp] or any(a.shape != b.shape for (_, a), (_, b) in zip(lp, sp)):
+            raise SganError("WeightEMA: the shadow network must have the live network's parameters (build it with the same define_G call)")
+        _, lr = arena_ranges([p for _, p in lp], "WeightEMA")
+        _, sr = arena_ranges([p for _, p in sp], "WeightEMA")
+        by_arena = {}
+        for (la, _, loff, n), (sa, _, soff, sn) in zip(lr, sr):
+            if n != sn:
+                raise SganError("WeightEMA: a parameter's storage differs between the live and the shadow network (%d / %d floats)" % (n, sn))
+            if la.data_ptr() == sa.data_ptr():
+                raise SganError("WeightEMA: the shadow network shares the live network's storage")
+            by_arena.setdefault((la.data_ptr(), sa.data_ptr()), (la, sa, []))[2].append((loff, n, soff))
+        self._segs = [(la, loff, sa, soff, n) for la, sa, rs in by_arena.values() for loff, n, soff in merge_ranges(rs)]
+        if len(self._segs) > 64:
+            raise SganError("WeightEMA: %d separate ranges; one sgan_ema_multi launch takes 64 (pack the networks into one arena)" % len(self._segs))
+        for p in shadow_net.parameters():
+            p.requires_grad_(False)
+        self._state = torch.zeros(4, dtype=torch.int32, device=self._segs[0][2].device)
+
+    def segments(self):
+        """[(shadow, live)] flat views of equal length: what update() hands to ops.ema_multi."""
+        return [(sa[soff: soff + n], la[loff: loff + n]) for la, loff, sa, soff, n in self._segs]
+
+    def _chains(self):
+        from .chain import ChainNet
+        return [m for m in self.shadow.modules() if isinstance(m, ChainNet)]
+
+    @torch.no_grad()
+    def update(self):
+        """One launch, no host synchronisation, nothing read on the host: capturable."""
+        ops.ema_multi(self.segments(), self.decay, self.warmup, self._state)      # the derived copies go stale: prepare_eval()
+
+    @torch.no_grad()
+    def prepare_eval(self):
+        """Before every evaluation of the shadow network: the live network's buffers (not averaged) into the shadow, and the shadow's
+        derived weight copies marked stale whatever the host-side keys say."""
+        for (k, sb), (kl, lb) in zip(self.shadow.named_buffers(), self.live.named_buffers()):
+            assert k == kl, (k, kl)
+            sb.copy_(lb)
+        for net in self._chains():
+            net.invalidate_derived()
+
+    @torch.no_grad()
+    def reset_from_live(self):
+        """shadow = live (parameters and buffers) and the counter back to 0: the average starts over."""
+        for s, p in self.segments():
+            s.copy_(p)
+        self._state.zero_()
+        self.prepare_eval()
+
+    def skip_warmup(self):
+        """The counter to its saturation value: a resumed average goes on at d_t = decay."""
+        self._state[:1].fill_(EMA_T_MAX)
+
+    @property
+    def count(self):
+        """Updates made so far (reads the device counter: synchronises)."""
+        return int(self._state[0].item())

@@ -138,6 +138,7 @@ class BaseOptions:
         check_clean_options(self.opt, self.parser)
         check_elastic_options(self.opt)
         check_tile_options(self.opt, self.parser)
+        check_ema_options(self.opt, self.parser)
         if self.opt.math is not None:
             from . import ops
             ops.set_math(self.opt.math)
@@ -237,6 +238,21 @@ def check_tile_options(opt, parser=None, size=None):
         raise ValueError(bad)
 
 
+def check_ema_options(opt, parser=None):
+    """--ema_decay D (train options): 0 <= D <= 1, unset = no average; --ema_warmup and --ema_eval need it.  Refused at parse time.
+    An options object without the flags (the test drivers, which have --use_ema) passes."""
+    decay = getattr(opt, 'ema_decay', None)
+    bad = None
+    if decay is not None and not 0.0 <= decay <= 1.0:      # a NaN fails both comparisons
+        bad = "--ema_decay: a decay of 0 .. 1 (got %g)" % decay
+    elif decay is None and (getattr(opt, 'ema_eval', False) or getattr(opt, 'ema_warmup', False)):
+        bad = "--ema_eval / --ema_warmup need --ema_decay: without it there is no averaged generator"
+    if bad is not None:
+        if parser is not None:
+            parser.error(bad)
+        raise ValueError(bad)
+
+
 def check_elastic_options(opt):
     """--elastic G SIGMA deforms the crops of the image-folder feeders (data.py): G cells a side, 1..13 (the device stages the (G + 3)^2
     control vectors, at most 256); SIGMA >= 0 source pixels.  Leaves opt.elastic as (int G, float SIGMA)."""
@@ -324,6 +340,15 @@ class TrainOptions(BaseOptions):
         a('--elastic_label_channels', type=str, default='rg',
           help='letters of the RGB channels that hold labels and are sampled at the nearest pixel under --elastic; the others are '
                'sampled bilinearly (default rg: the reference keeps labels in r and g and the image in b)')
+        # exponential moving average of the generator's weights (not in the reference, which evaluates the last iterate)
+        a('--ema_decay', type=float, default=None, metavar='D',
+          help='fcgan / cgan / cgan2 / segmentation: keep an exponential moving average of the generator, shadow += (1 - D) (G - shadow) '
+               'after every generator update (one launch, inside the graphed step), saved as <epoch>_net_G_ema.pth; 0 <= D <= 1, '
+               'unset: off.  BatchNorm statistics are not averaged: the average takes the live ones')
+        a('--ema_warmup', action='store_true', help='--ema_decay: use min(D, (1 + t) / (10 + t)) at update t, so that a short run is not '
+                                                    'dominated by the initial weights')
+        a('--ema_eval', action='store_true', help='--ema_decay: test() and the validation pass of train_ss.py (and so --best_metric) run '
+                                                  'the averaged generator')
         self.isTrain = True
 
 
@@ -348,4 +373,7 @@ class TestOptions(BaseOptions):
         a('--tile_stride', type=int, default=None, help='S: distance between tile origins, 1 .. T - 2 M (default T - 2 M - R, at least 1)')
         a('--tta', type=str, default='none', choices=['none', 'd4'],
           help='d4: average the prediction over the 8 flips and rotations of every tile; without --whole_image, of the one --fineSize crop')
+        a('--use_ema', action='store_true',
+          help='load <which_epoch>_net_G_ema.pth, the averaged generator a run with --ema_decay saves, in place of <which_epoch>_net_G.pth '
+               '(--model test, fcgan, cgan, cgan2, segmentation); everything downstream runs on the average')
         self.isTrain = False

@@ -109,12 +109,15 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
         ops.ccl_label(self._border_wall, self._border_cells)
         ops.border_weight(self._border_cells, self.opt.border_radius, w0, sigma, bmap=self.bmap)
 
-    def forward(self, val_mode=False):
-        """val_mode: the validation pass of train_ss.py draws its latent at --noiseSizeVal (segm_model.py:145-155)."""
+    def forward(self, val_mode=False, netG=None):
+        """val_mode: the validation pass of train_ss.py draws its latent at --noiseSizeVal (segm_model.py:145-155) and, under
+        --ema_eval, runs the averaged generator (so --best_metric scores the average); netG: the generator to run, None = that rule."""
+        if netG is None:
+            netG = self._eval_netG() if val_mode else self.netG
         self.real_A = self.input_A
         self.real_B = self.input_B
         self.noise = self._draw_noise_val() if val_mode else self._draw_noise()
-        self.logit = self.netG.forward(self.real_A, self.noise, activation=_identity)                 # :155
+        self.logit = netG.forward(self.real_A, self.noise, activation=_identity)                 # :155
         if getattr(self, 'no_netD', False):      # the loss is fake_B's one consumer: prediction, loss and d loss / d logit in one launch
             if self.use_sigmoid_ss:
                 self.fake_B, self._head_loss = seg_head(self.logit, self.real_B, self.class_weights, None, ops.SEGHEAD_SIGMOID)
@@ -140,7 +143,7 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
             if self._tiling:
                 self._test_tiled()
             else:
-                self.forward()
+                self.forward(netG=self._eval_netG())
 
     # ---- whole-image inference (--whole_image / --tta d4 of the test options; util.tile_plan) --------------------
     def _tile_state(self, H, W):

@@ -17,6 +17,8 @@ from .optim import AdamGroups, FusedAdam
 
 
 class TwoStageCycleModel(BaseModel):
+    supports_ema = False      # several generators: --ema_decay / --use_ema are refused (BaseModel.initialize)
+
     cycle = True      # TwoStageModel (below) is the same trainer without F2 and the cycle terms
 
     def name(self):

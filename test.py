@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Sampling driver with the reference's loop (test.py:10-60): load `<which_epoch>_net_*.pth`, run `model.test()` how_many
 times, write the visuals as PNGs under results_dir/name/<phase>_<which_epoch>/images/ and the index.html result page beside
-them (util/visualizer.py:136-154, util/html.py)."""
+them (util/visualizer.py:136-154, util/html.py).  `--use_ema` reads the generator from `<which_epoch>_net_G_ema.pth`, the average a
+run with `--ema_decay` saves."""
 import os
 import sys
 

@@ -8,7 +8,9 @@ optimize_parameters, error printing, `latest` / per-epoch checkpoints, linear LR
         --no_lsgan --which_channel rg            (README.md:33 with `--dataroot synthetic`)
 
 `--dataroot synthetic` feeds device-resident random images; any other `--dataroot` is read as the reference's image folder
-(`supervised_gan_amd/data.py`: single / aligned datasets, crop / flip / rotate / normalise on the device).  `--max_steps N` bounds a run."""
+(`supervised_gan_amd/data.py`: single / aligned datasets, crop / flip / rotate / normalise on the device).  `--max_steps N` bounds a run.
+`--ema_decay D [--ema_warmup]` (fcgan, cgan, cgan2, segmentation) keeps an exponential moving average of the generator, one launch
+after every generator update, and saves it as `<label>_net_G_ema.pth`; `test.py --use_ema` samples from it."""
 import os
 import random
 import sys

@@ -11,7 +11,11 @@ a validation pass over `<dataroot>/val` after every epoch, and a `best` checkpoi
 
 The accuracies are accumulated by kernels queued behind the step (supervised_gan_amd/csrc/sgan_metrics.hip); the host reads them at
 the print interval and after the validation pass only, and writes them to acc_log.txt beside loss_log.txt (the reference plots them
-in visdom panes, which this path does not carry)."""
+in visdom panes, which this path does not carry).
+
+`--ema_decay D [--ema_warmup]` keeps an exponential moving average of the generator (one launch after every generator update, inside
+the graphed step) and saves it as `<label>_net_G_ema.pth` beside every `<label>_net_G.pth`; with `--ema_eval` the validation pass, and
+so `--best_metric` and the `best` checkpoint, score the average (SegmentationModel.forward(val_mode=True))."""
 import copy
 import math
 import os
@@ -59,10 +63,12 @@ def validation_options(opt):
 def validate(model, dataset_val, img_dir=None):
     """One pass over the validation set: forward(val_mode=True) without gradients, accuracies accumulated from zero."""
     model.reset_accs()
+    averaged = model.averaged_generator()      # --ema_eval: prepared once, the weights do not change during the pass
+    kw = {} if averaged is None else {'netG': averaged}
     for data in dataset_val:
         model.set_input(data)
         with torch.no_grad():
-            model.forward(val_mode=True)
+            model.forward(val_mode=True, **kw)
         model.accum_accs()
         if img_dir is not None:
             name = os.path.splitext(os.path.basename(model.get_image_paths()[0]))[0]
