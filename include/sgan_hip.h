@@ -999,6 +999,56 @@ int sgan_tile_blend(const float* logits, int32_t ld, int32_t C, int32_t mode, in
 int sgan_tile_finish(const float* canvas, int32_t canvas_ld, int32_t H, int32_t W, int32_t C, const int32_t* Wy, const int32_t* Wx,
                      int32_t n_tta, float* prob, int32_t prob_ld, float* logp, int32_t logp_ld, void* stream);
 
+/* ---- differentiable augmentation of discriminator inputs (DiffAugment, Zhao et al. 2020; not in the reference, which trains its
+ * discriminators on the bare crops) ---------------------------------------------------------------------------------------------------
+ * util.diffaug_params / diffaug_ref / diffaug_bwd_ref are the NumPy fp64 restatement.  One image x[H][W][Cs] (padded
+ * NHWC fp32, C logical channels) and one 32-byte record sgan_diffaug_rec {b, a, ty, tx, cy0, cy1, cx0, cx1}:
+ *     m = mean of x over all pixels and the colour channels (the set bits of colour_mask), an fp64 sum in a fixed order, rounded once
+ *     K(h, w) = 0 inside the cutout cy0 <= h < cy1, cx0 <= w < cx1, 0 where (h + ty, w + tx) lies outside the image, else 1
+ *     y[h][w][c] = K(h, w) g_c(x[h + ty][w + tx][c]),  g_c(v) = a (v - m) + m + b on a colour channel, v on any other, 0 for c >= C
+ *   evaluated as t = v - m, u = fmaf(a, t, m) (skipped when a == 1), u + b (skipped when b == 0): the identity record copies bits.
+ *   Backward, n = colour channels x H x W, S = the sum of K(q) dy[q][c] over every q and colour c (fp64, fixed order):
+ *     dx[p][c] = fmaf(a, K(p - t) dy[p - t][c], (float)((1 - a) S / n)) on a colour channel when a != 1, K(p - t) dy[p - t][c] otherwise
+ *   Pixels with K = 0 are never read.  One 16-byte access per lane per group of 4 stored channels; no atomics: the same input and
+ *   record give the same bits on every run.
+ *
+ * sgan_diffaug_draw: one record per job into params_dev from Philox4x32-10 under `seed`: job j takes the blocks at counters
+ *   offset + 2 j (words w0..w3) and offset + 2 j + 1 (w4, w5), c2 = 0 -- whatever the policy, so that switching one operation off
+ *   does not move the others.  policy_bits: SGAN_DIFFAUG_TRANSLATION | _CUTOUT | _BRIGHTNESS | _CONTRAST.
+ *     b = (w0 >> 8) 2^-24 - 0.5 (else 0);  a = (w1 >> 8) 2^-24 + 0.5, one fp32 addition (else 1);  Sy = floor(H rt + 0.5), ty = -Sy + w2 mod (2 Sy + 1), tx
+ *     from w3 and W (else 0);  ch = floor(H rc + 0.5), oy = w4 mod (H + 1 - ch mod 2), cy0 = max(0, oy - ch / 2), cy1 = min(H, oy - ch / 2
+ *     + ch), cx0 / cx1 from w5 and W (else the empty rectangle 0, 0, 0, 0).  shapes: {H, W} per job, host memory.
+ *   One launch of one workgroup; `offset_dev` (a device uint64, NULL = 0) is read by the kernel and with advance != 0 moved on by
+ *   2 njobs, so a captured hipGraph draws afresh on every replay (sgan_normal_fill's convention).
+ * sgan_diffaug_multi_fwd / _bwd: every job {src, dst, H, W, C, Cs, colour_mask} of a step stage in one call; job j reads record j of
+ *   params_dev (written by sgan_diffaug_draw or by the caller).  For _bwd src is dy and dst is dx.
+ *   workspace == NULL: the contrast-free form, ONE launch; the record's `a` is not read and taken as 1 (the caller's policy has no
+ *   contrast).  Otherwise sgan_diffaug_workspace(njobs) bytes of device memory, 8-byte aligned, any content: TWO launches, the first
+ *   leaves every workgroup's partial fp64 sum in a slot of its own, the second sums a job's slots in a fixed order and transforms.
+ * Refused (status 1, nothing launched or written): njobs outside 1..8, a null or 16-byte-misaligned src / dst, src == dst, H or W
+ *   outside 1..32768, Cs not a multiple of 4 or outside 4..32, C outside 1..Cs, a colour_mask bit at or above C, H W Cs >= 2^31, rt or
+ *   rc outside [0, 1], unknown policy bits, a null params_dev. */
+#define SGAN_DIFFAUG_TRANSLATION 1
+#define SGAN_DIFFAUG_CUTOUT 2
+#define SGAN_DIFFAUG_BRIGHTNESS 4
+#define SGAN_DIFFAUG_CONTRAST 8
+#define SGAN_DIFFAUG_MAX_JOBS 8
+typedef struct sgan_diffaug_rec {
+    float b, a;
+    int32_t ty, tx, cy0, cy1, cx0, cx1;
+} sgan_diffaug_rec;
+typedef struct sgan_diffaug_job {
+    const float* src;
+    float* dst;
+    int32_t H, W, C, Cs;
+    uint32_t colour_mask;
+} sgan_diffaug_job;
+int64_t sgan_diffaug_workspace(int32_t njobs);
+int sgan_diffaug_draw(sgan_diffaug_rec* params_dev, const int32_t* shapes, int32_t njobs, int32_t policy_bits, double rt, double rc,
+                      uint64_t seed, uint64_t* offset_dev, int32_t advance, void* stream);
+int sgan_diffaug_multi_fwd(const sgan_diffaug_job* jobs, int32_t njobs, const sgan_diffaug_rec* params_dev, void* workspace, void* stream);
+int sgan_diffaug_multi_bwd(const sgan_diffaug_job* jobs, int32_t njobs, const sgan_diffaug_rec* params_dev, void* workspace, void* stream);
+
 /* ---- region statistics on the device (shape features of generated against real images: shape_stats.py) --------------------------
  * The reference's paper judges a generator by shape features of its cells and mitochondria; its repository holds only MATLAB that
  * loads precomputed features (experiments/plots).  These entries measure every region of a label map; util.region_table is the

@@ -88,6 +88,11 @@ class EmaSeg(C.Structure):
     _fields_ = [("shadow", C.c_void_p), ("p", C.c_void_p), ("n", C.c_int64)]
 
 
+class DiffaugJob(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("Cs", C.c_int32),
+                ("colour_mask", C.c_uint32)]
+
+
 # name -> argtypes; every entry returns int except the two string getters
 _P, _I, _L, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SIGNATURES = {
@@ -180,6 +185,10 @@ SIGNATURES = {
     "sgan_image_prep_tile": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P],
     "sgan_tile_blend": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P],
     "sgan_tile_finish": [_P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P, _I, _P],
+    "sgan_diffaug_workspace": [_I],
+    "sgan_diffaug_draw": [_P, C.POINTER(C.c_int32), _I, _I, C.c_double, C.c_double, C.c_uint64, _P, _I, _P],
+    "sgan_diffaug_multi_fwd": [C.POINTER(DiffaugJob), _I, _P, _P, _P],
+    "sgan_diffaug_multi_bwd": [C.POINTER(DiffaugJob), _I, _P, _P, _P],
     "sgan_confusion_accumulate": [_P, _I, _I, _P, _P, _I, _I, _L, _P, _P, _P],
     "sgan_thin_workspace": [_I, _I],
     "sgan_thin": [_P, _L, _I, _I, _P, _I, _P, _L, _P, _P, _P],
@@ -196,7 +205,8 @@ SIGNATURES = {
 RESTYPES = {"sgan_last_variant": C.c_char_p, "sgan_image_resize_workspace": C.c_int64, "sgan_rand_f_workspace": C.c_int64,
             "sgan_vinfo_workspace": C.c_int64, "sgan_thin_workspace": C.c_int64,
             "sgan_region_stats_workspace": C.c_int64, "sgan_object_match_workspace": C.c_int64,
-            "sgan_edt_workspace": C.c_int64, "sgan_boundary_workspace": C.c_int64, "sgan_clean_workspace": C.c_int64}      # everything else returns an int status
+            "sgan_edt_workspace": C.c_int64, "sgan_boundary_workspace": C.c_int64, "sgan_clean_workspace": C.c_int64,
+            "sgan_diffaug_workspace": C.c_int64}      # everything else returns an int status
 _lib = None
 
 

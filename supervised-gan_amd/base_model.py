@@ -18,6 +18,8 @@ class BaseModel:
     supports_ema = True       # --ema_decay / --use_ema: the models with ONE generator `netG` (fcgan, cgan, cgan2, segmentation, test); the
                               # cycle and two-stage trainers, which hold several, set it False
 
+    supports_diffaug = False  # --diffaug: the trainers whose backward_D / backward_G carry the hook (fcgan, cgan and what derives from it)
+
     def name(self):
         return 'BaseModel'
 
@@ -34,6 +36,12 @@ class BaseModel:
         if (getattr(opt, 'ema_decay', None) is not None or getattr(opt, 'use_ema', False)) and not self.supports_ema:
             raise NotImplementedError("--ema_decay / --use_ema average the one generator of fcgan, cgan, cgan2 and segmentation; "
                                       "--model %s is not among them" % getattr(opt, 'model', self.name()))
+
+        self.diffaug = None              # diffaug.DiffAugment under --diffaug (_init_diffaug)
+        if getattr(opt, 'diffaug', None) is not None and not self.supports_diffaug:
+            from .diffaug import SUPPORTED_MODELS
+            raise NotImplementedError("--diffaug augments the discriminator inputs of --model %s; --model %s is not among them"
+                                      % (', '.join(SUPPORTED_MODELS), getattr(opt, 'model', self.name())))
 
     def Tensor(self, *size):
         return torch.empty(*size, dtype=torch.float32, device=self.device)
@@ -96,6 +104,25 @@ class BaseModel:
     def _ema_nets(self):
         """checkpoint_nets() entry of the averaged generator: [('G_ema', netG_ema)] under --ema_decay, else nothing."""
         return [('G_ema', self.netG_ema)] if self.ema is not None else []
+
+    # ---- differentiable augmentation of the discriminator inputs (--diffaug; diffaug.DiffAugment, DESIGN.md R24) ---------------------
+    def _init_diffaug(self, has_netD=True):
+        """Under --diffaug (training only): self.diffaug, keyed by the trainer's seed.  Call it once _rng_seed is set."""
+        if not self.isTrain or getattr(self.opt, 'diffaug', None) is None:
+            return
+        from .diffaug import DiffAugment, check_options
+        if not has_netD:
+            raise ValueError("--diffaug with --which_model_netD None: there is no discriminator input to augment")
+        if getattr(self.opt, 'diffaug_policy', None) is None:      # an options object that did not go through parse()
+            check_options(self.opt)
+        self.diffaug = DiffAugment.from_options(self.opt, self._rng_seed, self.device)
+
+    def _augment(self, tensors, slot):
+        """The tensors a discriminator call is about to see, each through a transform drawn now (slots: DiffAugment.SLOTS); as they
+        are without --diffaug.  Sits between building fake / real and _d_losses, after the ImagePool query: the pool keeps plain images."""
+        if self.diffaug is None:
+            return tensors
+        return self.diffaug.augment(tensors, slot)
 
     def _file_label(self, net_label):
         """--use_ema (test side): netG is read from `<epoch>_net_G_ema.pth`."""

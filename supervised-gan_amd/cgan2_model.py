@@ -67,6 +67,7 @@ class CGAN2Model(CGANModel):
             netD.compute_param_grads = not skip
         a, b = self._pair(self.opt.train_G_on_fake_fake_pair)
         fake = b if self.opt.no_cgan else networks.cat_pair(a, b)
+        fake, = self._augment([fake], 2)
         trick = not self.opt.no_logD_trick
         self.loss_G_GAN, self._each_G = self._d_losses([(d, fake, trick) for d in self.netD],
                                                        [l if trick else -l for l in self.opt.lambda_D])

@@ -19,6 +19,8 @@ from .optim import FusedAdam
 
 
 class CGANModel(BaseModel):
+    supports_diffaug = True
+
     def name(self):
         return 'cGANModel'
 
@@ -69,6 +71,7 @@ class CGANModel(BaseModel):
             if self.gpu_ids:
                 networks.pack_flat(self.netD)
         self._init_ema(build_G)      # after netG's Philox key is set: the shadow takes it over
+        self._init_diffaug(self.has_netD)
         if not self.isTrain or opt.continue_train:
             self.load(opt.which_epoch)
 
@@ -169,6 +172,7 @@ class CGANModel(BaseModel):
         """loss_D = 0.5 * (sum_i GAN(D_i(fake), 0) + sum_i GAN(D_i(real), 1))   (cgan_model.py:158-182)"""
         fake = self._pooled(0).detach()
         real = self.real_B if self.opt.no_cgan else networks.cat_pair(self.real_A, self.real_B)
+        fake, real = self._augment([fake, real], 0)
         n = self.n_netD
         self.loss_D, self._each_D = self._d_losses([(d, fake, False) for d in self.netD] + [(d, real, True) for d in self.netD],
                                                    [0.5] * (2 * n))
@@ -180,6 +184,7 @@ class CGANModel(BaseModel):
         for netD in self.netD:
             netD.compute_param_grads = not skip
         fake = self.fake_B if self.opt.no_cgan else networks.cat_pair(self.real_A, self.fake_B)
+        fake, = self._augment([fake], 2)
         trick = not self.opt.no_logD_trick
         gan, self._each_G = self._d_losses([(d, fake, trick) for d in self.netD],
                                            [l if trick else -l for l in self.opt.lambda_D])

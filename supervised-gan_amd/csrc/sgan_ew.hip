@@ -2300,18 +2300,7 @@ extern "C" int sgan_ema_multi(const sgan_ema_seg* segs, int32_t nseg, float deca
 // ------------------------------------------------------------------------------------------
 // N(0,1) fill: Philox4x32-10, Box-Muller
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void sg_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                          uint32_t* out) {
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
+#include "sgan_philox.h"      // sg_philox, shared with sgan_diffaug.hip
 
 // advance_by != 0 (single-block launches only): the block moves the stream offset itself once every thread has read it
 // cs != 0: element i of the logical [C][H][W] tensor goes to the NHWC buffer position (i % hw) * cs + i / hw

@@ -21,6 +21,8 @@ from .optim import FusedAdam
 
 
 class FCGANModel(BaseModel):
+    supports_diffaug = True
+
     def name(self):
         return 'FCGANModel'
 
@@ -77,6 +79,7 @@ class FCGANModel(BaseModel):
             if self.gpu_ids:
                 networks.pack_flat(self.netD)   # one arena: single Adam segment, single gradient all-reduce
         self._init_ema(build_G)
+        self._init_diffaug()
         if not self.isTrain or opt.continue_train:
             self.load(opt.which_epoch)
 
@@ -231,8 +234,9 @@ class FCGANModel(BaseModel):
     def backward_D(self):
         """loss_D = 0.5 * (sum_i BCE(D_i(fake), 0) + sum_i BCE(D_i(real), 1))   (fcgan_model.py:146-163)"""
         fake = self._pooled(0).detach()
+        fake, real = self._augment([fake, self.real], 0)
         n = self.n_netD
-        self.loss_D, self._each_D = self._d_losses([(d, fake, False) for d in self.netD] + [(d, self.real, True) for d in self.netD],
+        self.loss_D, self._each_D = self._d_losses([(d, fake, False) for d in self.netD] + [(d, real, True) for d in self.netD],
                                                    [0.5] * (2 * n))
         self._backward(self.loss_D)
         self._join_streams()
@@ -244,7 +248,8 @@ class FCGANModel(BaseModel):
         for netD in self.netD:
             netD.compute_param_grads = not skip
         trick = not self.opt.no_logD_trick
-        self.loss_G, self._each_G = self._d_losses([(d, self.fake, trick) for d in self.netD],
+        fake, = self._augment([self.fake], 2)
+        self.loss_G, self._each_G = self._d_losses([(d, fake, trick) for d in self.netD],
                                                    [l if trick else -l for l in self.opt.lambda_D])
         for netD in self.netD:
             netD.compute_param_grads = True

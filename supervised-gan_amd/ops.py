@@ -1057,6 +1057,114 @@ def ema_multi(segs, decay, warmup, state):
     L.check(L.lib().sgan_ema_multi(arr, len(segs), float(decay), int(bool(warmup)), _ptr(state), _stream()), "sgan_ema_multi")
 
 
+# ------------------------------------------------------------------------------------------------
+# Differentiable augmentation of discriminator inputs (sgan_diffaug.hip).  A record is 8 words of device memory,
+# {b, a, ty, tx, cy0, cy1, cx0, cx1}: `records` below is an int32 [n, 8] tensor whose first two columns hold the bits of two floats.
+# ------------------------------------------------------------------------------------------------
+DIFFAUG_BITS = {'translation': 1, 'cutout': 2, 'brightness': 4, 'contrast': 8}      # SGAN_DIFFAUG_* of include/sgan_hip.h
+DIFFAUG_MAX_JOBS = 8
+
+
+def _diffaug_records(records, n, what):
+    if (records.dtype != torch.int32 or records.dim() != 2 or records.shape[1] != 8 or records.shape[0] < n or not records.is_contiguous()):
+        raise L.SganError(f"{what}: records must be a contiguous int32 [>= {n}, 8] tensor, got {tuple(records.shape)} {records.dtype}")
+    require_gpu(records, what)
+
+
+def diffaug_workspace(njobs, device):
+    """The fp64 slots sgan_diffaug_multi_fwd / _bwd need when a record may carry a contrast a != 1."""
+    nbytes = L.lib().sgan_diffaug_workspace(int(njobs))
+    if nbytes < 0:
+        raise L.SganError(f"diffaug_workspace: {njobs} jobs, 1..{DIFFAUG_MAX_JOBS} supported")
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def diffaug_draw(records, shapes, policy_bits, rt, rc, seed, offset_dev=None, advance=True):
+    """One sgan_diffaug_draw launch: record j of `records` for an image of shapes[j] = (H, W), from the Philox blocks at
+    offset + 2 j and offset + 2 j + 1 of the stream `seed`; `offset_dev` (device int64 [1]) moves on by 2 len(shapes) with `advance`."""
+    n = len(shapes)
+    _diffaug_records(records, n, "diffaug_draw")
+    arr = (C.c_int32 * (2 * max(n, 1)))(*[int(v) for hw in shapes for v in hw])
+    L.check(L.lib().sgan_diffaug_draw(_ptr(records), arr, n, int(policy_bits), float(rt), float(rc), C.c_uint64(seed & (2 ** 64 - 1)),
+                                      _ptr(offset_dev), int(bool(advance)), _stream()), "sgan_diffaug_draw")
+
+
+def _diffaug_multi(fn, what, srcs, dsts, Cs_real, colour_mask, records, workspace):
+    n = len(srcs)
+    _diffaug_records(records, n, what)
+    arr = (L.DiffaugJob * max(n, 1))()
+    for j, (s, d, Cr) in enumerate(zip(srcs, dsts, Cs_real)):
+        _act(s), _act(d)
+        require_gpu(s, what)
+        if not (s.is_contiguous() and d.is_contiguous() and s.shape == d.shape):
+            raise L.SganError(f"{what}: job {j} needs two contiguous [H, W, Cs] buffers of one shape, got {tuple(s.shape)} / {tuple(d.shape)}; "
+                              "nothing was launched")
+        H, W, Cs = s.shape
+        arr[j] = L.DiffaugJob(s.data_ptr(), d.data_ptr(), H, W, int(Cr), Cs, int(colour_mask))
+    if workspace is not None:
+        assert workspace.dtype == torch.float64 and workspace.is_contiguous() and workspace.numel() * 8 >= L.lib().sgan_diffaug_workspace(max(n, 1))
+        require_gpu(workspace, what)
+    L.check(fn(arr, n, _ptr(records), _ptr(workspace), _stream()), what)
+
+
+def diffaug_multi_fwd(srcs, dsts, Cs_real, colour_mask, records, workspace=None):
+    """One sgan_diffaug_multi_fwd call: dsts[j] = the transform of srcs[j] (padded NHWC buffers, Cs_real[j] logical channels) under
+    record j.  workspace None: the one-launch form, which takes every record's contrast as 1."""
+    _diffaug_multi(L.lib().sgan_diffaug_multi_fwd, "sgan_diffaug_multi_fwd", srcs, dsts, Cs_real, colour_mask, records, workspace)
+
+
+def diffaug_multi_bwd(dys, dxs, Cs_real, colour_mask, records, workspace=None):
+    """The adjoint of diffaug_multi_fwd under the same records: dxs[j] from dys[j]."""
+    _diffaug_multi(L.lib().sgan_diffaug_multi_bwd, "sgan_diffaug_multi_bwd", dys, dxs, Cs_real, colour_mask, records, workspace)
+
+
+class _DiffAugFn(torch.autograd.Function):
+    """The transform of several logical [1, C, H, W] tensors under consecutive records, one call forward; backward transforms the
+    gradients of the tensors that need one under the records the forward used (one call per run of consecutive such tensors)."""
+
+    @staticmethod
+    def forward(ctx, records, colour_mask, workspace, *xs):
+        xbs = [as_nhwc(x) for x in xs]
+        outs = [torch.empty_like(xb) for xb in xbs]
+        ctx.Cr = [x.shape[1] for x in xs]
+        diffaug_multi_fwd(xbs, outs, ctx.Cr, colour_mask, records, workspace)
+        ctx.records, ctx.colour_mask, ctx.workspace = records, colour_mask, workspace
+        ctx.outs = outs      # as _CatPairFn: the buffers outlive the call so that the views map back to them without a copy
+        return tuple(logical_view(o, c) for o, c in zip(outs, ctx.Cr))
+
+    @staticmethod
+    def backward(ctx, *gs):
+        n = len(gs)
+        dxs = [None] * n
+        j = 0
+        while j < n:
+            if not ctx.needs_input_grad[3 + j] or gs[j] is None:
+                j += 1
+                continue
+            k = j
+            while k < n and ctx.needs_input_grad[3 + k] and gs[k] is not None:
+                k += 1
+            gbs = [as_nhwc(g) for g in gs[j:k]]
+            dbs = [torch.empty_like(gb) for gb in gbs]
+            diffaug_multi_bwd(gbs, dbs, ctx.Cr[j:k], ctx.colour_mask, ctx.records[j:], ctx.workspace)
+            for i, db in enumerate(dbs):
+                dxs[j + i] = logical_view(db, ctx.Cr[j + i])
+            j = k
+        return (None, None, None) + tuple(dxs)
+
+
+def diffaug(x, state, slot=0):
+    """DiffAugment of a logical [1, C, H, W] tensor -- or of a list of them in one launch -- under the records state.records[slot],
+    state.records[slot + 1], ... (written by diffaug_draw, or by the caller), with state.colour_mask and state.workspace (None: no
+    record carries a contrast).  Differentiable: backward calls sgan_diffaug_multi_bwd with the same records; a tensor that needs no
+    gradient records no backward.  The records must not be redrawn between this call and its backward."""
+    xs = list(x) if isinstance(x, (list, tuple)) else [x]
+    for t in xs:
+        require_gpu(t, "diffaug")
+    outs = _DiffAugFn.apply(state.records[slot: slot + len(xs)], int(state.colour_mask), state.workspace, *xs)
+    return list(outs) if isinstance(x, (list, tuple)) else outs[0]
+
+
 def lbfgs_advance(state, J, n, x, grad, loss, d, prev_grad, hist_s, hist_y, hist_rho):
     """One sgan_lbfgs_advance launch over J problems of n unknowns (supervised_gan_amd.lbfgs.DeviceLBFGS owns the buffers).
     x, grad: [J, >= n] fp32 with unit element stride; loss: [J] fp32."""

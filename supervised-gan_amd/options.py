@@ -139,6 +139,7 @@ class BaseOptions:
         check_elastic_options(self.opt)
         check_tile_options(self.opt, self.parser)
         check_ema_options(self.opt, self.parser)
+        check_diffaug_options(self.opt, self.parser)
         if self.opt.math is not None:
             from . import ops
             ops.set_math(self.opt.math)
@@ -253,6 +254,18 @@ def check_ema_options(opt, parser=None):
         raise ValueError(bad)
 
 
+def check_diffaug_options(opt, parser=None):
+    """--diffaug POLICY (train options; diffaug.check_options): known operations, a supported --model with discriminators, ratios of
+    0 .. 1 and, for a colour operation, a colour channel in the discriminator input.  Refused at parse time; leaves opt.diffaug_policy."""
+    from .diffaug import check_options
+    try:
+        check_options(opt)
+    except ValueError as e:
+        if parser is not None:
+            parser.error(str(e))
+        raise
+
+
 def check_elastic_options(opt):
     """--elastic G SIGMA deforms the crops of the image-folder feeders (data.py): G cells a side, 1..13 (the device stages the (G + 3)^2
     control vectors, at most 256); SIGMA >= 0 source pixels.  Leaves opt.elastic as (int G, float SIGMA)."""
@@ -349,6 +362,16 @@ class TrainOptions(BaseOptions):
                                                     'dominated by the initial weights')
         a('--ema_eval', action='store_true', help='--ema_decay: test() and the validation pass of train_ss.py (and so --best_metric) run '
                                                   'the averaged generator')
+        # differentiable augmentation of the discriminator inputs (DiffAugment, Zhao et al. 2020; not in the reference)
+        a('--diffaug', type=str, default=None, metavar='POLICY',
+          help='fcgan / cgan / cgan2 / segmentation with discriminators: a comma list of translation, cutout, brightness, contrast '
+               '(color = brightness,contrast); every tensor a discriminator sees, real and fake, goes through one random transform '
+               'and the generator\'s gradient flows back through it (inside the graphed step).  Unset: off')
+        a('--diffaug_translation', type=float, default=0.125, help='--diffaug translation: largest shift as a fraction of the side')
+        a('--diffaug_cutout', type=float, default=0.5, help='--diffaug cutout: side of the zeroed square as a fraction of the side')
+        a('--diffaug_color_channels', type=str, default='b',
+          help='letters of the RGB channels that hold the image (letters as in --elastic_label_channels): brightness and contrast touch '
+               'these channels of the discriminator input only (default b: the reference keeps labels in r and g and the image in b)')
         self.isTrain = True
 
 

@@ -211,6 +211,7 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
         for netD in self.netD:
             netD.compute_param_grads = not skip
         fake = self.fake_B if self.opt.no_cgan else networks.cat_pair(self.real_A, self.fake_B)
+        fake, = self._augment([fake], 2)
         self.loss_G_GAN, self._each_G = self._d_losses([(d, fake, True) for d in self.netD], list(self.opt.lambda_D))
         for netD in self.netD:
             netD.compute_param_grads = True

@@ -5,7 +5,8 @@ thinning both scores are ranked after: `thin`, `compute_thinned_scores`), and th
 border term of the U-Net loss (`border_weight_map`, the yardstick of the device's sgan_border_weight), and the elastic deformation of
 a training crop (`elastic_field`, `elastic_prep`, the yardsticks of the device's sgan_image_prep_elastic), and the geometry of
 whole-image inference (`tile_plan`, `tile_window`, `prep_tile_ref`, `blend_tiles_ref`, the yardsticks of sgan_image_prep_tile /
-sgan_tile_blend / sgan_tile_finish)."""
+sgan_tile_blend / sgan_tile_finish), and the augmentation of discriminator inputs (`diffaug_params`, `diffaug_ref`,
+`diffaug_bwd_ref`, the yardsticks of sgan_diffaug_draw / sgan_diffaug_multi_fwd / sgan_diffaug_multi_bwd)."""
 import os
 
 import numpy as np
@@ -745,3 +746,96 @@ def boundary_scores(counts, sums, tolerance):
     return OrderedDict([('BoundF', boundary_pr(counts, tolerance)[2]),
                         ('HausD', float(sums[2]) / n_h if n_h else 0.0),
                         ('ASSD', (float(sums[0]) + float(sums[1])) / n_d if n_d else 0.0)])
+
+
+# ---- differentiable augmentation of discriminator inputs (--diffaug; the yardsticks of sgan_diffaug.hip) -----------------
+DIFFAUG_OPS = ('translation', 'cutout', 'brightness', 'contrast')
+
+
+def _philox4x32_10(ctr, key):
+    """The four 32-bit words of Philox4x32-10 (Salmon et al.) for the 64-bit block counter `ctr` (c2 = c3 = 0) under the 64-bit `key`,
+    in Python integers."""
+    c = [ctr & 0xFFFFFFFF, (ctr >> 32) & 0xFFFFFFFF, 0, 0]
+    k0, k1 = key & 0xFFFFFFFF, (key >> 32) & 0xFFFFFFFF
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c[0], 0xCD9E8D57 * c[2]
+        c = [(p1 >> 32) ^ c[1] ^ k0, p1 & 0xFFFFFFFF, (p0 >> 32) ^ c[3] ^ k1, p0 & 0xFFFFFFFF]
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return c
+
+
+def diffaug_params(seed, offset, shapes, policy, rt=0.125, rc=0.5):
+    """The records sgan_diffaug_draw writes for images of shapes = [(H, W), ...]: one tuple (b, a, ty, tx, cy0, cy1, cx0, cx1) per
+    image, b and a Python floats holding fp32 values (b exactly the formula's; a the formula's rounded to fp32, as the device's one
+    addition rounds it), the rest integers.  Image j takes the Philox blocks at counters offset + 2 j
+    (words w0..w3) and offset + 2 j + 1 (w4, w5) under the key `seed`, whatever `policy` (an iterable of DIFFAUG_OPS) switches on; the
+    stream moves on by 2 len(shapes)."""
+    policy = set(policy)
+    assert policy <= set(DIFFAUG_OPS), policy
+    seed, offset = int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1)
+    recs = []
+    for j, (H, W) in enumerate(shapes):
+        w = _philox4x32_10((offset + 2 * j) & (2 ** 64 - 1), seed) + _philox4x32_10((offset + 2 * j + 1) & (2 ** 64 - 1), seed)
+        b = (w[0] >> 8) * 2.0 ** -24 - 0.5 if 'brightness' in policy else 0.0
+        a = float(np.float32((w[1] >> 8) * 2.0 ** -24 + 0.5)) if 'contrast' in policy else 1.0      # one fp32 addition: 23 fraction bits from 1 up
+        ty = tx = 0
+        if 'translation' in policy:
+            Sy, Sx = int(np.floor(H * rt + 0.5)), int(np.floor(W * rt + 0.5))
+            ty, tx = -Sy + w[2] % (2 * Sy + 1), -Sx + w[3] % (2 * Sx + 1)
+        cy0 = cy1 = cx0 = cx1 = 0
+        if 'cutout' in policy:
+            ch, cw = int(np.floor(H * rc + 0.5)), int(np.floor(W * rc + 0.5))
+            oy, ox = w[4] % (H + 1 - ch % 2), w[5] % (W + 1 - cw % 2)
+            cy0, cy1 = max(0, oy - ch // 2), min(H, oy - ch // 2 + ch)
+            cx0, cx1 = max(0, ox - cw // 2), min(W, ox - cw // 2 + cw)
+        recs.append((b, a, ty, tx, cy0, cy1, cx0, cx1))
+    return recs
+
+
+def _diffaug_visible(rec, H, W):
+    """K [H, W] of a record: 0 inside the cutout and where the shifted source pixel lies outside the image."""
+    _, _, ty, tx, cy0, cy1, cx0, cx1 = rec
+    h, w = np.arange(H)[:, None], np.arange(W)[None, :]
+    cut = (h >= cy0) & (h < cy1) & (w >= cx0) & (w < cx1)
+    inside = (h + ty >= 0) & (h + ty < H) & (w + tx >= 0) & (w + tx < W)
+    return (~cut & inside).astype(np.float64)
+
+
+def _diffaug_shift(x, ty, tx):
+    """out[h][w] = x[h + ty][w + tx], 0 where that lies outside (x: [H, W, C])."""
+    H, W = x.shape[:2]
+    out = np.zeros_like(x)
+    h0, h1, w0, w1 = max(0, -ty), min(H, H - ty), max(0, -tx), min(W, W - tx)
+    if h0 < h1 and w0 < w1:
+        out[h0:h1, w0:w1] = x[h0 + ty:h1 + ty, w0 + tx:w1 + tx]
+    return out
+
+
+def diffaug_ref(x, rec, colour_mask):
+    """DiffAugment of one image x [H, W, C] under one record, in float64: on the channels whose bit of `colour_mask` is set
+    g(v) = a (v - m) + m + b with m the mean of x over all pixels and those channels, the other channels as they are; then
+    y[h][w] = K(h, w) g(x[h + ty][w + tx])."""
+    x = np.asarray(x, dtype=np.float64)
+    H, W, C = x.shape
+    b, a, ty, tx = rec[:4]
+    col = np.array([(int(colour_mask) >> c) & 1 for c in range(C)], dtype=bool)
+    g = x.copy()
+    if col.any():
+        m = x[:, :, col].mean()
+        g[:, :, col] = a * (x[:, :, col] - m) + m + b
+    return _diffaug_visible(rec, H, W)[:, :, None] * _diffaug_shift(g, ty, tx)
+
+
+def diffaug_bwd_ref(dy, rec, colour_mask):
+    """The adjoint of diffaug_ref at the same record, in float64: dx[p][c] = a_c K(p - t) dy[p - t][c], plus on the colour channels
+    (1 - a) S / n with S the sum of K dy over them and n their element count (the gradient through the mean)."""
+    dy = np.asarray(dy, dtype=np.float64)
+    H, W, C = dy.shape
+    b, a, ty, tx = rec[:4]
+    col = np.array([(int(colour_mask) >> c) & 1 for c in range(C)], dtype=bool)
+    kdy = _diffaug_visible(rec, H, W)[:, :, None] * dy
+    dx = _diffaug_shift(kdy, -ty, -tx)
+    if col.any():
+        S = kdy[:, :, col].sum()
+        dx[:, :, col] = a * dx[:, :, col] + (1.0 - a) * S / (int(col.sum()) * H * W)
+    return dx
