@@ -972,6 +972,48 @@ int64_t sgan_clean_workspace(int32_t H, int32_t W);
 int sgan_clean_wall(const float* plane, int64_t pix_stride, int32_t H, int32_t W, int32_t close_rsq, int32_t min_wall, int32_t min_cell,
                     float* out, int64_t* acc, void* workspace, int64_t workspace_bytes, int32_t* dev_err, void* stream);
 
+/* ---- splitting merged cells at wall gaps: a core-seeded flood of the free space and a cut where two floods meet -------------------
+ * One gap in a wall merges two cells into one component.  A closing only mends gaps narrower than its disk; this stage cuts a gap of
+ * any length at its neck, as long as the neck is narrower than the cells on either side: the distance transform of the free space,
+ * one marker per "core" (where the distance to the wall is large), the markers grown back, a wall set where two markers meet.
+ * util.split_cells is the NumPy / scipy restatement these entries are tested against.  All integers.
+ *
+ * The plane is read as sgan_ccl_label reads it: pixel (y, x) at plane[(y * W + x) * pix_stride], wall when x > 0.5 (a NaN and an
+ * exact 0.5 are not wall).  Parameters: split_rsq in 1 .. 4096, a squared Euclidean radius; max_rounds in 1 .. 4096.
+ *   1. d = edt_sq(wall).  A plane without wall (d == -1 everywhere) has no core: out is the empty wall map.
+ *   2. Cores: core = {p free : d(p) >= split_rsq}; its 8-connected components, each labelled 1 + its smallest raster index.
+ *   3. Flood: g(p) = the length of the shortest 8-connected path through free pixels from the free pixel p to a core pixel (0 on a
+ *      core).  If g(p) <= max_rounds, L(p) = the smallest core label among the core components at geodesic distance exactly g(p) from
+ *      p; otherwise, and on the wall, L(p) = 0.  This is max_rounds synchronous rounds of "an unlabelled free pixel takes the smallest
+ *      label among its 8 labelled neighbours of the round before", so it does not depend on scheduling.
+ *   4. Cut: a free pixel p with L(p) != 0 becomes wall when one of its neighbours E, SW, S, SE inside the image has L(q) != 0 and
+ *      L(q) != L(p).  Every 8-adjacent pair falls under this rule for one of its members: afterwards no two free 8-adjacent pixels
+ *      carry different nonzero labels.  A cell without a core, a cell with one core and what the budget did not reach are never cut.
+ *   5. out = wall | cut, a dense float [H * W] plane of 0.0 / 1.0, which sgan_ccl_label, sgan_thin, sgan_edt_sq and sgan_clean_wall
+ *      read as it lies; it may not alias the plane.
+ *   acc (optional, int64[SGAN_SPLIT_COUNTS], caller-owned on the device, zeroed by the caller once, pooled over a dataset):
+ *     [0] += core components;  [1] += cut pixels set;  [2] += free pixels with L != 0;  [3] += rounds that labelled at least one
+ *     pixel;  [4] += 1 if round max_rounds still labelled something (the budget was hit);  [5] += 1 (images).  Exact integers,
+ *     identical in every scheduling order.
+ *
+ * sgan_split_workspace: bytes of the workspace sgan_split_cells needs for an H x W plane (< 0: bad shape).
+ * sgan_split_cells: the launch sequence depends on (H, W, max_rounds) only; nothing is read back and nothing is decided on the host,
+ *   so the call captures into a hipGraph and replays on a plane that needs any other number of rounds.  sgan_edt_sq; a threshold
+ *   pass that writes the core plane and zeroes the round counters; sgan_ccl_label of it; ceil(max_rounds / 8) flood launches of up
+ *   to 8 rounds each (a 48 x 32 core with an 8-pixel halo of int32 labels in LDS, two label planes ping-ponged between launches);
+ *   one cut-and-emit pass that also finishes the counters.  Per-round "labelled something" counters in the workspace carry
+ *   convergence: a flood launch whose predecessor's last round labelled nothing returns at once.  No floating point after the
+ *   threshold; atomics only on integer counters and flags.
+ *   The workspace (16-byte aligned) may hold anything on entry.  dev_err as sgan_clean_wall: required; bit 1 from the labelling, and
+ *   bit 64 when round max_rounds still labelled something -- out is then still the map defined above, for that budget.  Shapes as
+ *   sgan_edt_sq.  Returns 1, the reason in sgan_last_error and nothing launched, for a null required pointer (acc alone is
+ *   optional), a bad shape, a pixel stride < 1, split_rsq or max_rounds outside 1 .. 4096, out == plane, and a short or misaligned
+ *   workspace. */
+#define SGAN_SPLIT_COUNTS 6
+int64_t sgan_split_workspace(int32_t H, int32_t W);
+int sgan_split_cells(const float* plane, int64_t pix_stride, int32_t H, int32_t W, int32_t split_rsq, int32_t max_rounds, float* out,
+                     int64_t* acc, void* workspace, int64_t workspace_bytes, int32_t* dev_err, void* stream);
+
 /* ---- whole-image inference: overlap tiles with blended seams, averaged over the 8 flips and rotations (not in the reference, whose
  * test_ss.py scores one crop; the overlap-tile strategy of Ronneberger et al. 2015, section 2) ------------------------------------
  * util.tile_plan / tile_window / prep_tile_ref / blend_tiles_ref are the NumPy restatement.  Per axis of length L: the

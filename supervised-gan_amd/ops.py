@@ -1315,6 +1315,8 @@ BOUNDARY_COUNTS = (tuple('hist_s_%d' % k for k in range(BOUNDARY_BINS)) + tuple(
                    + tuple('zero%d' % k for k in range(72, 80)))
 BOUNDARY_SUMS = ('sum_d_s', 'sum_d_t', 'sum_haus', 'zero3')
 CLEAN_COUNTS = ('closed_pixels', 'wall_components_removed', 'wall_pixels_removed', 'cells_filled', 'cell_pixels_filled', 'images')      # acc of clean_wall (SGAN_CLEAN_COUNTS)
+SPLIT_COUNTS = ('core_components', 'cut_pixels', 'labelled_pixels', 'rounds', 'budget_hits', 'images')      # acc of split_cells (SGAN_SPLIT_COUNTS)
+SPLIT_BUDGET_BIT = 64      # metric_err: split_cells' last round still labelled something; the map is complete for that budget, so no error
 VINFO_PARTS = ('SA', 'SB', 'SAB', 'aux', 'm', 'H_S', 'H_T', 'I', 'VInfo', 'split', 'merge')      # parts_out of vinfo_accumulate
 
 
@@ -1333,6 +1335,7 @@ def check_metric_err(device):
     code = int(e.item()) if e is not None else 0
     if code:
         e.zero_()
+    if code & ~SPLIT_BUDGET_BIT:      # a split budget that was hit is counted in SPLIT_COUNTS; its map is what the budget defines
         raise L.SganError(f"segmentation metric kernels gave up on part of their input (flags {code:#x}: 1 = union-find bound, "
                           "2 = pair table full, 4 / 8 = label out of range, 16 = thinning budget ran out, 32 = region table full); the accumulated values are incomplete")
 
@@ -1583,6 +1586,33 @@ def clean_wall(plane, close_rsq=0, min_wall=0, min_cell=0, out=None, acc=None, w
     ws = clean_workspace(H, W, dev) if workspace is None else workspace
     L.check(L.lib().sgan_clean_wall(_ptr(plane), plane.stride(1), H, W, int(close_rsq), int(min_wall), int(min_cell), _ptr(out), _ptr(acc),
                                     _ptr(ws), ws.numel() * ws.element_size(), _ptr(metric_err(dev)), _stream()), "sgan_clean_wall")
+    return out
+
+
+def split_workspace(H, W, device):
+    """The scratch of split_cells for H x W planes (edt_sq's workspace, the dsq plane, the core plane, two label planes and the round
+    counters), cached per (H, W, device) like clean_workspace; the kernels initialise what they use."""
+    return _metric_workspace("sgan_split_workspace", H, W, device)
+
+
+def split_cells(plane, split_rsq, max_rounds=64, out=None, acc=None, workspace=None):
+    """The wall map of the pixels of `plane` [H, W] that are > 0.5 with merged cells cut apart (sgan_split_cells; util.split_cells is
+    the host yardstick): the cores of the free space (distance^2 to the wall >= split_rsq) are labelled, flooded back through the
+    free pixels for max_rounds synchronous rounds, and a wall pixel is set where two different labels meet.  float32 [H, W] of
+    0.0 / 1.0, which ccl_label, thin, edt_sq and clean_wall read as it lies.  acc (int64[6] on the device, SPLIT_COUNTS) is added to.
+    A budget that was hit raises SPLIT_BUDGET_BIT of metric_err and acc[4]; the map is then the one for that budget.  Only
+    enqueues -- the launch sequence depends on the shape and max_rounds alone -- and reads `plane` in place when its rows are W
+    pixel strides apart."""
+    plane = _plane(plane, "split_cells")
+    H, W = plane.shape
+    dev = plane.device
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.float32, device=dev)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == H * W and out.device == dev
+    assert _is_acc(acc, torch.int64, len(SPLIT_COUNTS), dev)
+    ws = split_workspace(H, W, dev) if workspace is None else workspace
+    L.check(L.lib().sgan_split_cells(_ptr(plane), plane.stride(1), H, W, int(split_rsq), int(max_rounds), _ptr(out), _ptr(acc), _ptr(ws),
+                                     ws.numel() * ws.element_size(), _ptr(metric_err(dev)), _stream()), "sgan_split_cells")
     return out
 
 

@@ -67,6 +67,8 @@ class BaseOptions:
         a('--clean_close', type=float, default=0.0)           # clean the predicted wall before the label-based scores: close gaps with a disk of this radius, close_rsq = floor(R * R); 1 = the 4-neighbour plus, 1.5 = the 3 x 3 box; at most 64
         a('--clean_min_wall', type=int, default=0)            # ... then drop 8-connected wall components with fewer pixels than this
         a('--clean_min_cell', type=int, default=0)            # ... then fill 8-connected regions with fewer pixels than this (seg_metrics.py; all three off: the raw thresholded map)
+        a('--clean_split', type=float, default=0.0)           # ... and, between the specks and the small cells, cut merged cells apart: cores where the distance to the wall is >= this radius, split_rsq = floor(R * R), flooded back, a wall where two meet; 0 = off, at most 64
+        a('--clean_split_rounds', type=int, default=64)       # ... flood rounds of --clean_split (one per pixel of distance from a core): 1 .. 4096
         a('--boundary_tolerance', type=int, default=2, choices=range(31), metavar='0..30')      # BoundF: a wall pixel within this many pixels of the other map's wall is matched
         a('--boundary_thin', action='store_true')             # BoundF / HausD / ASSD: thin the predicted wall to one-pixel lines first, as BSDS does; the truth is not thinned
         a('--add_background_onehot', action='store_true')
@@ -182,16 +184,29 @@ def check_border_options(opt):
 
 def check_clean_options(opt, parser=None):
     """--clean_close R, --clean_min_wall N, --clean_min_cell N: none negative, R at most 64 (close_rsq = floor(R R) <= 4096, the
-    library's limit); refused at parse time."""
+    library's limit); --clean_split R: 0 or 1 .. 64, --clean_split_rounds N: 1 .. 4096; refused at parse time."""
     bad = None
     if not 0.0 <= opt.clean_close <= 64.0:      # a NaN fails both comparisons
         bad = "--clean_close: a radius of 0 .. 64 pixels (got %g)" % opt.clean_close
     elif opt.clean_min_wall < 0 or opt.clean_min_cell < 0:
         bad = "--clean_min_wall / --clean_min_cell: a pixel count, not negative (got %d / %d)" % (opt.clean_min_wall, opt.clean_min_cell)
+    elif not 0.0 <= getattr(opt, 'clean_split', 0.0) <= 64.0:
+        bad = "--clean_split: a radius of 0 .. 64 pixels (got %g)" % opt.clean_split
+    elif 0.0 < getattr(opt, 'clean_split', 0.0) < 1.0:
+        bad = "--clean_split: a radius below 1 has no core (split_rsq = floor(R R) = 0); 0 = off (got %g)" % opt.clean_split
+    elif not 1 <= getattr(opt, 'clean_split_rounds', 64) <= 4096:
+        bad = "--clean_split_rounds: 1 .. 4096 (got %d)" % opt.clean_split_rounds
     if bad is not None:
         if parser is not None:
             parser.error(bad)
         raise ValueError(bad)
+
+
+def split_params(opt):
+    """(split_rsq, max_rounds) of ops.split_cells from --clean_split / --clean_split_rounds; split_rsq 0 = off, also for an options
+    object without them."""
+    r = float(getattr(opt, 'clean_split', 0.0))
+    return int(math.floor(r * r)), int(getattr(opt, 'clean_split_rounds', 64))
 
 
 def clean_params(opt):

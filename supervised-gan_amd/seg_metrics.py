@@ -12,7 +12,10 @@ pixel scores NaN, and the NaN stays in the running sum until reset(), as in the 
 it before read().
 
 With --clean_close / --clean_min_wall / --clean_min_cell the predicted plane of every label-based score is the CLEANED wall map
-(ops.clean_wall: gaps closed with a disk, wall specks dropped, small regions filled), made once per accumulate().  meanIU and the
+(ops.clean_wall: gaps closed with a disk, wall specks dropped, small regions filled), made once per accumulate().  With
+--clean_split the merged cells of that map are cut apart (ops.split_cells) between the specks and the small cells: the stages run in
+the order close, specks, split, small cells -- splitting can shave slivers off a cell, which --clean_min_cell is there to fill -- as
+clean_wall without min_cell, split_cells, and clean_wall with min_cell alone.  meanIU and the
 confusion matrix stay on the logits: they are per-pixel class scores, and may be multi-class."""
 from collections import OrderedDict
 from functools import cached_property
@@ -21,7 +24,7 @@ import numpy as np
 import torch
 
 from . import ops, util
-from .options import clean_params
+from .options import clean_params, split_params
 
 # Every device accumulator: name, dtype, shape (k: the classes of the confusion matrix).  Each is made the first time a score adds
 # to it; reset(), read() and counts() walk this table.
@@ -39,6 +42,8 @@ ACCUMULATORS = (
 # The counters of the cleaning stage, made only when a --clean_* option is set; beside ACCUMULATORS, and walked with it.
 CLEAN_ACCUMULATORS = (
     ('clean_i', torch.int64, (len(ops.CLEAN_COUNTS),)),           # ops.clean_wall's pooled counters
+    ('clean_post_i', torch.int64, (len(ops.CLEAN_COUNTS),)),      # ... of the second call, small cells after --clean_split (its own image count)
+    ('split_i', torch.int64, (len(ops.SPLIT_COUNTS),)),           # ops.split_cells' pooled counters
 )
 COUNTS = {'objects': ('obj_i', 'obj_f', ops.OBJECT_COUNTS, ops.OBJECT_SUMS),
           'boundary': ('bnd_i', 'bnd_f', ops.BOUNDARY_COUNTS, ops.BOUNDARY_SUMS)}
@@ -59,10 +64,21 @@ class _Planes:
     @cached_property
     def s(self):
         """The predicted plane every label-based score reads: channel 0 as it lies, or its cleaned wall map with a --clean_* option."""
-        clean = clean_params(self.m.opt)
-        if not any(clean):
-            return self.fake_B.detach()[0, 0]
-        return ops.clean_wall(self.fake_B.detach()[0, 0], *clean, out=self._store('cleaned', torch.float32), acc=self.m._acc('clean_i'))
+        clean, (split_rsq, rounds) = clean_params(self.m.opt), split_params(self.m.opt)
+        s = self.fake_B.detach()[0, 0]
+        if not split_rsq:
+            if not any(clean):
+                return s
+            return ops.clean_wall(s, *clean, out=self._store('cleaned', torch.float32), acc=self.m._acc('clean_i'))
+        # close, specks | split | small cells: two planes are ping-ponged, the last stage that runs writes 'cleaned'
+        close_rsq, min_wall, min_cell = clean
+        last, other = ('cleaned', 'cleaned_mid') if not min_cell else ('cleaned_mid', 'cleaned')
+        if close_rsq or min_wall:
+            s = ops.clean_wall(s, close_rsq, min_wall, 0, out=self._store(other, torch.float32), acc=self.m._acc('clean_i'))
+        s = ops.split_cells(s, split_rsq, rounds, out=self._store(last, torch.float32), acc=self.m._acc('split_i'))
+        if min_cell:
+            s = ops.clean_wall(s, 0, 0, min_cell, out=self._store('cleaned', torch.float32), acc=self.m._acc('clean_post_i'))
+        return s
 
     @cached_property
     def t(self):
@@ -125,8 +141,8 @@ class SegMetrics:
 
     @property
     def cleaned(self):
-        """The cleaned predicted wall map as the last accumulate() left it (float32 [H, W] of 0.0 / 1.0), or None without a --clean_*
-        option.  Read only."""
+        """The cleaned predicted wall map as the last accumulate() left it (float32 [H, W] of 0.0 / 1.0; after every stage that is on,
+        --clean_split included), or None without a --clean_* option.  Read only."""
         return self.planes.get('cleaned')
 
     def accumulate(self, fake_B, real_B, logit, label, which=None):
@@ -139,7 +155,8 @@ class SegMetrics:
         below --min_object_area left out.  meanIU: conf[label, prediction] += 1 for every pixel (segm_model.py:309-331).
         BoundF .. ASSD: how far every predicted wall pixel lies from the true wall and every true wall pixel from the predicted one
         (ops.boundary_accumulate).
-        With a --clean_* option all of these but meanIU read the cleaned prediction (ops.clean_wall, once per call)."""
+        With a --clean_* option all of these but meanIU read the cleaned prediction (ops.clean_wall, once per call; with
+        --clean_split ops.split_cells between its specks and its small cells)."""
         o = self.opt
         which = o.which_metric if which is None else which
         if any(k in which for k in SCORES if k != 'meanIU'):      # the scores of the label maps and of the walls
@@ -171,16 +188,21 @@ class SegMetrics:
             ops.rand_f_accumulate(t_labels, s_labels, self._acc(rand))
 
     def counts(self, which):
-        """'clean': the six pooled integers of ops.CLEAN_COUNTS (pixels set by the closing, wall components / pixels removed, cells /
+        """'split': the six pooled integers of ops.SPLIT_COUNTS (core components, cut pixels, labelled pixels, rounds, budget hits,
+        images).  'clean': the six pooled integers of ops.CLEAN_COUNTS (pixels set by the closing, wall components / pixels removed, cells /
         cell pixels filled, images).  Otherwise the pooled numbers of 'objects' (the 16 integers of ops.OBJECT_COUNTS: TP_0 .. TP_9 at IoU > 0.5 .. 0.95, N_t, N_s, images,
         SEGn; the two sums of ops.OBJECT_SUMS) or 'boundary' (the 80 integers of ops.BOUNDARY_COUNTS: the two histograms by distance
         bin, N_s, N_t, images, ...; the four sums of ops.BOUNDARY_SUMS) since reset(), as a dict.  Synchronises, like read()."""
         if which == 'clean':
-            ints = [0] * len(ops.CLEAN_COUNTS)
-            if 'clean_i' in self.acc:
+            if 'clean_i' in self.acc or 'clean_post_i' in self.acc:
                 ops.check_metric_err(self.device)
-                ints = self.acc['clean_i'].cpu().tolist()
-            return OrderedDict(zip(ops.CLEAN_COUNTS, ints))
+            return OrderedDict(zip(ops.CLEAN_COUNTS, self._clean_counts()))
+        if which == 'split':
+            ints = [0] * len(ops.SPLIT_COUNTS)
+            if 'split_i' in self.acc:
+                ops.check_metric_err(self.device)
+                ints = self.acc['split_i'].cpu().tolist()
+            return OrderedDict(zip(ops.SPLIT_COUNTS, ints))
         acc_i, acc_f, names_i, names_f = COUNTS[which]
         ints, sums = [0] * len(names_i), [0.0] * len(names_f)
         if acc_i in self.acc:
@@ -188,13 +210,19 @@ class SegMetrics:
             ints, sums = self.acc[acc_i].cpu().tolist(), self.acc[acc_f].cpu().tolist()
         return OrderedDict(list(zip(names_i, ints)) + list(zip(names_f, sums)))
 
+    def _clean_counts(self):
+        """The pooled CLEAN_COUNTS: with --clean_split the two clean_wall calls of an image count into accumulators of their own, whose
+        stage counters add up and whose image counts are the same number."""
+        a, b = ([0] * len(ops.CLEAN_COUNTS) if n not in self.acc else self.acc[n].cpu().tolist() for n in ('clean_i', 'clean_post_i'))
+        return [x + y for x, y in zip(a[:5], b[:5])] + [max(a[5], b[5])]
+
     def read(self):
         """Reads the accumulators and derives every score from them into self.values; returns the ones --which_metric names, in the
         order RandScore, VInfo, meanIU, RandScoreThin, VInfoThin, then ObjF1 / ObjAP / SEG / PQ (util.object_scores of the pooled
         counts), then BoundF / HausD / ASSD (util.boundary_scores at --boundary_tolerance).  Built for evaluation (test_ss.py) it also
         prints the pooled TP_k / N_t / N_s line when an object score was taken, and the boundary precision / recall / F at the
         tolerances 0 .. 5 with the dataset's worst distance when a boundary score was, and the pooled counts of the cleaning stage
-        when a --clean_* option ran it."""
+        when a --clean_* option ran it, then those of --clean_split."""
         o, v = self.opt, self.values
         if self.acc:
             ops.check_metric_err(self.device)
@@ -217,10 +245,14 @@ class SegMetrics:
                       % (' '.join('%.4f/%.4f/%.4f' % util.boundary_pr(bnd_i, tol) for tol in range(6)),
                          float(np.sqrt(float(max(bnd_i[bc('max_dsq_s')], bnd_i[bc('max_dsq_t')])))), bnd_i[bc('N_s')], bnd_i[bc('N_t')],
                          ', prediction thinned' if o.boundary_thin else ''))
-            if not o.isTrain and 'clean_i' in self.acc:
-                c = self.acc['clean_i'].cpu().tolist()
+            if not o.isTrain and ('clean_i' in self.acc or 'clean_post_i' in self.acc):
+                c = self._clean_counts()
                 print('clean: closed %d pixels, removed %d wall components (%d pixels), filled %d cells (%d pixels) in %d images '
                       '(close_rsq %d, min wall %d, min cell %d)' % (tuple(c) + clean_params(o)))
+            if not o.isTrain and 'split_i' in self.acc:
+                c = self.acc['split_i'].cpu().tolist()
+                print('split: %d cores, cut %d pixels, labelled %d pixels in %d rounds, budget hit in %d of %d images '
+                      '(split_rsq %d, %d rounds)' % (tuple(c) + split_params(o)))
             conf = a['conf'].astype(np.float64)
             v['confusion'], v['numAveragedPixels'] = conf, int(conf.sum())
             rel, sel, tp = conf.sum(axis=1), conf.sum(axis=0), np.diag(conf)
@@ -261,10 +293,13 @@ class SegMetricsMixin:
     def get_clean_counts(self):
         return self.seg_metrics.counts('clean')
 
+    def get_split_counts(self):
+        return self.seg_metrics.counts('split')
+
     def with_cleaned_visual(self, visuals):
         """Built for evaluation with a --clean_* option: adds the wall map the label-based scores of the last accum_accs() were taken
         on to the trainer's visuals as `fake_B_clean` ([1, 1, H, W] in [-1, 1]), so that test_ss.py's result page shows it."""
         cleaned = self.seg_metrics.cleaned
-        if not self.opt.isTrain and any(clean_params(self.opt)) and cleaned is not None:
+        if not self.opt.isTrain and (any(clean_params(self.opt)) or split_params(self.opt)[0]) and cleaned is not None:
             visuals['fake_B_clean'] = cleaned.detach()[None, None] * 2 - 1
         return visuals

@@ -685,6 +685,60 @@ def clean_wall(mask, close_rsq=0, min_wall=0, min_cell=0):
     return wall, counts
 
 
+SPLIT_COUNTS = ('core_components', 'cut_pixels', 'labelled_pixels', 'rounds', 'budget_hits', 'images')
+
+
+def split_labels(mask, split_rsq, max_rounds=64):
+    """The flood of split_cells: (L int64 [H, W], core components, rounds that labelled something, whether round max_rounds did).
+    L is 0 on the wall and on the free pixels the budget did not reach, else 1 + the smallest raster index of the core component
+    that reaches the pixel first (the smallest such label when several arrive in the same round)."""
+    from scipy import ndimage
+    wall = np.array(_wall_mask(mask), dtype=bool)
+    assert wall.ndim == 2 and split_rsq >= 1 and max_rounds >= 1, (wall.shape, split_rsq, max_rounds)
+    H, W = wall.shape
+    d = edt_sq(wall)
+    comp, n = ndimage.label(~wall & (d >= split_rsq), structure=np.ones((3, 3)))
+    first = np.full(n + 1, H * W, dtype=np.int64)
+    np.minimum.at(first, comp.ravel(), np.arange(H * W, dtype=np.int64))      # the smallest raster index of every component
+    L = np.where(comp > 0, first[comp] + 1, 0).astype(np.int64)
+    none = np.int64(1) << 40      # "no labelled neighbour"
+    rounds, last = 0, False
+    for r in range(max_rounds):
+        padded = np.full((H + 2, W + 2), none, dtype=np.int64)
+        padded[1:-1, 1:-1] = np.where(L > 0, L, none)
+        best = np.full((H, W), none, dtype=np.int64)
+        for dy in (0, 1, 2):
+            for dx in (0, 1, 2):
+                if (dy, dx) != (1, 1):
+                    best = np.minimum(best, padded[dy:dy + H, dx:dx + W])
+        take = ~wall & (L == 0) & (best < none)
+        last = bool(take.any())
+        if not last:
+            break
+        L[take] = best[take]
+        rounds += 1
+    return L, n, rounds, last
+
+
+def split_cells(mask, split_rsq, max_rounds=64):
+    """The wall map with merged cells cut apart (include/sgan_hip.h, "splitting merged cells") of a [H, W] wall mask (bool, or a map
+    thresholded at > 0.5): (bool [H, W], counts int64[6] in SPLIT_COUNTS' order).  The cores of the free space, edt_sq >= split_rsq,
+    are labelled with the 8-structure; max_rounds synchronous rounds give every unlabelled free pixel the smallest label among its
+    eight labelled neighbours; a labelled free pixel whose E, SW, S or SE neighbour carries another nonzero label becomes wall.  The
+    host yardstick of ops.split_cells; the trainers do not call it."""
+    wall = np.array(_wall_mask(mask), dtype=bool)
+    L, n, rounds, last = split_labels(wall, split_rsq, max_rounds)
+    H, W = wall.shape
+    P = np.zeros((H + 1, W + 2), dtype=np.int64)      # L with a column of zeros on either side and a row below
+    P[:H, 1:W + 1] = L
+    cut = np.zeros((H, W), dtype=bool)
+    for dy, dx in ((0, 1), (1, -1), (1, 0), (1, 1)):      # E, SW, S, SE
+        q = P[dy:dy + H, 1 + dx:1 + dx + W]
+        cut |= (L > 0) & (q > 0) & (q != L)
+    counts = np.array([n, int(cut.sum()), int((L > 0).sum()), rounds, int(last), 1], dtype=np.int64)
+    return wall | cut, counts
+
+
 def boundary_bin(d):
     """The bin of a distance^2 (include/sgan_hip.h, "boundary scores"): k = ceil(sqrt(d)) in integers for 0 <= d <= 900, 31 beyond
     and for -1 (the other map has no wall)."""
