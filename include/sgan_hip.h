@@ -1149,6 +1149,51 @@ int sgan_region_stats(const int32_t* labels, int32_t H, int32_t W, int64_t* tabl
 int sgan_border_weight(const int32_t* labels, int32_t H, int32_t W, int32_t radius, float w0, float sigma, float* bmap, int32_t* d1sq,
                        int32_t* d2sq, int32_t* dev_err, void* stream);
 
+/* ---- sliced Wasserstein distance between two image sets (generated against real images: swd.py) ------------------------------------
+ * Karras et al. 2018 ("Progressive growing of GANs", section 5): per level of a Laplacian pyramid, N 7 x 7 patches of each set are
+ * normalised per channel by the set's own mean and standard deviation, projected onto J unit directions, sorted, and compared;
+ * the level's score is the mean over the directions of mean_i |sA_i - sB_i|.  util.lap_pyramid_ref, swd_descriptors_ref,
+ * swd_normalise_ref and swd_ref are the NumPy restatements these entries are tested against.  Every entry only enqueues, uses no
+ * atomic, sums in an order fixed by the launch shape (the same bits on every run), and refuses null pointers, short workspaces and
+ * uncovered shapes before any launch (a negative status, the reason in sgan_last_error).
+ *
+ * sgan_lap_pyramid: one step on C planar float32 planes (plane c of a tensor starts c * rows * ld floats after plane 0; ld = the row
+ *   pitch in floats).  `fine` is C x H x W, H and W even and >= 4.  The filter is g = outer(b, b), b = [1 4 6 4 1] / 16, and the border
+ *   is mirrored without repeating the edge (d c b | a b c d | c b a, scipy's mode='mirror').
+ *   mode SGAN_LAP_DOWN: out (C x H/2 x W/2) = the 5 x 5 correlation of `fine` with g at the even sites; `coarse` is not read.
+ *   mode SGAN_LAP_UP_SUB: out (C x H x W) = fine - up, up = the correlation with 4 g of `coarse` (C x H/2 x W/2) placed on the even
+ *   sites of a zero plane: a Laplacian level from a Gaussian level and the next one.  out is a buffer of its own.
+ * sgan_swd_gather: copies the P 7 x 7 patches of one image's level (img: C x H x W planar with row pitch ld, C <= 3) whose top-left
+ *   corners pos (int32 [P][3]: image, y, x as util.swd_draw gives them; the image column is not read) names into rows
+ *   [row0, row0 + P) of desc (float32 [rows][C * 49], order [c][dy][dx]; rows <= 16384), exactly, and adds the image's per-channel
+ *   sum and sum of squares of the copied values to acc (double [2 C]: C sums, then C sums of squares; zeroed by the caller once per
+ *   set).  One workgroup owns a channel and the calls of a stream follow each other, so acc grows in image order.  A position outside
+ *   [0, H - 7] x [0, W - 7] sets bit 128 of *dev_err (required; as the metric entries') and its row is zero-filled; nothing is read
+ *   out of bounds.
+ * sgan_swd_workspace: bytes of scratch sgan_swd_distances needs (< 0: a shape it does not cover).
+ * sgan_swd_distances: out[j] (double [J]) = sum_i |sA_i - sB_i| / N for direction j of dirs (float32 [J][K]), sA and sB the sorted
+ *   projections of the N rows of descA and descB (float32 [N][K]).  A value x of channel c is normalised on load as
+ *   float32(float32(x - m32) * r32) with mean = sum / count, var = max(sumsq / count - mean^2, 0), m32 = float32(mean),
+ *   r32 = float32(1 / sqrt(var)) or 0 where var is 0 (count = 49 N; statsA, statsB: double [2 C] in sgan_swd_gather's layout; every step
+ *   rounded once in fp64, util.swd_stats_from_sums).  Projections are fp32 FMA chains over k; each direction's two projections are
+ *   sorted by one bitonic network in LDS, padded with +inf to a power of two (2 x 64 KiB at N = 16384); the differences are summed in
+ *   fp64.  Covered: 1 <= N <= 16384, K in {49, 98, 147}, 1 <= J <= 4096; anything else is refused.  variant SGAN_SWD_SPLIT: a
+ *   projection pass writes [2][min(J, 512)][N] floats to the workspace and a sort pass (one workgroup per direction) reads them,
+ *   512 directions at a time; SGAN_SWD_FUSED: the sort workgroups project their own rows and the workspace is not touched;
+ *   SGAN_SWD_AUTO: the split form.  The workspace is 16-byte aligned and may hold anything on entry. */
+#define SGAN_LAP_DOWN 0
+#define SGAN_LAP_UP_SUB 1
+#define SGAN_SWD_AUTO 0
+#define SGAN_SWD_SPLIT 1
+#define SGAN_SWD_FUSED 2
+int sgan_lap_pyramid(int32_t mode, const float* fine, int64_t fine_ld, const float* coarse, int64_t coarse_ld, int32_t C, int32_t H,
+                     int32_t W, float* out, int64_t out_ld, void* stream);
+int sgan_swd_gather(const float* img, int64_t ld, int32_t C, int32_t H, int32_t W, const int32_t* pos, int32_t P, float* desc,
+                    int32_t row0, int32_t rows, double* acc, int32_t* dev_err, void* stream);
+int64_t sgan_swd_workspace(int32_t N, int32_t K, int32_t J);
+int sgan_swd_distances(const float* descA, const float* descB, const double* statsA, const double* statsB, const float* dirs, int32_t N,
+                       int32_t K, int32_t J, double* out, void* workspace, int64_t workspace_bytes, int32_t variant, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

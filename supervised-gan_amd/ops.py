@@ -1337,7 +1337,7 @@ def check_metric_err(device):
         e.zero_()
     if code & ~SPLIT_BUDGET_BIT:      # a split budget that was hit is counted in SPLIT_COUNTS; its map is what the budget defines
         raise L.SganError(f"segmentation metric kernels gave up on part of their input (flags {code:#x}: 1 = union-find bound, "
-                          "2 = pair table full, 4 / 8 = label out of range, 16 = thinning budget ran out, 32 = region table full); the accumulated values are incomplete")
+                          "2 = pair table full, 4 / 8 = label out of range, 16 = thinning budget ran out, 32 = region table full, 128 = patch position outside its level); the accumulated values are incomplete")
 
 
 def _metric_workspace(symbol, H, W, device):
@@ -1461,6 +1461,120 @@ def region_stats(labels, table, cursor, workspace=None):
     L.check(L.lib().sgan_region_stats(_ptr(labels), H, W, _ptr(table), table.shape[0], _ptr(cursor), _ptr(ws),
                                       ws.numel() * ws.element_size(), _ptr(metric_err(dev)), _stream()), "sgan_region_stats")
     return table
+
+
+# ------------------------------------------------------------------------------------------------
+# Sliced Wasserstein distance over Laplacian-pyramid patches (sgan_swd.hip; swd.py).  All of them only enqueue.
+# ------------------------------------------------------------------------------------------------
+SWD_MAX_N = 16384                                  # descriptors per set (include/sgan_hip.h, sgan_swd_distances)
+SWD_AUTO, SWD_SPLIT, SWD_FUSED = 0, 1, 2           # `variant` of swd_distances
+_swd_ws = {}
+
+
+def _planes(t, what):
+    """A [C, H, W] fp32 tensor whose planes follow each other H row pitches apart; returns (tensor, row pitch in floats)."""
+    require_gpu(t, what)
+    assert t.dim() == 3 and t.dtype == torch.float32, (t.shape, t.dtype)
+    C, H, W = t.shape
+    if t.stride(2) != 1 or t.stride(1) < W or (C > 1 and t.stride(0) != H * t.stride(1)):
+        t = t.contiguous()
+    if (C * H - 1) * t.stride(1) + W > _avail(t):
+        raise L.SganError(f"{what}: planes {tuple(t.shape)} / {tuple(t.stride())} do not lie inside their storage; nothing was launched")
+    return t, t.stride(1)
+
+
+def lap_down(x, out=None):
+    """One Gaussian pyramid step of x [C, H, W] (H, W even, >= 4): the 5 x 5 binomial blur with a mirrored border, even sites kept
+    (sgan_lap_pyramid, mode down; util.lap_down_ref is the host yardstick).  Returns [C, H / 2, W / 2]."""
+    x, ld = _planes(x, "lap_down")
+    C, H, W = x.shape
+    if out is None:
+        out = torch.empty((C, H // 2, W // 2), dtype=torch.float32, device=x.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (C, H // 2, W // 2) and out.device == x.device
+    L.check(L.lib().sgan_lap_pyramid(0, _ptr(x), ld, None, 0, C, H, W, _ptr(out), W // 2, _stream()), "sgan_lap_pyramid")
+    return out
+
+
+def lap_up_sub(fine, coarse, out=None):
+    """The Laplacian level fine - up(coarse): fine [C, H, W], coarse [C, H / 2, W / 2] (sgan_lap_pyramid, mode up-and-subtract;
+    util.lap_up_ref is the host yardstick of up)."""
+    fine, ld = _planes(fine, "lap_up_sub")
+    coarse, cld = _planes(coarse, "lap_up_sub")
+    C, H, W = fine.shape
+    assert tuple(coarse.shape) == (C, H // 2, W // 2) and coarse.device == fine.device, (fine.shape, coarse.shape)
+    if out is None:
+        out = torch.empty((C, H, W), dtype=torch.float32, device=fine.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (C, H, W) and out.device == fine.device
+    assert out.data_ptr() != fine.data_ptr()
+    L.check(L.lib().sgan_lap_pyramid(1, _ptr(fine), ld, _ptr(coarse), cld, C, H, W, _ptr(out), W, _stream()), "sgan_lap_pyramid")
+    return out
+
+
+def lap_pyramid(img):
+    """The Laplacian pyramid of img [C, H, W] on the device, finest first, with the levels of util.lap_pyramid_ref: a further level
+    while both sides are even and half the smaller side is at least 16; the last level is the Gaussian one."""
+    from .util import lap_level_sizes
+    g, _ = _planes(img, "lap_pyramid")
+    levels = []
+    for _ in lap_level_sizes(*g.shape[1:])[1:]:
+        nxt = lap_down(g)
+        levels.append(lap_up_sub(g, nxt))
+        g = nxt
+    levels.append(g)
+    return levels
+
+
+def swd_gather(level, pos, desc, row0, acc):
+    """Copies the 7 x 7 patches of `level` [C, H, W] at the top-left corners pos (int32 [P, 3] on the device: image, y, x) into rows
+    [row0, row0 + P) of desc (float32 [N, C * 49], order [c][dy][dx]) and adds the per-channel sum and sum of squares to acc (float64
+    [2 C], zeroed by the caller once per set): sgan_swd_gather.  A position outside the level zero-fills its row and raises bit 128
+    of metric_err."""
+    level, ld = _planes(level, "swd_gather")
+    C, H, W = level.shape
+    dev = level.device
+    assert pos.dtype == torch.int32 and pos.dim() == 2 and pos.shape[1] == 3 and pos.is_contiguous() and pos.device == dev, (pos.shape, pos.dtype)
+    assert desc.dtype == torch.float32 and desc.dim() == 2 and desc.shape[1] == C * 49 and desc.is_contiguous() and desc.device == dev, desc.shape
+    assert _is_acc(acc, torch.float64, 2 * C, dev) and acc is not None
+    L.check(L.lib().sgan_swd_gather(_ptr(level), ld, C, H, W, _ptr(pos), pos.shape[0], _ptr(desc), int(row0), desc.shape[0], _ptr(acc),
+                                    _ptr(metric_err(dev)), _stream()), "sgan_swd_gather")
+    return desc
+
+
+def swd_workspace(N, K, J, device):
+    """The scratch of swd_distances (the projections of up to 512 directions of both sets), cached per (N, K, J, device)."""
+    key = (N, K, J, device.index)
+    ws = _swd_ws.get(key)
+    if ws is None:
+        nbytes = L.lib().sgan_swd_workspace(N, K, J)
+        if nbytes < 0:
+            raise L.SganError(f"sgan_swd_workspace({N}, {K}, {J}): {L.lib().sgan_last_error().decode()}")
+        ws = _swd_ws[key] = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
+    return ws
+
+
+def swd_distances(descA, descB, statsA, statsB, dirs, out=None, workspace=None, variant=SWD_AUTO):
+    """Per-direction sliced Wasserstein distances of two descriptor matrices (float32 [N, K], K in {49, 98, 147}, N <= 16384):
+    each normalised by its own statistics (float64 [2 C] as swd_gather accumulates them), projected onto dirs (float32 [J, K]),
+    sorted, compared: out float64 [J] = mean_i |sA_i - sB_i| (sgan_swd_distances; util.swd_ref is the host yardstick).  The same
+    bits on every run."""
+    require_gpu(descA, "swd_distances")
+    dev = descA.device
+    assert descA.dim() == 2 and descA.dtype == torch.float32 and descA.is_contiguous(), (descA.shape, descA.dtype)
+    N, K = descA.shape
+    assert descB.dtype == torch.float32 and descB.is_contiguous() and tuple(descB.shape) == (N, K) and descB.device == dev, descB.shape
+    assert dirs.dtype == torch.float32 and dirs.dim() == 2 and dirs.shape[1] == K and dirs.is_contiguous() and dirs.device == dev, dirs.shape
+    J = dirs.shape[0]
+    if K % 49:
+        raise L.SganError(f"swd_distances: K = {K} is not 49, 98 or 147; nothing was launched")
+    for s in (statsA, statsB):
+        assert _is_acc(s, torch.float64, 2 * (K // 49), dev) and s is not None
+    if out is None:
+        out = torch.empty(max(J, 1), dtype=torch.float64, device=dev)[:J]
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == J and out.device == dev
+    ws = swd_workspace(N, K, J, dev) if workspace is None else workspace
+    L.check(L.lib().sgan_swd_distances(_ptr(descA), _ptr(descB), _ptr(statsA), _ptr(statsB), _ptr(dirs), N, K, J, _ptr(out), _ptr(ws),
+                                       ws.numel() * ws.element_size(), int(variant), _stream()), "sgan_swd_distances")
+    return out
 
 
 def rand_f_workspace(H, W, device):

@@ -893,3 +893,115 @@ def diffaug_bwd_ref(dy, rec, colour_mask):
         S = kdy[:, :, col].sum()
         dx[:, :, col] = a * dx[:, :, col] + (1.0 - a) * S / (int(col.sum()) * H * W)
     return dx
+
+
+# ---- sliced Wasserstein distance over Laplacian-pyramid patches (swd.py; include/sgan_hip.h, "sliced Wasserstein distance") ----------
+SWD_PATCH = 7
+SWD_MAX_N = 16384      # descriptors per set the device sorts in one workgroup's LDS (sgan_swd_distances)
+SWD_MIN_SIDE = 16      # a further pyramid level exists while half the smaller side is at least this
+_LAP_B = np.array([1.0, 4.0, 6.0, 4.0, 1.0]) / 16.0
+
+
+def _lap_correlate(x, scale):
+    """5 x 5 correlation of the planes [C, H, W] with scale * outer(b, b) in float64, the border mirrored without repeating the edge
+    (d c b | a b c d | c b a: numpy's 'reflect', scipy.ndimage's 'mirror')."""
+    p = np.pad(np.asarray(x, dtype=np.float64), ((0, 0), (2, 2), (2, 2)), mode='reflect')
+    H, W = x.shape[1:]
+    out = np.zeros(x.shape, dtype=np.float64)
+    for dy in range(5):
+        for dx in range(5):
+            out += (scale * _LAP_B[dy] * _LAP_B[dx]) * p[:, dy:dy + H, dx:dx + W]
+    return out
+
+
+def lap_down_ref(x):
+    """[C, H, W] -> [C, H / 2, W / 2]: blur with g = outer(b, b), b = [1 4 6 4 1] / 16, keep the even sites."""
+    return _lap_correlate(x, 1.0)[:, ::2, ::2]
+
+
+def lap_up_ref(x):
+    """[C, h, w] -> [C, 2 h, 2 w]: x on the even sites of a zero plane, blurred with 4 g."""
+    z = np.zeros((x.shape[0], 2 * x.shape[1], 2 * x.shape[2]), dtype=np.float64)
+    z[:, ::2, ::2] = x
+    return _lap_correlate(z, 4.0)
+
+
+def lap_level_sizes(H, W):
+    """Sizes of the pyramid's levels, finest first: a further level while both sides are even and half the smaller is >= 16."""
+    sizes = [(H, W)]
+    while H % 2 == 0 and W % 2 == 0 and min(H, W) // 2 >= SWD_MIN_SIDE:
+        H, W = H // 2, W // 2
+        sizes.append((H, W))
+    return sizes
+
+
+def lap_pyramid_ref(img):
+    """Laplacian pyramid of img [C, H, W] in float64, finest first: G_0 = img, G_{l+1} = down(G_l), L_l = G_l - up(G_{l+1}); the last
+    level is G_last itself, so that the levels, each upsampled back to the image's size and added, give the image."""
+    g = np.asarray(img, dtype=np.float64)
+    levels = []
+    for _ in lap_level_sizes(*g.shape[1:])[1:]:
+        nxt = lap_down_ref(g)
+        levels.append(g - lap_up_ref(nxt))
+        g = nxt
+    levels.append(g)
+    return levels
+
+
+def swd_descriptors_ref(levels_of_images, pos):
+    """levels_of_images: one [C, H, W] level per image; pos: int32 [N, 3] of (image, y, x), the top-left corner of a 7 x 7 patch.
+    Returns (desc [N, C * 49] in the order [c][dy][dx], in the level's dtype; mean [C]; population std [C]), the statistics in
+    float64 over all N * 49 values of a channel."""
+    pos = np.asarray(pos)
+    C = levels_of_images[0].shape[0]
+    desc = np.stack([np.asarray(levels_of_images[i])[:, y:y + SWD_PATCH, x:x + SWD_PATCH].reshape(C * SWD_PATCH * SWD_PATCH)
+                     for i, y, x in pos])
+    per_channel = desc.reshape(len(pos), C, -1).astype(np.float64).transpose(1, 0, 2).reshape(C, -1)
+    return desc, per_channel.mean(axis=1), per_channel.std(axis=1)
+
+
+def swd_stats_from_sums(sums, count):
+    """(mean, std) per channel from the device's accumulators (float64 [2 C]: C sums, then C sums of squares) with the device's own
+    roundings: mean = sum / count, var = max(sumsq / count - mean * mean, 0), std = sqrt(var), each step rounded once in float64."""
+    sums = np.asarray(sums, dtype=np.float64)
+    C = len(sums) // 2
+    mean = sums[:C] / np.float64(count)
+    var = sums[C:] / np.float64(count) - mean * mean
+    return mean, np.sqrt(np.where(var > 0.0, var, 0.0))
+
+
+def swd_normalise_ref(desc, mean, std):
+    """The one yardstick that mirrors the device's roundings, in float32: n = float32(float32(x - m32) * r32) with m32 = float32(mean)
+    and r32 = float32(1 / std), 0 where std == 0 (a constant level gives zero descriptors, not NaN).  No multiply-add can be
+    contracted out of a subtract-then-multiply, so the device matches this bit for bit."""
+    desc = np.asarray(desc, dtype=np.float32)
+    mean, std = np.asarray(mean, dtype=np.float64), np.asarray(std, dtype=np.float64)
+    C = len(mean)
+    m32 = mean.astype(np.float32)
+    r32 = np.where(std == 0.0, 0.0, 1.0 / np.where(std == 0.0, 1.0, std)).astype(np.float32)
+    x = desc.reshape(len(desc), C, -1)
+    d = (x - m32[None, :, None]).astype(np.float32)
+    return (d * r32[None, :, None]).astype(np.float32).reshape(desc.shape)
+
+
+def swd_ref(nA, nB, dirs):
+    """Per-direction sliced Wasserstein distances in float64: nA, nB [N, K] float32 with equal N, dirs [J, K] float32; project in
+    float64, sort both, mean |sA - sB|.  A level's score is the mean of the J values (printed x 1e3)."""
+    nA, nB, dirs = (np.asarray(a, dtype=np.float64) for a in (nA, nB, dirs))
+    assert nA.shape == nB.shape and dirs.shape[1] == nA.shape[1], (nA.shape, nB.shape, dirs.shape)
+    pA, pB = np.sort(nA @ dirs.T, axis=0), np.sort(nB @ dirs.T, axis=0)
+    return np.abs(pA - pB).mean(axis=0)
+
+
+def swd_draw(seed, level, n_images, P, H_l, W_l, K, J, set_index=0):
+    """The only source of randomness of the score.  Returns (pos int32 [n_images * P, 3] of (image, y, x) with 0 <= y <= H_l - 7,
+    dirs float32 [J, K]).  The directions come from RandomState([seed, level]) -- randn, each row divided by its L2 norm in float64,
+    then cast -- and are the same for both sets; the positions from RandomState([seed, level, 1 + set_index]), one stream per set."""
+    d = np.random.RandomState([int(seed), int(level)]).randn(J, K)
+    dirs = (d / np.sqrt((d * d).sum(axis=1, keepdims=True))).astype(np.float32)
+    rs = np.random.RandomState([int(seed), int(level), 1 + int(set_index)])
+    pos = np.empty((n_images * P, 3), dtype=np.int32)
+    pos[:, 0] = np.repeat(np.arange(n_images), P)
+    pos[:, 1] = rs.randint(0, H_l - SWD_PATCH + 1, size=n_images * P)
+    pos[:, 2] = rs.randint(0, W_l - SWD_PATCH + 1, size=n_images * P)
+    return pos, dirs
