@@ -1194,6 +1194,43 @@ int64_t sgan_swd_workspace(int32_t N, int32_t K, int32_t J);
 int sgan_swd_distances(const float* descA, const float* descB, const double* statsA, const double* statsB, const float* dirs, int32_t N,
                        int32_t K, int32_t J, double* out, void* workspace, int64_t workspace_bytes, int32_t variant, void* stream);
 
+/* ---- precision, recall, density, coverage of a generated set against a real one (swd.py --prd_k) --------------------------------------
+ * Improved precision / recall (Kynkaanniemi et al. 2019) and density / coverage (Naeem et al. 2020) in the descriptor space of the
+ * sliced Wasserstein score: balls around every row whose radius is the distance to its k-th nearest neighbour in its own set.  BOTH
+ * sets are normalised by ONE set's statistics (the real set's), on load and exactly as sgan_swd_distances does it:
+ * float32(float32(x - m32) * r32) from `stats` (double [2 C], sgan_swd_gather's layout) with count = 49 * the rows of the set the
+ * statistics describe.  d2(x, y) is the squared Euclidean distance of two normalised rows.  util.knn_radii_ref, prd_rows_ref and
+ * prd_scores_ref are the float64 NumPy yardsticks.  Every entry only enqueues, uses no atomic (a workgroup owns 64 query rows, walks
+ * every reference column and finishes its rows itself: the same bits on every run), and refuses null pointers, short workspaces and
+ * uncovered shapes before any launch (a negative status, the reason in sgan_last_error; no output is touched).
+ * Covered: 1 <= N, Nq, Nr <= 16384, K in {49, 98, 147}, 1 <= k <= 8, group >= 1, k <= N - group.
+ *
+ * sgan_prd_workspace: bytes of scratch the two passes need for Nq query and Nr reference rows (< 0: a shape they do not cover);
+ *   sgan_knn_radii takes sgan_prd_workspace(N, N, K).  16-byte aligned; it may hold anything on entry.
+ * sgan_knn_radii: desc float32 [N][K]; count = 49 N.  Rows of one image follow each other, `group` rows each (the last group may be
+ *   short), and the neighbours of row i exclude every row j with j / group == i / group; group = 1 excludes the row alone.
+ *   rad[i] = the k-th smallest d2(x_i, x_j) over the admitted j (equal values each count), nn1[i] = the smallest.
+ * sgan_prd_rows: descQ float32 [Nq][K], descR float32 [Nr][K], radR float32 [Nr]; count = 49 Nr (in swd.py both sets have N rows).
+ *   cnt[i] = #{j : d2(q_i, r_j) <= radR[j]}, nn_d2[i] = min_j d2(q_i, r_j), nn_idx[i] = the smallest j that attains it.
+ * variant: two forms of d2.  SGAN_PRD_DIRECT: diff = fl(q_k - r_k), then an FMA chain over k ascending; error per pair <=
+ *   gamma_{K+2} d2 (gamma_n = n u / (1 - n u), u = 2^-24).  SGAN_PRD_GRAM: d2 = max(fl(n_q + n_r) - 2 q.r, 0) in one FMA, q.r by the
+ *   exact fp32 MFMA (v_mfma_f32_32x32x2_f32), the row norms n as fp32 FMA chains written to the workspace by a pre-pass; error per
+ *   pair <= gamma_{K+3} (n_q + n_r + 2 sum_k |q_k r_k|).  On integer descriptors below 2^24 / K in square both are exact.
+ *   SGAN_PRD_AUTO: the gram form, the faster one at N = 16384, K = 147.
+ * sgan_prd_finish: out4 (int64 [4]) = #{cntB > 0} (precision hits), #{cntA > 0} (recall hits), sum cntB (density = / (k N)),
+ *   #{nn_d2_A[i] <= radA[i]} (coverage hits: the nearest generated row of each real row against that row's own radius), from two
+ *   sgan_prd_rows passes -- B against A with radA, A against B with radB -- of N rows each.  Exact integers; the caller divides. */
+#define SGAN_PRD_AUTO 0
+#define SGAN_PRD_DIRECT 1
+#define SGAN_PRD_GRAM 2
+int64_t sgan_prd_workspace(int32_t Nq, int32_t Nr, int32_t K);
+int sgan_knn_radii(const float* desc, const double* stats, int32_t N, int32_t K, int32_t k, int32_t group, float* rad, float* nn1, void* ws,
+                   int64_t ws_bytes, int32_t variant, void* stream);
+int sgan_prd_rows(const float* descQ, const float* descR, const double* stats, const float* radR, int32_t Nq, int32_t Nr, int32_t K,
+                  int32_t* cnt, float* nn_d2, int32_t* nn_idx, void* ws, int64_t ws_bytes, int32_t variant, void* stream);
+int sgan_prd_finish(const int32_t* cntB, const int32_t* cntA, const float* nn_d2_A, const float* radA, int32_t N, int64_t* out4,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

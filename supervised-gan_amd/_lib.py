@@ -201,6 +201,10 @@ SIGNATURES = {
     "sgan_swd_gather": [_P, _L, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P],
     "sgan_swd_workspace": [_I, _I, _I],
     "sgan_swd_distances": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _L, _I, _P],
+    "sgan_prd_workspace": [_I, _I, _I],
+    "sgan_knn_radii": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _I, _P],
+    "sgan_prd_rows": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _I, _P],
+    "sgan_prd_finish": [_P, _P, _P, _P, _I, _P, _P],
     "sgan_last_variant": [],
     "sgan_profile_enable": [_I],
     "sgan_profile_count": [],
@@ -213,7 +217,8 @@ RESTYPES = {"sgan_last_variant": C.c_char_p, "sgan_image_resize_workspace": C.c_
             "sgan_region_stats_workspace": C.c_int64, "sgan_object_match_workspace": C.c_int64,
             "sgan_edt_workspace": C.c_int64, "sgan_boundary_workspace": C.c_int64, "sgan_clean_workspace": C.c_int64,
             "sgan_split_workspace": C.c_int64,
-            "sgan_diffaug_workspace": C.c_int64, "sgan_swd_workspace": C.c_int64}      # everything else returns an int status
+            "sgan_diffaug_workspace": C.c_int64, "sgan_swd_workspace": C.c_int64,
+            "sgan_prd_workspace": C.c_int64}      # everything else returns an int status
 _lib = None
 
 

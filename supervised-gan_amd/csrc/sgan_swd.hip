@@ -3,10 +3,8 @@
 // No kernel of this file uses an atomic: every sum is taken in an order the launch shape fixes, so every result has the same bits on
 // every run.  DESIGN.md §R26.
 #include "sgan_reduce.h"
+#include "sgan_swd.h"
 
-#define SG_SWD_PATCH 7
-#define SG_SWD_TAPS 49          // values of one channel of a descriptor
-#define SG_SWD_MAX_N 16384
 #define SG_SWD_MAX_J 4096
 #define SG_SWD_CHUNK_J 512      // directions whose projections the workspace holds at a time
 #define SG_SWD_ERR_POS 128      // dev_err: a patch position outside the level
@@ -102,19 +100,7 @@ __global__ __launch_bounds__(256) void sg_swd_gather_kernel(const float* __restr
 }
 
 // ---- distances ------------------------------------------------------------------------------------------------------------------------
-// mean and 1 / std of channel c from (sum, sum of squares, count) exactly as util.swd_stats_from_sums: no contraction anywhere
-__device__ __forceinline__ void sg_swd_norm(const double* stats, int C, int c, double count, float& m32, float& r32) {
-    const double mean = __ddiv_rn(stats[c], count);
-    double var = __dsub_rn(__ddiv_rn(stats[C + c], count), __dmul_rn(mean, mean));
-    if (!(var > 0.0)) var = 0.0;
-    const double sd = __dsqrt_rn(var);
-    m32 = (float)mean;
-    r32 = sd == 0.0 ? 0.f : (float)__ddiv_rn(1.0, sd);
-}
-
-// util.swd_normalise_ref: float32(float32(x - m32) * r32)
-__device__ __forceinline__ float sg_swd_normalise(float x, float m32, float r32) { return __fmul_rn(__fsub_rn(x, m32), r32); }
-
+// the normalisation on load (sg_swd_norm, sg_swd_normalise) is sgan_swd.h's, shared with sgan_prd.hip
 // Projection pass: proj[set][j - j0][i] = sum_k n_ik d_jk, k ascending, for a 64 x 64 tile of (rows, directions) per workgroup, one
 // channel (49 values of k) staged at a time.  A thread owns rows ti + 16 a and directions 4 tj + b; the sum of one (row, direction)
 // is the same chain of FMAs wherever the row stands, so equal rows give equal bits.
@@ -244,8 +230,6 @@ __global__ __launch_bounds__(SgSwdShape<NP>::T) void sg_swd_sort_kernel(const fl
     acc = sg_block_sum<T / 64>(acc, red);
     if (tid == 0) out[j0 + jj] = acc / (double)N;
 }
-
-static int sg_swd_channels(int32_t K) { return (K == 49 || K == 98 || K == 147) ? K / SG_SWD_TAPS : 0; }
 
 static bool sg_swd_covered(int32_t N, int32_t K, int32_t J) {
     return N >= 1 && N <= SG_SWD_MAX_N && sg_swd_channels(K) && J >= 1 && J <= SG_SWD_MAX_J;

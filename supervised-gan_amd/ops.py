@@ -1577,6 +1577,84 @@ def swd_distances(descA, descB, statsA, statsB, dirs, out=None, workspace=None, 
     return out
 
 
+PRD_AUTO, PRD_DIRECT, PRD_GRAM = 0, 1, 2           # `variant` of knn_radii and prd_rows
+_prd_ws = {}
+
+
+def _prd_desc(t, what):
+    assert t.dim() == 2 and t.dtype == torch.float32 and t.is_contiguous(), (what, t.shape, t.dtype)
+    if t.shape[1] % 49:
+        raise L.SganError(f"{what}: K = {t.shape[1]} is not 49, 98 or 147; nothing was launched")
+    return t.shape
+
+
+def _prd_out(t, dtype, n, dev):
+    if t is None:
+        return torch.empty(max(n, 1), dtype=dtype, device=dev)[:n]
+    assert _is_acc(t, dtype, n, dev), (t.shape, t.dtype)
+    return t
+
+
+def prd_workspace(Nq, Nr, K, device):
+    """The scratch of knn_radii (Nq = Nr = N) and prd_rows (the row norms of the Gram form), cached per (Nq, Nr, K, device)."""
+    key = (Nq, Nr, K, device.index)
+    ws = _prd_ws.get(key)
+    if ws is None:
+        nbytes = L.lib().sgan_prd_workspace(Nq, Nr, K)
+        if nbytes < 0:
+            raise L.SganError(f"sgan_prd_workspace({Nq}, {Nr}, {K}): {L.lib().sgan_last_error().decode()}")
+        ws = _prd_ws[key] = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
+    return ws
+
+
+def knn_radii(desc, stats, k, group=1, rad=None, nn1=None, workspace=None, variant=PRD_AUTO):
+    """(rad, nn1) float32 [N] of a descriptor matrix (float32 [N, K], K in {49, 98, 147}, N <= 16384) normalised by stats (float64
+    [2 C] as swd_gather accumulates them, over N rows): the squared distance of every row to its k-th (k <= 8) and to its first
+    nearest neighbour among the rows of other groups of `group` consecutive rows (sgan_knn_radii; util.knn_radii_ref is the host
+    yardstick).  The same bits on every run."""
+    require_gpu(desc, "knn_radii")
+    dev = desc.device
+    N, K = _prd_desc(desc, "knn_radii")
+    assert _is_acc(stats, torch.float64, 2 * (K // 49), dev) and stats is not None
+    rad, nn1 = _prd_out(rad, torch.float32, N, dev), _prd_out(nn1, torch.float32, N, dev)
+    ws = prd_workspace(N, N, K, dev) if workspace is None else workspace
+    L.check(L.lib().sgan_knn_radii(_ptr(desc), _ptr(stats), N, K, int(k), int(group), _ptr(rad), _ptr(nn1), _ptr(ws),
+                                   ws.numel() * ws.element_size(), int(variant), _stream()), "sgan_knn_radii")
+    return rad, nn1
+
+
+def prd_rows(descQ, descR, stats, radR, cnt=None, nn_d2=None, nn_idx=None, workspace=None, variant=PRD_AUTO):
+    """Per row of descQ (float32 [Nq, K]) against descR (float32 [Nr, K]) and the radii of its rows (float32 [Nr]), both normalised
+    by stats (float64 [2 C], over Nr rows): (cnt int32 [Nq] = how many balls of R hold the row, nn_d2 float32 [Nq] = the squared
+    distance to the nearest row of R, nn_idx int32 [Nq] = the smallest index that attains it): sgan_prd_rows; util.prd_rows_ref is
+    the host yardstick.  The same bits on every run."""
+    require_gpu(descQ, "prd_rows")
+    dev = descQ.device
+    Nq, K = _prd_desc(descQ, "prd_rows")
+    Nr, Kr = _prd_desc(descR, "prd_rows")
+    assert Kr == K and descR.device == dev, (descQ.shape, descR.shape)
+    assert _is_acc(stats, torch.float64, 2 * (K // 49), dev) and stats is not None
+    assert _is_acc(radR, torch.float32, Nr, dev) and radR is not None
+    cnt, nn_d2, nn_idx = _prd_out(cnt, torch.int32, Nq, dev), _prd_out(nn_d2, torch.float32, Nq, dev), _prd_out(nn_idx, torch.int32, Nq, dev)
+    ws = prd_workspace(Nq, Nr, K, dev) if workspace is None else workspace
+    L.check(L.lib().sgan_prd_rows(_ptr(descQ), _ptr(descR), _ptr(stats), _ptr(radR), Nq, Nr, K, _ptr(cnt), _ptr(nn_d2), _ptr(nn_idx),
+                                  _ptr(ws), ws.numel() * ws.element_size(), int(variant), _stream()), "sgan_prd_rows")
+    return cnt, nn_d2, nn_idx
+
+
+def prd_finish(cntB, cntA, nn_d2_A, radA, out=None):
+    """int64 [4] on the device: precision hits #{cntB > 0}, recall hits #{cntA > 0}, sum cntB, coverage hits #{nn_d2_A <= radA}
+    (sgan_prd_finish; util.prd_from_counts divides)."""
+    require_gpu(cntB, "prd_finish")
+    dev = cntB.device
+    N = cntB.numel()
+    assert _is_acc(cntB, torch.int32, N, dev) and _is_acc(cntA, torch.int32, N, dev) and cntA is not None
+    assert _is_acc(nn_d2_A, torch.float32, N, dev) and nn_d2_A is not None and _is_acc(radA, torch.float32, N, dev) and radA is not None
+    out = _prd_out(out, torch.int64, 4, dev)
+    L.check(L.lib().sgan_prd_finish(_ptr(cntB), _ptr(cntA), _ptr(nn_d2_A), _ptr(radA), N, _ptr(out), _stream()), "sgan_prd_finish")
+    return out
+
+
 def rand_f_workspace(H, W, device):
     """The scratch of rand_f_accumulate for H x W maps, cached per (H, W, device); the kernels zero it themselves."""
     return _metric_workspace("sgan_rand_f_workspace", H, W, device)

@@ -1005,3 +1005,73 @@ def swd_draw(seed, level, n_images, P, H_l, W_l, K, J, set_index=0):
     pos[:, 1] = rs.randint(0, H_l - SWD_PATCH + 1, size=n_images * P)
     pos[:, 2] = rs.randint(0, W_l - SWD_PATCH + 1, size=n_images * P)
     return pos, dirs
+
+
+# ---- precision / recall / density / coverage by k-nearest-neighbour balls (swd.py --prd_k; include/sgan_hip.h) -----------------------
+PRD_MAX_K = 8          # neighbours a row keeps on the device (sgan_knn_radii)
+
+
+def _prd_d2(X, Y, chunk=32):
+    """All-pairs squared Euclidean distances [len(X), len(Y)] in float64, as sums of squared differences (never the Gram form: equal
+    rows give exactly 0), `chunk` rows of X at a time."""
+    X, Y = np.asarray(X, dtype=np.float64), np.asarray(Y, dtype=np.float64)
+    out = np.empty((len(X), len(Y)), dtype=np.float64)
+    for i in range(0, len(X), chunk):
+        d = X[i:i + chunk, None, :] - Y[None, :, :]
+        out[i:i + chunk] = np.einsum('ijk,ijk->ij', d, d)
+    return out
+
+
+def knn_radii_ref(X, k, group=1, d2=None):
+    """X [N, K]: normalised descriptors, the rows of one image contiguous, `group` rows each.  The in-set neighbours of row i are the
+    rows j with j // group != i // group (group = 1: every other row).  Returns (rad, nn1) in float64: rad[i] the k-th smallest
+    d2(x_i, x_j) over them (equal values each count), nn1[i] the smallest.  d2: the all-pairs matrix, if the caller has it."""
+    N = len(X)
+    assert 1 <= k <= N - group, (k, N, group)
+    d2 = np.array(_prd_d2(X, X) if d2 is None else d2, dtype=np.float64)
+    g = np.arange(N) // group
+    d2[g[:, None] == g[None, :]] = np.inf
+    s = np.sort(d2, axis=1)
+    return s[:, k - 1].copy(), s[:, 0].copy()
+
+
+def prd_rows_ref(Q, R, radR, d2=None):
+    """Per row of Q against the balls of R: (cnt, nn_d2, nn_idx) with cnt[i] = #{j : d2(q_i, r_j) <= radR[j]} (int64), nn_d2[i] =
+    min_j d2(q_i, r_j) (float64) and nn_idx[i] the smallest j that attains it."""
+    d2 = _prd_d2(Q, R) if d2 is None else np.asarray(d2, dtype=np.float64)
+    cnt = (d2 <= np.asarray(radR, dtype=np.float64)[None, :]).sum(axis=1).astype(np.int64)
+    idx = d2.argmin(axis=1)      # the first of equal minima
+    return cnt, d2[np.arange(len(d2)), idx], idx.astype(np.int64)
+
+
+def prd_scores_ref(rows_B, rows_A, knn_A, knn_B, k):
+    """The scores of a generated set B against a real set A, N rows each, both normalised by A's statistics.  rows_B = prd_rows_ref(B,
+    A, radA), rows_A = prd_rows_ref(A, B, radB), knn_A = knn_radii_ref(A, k, group), knn_B = knn_radii_ref(B, k, group) (its radii are
+    what rows_A was counted with).  precision = share of B's rows inside some ball of A; recall = share of A's rows inside some ball
+    of B; density = sum of B's ball counts / (k N); coverage = share of A's rows whose nearest row of B lies inside their OWN ball;
+    nn_fake_real = median over B of the squared distance to the nearest row of A, nn_real_real = median over A of the squared
+    distance to the nearest row of another image of A, nn_ratio their quotient (far below 1: B sits closer to A than A to itself).
+    Returns a dict; 'counts' holds the four integers the device's finish gives."""
+    cntB, nnB = np.asarray(rows_B[0]), np.asarray(rows_B[1], dtype=np.float64)
+    cntA, nnA = np.asarray(rows_A[0]), np.asarray(rows_A[1], dtype=np.float64)
+    radA, nn1A = np.asarray(knn_A[0], dtype=np.float64), np.asarray(knn_A[1], dtype=np.float64)
+    N = len(cntB)
+    assert len(cntA) == N and len(radA) == N and len(knn_B[0]) == N, (len(cntA), N)
+    counts = np.array([(cntB > 0).sum(), (cntA > 0).sum(), cntB.sum(), (nnA <= radA).sum()], dtype=np.int64)
+    out = prd_from_counts(counts, N, k)
+    fr, rr = float(np.median(nnB)), float(np.median(nn1A))
+    out.update(nn_fake_real=fr, nn_real_real=rr, nn_ratio=prd_ratio(fr, rr), counts=counts)
+    return out
+
+
+def prd_from_counts(counts, N, k):
+    """precision, recall, density, coverage from the four integers of sgan_prd_finish."""
+    c = [int(v) for v in counts]
+    return dict(precision=c[0] / N, recall=c[1] / N, density=c[2] / (k * N), coverage=c[3] / N)
+
+
+def prd_ratio(fake_real, real_real):
+    """nn_fake_real / nn_real_real; 0 / 0 (both sets the same single texture) reads as 1."""
+    if real_real == 0.0:
+        return 1.0 if fake_real == 0.0 else float('inf')
+    return fake_real / real_real

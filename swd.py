@@ -17,7 +17,22 @@ alone (`--swd_seed`); both sets share the directions.  In real_fake each set dra
 use one draw, so that a set split against itself scores exactly 0 and the floor is the image-to-image variation alone.
 
 N = how_many * swd_patches descriptors per set, at most 16384 (what one workgroup sorts in LDS), and every image of a run has one
-size; anything else exits with status 2.  Written under results_dir/name/<phase>_<which_epoch>/: swd.npz (distances [levels,
+size; anything else exits with status 2.
+
+`--prd_k K` (default 0: off, and then nothing of the run or its files changes) adds, per level and in the same descriptor space,
+improved precision / recall (Kynkaanniemi et al. 2019) and density / coverage (Naeem et al. 2020): balls around every descriptor
+that reach its K-th nearest neighbour among the patches of OTHER images of its set (the patches of one image overlap, and repeat at
+coarse levels, so they do not count as neighbours).  Here BOTH sets are normalised by set A's statistics -- the two sets must live
+in one space -- unlike the distances above.  precision: share of set B's patches inside some ball of A ("share of generated local
+textures that occur in real images" -- patch descriptors are not image features); recall: share of A's patches inside some ball of
+B; density: B's ball hits / (K N); coverage: share of A's patches whose nearest patch of B lies inside their own ball; and, to tell
+copying from fidelity, nn_fake_real (median squared distance of a patch of B to its nearest patch of A) beside nn_real_real (of a
+patch of A to its nearest patch of another image of A) and their quotient nn_ratio: far below 1 means the generated patches sit
+closer to training patches than training patches of different images sit to each other.  K is 1..8 and at most N - swd_patches
+(every patch needs K neighbours in other images); anything else exits with status 2 before anything runs.  ops.knn_radii twice,
+ops.prd_rows twice and ops.prd_finish once per level, read back with the distances; prd.txt and prd.npz are written beside swd.txt.
+
+Written under results_dir/name/<phase>_<which_epoch>/: swd.npz (distances [levels,
 dirs], sizes, scores, the options) and swd.txt (one line `<H>x<W>: <score x 1e3>` per level, and their average)."""
 import argparse
 import os
@@ -28,10 +43,11 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from supervised_gan_amd.options import TestOptions  # noqa: E402
 from supervised_gan_amd.synthetic_data import SyntheticDataset  # noqa: E402
-from supervised_gan_amd.util import SWD_MAX_N, SWD_PATCH, lap_level_sizes, swd_draw  # noqa: E402
+from supervised_gan_amd.util import PRD_MAX_K, SWD_MAX_N, SWD_PATCH, lap_level_sizes, prd_from_counts, prd_ratio, swd_draw  # noqa: E402
 
 MODELS = ('fcgan', 'cgan', 'cgan2')
 MAX_DIRS = 4096
+PRD_KEYS = ('precision', 'recall', 'density', 'coverage', 'nn_fake_real', 'nn_real_real', 'nn_ratio')
 
 
 def _swd_args(argv):
@@ -43,6 +59,8 @@ def _swd_args(argv):
     p.add_argument('--swd_seed', type=int, default=0)
     p.add_argument('--swd_channels', type=int, nargs='+', default=None,
                    help='indices into the generated side\'s channels of --which_channel (default: all of them)')
+    p.add_argument('--prd_k', type=int, default=0,
+                   help='> 0: precision / recall / density / coverage with k-th-nearest-neighbour balls (1..8); 0: off')
     return p.parse_known_args(argv)
 
 
@@ -66,6 +84,21 @@ def summary_text(sizes, scores):
     lines = ['%dx%d: %.6f' % (h, w, s * 1e3) for (h, w), s in zip(sizes, scores)]
     lines.append('average: %.6f' % (float(np.mean(scores)) * 1e3))
     return '\n'.join(lines) + '\n'
+
+
+def prd_summary_text(sizes, prd):
+    """prd: {key: [levels]} of PRD_KEYS."""
+    fmt = ' '.join('%s %%.6f' % key for key in PRD_KEYS)
+    lines = ['%dx%d: ' % (h, w) + fmt % tuple(prd[key][l] for key in PRD_KEYS) for l, (h, w) in enumerate(sizes)]
+    lines.append('average: ' + fmt % tuple(float(np.mean(prd[key])) for key in PRD_KEYS))
+    return '\n'.join(lines) + '\n'
+
+
+def _median64(x):
+    """numpy's median of a float32 vector, on the device in float64: the mean of the two middle values of an even count."""
+    s = x.double().sort().values
+    n = s.numel()
+    return (s[(n - 1) // 2] + s[n // 2]) * 0.5
 
 
 class _Sets:
@@ -112,6 +145,21 @@ class _Sets:
         return torch.stack([ops.swd_distances(self.desc[0][l], self.desc[1][l], self.acc[0][l], self.acc[1][l], self.dirs[l])
                             for l in range(len(self.sizes))])
 
+    def prd(self, k):
+        """[levels, 6] float64 on the device: the four counts of ops.prd_finish (exact in float64) and the medians of the nearest
+        fake-to-real and real-to-real squared distances.  Both sets in set A's normalisation; group = the patches of one image."""
+        import torch
+        from supervised_gan_amd import ops
+        rows, P = [], self.sargs.swd_patches
+        for l in range(len(self.sizes)):
+            A, B, stats = self.desc[0][l], self.desc[1][l], self.acc[0][l]
+            radA, nn1A = ops.knn_radii(A, stats, k, P)
+            radB, _ = ops.knn_radii(B, stats, k, P)
+            cntB, nnB, _ = ops.prd_rows(B, A, stats, radA)
+            cntA, nnA, _ = ops.prd_rows(A, B, stats, radB)
+            rows.append(torch.cat([ops.prd_finish(cntB, cntA, nnA, radA).double(), torch.stack([_median64(nnB), _median64(nn1A)])]))
+        return torch.stack(rows)
+
 
 def main(argv=None, keep=None):
     """keep: an optional dict that receives {'A': [...], 'B': [...]}, the planar images of the two sets as they were scored (device
@@ -130,6 +178,10 @@ def main(argv=None, keep=None):
     if N > SWD_MAX_N:
         _refuse('N = how_many * swd_patches = %d * %d = %d descriptors per set; the limit is %d'
                 % (opt.how_many, sargs.swd_patches, N, SWD_MAX_N))
+    if sargs.prd_k and not 1 <= sargs.prd_k <= min(PRD_MAX_K, N - sargs.swd_patches):
+        _refuse('--prd_k is 0 (off) or 1..%d and at most N - swd_patches = %d - %d = %d: every patch needs that many neighbours among '
+                'the patches of other images (got %d); a level with fewer is refused, not scored'
+                % (PRD_MAX_K, N, sargs.swd_patches, N - sargs.swd_patches, sargs.prd_k))
     side = side_channels(opt, sargs.swd_pair)
     picks = list(range(len(side))) if sargs.swd_channels is None else sargs.swd_channels
     if not 1 <= len(picks) <= 3 or any(not 0 <= c < len(side) for c in picks):
@@ -190,19 +242,41 @@ def main(argv=None, keep=None):
         _refuse('the dataset gave %d and %d images for the two sets; --how_many %d needs %d files'
                 % (sets.count[0], sets.count[1], opt.how_many, opt.how_many * (1 if fake else 2)))
 
-    dist = sets.distances().cpu().numpy()      # the one read-back
+    if sargs.prd_k:
+        L, J = len(sets.sizes), sargs.swd_dirs
+        both = torch.cat([sets.distances().reshape(-1), sets.prd(sargs.prd_k).reshape(-1)]).cpu().numpy()      # the one read-back
+        dist, prd_raw = both[:L * J].reshape(L, J), both[L * J:].reshape(L, 6)
+    else:
+        dist = sets.distances().cpu().numpy()      # the one read-back
     ops.check_metric_err(dev)
     scores = dist.mean(axis=1)
     out_dir = os.path.join(opt.results_dir, opt.name, '%s_%s' % (opt.phase, opt.which_epoch))
     os.makedirs(out_dir, exist_ok=True)
     npz, txt = os.path.join(out_dir, 'swd.npz'), os.path.join(out_dir, 'swd.txt')
-    options = {k: str(v) for k, v in sorted(list(vars(opt).items()) + list(vars(sargs).items()))}
+    own = {k: v for k, v in vars(sargs).items() if k != 'prd_k' or v}      # without --prd_k, swd.npz is what it was before the flag existed
+    options = {k: str(v) for k, v in sorted(list(vars(opt).items()) + list(own.items()))}
     np.savez(npz, distances=dist, sizes=np.array(sets.sizes, dtype=np.int64), scores=scores, channels=np.array(picks, dtype=np.int64),
              option_names=np.array(list(options)), option_values=np.array(list(options.values())))
     text = summary_text(sets.sizes, scores)
     with open(txt, 'w') as f:
         f.write(text)
     print(text, end='')
+    if sargs.prd_k:
+        counts = np.rint(prd_raw[:, :4]).astype(np.int64)
+        prd = {key: [] for key in PRD_KEYS}
+        for l in range(len(sets.sizes)):
+            level = prd_from_counts(counts[l], N, sargs.prd_k)
+            level.update(nn_fake_real=float(prd_raw[l, 4]), nn_real_real=float(prd_raw[l, 5]), nn_ratio=prd_ratio(prd_raw[l, 4], prd_raw[l, 5]))
+            for key in PRD_KEYS:
+                prd[key].append(level[key])
+        np.savez(os.path.join(out_dir, 'prd.npz'), counts=counts, sizes=np.array(sets.sizes, dtype=np.int64), k=np.int64(sargs.prd_k),
+                 N=np.int64(N), group=np.int64(sargs.swd_patches), channels=np.array(picks, dtype=np.int64),
+                 option_names=np.array(list(options)), option_values=np.array(list(options.values())),
+                 **{key: np.array(prd[key], dtype=np.float64) for key in PRD_KEYS})
+        text = prd_summary_text(sets.sizes, prd)
+        with open(os.path.join(out_dir, 'prd.txt'), 'w') as f:
+            f.write(text)
+        print(text, end='')
     return npz, txt
 
 
