@@ -1014,6 +1014,50 @@ int64_t sgan_split_workspace(int32_t H, int32_t W);
 int sgan_split_cells(const float* plane, int64_t pix_stride, int32_t H, int32_t W, int32_t split_rsq, int32_t max_rounds, float* out,
                      int64_t* acc, void* workspace, int64_t workspace_bytes, int32_t* dev_err, void* stream);
 
+/* ---- topology scores on the device: windowed Betti errors and clDice ------------------------------------------------------------
+ * Whether the predicted wall has the topology of the true one, which neither the region nor the boundary scores say: the Betti
+ * error of the membrane-segmentation literature (the absolute difference in the number of wall components and of enclosed cells,
+ * window by window) and clDice, the centre-line Dice (Shit et al. 2021), with the library's Guo-Hall thinning for its skeletons.
+ * util.betti_window and util.topo_counts are the NumPy / scipy restatements this entry is tested against, util.topo_scores derives
+ * the scores.
+ *
+ * Planes: t (truth) and s (prediction) are read as sgan_ccl_label reads its plane, pixel (y, x) at t[(y * W + x) * t_ld]; a pixel is
+ *   wall when its value is > 0.5 (a NaN and an exact 0.5 are not wall).  t_thin and s_thin are dense [H * W] planes, the sgan_thin
+ *   outputs of t and s; each may be null, and the two counters of a null side are then left alone (counts_out: 0).
+ * Windows: wh = min(window, H) by ww = min(window, W) pixels, at the origins oy = 0, stride, 2 stride, ... while oy + wh <= H and
+ *   likewise in x; a strip at the bottom or the right that no full window covers is not scored.  8 <= window <= 64 and
+ *   1 <= stride <= window.
+ * Betti numbers of a window, everything outside the window counting as free:
+ *   b0 = the number of 8-connected components of its wall pixels;
+ *   b1 = the number of 4-connected components of its free pixels that own no pixel of the window's edge (the enclosed cells).
+ *   Then b0 - b1 = (Q1 - Q3 - 2 Qd) / 4, Gray's bit-quad count for 8-connectivity over the window padded with one free ring.
+ * acc_i, int64[SGAN_TOPO_COUNTS], caller-owned on the device, zeroed by the caller once, pooled over a dataset:
+ *   [0] += windows;  [1] += sum over the windows of |b0(S) - b0(T)|;  [2] += the same of b1;  [3] += sum of b0(S);  [4] += sum of b0(T);
+ *   [5] += sum of b1(S);  [6] += sum of b1(T);  [7] += pixels of s_thin (skel_s);  [8] += those of them that are wall in t;
+ *   [9] += pixels of t_thin (skel_t);  [10] += those of them that are wall in s;  [11] += 1 (images).
+ *   counts_out (int64[SGAN_TOPO_COUNTS], optional) receives this pair's contribution alone.
+ * Scores, derived on the host from the pooled integers (util.topo_scores); a score whose denominator is 0 reads 0:
+ *   Betti0Err = [1] / [0],  Betti1Err = [2] / [0],  Tprec = [8] / [7],  Tsens = [10] / [9],  clDice = 2 Tprec Tsens / (Tprec + Tsens).
+ * Exactness: integers only, 64-bit atomic adds: the same bits in every scheduling order.
+ * Launches: one workgroup per (window, map) stages the window's wall bits in LDS, labels wall (8-connected) and free (4-connected)
+ *   pixels in one union-find forest in LDS, counts the roots and writes (b0, b1) to the workspace; a grid-stride launch sums them;
+ *   with a thinned plane a grid-stride launch over the pixels counts the skeletons.  The grids depend on (H, W, window, stride)
+ *   alone, nothing is read back, no workgroup waits for another: the call captures into a hipGraph and replays on any other pair.
+ *   Every loop of the labelling is bounded by the window's 4096 nodes; a window whose loop ran out sets bit SGAN_TOPO_ERR_BIT of
+ *   dev_err and contributes nothing.  The workspace may hold anything on entry; 16-byte aligned.
+ * sgan_topo_workspace_bytes: bytes of that workspace (< 0: a window or stride that is not covered, or a bad shape).
+ * Returns 1 ("not covered"), the reason in sgan_last_error and nothing launched, for a window outside 8 .. 64 or a stride outside
+ *   1 .. window, and likewise for a null required pointer (t_thin, s_thin and counts_out are optional), a shape outside
+ *   H, W <= 32768 and H W < 2^30, a pixel stride < 1 and a short or misaligned workspace. */
+#define SGAN_TOPO_COUNTS 12
+#define SGAN_TOPO_SKEL_S 7
+#define SGAN_TOPO_IMAGES 11
+#define SGAN_TOPO_ERR_BIT 256
+int64_t sgan_topo_workspace_bytes(int32_t H, int32_t W, int32_t window, int32_t stride);
+int sgan_topo_accumulate(const float* t, int64_t t_ld, const float* s, int64_t s_ld, const float* t_thin, const float* s_thin, int32_t H,
+                         int32_t W, int32_t window, int32_t stride, void* workspace, int64_t workspace_bytes, int64_t* acc_i,
+                         int64_t* counts_out, int32_t* dev_err, void* stream);
+
 /* ---- whole-image inference: overlap tiles with blended seams, averaged over the 8 flips and rotations (not in the reference, whose
  * test_ss.py scores one crop; the overlap-tile strategy of Ronneberger et al. 2015, section 2) ------------------------------------
  * util.tile_plan / tile_window / prep_tile_ref / blend_tiles_ref are the NumPy restatement.  Per axis of length L: the

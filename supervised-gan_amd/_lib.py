@@ -183,6 +183,8 @@ SIGNATURES = {
     "sgan_clean_workspace": [_I, _I],
     "sgan_clean_wall": [_P, _L, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P],
     "sgan_split_workspace": [_I, _I],
+    "sgan_topo_workspace_bytes": [_I, _I, _I, _I],
+    "sgan_topo_accumulate": [_P, _L, _P, _L, _P, _P, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P],
     "sgan_split_cells": [_P, _L, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P],
     "sgan_image_prep_tile": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P],
     "sgan_tile_blend": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P],
@@ -216,7 +218,7 @@ RESTYPES = {"sgan_last_variant": C.c_char_p, "sgan_image_resize_workspace": C.c_
             "sgan_vinfo_workspace": C.c_int64, "sgan_thin_workspace": C.c_int64,
             "sgan_region_stats_workspace": C.c_int64, "sgan_object_match_workspace": C.c_int64,
             "sgan_edt_workspace": C.c_int64, "sgan_boundary_workspace": C.c_int64, "sgan_clean_workspace": C.c_int64,
-            "sgan_split_workspace": C.c_int64,
+            "sgan_split_workspace": C.c_int64, "sgan_topo_workspace_bytes": C.c_int64,
             "sgan_diffaug_workspace": C.c_int64, "sgan_swd_workspace": C.c_int64,
             "sgan_prd_workspace": C.c_int64}      # everything else returns an int status
 _lib = None

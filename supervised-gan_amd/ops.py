@@ -1317,6 +1317,9 @@ BOUNDARY_SUMS = ('sum_d_s', 'sum_d_t', 'sum_haus', 'zero3')
 CLEAN_COUNTS = ('closed_pixels', 'wall_components_removed', 'wall_pixels_removed', 'cells_filled', 'cell_pixels_filled', 'images')      # acc of clean_wall (SGAN_CLEAN_COUNTS)
 SPLIT_COUNTS = ('core_components', 'cut_pixels', 'labelled_pixels', 'rounds', 'budget_hits', 'images')      # acc of split_cells (SGAN_SPLIT_COUNTS)
 SPLIT_BUDGET_BIT = 64      # metric_err: split_cells' last round still labelled something; the map is complete for that budget, so no error
+# acc_i / counts_out of topo_accumulate (SGAN_TOPO_COUNTS of include/sgan_hip.h): windows scored, the summed |difference| of the windows'
+# Betti numbers, their plain sums per map (s: prediction, t: truth), the skeleton pixels of clDice, images
+TOPO_COUNTS = ('windows', 'abs_d0', 'abs_d1', 'b0_s', 'b0_t', 'b1_s', 'b1_t', 'skel_s', 'skel_s_in_t', 'skel_t', 'skel_t_in_s', 'images')
 VINFO_PARTS = ('SA', 'SB', 'SAB', 'aux', 'm', 'H_S', 'H_T', 'I', 'VInfo', 'split', 'merge')      # parts_out of vinfo_accumulate
 
 
@@ -1337,7 +1340,7 @@ def check_metric_err(device):
         e.zero_()
     if code & ~SPLIT_BUDGET_BIT:      # a split budget that was hit is counted in SPLIT_COUNTS; its map is what the budget defines
         raise L.SganError(f"segmentation metric kernels gave up on part of their input (flags {code:#x}: 1 = union-find bound, "
-                          "2 = pair table full, 4 / 8 = label out of range, 16 = thinning budget ran out, 32 = region table full, 128 = patch position outside its level); the accumulated values are incomplete")
+                          "2 = pair table full, 4 / 8 = label out of range, 16 = thinning budget ran out, 32 = region table full, 128 = patch position outside its level, 256 = a topology window's labelling did not converge); the accumulated values are incomplete")
 
 
 def _metric_workspace(symbol, H, W, device):
@@ -1754,6 +1757,51 @@ def boundary_accumulate(t_dsq, s_dsq, acc_i, acc_f, counts_out=None, sums_out=No
     L.check(L.lib().sgan_boundary_accumulate(_ptr(t_dsq), _ptr(s_dsq), H, W, _ptr(ws), ws.numel() * ws.element_size(), _ptr(acc_i),
                                              _ptr(acc_f), _ptr(counts_out), _ptr(sums_out), _ptr(metric_err(dev)), _stream()),
             "sgan_boundary_accumulate")
+
+
+_topo_ws = {}         # (H, W, window, stride, device index) -> the int64 scratch of topo_accumulate
+
+
+def topo_workspace(H, W, window, stride, device):
+    """The scratch of topo_accumulate for H x W maps (the two Betti numbers of every window of both maps), cached per
+    (H, W, window, stride, device); the kernels initialise what they use."""
+    key = (H, W, int(window), int(stride), device.index)
+    ws = _topo_ws.get(key)
+    if ws is None:
+        nbytes = L.lib().sgan_topo_workspace_bytes(H, W, int(window), int(stride))
+        if nbytes < 0:
+            raise L.SganError(f"sgan_topo_workspace_bytes({H}, {W}, {window}, {stride}): {L.lib().sgan_last_error().decode()}")
+        ws = _topo_ws[key] = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
+    return ws
+
+
+def topo_accumulate(t, s, acc_i, t_thin=None, s_thin=None, window=64, stride=None, counts_out=None, workspace=None):
+    """Adds the topology counts (include/sgan_hip.h, "topology scores") of the predicted plane s against the truth t, both [H, W]
+    float32 with wall where > 0.5, to acc_i (int64[12], TOPO_COUNTS) on the device, zeroed by the caller once
+    (sgan_topo_accumulate): over the windows of `window` pixels every `stride` (None: window) the numbers of 8-connected wall
+    components and of enclosed 4-connected free components of either map and the absolute differences between the maps; with
+    t_thin / s_thin (thin's outputs of t / s, dense) the skeleton pixels of clDice.  A side whose thinned plane is None leaves its
+    two counters alone.  counts_out (int64[12]) receives this pair's contribution alone.  Only enqueues -- the launch sequence
+    depends on (H, W, window, stride) and on which thinned planes are given alone -- and reads t and s in place when their rows
+    are W pixel strides apart.  util.topo_counts is the host yardstick and util.topo_scores derives Betti0Err, Betti1Err and
+    clDice.  A window outside 8 .. 64 or a stride outside 1 .. window is not covered."""
+    t, s = _plane(t, "topo_accumulate"), _plane(s, "topo_accumulate")
+    H, W = t.shape
+    dev = t.device
+    stride = window if stride is None else stride
+    assert tuple(s.shape) == (H, W) and s.device == dev, (s.shape, t.shape)
+    for thin_plane in (t_thin, s_thin):
+        assert thin_plane is None or (thin_plane.dtype == torch.float32 and thin_plane.is_contiguous() and tuple(thin_plane.shape) == (H, W)
+                                      and thin_plane.device == dev), (thin_plane.shape, thin_plane.dtype)
+    assert acc_i is not None and all(_is_acc(a, torch.int64, len(TOPO_COUNTS), dev) for a in (acc_i, counts_out))
+    if not (8 <= int(window) <= 64 and 1 <= int(stride) <= int(window)):
+        raise L.SganError(f"sgan_topo_accumulate: not covered (window {window}: 8 .. 64, stride {stride}: 1 .. window); nothing was launched")
+    ws = topo_workspace(H, W, window, stride, dev) if workspace is None else workspace
+    rc = L.lib().sgan_topo_accumulate(_ptr(t), t.stride(1), _ptr(s), s.stride(1), _ptr(t_thin), _ptr(s_thin), H, W, int(window), int(stride),
+                                      _ptr(ws), ws.numel() * ws.element_size(), _ptr(acc_i), _ptr(counts_out), _ptr(metric_err(dev)), _stream())
+    if rc == 1:
+        raise L.SganError(f"sgan_topo_accumulate: {L.lib().sgan_last_error().decode()}; nothing was launched")
+    L.check(rc, "sgan_topo_accumulate")
 
 
 def clean_workspace(H, W, device):

@@ -62,7 +62,7 @@ class BaseOptions:
         a('--n_layers_G_skip', type=int, default=-1)
         a('--weights', type=float, default=None, nargs='+')
         a('--use_sigmoid_ss', action='store_true')            # segmentation: sigmoid instead of softmax (base_options.py:55)
-        a('--which_metric', default=['None'], nargs='+')      # any of RandScore, VInfo, meanIU, RandScoreThin, VInfoThin, ObjF1, ObjAP, SEG, PQ, BoundF, HausD, ASSD (device accumulators, seg_metrics.py)
+        a('--which_metric', default=['None'], nargs='+')      # any of RandScore, VInfo, meanIU, RandScoreThin, VInfoThin, ObjF1, ObjAP, SEG, PQ, BoundF, HausD, ASSD, Betti0Err, Betti1Err, clDice (device accumulators, seg_metrics.py)
         a('--min_object_area', type=int, default=1)           # ObjF1 / ObjAP / SEG / PQ: regions with fewer pixels count as absent, on both sides
         a('--clean_close', type=float, default=0.0)           # clean the predicted wall before the label-based scores: close gaps with a disk of this radius, close_rsq = floor(R * R); 1 = the 4-neighbour plus, 1.5 = the 3 x 3 box; at most 64
         a('--clean_min_wall', type=int, default=0)            # ... then drop 8-connected wall components with fewer pixels than this
@@ -71,6 +71,8 @@ class BaseOptions:
         a('--clean_split_rounds', type=int, default=64)       # ... flood rounds of --clean_split (one per pixel of distance from a core): 1 .. 4096
         a('--boundary_tolerance', type=int, default=2, choices=range(31), metavar='0..30')      # BoundF: a wall pixel within this many pixels of the other map's wall is matched
         a('--boundary_thin', action='store_true')             # BoundF / HausD / ASSD: thin the predicted wall to one-pixel lines first, as BSDS does; the truth is not thinned
+        a('--topo_window', type=int, default=64)              # Betti0Err / Betti1Err: the side of the windows the Betti numbers are taken in, 8 .. 64 (clamped to the image); a strip no full window covers is not scored
+        a('--topo_stride', type=int, default=None)            # ... and the step between window origins, 1 .. --topo_window; default: the window, no overlap
         a('--add_background_onehot', action='store_true')
         a('--add_background_onehot_acc', action='store_true')
         a('--valSize', type=int, default=0)                   # train_ss.py: size of the validation images, 0 = loadSize (base_options.py:102)
@@ -138,6 +140,7 @@ class BaseOptions:
         self.opt.isTrain = self.isTrain
         check_border_options(self.opt)
         check_clean_options(self.opt, self.parser)
+        check_topo_options(self.opt, self.parser)
         check_elastic_options(self.opt)
         check_tile_options(self.opt, self.parser)
         check_ema_options(self.opt, self.parser)
@@ -200,6 +203,29 @@ def check_clean_options(opt, parser=None):
         if parser is not None:
             parser.error(bad)
         raise ValueError(bad)
+
+
+def check_topo_options(opt, parser=None):
+    """--topo_window N: 8 .. 64 (a window is labelled in one workgroup's LDS); --topo_stride S: 1 .. N, default N; refused at parse
+    time.  Leaves opt.topo_stride filled in."""
+    window, stride = topo_params(opt)
+    bad = None
+    if not 8 <= window <= 64:
+        bad = "--topo_window: 8 .. 64 (got %d)" % window
+    elif not 1 <= stride <= window:
+        bad = "--topo_stride: 1 .. --topo_window = %d (got %d)" % (window, stride)
+    if bad is not None:
+        if parser is not None:
+            parser.error(bad)
+        raise ValueError(bad)
+    opt.topo_stride = stride
+
+
+def topo_params(opt):
+    """(window, stride) of ops.topo_accumulate from --topo_window / --topo_stride; (64, 64) for an options object without them."""
+    window = int(getattr(opt, 'topo_window', 64))
+    stride = getattr(opt, 'topo_stride', None)
+    return window, window if stride is None else int(stride)
 
 
 def split_params(opt):

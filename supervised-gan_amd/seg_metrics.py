@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import ops, util
-from .options import clean_params, split_params
+from .options import clean_params, split_params, topo_params
 
 # Every device accumulator: name, dtype, shape (k: the classes of the confusion matrix).  Each is made the first time a score adds
 # to it; reset(), read() and counts() walk this table.
@@ -45,9 +45,13 @@ CLEAN_ACCUMULATORS = (
     ('clean_post_i', torch.int64, (len(ops.CLEAN_COUNTS),)),      # ... of the second call, small cells after --clean_split (its own image count)
     ('split_i', torch.int64, (len(ops.SPLIT_COUNTS),)),           # ops.split_cells' pooled counters
 )
+# The pooled integers of the topology scores, made only when Betti0Err, Betti1Err or clDice is asked for; beside ACCUMULATORS too.
+TOPO_ACCUMULATORS = (
+    ('topo_i', torch.int64, (len(ops.TOPO_COUNTS),)),             # ops.topo_accumulate's pooled counters
+)
 COUNTS = {'objects': ('obj_i', 'obj_f', ops.OBJECT_COUNTS, ops.OBJECT_SUMS),
           'boundary': ('bnd_i', 'bnd_f', ops.BOUNDARY_COUNTS, ops.BOUNDARY_SUMS)}
-SCORES = ('RandScore', 'VInfo', 'meanIU', 'RandScoreThin', 'VInfoThin') + util.OBJECT_METRICS + util.BOUNDARY_METRICS      # as read() orders them
+SCORES = ('RandScore', 'VInfo', 'meanIU', 'RandScoreThin', 'VInfoThin') + util.OBJECT_METRICS + util.BOUNDARY_METRICS + util.TOPO_METRICS      # as read() orders them
 VALUES = ('confusion', 'numAveragedPixels', 'numAveragedImages', 'pixelAcc', 'meanAcc') + SCORES
 
 
@@ -98,6 +102,11 @@ class _Planes:
         return ops.thin(self.s, out=self._store('thinned', torch.float32))
 
     @cached_property
+    def thinned_truth(self):
+        """The truth thinned by the same ops.thin: the skeleton clDice's sensitivity is taken on."""
+        return ops.thin(self.t, out=self._store('thinned_truth', torch.float32))
+
+    @cached_property
     def thinned_labels(self):
         return ops.ccl_label(self.thinned, self._store('thinned_labels', torch.int32))
 
@@ -123,7 +132,7 @@ class SegMetrics:
     def _acc(self, name):
         if name not in self.acc:
             k = self.num_classes + 1 if self.opt.add_background_onehot_acc else self.num_classes
-            dtype, shape = next((d, s(k) if callable(s) else s) for n, d, s in ACCUMULATORS + CLEAN_ACCUMULATORS if n == name)
+            dtype, shape = next((d, s(k) if callable(s) else s) for n, d, s in ACCUMULATORS + CLEAN_ACCUMULATORS + TOPO_ACCUMULATORS if n == name)
             self.acc[name] = torch.zeros(shape, dtype=dtype, device=self.device)
         return self.acc[name]
 
@@ -155,6 +164,8 @@ class SegMetrics:
         below --min_object_area left out.  meanIU: conf[label, prediction] += 1 for every pixel (segm_model.py:309-331).
         BoundF .. ASSD: how far every predicted wall pixel lies from the true wall and every true wall pixel from the predicted one
         (ops.boundary_accumulate).
+        Betti0Err / Betti1Err / clDice: the Betti numbers of every --topo_window window of both walls and, for clDice alone, the
+        skeleton pixels of the thinned prediction and of the thinned truth (ops.topo_accumulate, one call for the three).
         With a --clean_* option all of these but meanIU read the cleaned prediction (ops.clean_wall, once per call; with
         --clean_split ops.split_cells between its specks and its small cells)."""
         o = self.opt
@@ -180,6 +191,11 @@ class SegMetrics:
         if any(k in which for k in util.BOUNDARY_METRICS):
             t_dsq, s_dsq = p.dsq
             ops.boundary_accumulate(t_dsq, s_dsq, self._acc('bnd_i'), self._acc('bnd_f'))
+        if any(k in which for k in util.TOPO_METRICS):
+            window, stride = topo_params(o)
+            cl = 'clDice' in which
+            ops.topo_accumulate(p.t, p.s, self._acc('topo_i'), t_thin=p.thinned_truth if cl else None, s_thin=p.thinned if cl else None,
+                                window=window, stride=stride)
 
     def _rand_vinfo(self, t_labels, s_labels, rand, vinfo):
         if vinfo is not None:          # one counting pass feeds both scores
@@ -188,7 +204,8 @@ class SegMetrics:
             ops.rand_f_accumulate(t_labels, s_labels, self._acc(rand))
 
     def counts(self, which):
-        """'split': the six pooled integers of ops.SPLIT_COUNTS (core components, cut pixels, labelled pixels, rounds, budget hits,
+        """'topology': the twelve pooled integers of ops.TOPO_COUNTS (windows, the summed Betti differences and Betti numbers, the
+        skeleton pixels, images).  'split': the six pooled integers of ops.SPLIT_COUNTS (core components, cut pixels, labelled pixels, rounds, budget hits,
         images).  'clean': the six pooled integers of ops.CLEAN_COUNTS (pixels set by the closing, wall components / pixels removed, cells /
         cell pixels filled, images).  Otherwise the pooled numbers of 'objects' (the 16 integers of ops.OBJECT_COUNTS: TP_0 .. TP_9 at IoU > 0.5 .. 0.95, N_t, N_s, images,
         SEGn; the two sums of ops.OBJECT_SUMS) or 'boundary' (the 80 integers of ops.BOUNDARY_COUNTS: the two histograms by distance
@@ -197,6 +214,12 @@ class SegMetrics:
             if 'clean_i' in self.acc or 'clean_post_i' in self.acc:
                 ops.check_metric_err(self.device)
             return OrderedDict(zip(ops.CLEAN_COUNTS, self._clean_counts()))
+        if which == 'topology':
+            ints = [0] * len(ops.TOPO_COUNTS)
+            if 'topo_i' in self.acc:
+                ops.check_metric_err(self.device)
+                ints = self.acc['topo_i'].cpu().tolist()
+            return OrderedDict(zip(ops.TOPO_COUNTS, ints))
         if which == 'split':
             ints = [0] * len(ops.SPLIT_COUNTS)
             if 'split_i' in self.acc:
@@ -222,20 +245,24 @@ class SegMetrics:
         counts), then BoundF / HausD / ASSD (util.boundary_scores at --boundary_tolerance).  Built for evaluation (test_ss.py) it also
         prints the pooled TP_k / N_t / N_s line when an object score was taken, and the boundary precision / recall / F at the
         tolerances 0 .. 5 with the dataset's worst distance when a boundary score was, and the pooled counts of the cleaning stage
-        when a --clean_* option ran it, then those of --clean_split."""
+        when a --clean_* option ran it, then those of --clean_split, then the `topology:` line (windows, the mean Betti numbers
+        of either map, Tprec / Tsens) when a topology score was taken.  Betti0Err / Betti1Err / clDice (util.topo_scores of the pooled
+        integers) come last."""
         o, v = self.opt, self.values
         if self.acc:
             ops.check_metric_err(self.device)
             k = self.num_classes + 1 if o.add_background_onehot_acc else self.num_classes
             a = {n: self.acc[n].cpu().numpy() if n in self.acc else np.zeros(s(k) if callable(s) else s) for n, _, s in ACCUMULATORS}
             obj_i, bnd_i = a['obj_i'], a['bnd_i']
+            topo_i = self.acc['topo_i'].cpu().numpy() if 'topo_i' in self.acc else np.zeros(len(ops.TOPO_COUNTS), dtype=np.int64)
             oc, bc = ops.OBJECT_COUNTS.index, ops.BOUNDARY_COUNTS.index
             for key, n in (('RandScore', 'rand'), ('VInfo', 'vinfo'), ('RandScoreThin', 'rand_thin'), ('VInfoThin', 'vinfo_thin')):
                 v[key] = a[n][0] / a[n][1] if a[n][1] else 0
             v['numAveragedImages'] = int(max(a['rand'][1], a['vinfo'][1], a['rand_thin'][1], a['vinfo_thin'][1],
-                                             obj_i[oc('images')], bnd_i[bc('images')]))
+                                             obj_i[oc('images')], bnd_i[bc('images')], topo_i[ops.TOPO_COUNTS.index('images')]))
             v.update(util.object_scores(obj_i, a['obj_f']))
             v.update(util.boundary_scores(bnd_i, a['bnd_f'], o.boundary_tolerance))
+            v.update(util.topo_scores(topo_i))
             if not o.isTrain and 'obj_i' in self.acc and any(key in o.which_metric for key in util.OBJECT_METRICS):
                 # the evaluation drivers read the accuracies once, after the dataset: the per-threshold table goes beside them
                 print('objects: TP at IoU > 0.50 .. 0.95: %s, N_t %d, N_s %d (min area %d)'
@@ -253,6 +280,12 @@ class SegMetrics:
                 c = self.acc['split_i'].cpu().tolist()
                 print('split: %d cores, cut %d pixels, labelled %d pixels in %d rounds, budget hit in %d of %d images '
                       '(split_rsq %d, %d rounds)' % (tuple(c) + split_params(o)))
+            if not o.isTrain and 'topo_i' in self.acc and any(key in o.which_metric for key in util.TOPO_METRICS):
+                c = dict(zip(ops.TOPO_COUNTS, (int(x) for x in topo_i)))
+                n = max(1, c['windows'])
+                print('topology: %d windows of %d at stride %d, mean b0 / b1 of the prediction %.3f / %.3f, of the truth %.3f / %.3f, '
+                      'Tprec %.4f, Tsens %.4f' % ((c['windows'],) + topo_params(o) + (c['b0_s'] / n, c['b1_s'] / n, c['b0_t'] / n, c['b1_t'] / n,
+                                                   c['skel_s_in_t'] / max(1, c['skel_s']), c['skel_t_in_s'] / max(1, c['skel_t']))))
             conf = a['conf'].astype(np.float64)
             v['confusion'], v['numAveragedPixels'] = conf, int(conf.sum())
             rel, sel, tp = conf.sum(axis=1), conf.sum(axis=0), np.diag(conf)
@@ -295,6 +328,9 @@ class SegMetricsMixin:
 
     def get_split_counts(self):
         return self.seg_metrics.counts('split')
+
+    def get_topology_counts(self):
+        return self.seg_metrics.counts('topology')
 
     def with_cleaned_visual(self, visuals):
         """Built for evaluation with a --clean_* option: adds the wall map the label-based scores of the last accum_accs() were taken

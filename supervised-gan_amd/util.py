@@ -802,6 +802,85 @@ def boundary_scores(counts, sums, tolerance):
                         ('ASSD', (float(sums[0]) + float(sums[1])) / n_d if n_d else 0.0)])
 
 
+# ---- topology scores: windowed Betti errors and clDice (the yardsticks of sgan_topo.hip) -----------------------------------
+TOPO_METRICS = ('Betti0Err', 'Betti1Err', 'clDice')      # the --which_metric names topo_scores derives, in the order they are reported
+TOPO_COUNTS = ('windows', 'abs_d0', 'abs_d1', 'b0_s', 'b0_t', 'b1_s', 'b1_t', 'skel_s', 'skel_s_in_t', 'skel_t', 'skel_t_in_s', 'images')
+
+
+def betti_window(wall):
+    """(b0, b1) of one window, a [h, w] wall mask (bool, or a map thresholded at > 0.5) cut out of its image, so that everything
+    outside it is free: b0 = the 8-connected components of the wall, b1 = the 4-connected components of the free pixels that touch no
+    edge of the window -- the enclosed cells.  scipy.ndimage.label on the window padded with one ring of free pixels, whose component
+    is the outside."""
+    from scipy import ndimage
+    wall = np.array(_wall_mask(wall), dtype=bool)
+    assert wall.ndim == 2, wall.shape
+    _, b0 = ndimage.label(wall, structure=np.ones((3, 3)))
+    _, n_free = ndimage.label(~np.pad(wall, 1, constant_values=False))      # the default structure: 4-connected
+    return int(b0), int(n_free) - 1
+
+
+def euler_bitquads(wall):
+    """The Euler number of a window for 8-connectivity from Gray's bit quads, (Q1 - Q3 - 2 Qd) / 4 over every 2 x 2 block of the
+    window padded with one ring of free pixels: Q1 / Q3 the blocks with one / three wall pixels, Qd those with two on a diagonal.
+    Equals b0 - b1 of betti_window."""
+    p = np.pad(np.array(_wall_mask(wall), dtype=bool), 1, constant_values=False).astype(np.int64)
+    a, b, c, d = p[:-1, :-1], p[:-1, 1:], p[1:, :-1], p[1:, 1:]
+    n = a + b + c + d
+    q1, q3 = int((n == 1).sum()), int((n == 3).sum())
+    qd = int(((n == 2) & (a == d)).sum())
+    assert (q1 - q3 - 2 * qd) % 4 == 0
+    return (q1 - q3 - 2 * qd) // 4
+
+
+def topo_windows(H, W, window, stride):
+    """(wh, ww, the origins in y, the origins in x) of the windows of an H x W map: wh = min(window, H) by ww = min(window, W) pixels
+    at 0, stride, 2 stride, ... while the window lies inside the map.  A strip at the bottom or the right that no full window covers
+    is not scored."""
+    assert H >= 1 and W >= 1 and 8 <= window <= 64 and 1 <= stride <= window, (H, W, window, stride)
+    wh, ww = min(window, H), min(window, W)
+    return wh, ww, list(range(0, H - wh + 1, stride)), list(range(0, W - ww + 1, stride))
+
+
+def topo_counts(s_wall, t_wall, window=64, stride=None, s_thin=None, t_thin=None):
+    """The topology counts (include/sgan_hip.h, "topology scores") of the predicted wall s_wall against the true wall t_wall, two
+    [H, W] masks (bool, or maps thresholded at > 0.5): int64[12] in TOPO_COUNTS' order.  Over topo_windows: the windows, the sums
+    of |b0(S) - b0(T)| and |b1(S) - b1(T)| and the plain sums of betti_window.  s_thin / t_thin: the thinned maps (thin of s_wall /
+    t_wall), for the skeleton pixels and how many of them are wall in the other map; a side that is None counts nothing.  The host
+    yardstick of ops.topo_accumulate; the trainers do not call it."""
+    s_wall, t_wall = _wall_mask(s_wall), _wall_mask(t_wall)
+    assert s_wall.ndim == 2 and s_wall.shape == t_wall.shape, (s_wall.shape, t_wall.shape)
+    H, W = s_wall.shape
+    wh, ww, ys, xs = topo_windows(H, W, window, window if stride is None else stride)
+    c = np.zeros(len(TOPO_COUNTS), dtype=np.int64)
+    for oy in ys:
+        for ox in xs:
+            (b0s, b1s), (b0t, b1t) = (betti_window(m[oy:oy + wh, ox:ox + ww]) for m in (s_wall, t_wall))
+            c[:7] += (1, abs(b0s - b0t), abs(b1s - b1t), b0s, b0t, b1s, b1t)
+    if s_thin is not None:
+        k = _wall_mask(s_thin)
+        c[7], c[8] = int(k.sum()), int((k & t_wall).sum())
+    if t_thin is not None:
+        k = _wall_mask(t_thin)
+        c[9], c[10] = int(k.sum()), int((k & s_wall).sum())
+    c[11] = 1
+    return c
+
+
+def topo_scores(counts):
+    """Betti0Err, Betti1Err and clDice (an OrderedDict in that order) from pooled topo_counts / ops.topo_accumulate integers: the mean
+    over the windows of |b0(S) - b0(T)| and of |b1(S) - b1(T)|, and the harmonic mean of Tprec = skel_s_in_t / skel_s and
+    Tsens = skel_t_in_s / skel_t.  A zero denominator reads 0, as in boundary_pr.  The one place the trainers and the tests derive
+    them."""
+    from collections import OrderedDict
+    n, n_s, n_t = int(counts[0]), int(counts[7]), int(counts[9])
+    p = int(counts[8]) / n_s if n_s else 0.0
+    r = int(counts[10]) / n_t if n_t else 0.0
+    return OrderedDict([('Betti0Err', int(counts[1]) / n if n else 0.0),
+                        ('Betti1Err', int(counts[2]) / n if n else 0.0),
+                        ('clDice', 2.0 * p * r / (p + r) if p + r else 0.0)])
+
+
 # ---- differentiable augmentation of discriminator inputs (--diffaug; the yardsticks of sgan_diffaug.hip, DESIGN.md R24) -----------------
 DIFFAUG_OPS = ('translation', 'cutout', 'brightness', 'contrast')
 

@@ -34,7 +34,7 @@ from supervised_gan_amd.util import save_image, tensor2im  # noqa: E402
 from supervised_gan_amd.visualizer import Visualizer  # noqa: E402
 
 
-LOWER_IS_BETTER = ('HausD', 'ASSD')      # distances in pixels: reported, never the --best_metric
+LOWER_IS_BETTER = ('HausD', 'ASSD', 'Betti0Err', 'Betti1Err')      # distances in pixels and Betti errors: reported, never the --best_metric
 
 
 def improves(value, best):
@@ -106,8 +106,8 @@ def main(argv=None):
         raise ValueError("--graph: the captured step owns the trainer's input buffers, so --valSize (%d) must equal --fineSize (%d)"
                          % (opt_val.valSize, opt.fineSize))
     if opt.best_metric in LOWER_IS_BETTER:
-        raise ValueError("--best_metric %s: a distance, lower is better, and the `best` checkpoint is kept by the highest value; "
-                         "choose a score among --which_metric (BoundF is the boundary score that rises)" % opt.best_metric)
+        raise ValueError("--best_metric %s: a distance or an error count, lower is better, and the `best` checkpoint is kept by the highest "
+                         "value; choose a score among --which_metric (BoundF is the boundary score that rises, clDice the topology score)" % opt.best_metric)
     if opt.best_metric != 'None' and opt.best_metric not in opt.which_metric:
         raise ValueError("--best_metric %s is not among --which_metric %s" % (opt.best_metric, ' '.join(opt.which_metric)))
     model = create_model(opt)
