@@ -70,7 +70,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 extern thread_local char g_sgan_err[512];
 int sgan_fail(int code, const char* fmt, ...);
 extern thread_local const char* g_sgan_last_kernel;  // name of the kernel the last conv entry point launched
-extern thread_local char g_sgan_last_variant[96];    // what the name does not tell (sgan_last_variant()): set by the launchers of the 4-channel-side kernels, of the exact-fp32 MFMA kernels and of the split 16-bit-plane kernels
+extern thread_local char g_sgan_last_variant[96];    // what the name does not tell (sgan_last_variant()): set by the launchers of the 4-channel-side kernels, of the exact-fp32 MFMA kernels, of the split 16-bit-plane kernels and of the one-channel head kernels
 
 // Optional per-launch timing (sgan_profile_*): when enabled, every main conv kernel launch is bracketed by two
 // HIP events recorded on the launch stream from inside the library (back to back with the launch, so a busy

@@ -174,6 +174,13 @@ __global__ __launch_bounds__(256) void sg_head_bwd_kernel(const SgHeadParams G) 
     }
 }
 
+// both plain reads, or the same statistics, affine, activation and strides
+static bool sg_head_same_norm(const sgan_norm_desc* a, const sgan_norm_desc* b) {
+    if (!a || !b) return a == b;
+    return a->stats == b->stats && a->gamma == b->gamma && a->beta == b->beta && a->count == b->count && a->eps == b->eps && a->act == b->act &&
+           a->slope == b->slope && a->sq_stride == b->sq_stride && a->rep_stride == b->rep_stride;
+}
+
 // 0: launched; 1: not this layer type (the caller issues the generic calls); < 0: error
 extern "C" int sgan_conv_head_bwd(const sgan_conv_dgrad_job* djobs, const sgan_conv_wgrad_job* wjobs, int32_t n, void* stream) {
     static const int off = getenv("SGAN_NO_HEAD_BWD") ? 1 : 0;
@@ -201,6 +208,8 @@ extern "C" int sgan_conv_head_bwd(const sgan_conv_dgrad_job* djobs, const sgan_c
         const sgan_norm_desc* xn = J.x_norm;
         if ((xn ? xn->act : SGAN_ACT_NONE) != P.xn_act) return sgan_fail(SGAN_ERR_INVALID, "grouped jobs must share the activation");
         if (wjobs && (wjobs[g].dout != J.dout || wjobs[g].in != J.x || wjobs[g].d != J.d)) return 1;      // the two job lists must describe the same pass
+        // ... and read the forward tensor the same way: the kernel takes its pixel stride and its normalisation from the backward-data job
+        if (wjobs && (wjobs[g].in_ld != J.x_ld || !sg_head_same_norm(wjobs[g].in_norm, xn))) return 1;
         SgHeadProb& Q = P.q[g];
         Q.x = J.x; Q.din = J.din; Q.dz = J.dout; Q.w = J.w; Q.dw = wjobs ? wjobs[g].dw : nullptr; Q.dbias = wjobs ? wjobs[g].dbias : nullptr;
         Q.sums = J.bwd_sums;
@@ -231,6 +240,7 @@ extern "C" int sgan_conv_head_bwd(const sgan_conv_dgrad_job* djobs, const sgan_c
     else hipLaunchKernelGGL(sg_head_bwd_kernel<3>, grid, dim3(256), 0, st, P);
     SGAN_LAUNCH_CHECK();
     g_sgan_last_kernel = "sg_head_bwd_kernel";
+    snprintf(g_sgan_last_variant, sizeof(g_sgan_last_variant), "K%d tiles%d gy%d", P.k, tiles, (int)grid.y);
     sg_prof_end(st, g_sgan_last_kernel);
     return SGAN_OK;
 }
@@ -375,8 +385,8 @@ __global__ __launch_bounds__(256) void sg_conv_head2_kernel(const SgIgemmParams 
 
 // 0: launched; 1: not covered (the caller goes on to sg_conv_head_kernel); called after sg_head_plan() accepted the launch
 int sg_launch_head2(SgIgemmParams& P, hipStream_t st) {
-    static const int off = getenv("SGAN_NO_HEAD2") ? 1 : 0;
-    if (off || P.Ck < 64 || P.nphase != 1 || P.is != 1 || P.os != 1 || P.w_ks != 1) return 1;
+    // SGAN_NO_HEAD2 and SGAN_HEAD2_R are read per call: tests walk the instantiations in one process
+    if (getenv("SGAN_NO_HEAD2") || P.Ck < 64 || P.nphase != 1 || P.is != 1 || P.os != 1 || P.w_ks != 1) return 1;
     const int nt = P.ntaps[0];
     const int K = nt == 16 ? 4 : nt == 9 ? 3 : 0;
     if (!K) return 1;
@@ -389,7 +399,8 @@ int sg_launch_head2(SgIgemmParams& P, hipStream_t st) {
     const int pad = -dy0;
     const int nch = (P.Ck + 63) / 64;
     const int nrg = nch >= 3 ? 1 : nch == 2 ? 2 : 4;      // row groups per workgroup: waves that have no channel chunk of their own take rows
-    static const int r_env = getenv("SGAN_HEAD2_R") ? atoi(getenv("SGAN_HEAD2_R")) : 0;      // tuning knob: 2 or 4 result rows per wave
+    const char* r_str = getenv("SGAN_HEAD2_R");
+    const int r_env = r_str ? atoi(r_str) : 0;      // tuning knob: 2 or 4 result rows per wave
     const int R = r_env == 4 ? 4 : 2;
     int t = 0;
     for (int g = 0; g < P.nprob; ++g) {
@@ -406,6 +417,7 @@ int sg_launch_head2(SgIgemmParams& P, hipStream_t st) {
     else hipLaunchKernelGGL((sg_conv_head2_kernel<3, 4>), dim3(t), dim3(256), 0, st, P, pad, nrg);
     SGAN_LAUNCH_CHECK();
     g_sgan_last_kernel = "sg_conv_head2_kernel";
+    snprintf(g_sgan_last_variant, sizeof(g_sgan_last_variant), "K%d R%d nrg%d", K, R, nrg);
     sg_prof_end(st, g_sgan_last_kernel);
     return SGAN_OK;
 }

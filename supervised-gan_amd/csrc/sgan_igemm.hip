@@ -820,7 +820,8 @@ static bool sg_head_plan(SgIgemmParams& P) {
     // tile height: 8 rows when that alone gives every CU a few workgroups, else 4 (SGAN_HEAD_TH = 8 / 4 / 2 overrides: tuning knob)
     long t8 = 0;
     for (int g = 0; g < P.nprob; ++g) t8 += (long)((P.q[g].Hp[0] + 7) / 8) * ((P.q[g].Wp[0] + 7) / 8);
-    static const int th_env = getenv("SGAN_HEAD_TH") ? atoi(getenv("SGAN_HEAD_TH")) : 0;
+    const char* th_str = getenv("SGAN_HEAD_TH");      // read per call: tests walk the tile heights in one process
+    const int th_env = th_str ? atoi(th_str) : 0;
     int th = t8 >= 1024 ? 8 : 4;      // fcgan heads (230 tall tiles): 27.6 us with 8 rows, 21.6 with 4, 22.5 with 2
     if (th_env == 8 || th_env == 4 || th_env == 2) th = th_env;
     P.pph[0] = th + dy1 - dy0; P.ppw[0] = 8 + dx1 - dx0;
@@ -851,6 +852,7 @@ static int sg_launch_head(SgIgemmParams& P, hipStream_t st) {
     else hipLaunchKernelGGL(sg_conv_head_kernel<2>, dim3(t), dim3(256), lds, st, P);
     SGAN_LAUNCH_CHECK();
     g_sgan_last_kernel = "sg_conv_head_kernel";
+    snprintf(g_sgan_last_variant, sizeof(g_sgan_last_variant), "TH%d", th);
     sg_prof_end(st, g_sgan_last_kernel);
     return SGAN_OK;
 }

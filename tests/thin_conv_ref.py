@@ -29,6 +29,13 @@ The constants, derived (every term an upper bound, none measured):
   bias 1, accumulate 1 (|previous| joins both magnitudes), act' 1 (the multiply by the negative slope, backward-data): c_a.
   => forward (L + 1) u M_a + 8 u M_A;  backward-weight (L + 1) u M_a + 8 u M_A;  backward-data reads dY plain: (L + 4) u M;
      bias gradient (L + 3) u M.
+  xhat form    c_A 9  sg_head_bwd_kernel forms its backward-weight operand as y = gamma ((x - mean) rstd) + beta, the reference as
+                      x sc + sh.  Against the exact value from the fp32 mean / rstd / gamma / beta the kernel's three roundings before the
+                      last addition cost 3 u (|x| + |mean|) |gamma rstd| and the addition u |y|; the reference's sc, x sc, mean sc, sh and
+                      the addition 2 u |x sc| + 2 u |mean sc| + u |sh| + u |y|: together 5 u (|x sc| + |mean sc|) + u |sh| + 2 u |y|
+                      <= 7 u A' (|y| <= |x sc| + |sh|), and slope y 2 u as above.  The sign of y cannot differ while 7 u A' < |y| / 2.
+  long         past L_MAX the second-order 2 becomes second_order(L + c) (below): the two decline-boundary maps of the head backward
+                      (16384 and 18432 pixels per tap) and the forward rows with 8192 and 16384 products per result.
 tanh: |tanh'| <= 1 passes the bound through; tanhf itself is allowed 2 ulp = 4 u |tanh| on top.
 Statistics and norm-backward sums are fp64 sums of the kernel's fp32 values: the element bounds summed, plus N 2^-53 sum |v| for the
 order of the N fp64 additions (bound_sum); the fp32 product v xhat of the second norm sum adds u |v xhat| per pixel."""
@@ -39,6 +46,7 @@ import plane_model as PM
 
 U = 2.0 ** -24
 CA_FWD, CA_WGRAD, C_PRO = 1, 1, 8      # c_a of forward / backward-weight; c_A (prologue 6 + second order 2)
+C_PRO_XHAT = 11                        # c_A where the kernel forms y = gamma ((x - mean) rstd) + beta (xhat form 9 + second order 2)
 C0_DGRAD, C0_DBIAS = 4, 3
 L_MAX = 5792
 MASK_MARGIN = 1e-5
@@ -206,21 +214,33 @@ def margin(y):
 
 
 # ---- the operations: (ref, M, L) --------------------------------------------------------------------------------------------------------
-def _bound(Lc, c_a, M_a, c_A=0, M_A=0.0):
-    """(L + c_a) u M_a + c_A u M_A"""
+def second_order(n):
+    """An integer c with (1 + u)^n - 1 <= (n + c) u: with x = n u, (1 + u)^n <= e^x and e^x - 1 - x = x^2 / 2 (1 + x / 3 + x^2 / 12 + ...)
+    <= x^2 / (2 (1 - x / 3)) (the coefficients 2 / (k + 2)! stay under 3^-k), so c = ceil(n^2 u / (2 (1 - n u / 3))).
+    1 at n = L_MAX (the constant 2 above is generous), 3 at 8201, 9 at 16393."""
+    assert n * U < 0.5, n
+    return int(np.ceil(n * n * U / (2.0 * (1.0 - n * U / 3.0))))
+
+
+def _bound(Lc, c_a, M_a, c_A=0, M_A=0.0, long=False):
+    """(L + c_a) u M_a + c_A u M_A.  long: reductions past L_MAX -- the 2 that every constant above holds for the second-order term
+    becomes second_order(L + c), on the larger magnitude (M_A, or M_a for an operation without a prologue)."""
     n = float(torch.as_tensor(Lc).max()) + c_a + c_A
+    if long:
+        extra = max(0, second_order(n) - 2)
+        return (Lc + c_a) * U * M_a + c_A * U * M_A + extra * U * (M_A if c_A else M_a)
     assert n <= L_MAX, n
     return (Lc + c_a) * U * M_a + c_A * U * M_A
 
 
-def op_forward(L, x, w, bias=None, norm=None, act=0, gamma=None, beta=None, tanh=False):
+def op_forward(L, x, w, bias=None, norm=None, act=0, gamma=None, beta=None, tanh=False, long=False):
     """-> dict(ref, bound, pre, pre_bound, y): ref = [tanh](conv(prologue(x)) + bias); pre = before tanh (what the statistics sum)."""
     a, A, y = prologue(x, norm, act, gamma, beta)
     pre, M, MA = forward(L, a, w.double()), forward(L, a.abs(), w.double().abs()), forward(L, A, w.double().abs())
     if bias is not None:
         ab = bias.double().abs().view(-1, 1, 1)
         pre, M, MA = pre + bias.double().view(-1, 1, 1), M + ab, MA + ab
-    b = _bound(count_fwd(L, *x.shape[1:]), CA_FWD, M, C_PRO, MA)
+    b = _bound(count_fwd(L, *x.shape[1:]), CA_FWD, M, C_PRO, MA, long=long)
     r = dict(pre=pre, pre_bound=b, ref=pre, bound=b, M=M, MA=MA, y=y, a=a)
     if tanh:
         r["ref"] = torch.tanh(pre)
@@ -242,8 +262,9 @@ def op_dgrad(L, dy, w, H, W, x=None, norm=None, act=0, gamma=None, beta=None, pr
     return r
 
 
-def op_wgrad(L, probs, prev_w=None, prev_b=None):
-    """probs: [(x, dy, norm, act, gamma, beta)] sharing one dw / dbias -> dict(dw, dw_bound, db, db_bound, ys)."""
+def op_wgrad(L, probs, prev_w=None, prev_b=None, c_pro=C_PRO, long=False):
+    """probs: [(x, dy, norm, act, gamma, beta)] sharing one dw / dbias -> dict(dw, dw_bound, db, db_bound, ys).  c_pro: C_PRO, or
+    C_PRO_XHAT for a kernel that forms the operand from xhat."""
     dw = M = MA = Lw = db = Mb = Lb = 0
     ys = []
     for x, dy, norm, act, gamma, beta in probs:
@@ -256,17 +277,20 @@ def op_wgrad(L, probs, prev_w=None, prev_b=None):
         dw, M, MA = dw + prev_w.double(), M + prev_w.double().abs(), MA + prev_w.double().abs()
     if prev_b is not None:
         db, Mb = db + prev_b.double(), Mb + prev_b.double().abs()
-    return dict(dw=dw, dw_bound=_bound(Lw, CA_WGRAD, M, C_PRO, MA), db=db, db_bound=_bound(float(Lb), C0_DBIAS, Mb), ys=ys, M=M, MA=MA, L=Lw)
+    return dict(dw=dw, dw_bound=_bound(Lw, CA_WGRAD, M, c_pro, MA, long=long), db=db, db_bound=_bound(float(Lb), C0_DBIAS, Mb, long=long), ys=ys,
+                M=M, MA=MA, L=Lw)
 
 
-def bound_sum(v, b, w=None):
+def bound_sum(v, b, w=None, run=1):
     """Bound on |fp64 sum of the kernel's values - sum of the reference's| over the pixels of each channel ([C, H, W] inputs): the
-    element bounds summed and N 2^-53 sum |v| for the additions; w (xhat): the summed quantity is fl32(v w)."""
+    element bounds summed and N 2^-53 sum |v| for the additions; w (xhat): the summed quantity is fl32(v w).  run: the kernel adds
+    runs of that many values in fp32 before the fp64 sum (sg_head_bwd_kernel: the 8 pixels of a half row) -- run - 1 more roundings,
+    each relative to a partial sum that the run's sum of magnitudes bounds: (run - 1) u sum |value| on top."""
     N = v.shape[1] * v.shape[2]
     if w is None:
-        return b.sum((1, 2)) + N * 2.0 ** -53 * (v.abs() + b).sum((1, 2))
+        return b.sum((1, 2)) + ((run - 1) * U + N * 2.0 ** -53) * (v.abs() + b).sum((1, 2))
     t = (v.abs() + b) * w.abs()
-    return (b * w.abs() + U * t).sum((1, 2)) + N * 2.0 ** -53 * t.sum((1, 2))
+    return (b * w.abs() + run * U * t).sum((1, 2)) + N * 2.0 ** -53 * t.sum((1, 2))
 
 
 def bound_sumsq(v, b):
