@@ -1275,6 +1275,45 @@ int sgan_prd_rows(const float* descQ, const float* descR, const double* stats, c
 int sgan_prd_finish(const int32_t* cntB, const int32_t* cntA, const float* nn_d2_A, const float* radA, int32_t N, int64_t* out4,
                     void* stream);
 
+/* ---- soft-clDice: the differentiable centre-line Dice as a loss term (Shit et al., CVPR 2021; not in the reference) ----------------
+ * The loss whose hard form the "topology scores" above report as clDice.  util.soft_cldice_ref is the NumPy fp64 restatement
+ * (DESIGN.md R29).  On one plane X [H][W] of values in [0, 1]:
+ *   erode(X)(y, x)  = min of X over the in-image pixels of the plus neighbourhood, taken in the order centre, up, left, right, down;
+ *   dilate(X)(y, x) = max over the in-image pixels of the 3 x 3 box, centre first, then row-major;
+ *   the gradient of a min or max goes entirely to the first pixel in that order that attains it.
+ *   I_0 = X, I_{j+1} = erode(I_j) for j = 0 .. K;  delta_j = max(I_j - dilate(I_{j+1}), 0), derivative 0 at 0;
+ *   S_0 = delta_0, S_j = S_{j-1} + delta_j (1 - S_{j-1});  the soft skeleton is S(X) = S_K.
+ * With the probability plane P and the binary truth T:  A = sum S(P) T, B = sum S(P), C = sum S(T) P, D = sum S(T),
+ *   Tprec = (A + 1) / (B + 1), Tsens = (C + 1) / (D + 1), L = 1 - 2 Tprec Tsens / (Tprec + Tsens).
+ *
+ * Planes: an input plane is read at x[y * rs + x * ps] (row and pixel stride in floats: a channel of an NHWC buffer, a window of a
+ *   wider map); skeletons, dp and the planes of the workspace are dense [H * W].
+ * sgan_cldice_workspace_bytes: bytes of the workspace for H x W and K = iters: the K + 2 planes I_j of sgan_soft_skeleton and, with
+ *   with_backward != 0, the K + 3 planes more of sgan_cldice_backward (< 0: iters outside 1 .. 16 or a bad shape).  4-byte aligned;
+ *   it may hold anything on entry.
+ * sgan_soft_skeleton: I_0 .. I_{K+1} into the workspace (bits of the input: min rounds nothing) and S_K into skel.  K + 2 launches.
+ * sgan_cldice_finish: sp = S(P), st = S(T).  The four sums in fp64, in an order fixed by the shape; state (double
+ *   [SGAN_CLDICE_STATE_BYTES / 8], zeroed by the caller once, left ready for the next call) receives [0..3] A, B, C, D, [4] L,
+ *   [5] gA, [6] gB with d L / d S(P)(x) = gA T(x) + gB, and [7] gC with the direct term d L / d P(x) = gC S(T)(x); loss_out = (float)L.
+ *   One launch of at most 64 workgroups; the last to arrive finishes.
+ * sgan_cldice_backward: dp = gout (gC S(T) + the gradient of sum_x (gA T(x) + gB) S(P)(x) through the skeleton chain), from the I_j
+ *   sgan_soft_skeleton left in the SAME workspace and the state of sgan_cldice_finish; gout: a device float, null = 1.  The chain
+ *   runs in reverse as gather launches: a pixel collects from the <= 9 dilate and <= 5 erode windows that contain it, each
+ *   window's selection recomputed from I_j.  No atomics and no saved indices: the same bits on every run.  K + 3 launches.
+ * Nothing is read back, nothing is allocated, every grid depends on (H, W) and the launch count on K alone: the calls capture into a
+ * hipGraph.  Returns 1 ("not covered"), the reason in sgan_last_error and nothing launched, for iters outside 1 .. 16, a null
+ * pointer, a shape outside H, W <= 32768 and H W < 2^30, a pixel stride < 1, a row stride below (W - 1) ps + 1 and a short or
+ * misaligned workspace. */
+#define SGAN_CLDICE_MAX_ITERS 16
+#define SGAN_CLDICE_STATE_BYTES 4096
+int64_t sgan_cldice_workspace_bytes(int32_t H, int32_t W, int32_t iters, int32_t with_backward);
+int sgan_soft_skeleton(const float* x, int64_t x_rs, int64_t x_ps, int32_t H, int32_t W, int32_t iters, float* skel, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+int sgan_cldice_finish(const float* sp, const float* t, int64_t t_rs, int64_t t_ps, const float* st, const float* p, int64_t p_rs,
+                       int64_t p_ps, int32_t H, int32_t W, double* state, float* loss_out, void* stream);
+int sgan_cldice_backward(const float* t, int64_t t_rs, int64_t t_ps, const float* st, const double* state, const float* gout, int32_t H,
+                         int32_t W, int32_t iters, float* dp, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

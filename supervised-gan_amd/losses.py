@@ -442,6 +442,73 @@ def seg_head(logits, label_or_target, class_weights=None, norm=None, mode=0, pix
     return p, weighted_bce(p, lt, class_weights)
 
 
+class ClDiceBuffers:
+    """What a soft-clDice node keeps between calls for H x W planes and K = iters: the workspace with the I_j of the forward (read
+    again by the backward), the skeleton of the prediction, the state with the sums and scalar derivatives, the loss scalar and the
+    gradient plane the node hands out, so that a step allocates nothing.  One node at a time: the backward of a forward must run, and
+    its gradient be consumed, before the next forward on the same buffers."""
+
+    def __init__(self, H, W, iters, device):
+        self.shape, self.iters = (H, W), int(iters)
+        self.work = ops.new_cldice_workspace(H, W, iters, device, backward=True)
+        self.sp = torch.empty((H, W), dtype=torch.float32, device=device)
+        self.state = ops.new_cldice_state(device)
+        self.loss = torch.empty((), dtype=torch.float32, device=device)
+        self.dp = torch.empty((H, W), dtype=torch.float32, device=device)
+
+    def fits(self, H, W, iters, device):
+        return self.shape == (H, W) and self.iters == int(iters) and self.sp.device == device
+
+
+class _SoftClDiceFn(torch.autograd.Function):
+    """L = 1 - 2 Tprec Tsens / (Tprec + Tsens) of the soft skeletons (sgan_soft_skeleton, sgan_cldice_finish); the backward is
+    sgan_cldice_backward, which takes the upstream gradient as a device scalar.  Gradient w.r.t. the probability plane only."""
+
+    @staticmethod
+    def forward(ctx, p, t, st, iters, bufs):
+        ops.soft_skeleton(p, iters, out=bufs.sp, work=bufs.work)
+        ops.cldice_finish(bufs.sp, t, st, p, bufs.state, bufs.loss)
+        ctx.t, ctx.st, ctx.iters, ctx.bufs = t, st, iters, bufs
+        return bufs.loss.detach()      # an alias of the persistent scalar: the node hangs on a tensor of its own, as _SegHeadFn's p
+
+    @staticmethod
+    def backward(ctx, gout):
+        if gout is None:
+            return None, None, None, None, None
+        g = None if ops.is_unit_grad(gout) else gout.contiguous().float()
+        dp = ops.cldice_backward(ctx.t, ctx.st, ctx.bufs.state, ctx.iters, ctx.bufs.work, dp=ctx.bufs.dp, gout=g)
+        return dp.detach(), None, None, None, None
+
+
+def soft_cldice(p_plane, t_plane, iters, t_skel=None, buffers=None):
+    """The soft-clDice loss (Shit et al., CVPR 2021; util.soft_cldice_ref) of the probability plane p_plane [H, W] against the binary
+    truth t_plane [H, W], both fp32 on the device, with K = iters: a float32 device scalar whose backward hands d L / d P times the
+    upstream gradient to p_plane.  t_skel: ops.soft_skeleton(t_plane, iters) where the caller keeps it (None: computed here);
+    buffers: a ClDiceBuffers the caller keeps between steps (None: made here).  The planes are read where they lie when their
+    strides are positive (a channel of an NHWC buffer).  No fallback: off the device or outside 1 .. 16 iterations it raises."""
+    ops.require_gpu(p_plane, "soft_cldice")
+    assert p_plane.dim() == 2 and p_plane.shape == t_plane.shape and p_plane.dtype == t_plane.dtype == torch.float32, (p_plane.shape, t_plane.shape)
+    if not 1 <= int(iters) <= ops.CLDICE_MAX_ITERS:
+        raise SganError(f"soft_cldice: not covered ({iters} iterations: 1 .. {ops.CLDICE_MAX_ITERS})")
+    H, W = p_plane.shape
+    t_plane = t_plane.detach()
+    if buffers is None:
+        buffers = ClDiceBuffers(H, W, iters, p_plane.device)
+    assert buffers.fits(H, W, iters, p_plane.device), (buffers.shape, buffers.iters, (H, W), iters)
+    if t_skel is None:
+        t_skel = ops.soft_skeleton(t_plane, iters)
+    return _SoftClDiceFn.apply(p_plane, t_plane, t_skel.detach(), int(iters), buffers)
+
+
+def class_probability_plane(logits, cls, use_sigmoid=False):
+    """The probability plane [H, W] of class `cls` from the [1, C, H, W] logits, with a gradient path back into them: softmax over the
+    channels, or the sigmoid of each under `--use_sigmoid_ss` (softmax_channels / sigmoid_channels, both with HIP backwards).  A
+    view into the NHWC-backed prediction: nothing is copied."""
+    assert logits.dim() == 4 and logits.shape[0] == 1 and 0 <= int(cls) < logits.shape[1], (logits.shape, cls)
+    p = sigmoid_channels(logits) if use_sigmoid else softmax_channels(logits)
+    return p[0, int(cls)]
+
+
 class GANLossMultiClass(nn.Module):
     """GANLossMultiClass (models/networks.py:188-202): CrossEntropyLoss over the class channel of every pixel of a
     discriminator map against one class: one forward and one backward launch (sgan_ce_fwd / sgan_ce_bwd)."""

@@ -1804,6 +1804,118 @@ def topo_accumulate(t, s, acc_i, t_thin=None, s_thin=None, window=64, stride=Non
     L.check(rc, "sgan_topo_accumulate")
 
 
+# ---- soft-clDice (sgan_cldice.hip; include/sgan_hip.h, "soft-clDice"): the loss whose hard form topo_accumulate scores ---------------
+CLDICE_MAX_ITERS = 16          # SGAN_CLDICE_MAX_ITERS
+CLDICE_STATE_BYTES = 4096      # SGAN_CLDICE_STATE_BYTES
+CLDICE_STATE = ('A', 'B', 'C', 'D', 'L', 'gA', 'gB', 'gC')      # the first doubles of the state sgan_cldice_finish writes
+_cldice_ws = {}                # (H, W, iters, backward, device index) -> the float32 scratch
+
+
+def _strided_plane(t, what):
+    """A [H, W] fp32 view with positive strides whose rows do not overlap (a channel of an NHWC buffer, a window of a wider map, a
+    dense map), inside its storage: (tensor, row stride, pixel stride).  Anything else is made contiguous."""
+    require_gpu(t, what)
+    assert t.dim() == 2 and t.dtype == torch.float32, (t.shape, t.dtype)
+    H, W = t.shape
+    if t.stride(1) < 1 or (H > 1 and t.stride(0) < (W - 1) * t.stride(1) + 1):
+        t = t.contiguous()
+    if (H - 1) * t.stride(0) + (W - 1) * t.stride(1) + 1 > _avail(t):
+        raise L.SganError(f"{what}: plane {tuple(t.shape)} / {tuple(t.stride())} does not lie inside its storage; nothing was launched")
+    return t, (t.stride(0) if H > 1 else W * t.stride(1)), t.stride(1)
+
+
+def _dense_plane(t, H, W, dev):
+    return t.dtype == torch.float32 and t.is_contiguous() and t.numel() == H * W and t.device == dev
+
+
+def _cldice_refused(what, iters):
+    if not 1 <= int(iters) <= CLDICE_MAX_ITERS:
+        raise L.SganError(f"{what}: not covered ({iters} iterations: 1 .. {CLDICE_MAX_ITERS}); nothing was launched")
+
+
+def cldice_workspace(H, W, iters, device, backward=False):
+    """The scratch of soft_skeleton for H x W planes and K = iters (the K + 2 planes I_j) and, with backward, of cldice_backward
+    (K + 3 planes more), cached per (H, W, iters, backward, device); the kernels initialise what they use.  A caller that keeps
+    the I_j for a backward owns a workspace of its own (losses.soft_cldice does)."""
+    key = (H, W, int(iters), bool(backward), device.index)
+    ws = _cldice_ws.get(key)
+    if ws is None:
+        ws = _cldice_ws[key] = new_cldice_workspace(H, W, iters, device, backward)
+    return ws
+
+
+def new_cldice_workspace(H, W, iters, device, backward=False):
+    nbytes = L.lib().sgan_cldice_workspace_bytes(H, W, int(iters), int(bool(backward)))
+    if nbytes < 0:
+        raise L.SganError(f"sgan_cldice_workspace_bytes({H}, {W}, {iters}): {L.lib().sgan_last_error().decode()}")
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+
+
+def new_cldice_state(device):
+    """The zeroed state of cldice_finish (sums, loss, scalar derivatives, slots and ticket): one per loss node, so that a backward
+    reads the scalars of its own forward."""
+    return torch.zeros(CLDICE_STATE_BYTES // 8, dtype=torch.float64, device=device)
+
+
+def soft_skeleton(x, iters, out=None, work=None):
+    """The soft skeleton S_K of the plane x [H, W] float32 in [0, 1] with K = iters (sgan_soft_skeleton; util.soft_skeleton_ref is
+    the host yardstick): iterated plus-shaped min and 3 x 3 max selections, float32 [H, W].  `work` (cldice_workspace) receives the
+    K + 2 planes I_j, bits of x, which cldice_backward reads.  Only enqueues -- K + 2 launches whose grids depend on the shape
+    alone -- and reads x in place where its strides are positive (a channel of an NHWC buffer, a window of a wider map)."""
+    _cldice_refused("sgan_soft_skeleton", iters)
+    x, rs, ps = _strided_plane(x, "soft_skeleton")
+    H, W = x.shape
+    dev = x.device
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.float32, device=dev)
+    assert _dense_plane(out, H, W, dev), (out.shape, out.dtype)
+    ws = cldice_workspace(H, W, iters, dev) if work is None else work
+    rc = L.lib().sgan_soft_skeleton(_ptr(x), rs, ps, H, W, int(iters), _ptr(out), _ptr(ws), ws.numel() * ws.element_size(), _stream())
+    if rc == 1:
+        raise L.SganError(f"sgan_soft_skeleton: {L.lib().sgan_last_error().decode()}; nothing was launched")
+    L.check(rc, "sgan_soft_skeleton")
+    return out
+
+
+def cldice_finish(sp, t, st, p, state, loss_out):
+    """The four sums, L and the scalar derivatives of soft-clDice from sp = S(P), st = S(T) (dense) and the planes t, p (strided)
+    into `state` (new_cldice_state; CLDICE_STATE names its first doubles) and loss_out (a float32 device scalar):
+    sgan_cldice_finish, one launch, nothing read back."""
+    t, t_rs, t_ps = _strided_plane(t, "cldice_finish")
+    p, p_rs, p_ps = _strided_plane(p, "cldice_finish")
+    H, W = t.shape
+    dev = t.device
+    assert tuple(p.shape) == (H, W) and p.device == dev and _dense_plane(sp, H, W, dev) and _dense_plane(st, H, W, dev)
+    assert state.dtype == torch.float64 and state.is_contiguous() and state.numel() * 8 >= CLDICE_STATE_BYTES and state.device == dev
+    assert loss_out.dtype == torch.float32 and loss_out.numel() == 1 and loss_out.device == dev
+    rc = L.lib().sgan_cldice_finish(_ptr(sp), _ptr(t), t_rs, t_ps, _ptr(st), _ptr(p), p_rs, p_ps, H, W, _ptr(state), _ptr(loss_out), _stream())
+    if rc == 1:
+        raise L.SganError(f"sgan_cldice_finish: {L.lib().sgan_last_error().decode()}; nothing was launched")
+    L.check(rc, "sgan_cldice_finish")
+    return loss_out
+
+
+def cldice_backward(t, st, state, iters, work, dp=None, gout=None):
+    """dp [H, W] = gout * d L / d P of soft-clDice (sgan_cldice_backward) from the planes I_j soft_skeleton(P, work=work) left in
+    `work` (cldice_workspace(..., backward=True)), the truth t, its skeleton st and the state of cldice_finish; gout: a float32
+    device scalar, None = 1.  K + 3 launches, gathers only: the same bits on every run."""
+    _cldice_refused("sgan_cldice_backward", iters)
+    t, t_rs, t_ps = _strided_plane(t, "cldice_backward")
+    H, W = t.shape
+    dev = t.device
+    if dp is None:
+        dp = torch.empty((H, W), dtype=torch.float32, device=dev)
+    assert _dense_plane(dp, H, W, dev) and _dense_plane(st, H, W, dev)
+    assert state.dtype == torch.float64 and state.numel() * 8 >= CLDICE_STATE_BYTES and state.device == dev
+    assert gout is None or (gout.dtype == torch.float32 and gout.numel() == 1 and gout.device == dev)
+    rc = L.lib().sgan_cldice_backward(_ptr(t), t_rs, t_ps, _ptr(st), _ptr(state), _ptr(gout), H, W, int(iters), _ptr(dp), _ptr(work),
+                                      work.numel() * work.element_size(), _stream())
+    if rc == 1:
+        raise L.SganError(f"sgan_cldice_backward: {L.lib().sgan_last_error().decode()}; nothing was launched")
+    L.check(rc, "sgan_cldice_backward")
+    return dp
+
+
 def clean_workspace(H, W, device):
     """The scratch of clean_wall for H x W planes (edt_sq's workspace, one int32 plane for dsq / labels, the area table and the
     complement plane), cached per (H, W, device) like edt_workspace; the kernels initialise what they use."""

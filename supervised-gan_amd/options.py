@@ -139,6 +139,7 @@ class BaseOptions:
         self.opt = self.parser.parse_args(args)
         self.opt.isTrain = self.isTrain
         check_border_options(self.opt)
+        check_cldice_options(self.opt)
         check_clean_options(self.opt, self.parser)
         check_topo_options(self.opt, self.parser)
         check_elastic_options(self.opt)
@@ -183,6 +184,21 @@ def check_border_options(opt):
         opt.border_radius = min(32, int(math.ceil(4 * sigma)))
     assert 1 <= opt.border_radius <= 32, "--border_radius: 1..32 (got %d)" % opt.border_radius
     assert opt.border_class >= 0, "--border_class: a class index (got %d)" % opt.border_class
+
+
+def check_cldice_options(opt):
+    """--cldice_weight LAMBDA adds the soft-clDice term to the generator loss of --model segmentation (any head, with or without
+    discriminators); LAMBDA >= 0 with 0 = off, --cldice_iters 1..16, --cldice_class a class index.  Another model refuses it.  With
+    the weight at 0 nothing is looked at and nothing is changed."""
+    weight = getattr(opt, 'cldice_weight', 0.0)
+    if weight == 0.0:
+        return
+    assert weight > 0.0, "--cldice_weight LAMBDA: a weight >= 0, 0 = off (got %g)" % weight      # a NaN fails the comparison
+    assert getattr(opt, 'model', None) == 'segmentation', \
+        "--cldice_weight adds the soft-clDice term to the segmentation trainer's generator loss: it needs --model segmentation (got '%s')" % \
+        getattr(opt, 'model', None)
+    assert 1 <= opt.cldice_iters <= 16, "--cldice_iters: 1..16 (got %d)" % opt.cldice_iters
+    assert opt.cldice_class >= 0, "--cldice_class: a class index (got %d)" % opt.cldice_class
 
 
 def check_clean_options(opt, parser=None):
@@ -386,6 +402,12 @@ class TrainOptions(BaseOptions):
                'cross-entropy weight of every wall pixel between two cells (not in the reference; default off)')
         a('--border_radius', type=int, default=None, help='search radius of --border_weight in pixels, 1..32; default min(32, ceil(4 SIGMA))')
         a('--border_class', type=int, default=0, help='the class whose pixels form the wall between objects (--border_weight)')
+        # the soft-clDice term of the segmentation trainers (Shit et al., CVPR 2021; not in the reference)
+        a('--cldice_weight', type=float, default=0.0, metavar='LAMBDA',
+          help='--model segmentation: add LAMBDA * soft-clDice of the --cldice_class probability plane against the truth to the '
+               'generator loss (with or without discriminators, softmax or sigmoid head); 0 = off')
+        a('--cldice_iters', type=int, default=5, metavar='K', help='soft-skeleton iterations of --cldice_weight, 1..16')
+        a('--cldice_class', type=int, default=0, help='the class whose plane the soft-clDice term reads (the wall, as the label-based scores)')
         # random elastic deformation of every training crop, on the device (not in the reference, which augments with crop, flip and rot90)
         a('--elastic', type=float, default=None, nargs=2, metavar=('G', 'SIGMA'),
           help='image-folder feeders: deform every training crop by a smooth random field -- (G + 3)^2 displacement vectors drawn from '

@@ -17,7 +17,8 @@ import torch
 
 from . import networks, ops, util
 from .cgan_model import CGANModel
-from .losses import cross_entropy_logits, seg_head, sigmoid_channels, softmax_channels, weighted_bce
+from .losses import (ClDiceBuffers, class_probability_plane, cross_entropy_logits, seg_head, sigmoid_channels, soft_cldice, softmax_channels,
+                     weighted_bce)
 from .options import check_tile_options
 from .seg_metrics import SegMetrics, SegMetricsMixin
 
@@ -52,6 +53,13 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
                 "--border_weight: softmax training with --which_model_netD None only (options.check_border_options)"
             assert opt.border_class < self.num_classes, "--border_class %d: there are %d classes" % (opt.border_class, self.num_classes)
             assert opt.batchSize == 1 and self.device.type == 'cuda', "--border_weight: batch 1 on the device, like every kernel of this path"
+        self.cldice = None      # (lambda, K, class) of the soft-clDice term, or None: then nothing of it runs
+        if self.isTrain and getattr(opt, 'cldice_weight', 0.0) > 0.0:
+            assert opt.cldice_class < self.num_classes, "--cldice_class %d: there are %d classes" % (opt.cldice_class, self.num_classes)
+            assert opt.batchSize == 1 and self.device.type == 'cuda', "--cldice_weight: batch 1 on the device, like every kernel of this path"
+            self.cldice = (float(opt.cldice_weight), int(opt.cldice_iters), int(opt.cldice_class))
+            self._cld_truth = self._cld_tskel = self._cld_bufs = None      # persistent: the truth plane, its skeleton, the node's buffers
+            self.loss_G_clDice = 0
         self.seg_metrics = SegMetrics(opt, self.device, self.num_classes)
         self.reset_accs()
         self._tiling = not self.isTrain and getattr(opt, 'tiling', False)      # test(): whole-image inference (check_tile_options)
@@ -90,6 +98,33 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
                 ops.pixel_weight_sum(self.label.reshape(-1), self.num_classes, self.class_weights, self.bmap.reshape(-1), self.norm)
             else:
                 ops.label_weight_sum(self.label.reshape(-1), self.num_classes, self.class_weights, self.norm)
+        if getattr(self, 'cldice', None) is not None:
+            self._cldice_truth()
+
+    def _cldice_truth(self):
+        """The truth plane of --cldice_class (1.0 where the label is that class) and its soft skeleton into persistent buffers, once per
+        set_input like the border map: a captured step keeps reading them.  Enqueues only."""
+        _, K, cls = self.cldice
+        hw = tuple(self.label.shape[1:])
+        if self._cld_truth is None or tuple(self._cld_truth.shape) != hw:
+            self._cld_is = torch.empty(hw, dtype=torch.bool, device=self.device)
+            self._cld_truth = torch.empty(hw, dtype=torch.float32, device=self.device)
+            self._cld_tskel = torch.empty(hw, dtype=torch.float32, device=self.device)
+            self._cld_bufs = ClDiceBuffers(hw[0], hw[1], K, self.device)
+        torch.eq(self.label[0], cls, out=self._cld_is)
+        self._cld_truth.copy_(self._cld_is)
+        ops.soft_skeleton(self._cld_truth, K, out=self._cld_tskel)
+
+    def _with_cldice(self, loss):
+        """loss + lambda * soft-clDice of the class plane; the loss unchanged with the option off.  With discriminators fake_B is the
+        softmax / sigmoid of the logits with a gradient path and the term reads its plane; the fused head's p takes no gradient, so
+        without them the term computes its own from the logits of the last forward()."""
+        if self.cldice is None:
+            return loss
+        lam, K, cls = self.cldice
+        p = class_probability_plane(self.logit, cls, self.use_sigmoid_ss) if self.no_netD else self.fake_B[0, cls]
+        self.loss_G_clDice = soft_cldice(p, self._cld_truth, K, t_skel=self._cld_tskel, buffers=self._cld_bufs)
+        return loss + lam * self.loss_G_clDice
 
     def _border_weight_map(self):
         """The U-Net border term of the current label into self.bmap: the pixels of --border_class are the wall, its complement is
@@ -204,7 +239,8 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
         """loss_G = sum_i lambda_i * GAN(D_i(cat(A, fake_B)), 1) + CE   (segm_model.py:203-232)"""
         if self.no_netD:      # :202-203,227: loss_G_GAN = 0, the cross-entropy forward() left behind is the whole loss
             self.loss_G_GAN = 0
-            self.loss_G = self.loss_G_CE = self._head_loss
+            self.loss_G_CE = self._head_loss
+            self.loss_G = self._with_cldice(self.loss_G_CE)
             self._backward(self.loss_G)
             return
         skip = getattr(self.opt, 'skip_wasted_D_wgrad', False)
@@ -215,14 +251,15 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
         self.loss_G_GAN, self._each_G = self._d_losses([(d, fake, True) for d in self.netD], list(self.opt.lambda_D))
         for netD in self.netD:
             netD.compute_param_grads = True
-        self.loss_G = self.loss_G_GAN + self.compute_cross_entropy_loss(weighted=True)
+        self.loss_G = self._with_cldice(self.loss_G_GAN + self.compute_cross_entropy_loss(weighted=True))
         self._backward(self.loss_G)
 
     def get_current_errors(self):
+        extra = [('G_clDice', float(self.loss_G_clDice.detach() if torch.is_tensor(self.loss_G_clDice) else 0.0))] if self.cldice is not None else []
         if self.no_netD:                                     # :253-257
-            return OrderedDict([('G_CE', float(self.loss_G_CE.detach()))])
+            return OrderedDict([('G_CE', float(self.loss_G_CE.detach()))] + extra)
         return OrderedDict([('G_CE', float(self.loss_G_CE.detach())), ('G_GAN', float(self.loss_G_GAN.detach())),
-                            ('D_real', float(self.loss_D_real)), ('D_fake', float(self.loss_D_fake))])
+                            ('D_real', float(self.loss_D_real)), ('D_fake', float(self.loss_D_fake))] + extra)
 
     def get_current_visuals(self, save_as_single_image=False):
         three = lambda t: t if t.shape[1] in (1, 3) else torch.cat([t, torch.zeros_like(t[:, :1])], 1)[:, :3]      # noqa: E731

@@ -1154,3 +1154,85 @@ def prd_ratio(fake_real, real_real):
     if real_real == 0.0:
         return 1.0 if fake_real == 0.0 else float('inf')
     return fake_real / real_real
+
+
+# ---- soft-clDice (Shit et al., CVPR 2021): the host yardstick of ops.soft_skeleton / losses.soft_cldice ------------
+CLDICE_ERODE_ORDER = ((0, 0), (-1, 0), (0, -1), (0, 1), (1, 0))                                      # centre, up, left, right, down
+CLDICE_DILATE_ORDER = ((0, 0), (-1, -1), (-1, 0), (-1, 1), (0, -1), (0, 1), (1, -1), (1, 0), (1, 1))      # centre, then row-major
+
+
+def _cldice_select(X, order, pad, pick):
+    """(value, position in `order`) of the extreme of X over the in-image pixels of the neighbourhood `order`, the first pixel in
+    that order that attains it winning (np.argmin / argmax return the first occurrence); out-of-image neighbours hold `pad`."""
+    H, W = X.shape
+    Xp = np.full((H + 2, W + 2), pad, dtype=X.dtype)
+    Xp[1:-1, 1:-1] = X
+    stack = np.stack([Xp[1 + dy:1 + dy + H, 1 + dx:1 + dx + W] for dy, dx in order])
+    sel = pick(stack, axis=0)
+    return np.take_along_axis(stack, sel[None], 0)[0], sel
+
+
+def _cldice_scatter(g, sel, order):
+    """Hands g(y) to the pixel y + order[sel(y)]: the transpose of the selection."""
+    H, W = g.shape
+    out = np.zeros((H, W), dtype=np.float64)
+    yy, xx = np.mgrid[0:H, 0:W]
+    off = np.asarray(order)
+    np.add.at(out, (yy + off[sel, 0], xx + off[sel, 1]), g)
+    return out
+
+
+def soft_skeleton_ref(X, iters):
+    """The soft skeleton of the fp32 plane X with K = iters: (S_K in fp64, [I_0 .. I_{K+1}] in fp32 (bits of X), [delta_j], [S_j],
+    erode selections of I_0 .. I_K, dilate selections of I_1 .. I_{K+1}).  Selections are made on the fp32 values."""
+    K = int(iters)
+    assert 1 <= K <= 16, K
+    I = [np.ascontiguousarray(X, dtype=np.float32)]
+    esel, dsel, delta, S = [], [], [], []
+    for j in range(K + 1):
+        v, s = _cldice_select(I[j], CLDICE_ERODE_ORDER, np.float32(np.inf), np.argmin)
+        I.append(v)
+        esel.append(s)
+    for j in range(K + 1):
+        d, s = _cldice_select(I[j + 1], CLDICE_DILATE_ORDER, np.float32(-np.inf), np.argmax)
+        dsel.append(s)
+        delta.append(np.maximum(I[j].astype(np.float64) - d.astype(np.float64), 0.0))
+        S.append(delta[0] if j == 0 else S[-1] + delta[j] * (1.0 - S[-1]))
+    return S[-1], I, delta, S, esel, dsel
+
+
+def soft_cldice_sums(SP, T, ST, P):
+    """(A, B, C, D, L, gA, gB, gC) of the loss from the two skeletons: d L / d S(P) = gA T + gB, the direct term gC S(T)."""
+    A, B, C, D = float((SP * T).sum()), float(SP.sum()), float((ST * P).sum()), float(ST.sum())
+    tp, ts = (A + 1.0) / (B + 1.0), (C + 1.0) / (D + 1.0)
+    L = 1.0 - 2.0 * tp * ts / (tp + ts)
+    dLdp, dLds = -2.0 * ts * ts / (tp + ts) ** 2, -2.0 * tp * tp / (tp + ts) ** 2
+    return A, B, C, D, L, dLdp / (B + 1.0), -dLdp * (A + 1.0) / (B + 1.0) ** 2, dLds / (D + 1.0)
+
+
+def soft_cldice_ref(P, T, iters):
+    """soft-clDice of the probability plane P against the binary truth T (both read as fp32 [H, W]) with K = iters, in fp64:
+    (L, dL/dP, S(P), S(T), [I_j of P], M).  M is the same backward run with every contribution taken in absolute value: the scale
+    against which a rounding of the fp32 backward is measured."""
+    P32, T32 = np.ascontiguousarray(P, dtype=np.float32), np.ascontiguousarray(T, dtype=np.float32)
+    K = int(iters)
+    SP, I, delta, S, esel, dsel = soft_skeleton_ref(P32, K)
+    ST = soft_skeleton_ref(T32, K)[0]
+    P64, T64 = P32.astype(np.float64), T32.astype(np.float64)
+    _, _, _, _, L, gA, gB, gC = soft_cldice_sums(SP, T64, ST, P64)
+    grads = []
+    for absolute in (False, True):
+        gS = abs(gA) * T64 + abs(gB) if absolute else gA * T64 + gB
+        E = [None] * (K + 1)
+        for j in range(K, 0, -1):
+            E[j] = gS * (1.0 - S[j - 1]) * (delta[j] > 0)
+            gS = gS * (1.0 - delta[j])
+        E[0] = gS * (delta[0] > 0)
+        sign = 1.0 if absolute else -1.0
+        G = _cldice_scatter(sign * E[K], dsel[K], CLDICE_DILATE_ORDER)                   # d L / d I_{K+1}
+        for j in range(K, -1, -1):
+            G = E[j] + _cldice_scatter(G, esel[j], CLDICE_ERODE_ORDER)
+            if j >= 1:
+                G = G + _cldice_scatter(sign * E[j - 1], dsel[j - 1], CLDICE_DILATE_ORDER)
+        grads.append(G + (abs(gC) if absolute else gC) * ST)
+    return L, grads[0], SP, ST, I, grads[1]
