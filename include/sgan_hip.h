@@ -1314,6 +1314,43 @@ int sgan_cldice_finish(const float* sp, const float* t, int64_t t_rs, int64_t t_
 int sgan_cldice_backward(const float* t, int64_t t_rs, int64_t t_ps, const float* st, const double* state, const float* gout, int32_t H,
                          int32_t W, int32_t iters, float* dp, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- Lovasz-softmax: the Lovasz extension of the Jaccard loss as a loss term (Berman, Triki, Blaschko, CVPR 2018; not in the
+ * reference) ----  util.lovasz_ref is the NumPy fp64 restatement.  For every listed class c of the prediction
+ * p [C][H][W] (fp32 in [0, 1], read at p[c * cs + y * rs + x * ps]: class, row and pixel stride in floats, so NCHW, a window of a
+ * wider buffer or the channels of an NHWC buffer) against the index label [H][W] (int64, dense), N = H W:
+ *   fg_i = (label_i == c), G = sum fg; a class with G = 0 is absent and takes no part ("classes = present");
+ *   e_i = |fg_i - p_i(c)| in fp32; pi orders the pixels by e descending, ties by the pixel index i = y W + x ascending (a total
+ *   order: the sort key ((0xFFFFFFFF - bits(e)) << 32) | (i << 1) | fg is unique);
+ *   c_k = foreground among the first k + 1 sorted pixels, I_k = G - c_k, U_k = G + (k + 1 - c_k) in exact integers;
+ *   g_k = 1 / U_k if sorted pixel k is foreground, else I_k / (U_k (U_k - 1)) (0 where I_k = 0): one fp64 division;
+ *   L_c = sum_k e_pi(k) g_k in fp64, in an order fixed by the shape.
+ * L = the mean of L_c over the m present listed classes, rounded to fp32 once; 0 if m = 0.
+ * d L / d p_pi(k)(c) = gout * sign(p - fg) * g_k / m (sign(0) = 0), exactly 0 on absent and unlisted classes.
+ *
+ * The workspace (8-byte aligned; it may hold anything on entry), with P = max(4096, 2^ceil(log2 N)) and nb = ceil(N / 1024), in
+ * this order: the state, SGAN_LOVASZ_STATE_BYTES: doubles [0] L, [1] m, [2 + j] L_c of the j-th listed class (0 if absent),
+ * [10 + j] its scale 1 / m (0 if absent), and at byte 192 the int32 G of the listed classes; g, double [n][N], by sorted position;
+ * the sorted keys, uint64 [n][P]; the block sums, double [n][nb]; pi, int32 [n][N] (the pixel index of sorted position k);
+ * the block counts, int32 [n][nb]; rounded up to 8 bytes.
+ * sgan_lovasz_workspace_bytes: its size (< 0, "not covered": H or W < 1, H W > 2^20, n outside 1 .. 8).
+ * sgan_lovasz_forward: a bitonic sorting network on the keys (chunks of 4096 in LDS, the wider strides in global memory), an
+ *   integer scan as count / offsets / apply launches, the weights and the ordered fp64 sums, the finish.  classes: n distinct class
+ *   indices below C, on the HOST, read during the call.  loss_out: a device float.  The launches depend on (H, W, n) only.
+ * sgan_lovasz_backward: dp [C][H][W], dense, from the workspace the forward left and the same p: every listed plane is scattered
+ *   through pi (each pixel once), every other plane zeroed; gout: a device float, null = 1.  One launch.
+ * No floating-point atomics, no workgroup waits on another, nothing is read back or allocated: the calls capture into a hipGraph and
+ * give the same bits on every run.  Return 1, the reason in sgan_last_error and nothing launched, for "not covered" (as above), a
+ * null pointer, classes that repeat or lie outside 0 .. C - 1 (C <= 64), a stride < 1 or rows that overlap, and a workspace that is
+ * too small or misaligned. */
+#define SGAN_LOVASZ_MAX_CLASSES 8
+#define SGAN_LOVASZ_MAX_PIXELS (1 << 20)
+#define SGAN_LOVASZ_STATE_BYTES 256
+int64_t sgan_lovasz_workspace_bytes(int32_t H, int32_t W, int32_t n);
+int sgan_lovasz_forward(const float* p, int64_t p_cs, int64_t p_rs, int64_t p_ps, const int64_t* label, const int32_t* classes, int32_t n,
+                        int32_t C, int32_t H, int32_t W, float* loss_out, void* workspace, int64_t workspace_bytes, void* stream);
+int sgan_lovasz_backward(const float* p, int64_t p_cs, int64_t p_rs, int64_t p_ps, const int32_t* classes, int32_t n, int32_t C, int32_t H,
+                         int32_t W, const float* gout, float* dp, const void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

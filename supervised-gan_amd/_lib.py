@@ -211,6 +211,9 @@ SIGNATURES = {
     "sgan_soft_skeleton": [_P, _L, _L, _I, _I, _I, _P, _P, _L, _P],
     "sgan_cldice_finish": [_P, _P, _L, _L, _P, _P, _L, _L, _I, _I, _P, _P, _P],
     "sgan_cldice_backward": [_P, _L, _L, _P, _P, _P, _I, _I, _I, _P, _P, _L, _P],
+    "sgan_lovasz_workspace_bytes": [_I, _I, _I],
+    "sgan_lovasz_forward": [_P, _L, _L, _L, _P, _P, _I, _I, _I, _I, _P, _P, _L, _P],
+    "sgan_lovasz_backward": [_P, _L, _L, _L, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P],
     "sgan_last_variant": [],
     "sgan_profile_enable": [_I],
     "sgan_profile_count": [],
@@ -224,7 +227,8 @@ RESTYPES = {"sgan_last_variant": C.c_char_p, "sgan_image_resize_workspace": C.c_
             "sgan_edt_workspace": C.c_int64, "sgan_boundary_workspace": C.c_int64, "sgan_clean_workspace": C.c_int64,
             "sgan_split_workspace": C.c_int64, "sgan_topo_workspace_bytes": C.c_int64,
             "sgan_diffaug_workspace": C.c_int64, "sgan_swd_workspace": C.c_int64,
-            "sgan_prd_workspace": C.c_int64, "sgan_cldice_workspace_bytes": C.c_int64}      # everything else returns an int status
+            "sgan_prd_workspace": C.c_int64, "sgan_cldice_workspace_bytes": C.c_int64,
+            "sgan_lovasz_workspace_bytes": C.c_int64}      # everything else returns an int status
 _lib = None
 
 

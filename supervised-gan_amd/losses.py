@@ -509,6 +509,58 @@ def class_probability_plane(logits, cls, use_sigmoid=False):
     return p[0, int(cls)]
 
 
+class LovaszBuffers:
+    """What a Lovasz-softmax node keeps between calls for a [1, C, H, W] prediction and n listed classes: the workspace with pi, g and
+    the scales of the forward (read again by the backward), the loss scalar and the gradient of the whole prediction the node hands
+    out, so that a step allocates nothing.  One node at a time, as ClDiceBuffers."""
+
+    def __init__(self, C, H, W, n, device):
+        self.shape, self.n = (C, H, W), int(n)
+        self.work = ops.new_lovasz_workspace(H, W, n, device)
+        self.loss = torch.empty((), dtype=torch.float32, device=device)
+        self.dp = torch.empty((1, C, H, W), dtype=torch.float32, device=device)
+
+    def fits(self, C, H, W, n, device):
+        return self.shape == (C, H, W) and self.n == int(n) and self.dp.device == device
+
+
+class _LovaszSoftmaxFn(torch.autograd.Function):
+    """L = the mean Lovasz extension of the Jaccard loss over the present listed classes (sgan_lovasz_forward); the backward is
+    sgan_lovasz_backward, which takes the upstream gradient as a device scalar and writes the gradient of the whole prediction."""
+
+    @staticmethod
+    def forward(ctx, p, label, classes, bufs):
+        ops.lovasz_forward(p, label, classes, bufs.work, loss_out=bufs.loss)
+        ctx.p, ctx.classes, ctx.bufs = p.detach(), classes, bufs
+        return bufs.loss.detach()
+
+    @staticmethod
+    def backward(ctx, gout):
+        if gout is None:
+            return None, None, None, None
+        g = None if ops.is_unit_grad(gout) else gout.contiguous().float()
+        dp = ops.lovasz_backward(ctx.p, ctx.classes, ctx.bufs.work, dp=ctx.bufs.dp, gout=g)
+        return dp.detach(), None, None, None
+
+
+def lovasz_softmax(p, label, classes, buffers=None):
+    """The Lovasz-softmax loss (Berman, Triki, Blaschko, CVPR 2018, classes = 'present'; util.lovasz_ref) of the prediction
+    p [1, C, H, W] (fp32 probabilities on the device) against the index label [H, W] (int64) over the listed classes: a float32
+    device scalar whose backward hands d L / d p times the upstream gradient to p, zeros in the unlisted channels.  p is read where it
+    lies when its strides are positive (the NHWC-backed prediction of the trainer).  buffers: a LovaszBuffers the caller keeps
+    between steps (None: made here).  No fallback: off the device, above 2^20 pixels or outside 1 .. 8 classes it raises."""
+    ops.require_gpu(p, "lovasz_softmax")
+    assert p.dim() == 4 and p.shape[0] == 1 and p.dtype == torch.float32, (p.shape, p.dtype)
+    classes = tuple(int(c) for c in classes)
+    _, C, H, W = p.shape
+    if H * W > ops.LOVASZ_MAX_PIXELS or not 1 <= len(classes) <= ops.LOVASZ_MAX_CLASSES:
+        raise SganError(f"lovasz_softmax: not covered ({H} x {W} pixels, {len(classes)} classes: H W <= 2^20, 1 .. {ops.LOVASZ_MAX_CLASSES})")
+    if buffers is None:
+        buffers = LovaszBuffers(C, H, W, len(classes), p.device)
+    assert buffers.fits(C, H, W, len(classes), p.device), (buffers.shape, buffers.n, p.shape, classes)
+    return _LovaszSoftmaxFn.apply(p, label.detach(), classes, buffers)
+
+
 class GANLossMultiClass(nn.Module):
     """GANLossMultiClass (models/networks.py:188-202): CrossEntropyLoss over the class channel of every pixel of a
     discriminator map against one class: one forward and one backward launch (sgan_ce_fwd / sgan_ce_bwd)."""

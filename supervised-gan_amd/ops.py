@@ -1916,6 +1916,128 @@ def cldice_backward(t, st, state, iters, work, dp=None, gout=None):
     return dp
 
 
+# ---- Lovasz-softmax (sgan_lovasz.hip; include/sgan_hip.h, "Lovasz-softmax") ------------------------------------------------------------
+LOVASZ_MAX_CLASSES = 8           # SGAN_LOVASZ_MAX_CLASSES
+LOVASZ_MAX_PIXELS = 1 << 20      # SGAN_LOVASZ_MAX_PIXELS
+LOVASZ_STATE_BYTES = 256         # SGAN_LOVASZ_STATE_BYTES
+LOVASZ_STATE = {'L': 0, 'm': 1, 'Lc': 2, 'scale': 10}      # doubles of the state; the int32 G of the listed classes at byte 192
+
+
+def _lovasz_refused(what, H, W, n):
+    if H < 1 or W < 1 or H * W > LOVASZ_MAX_PIXELS or not 1 <= n <= LOVASZ_MAX_CLASSES:
+        raise L.SganError(f"{what}: not covered ({H} x {W} pixels, {n} classes: H, W >= 1, H W <= 2^20, 1 .. {LOVASZ_MAX_CLASSES} classes); "
+                          "nothing was launched")
+
+
+def lovasz_layout(H, W, n):
+    """Byte offsets of the regions of the Lovasz workspace for H x W pixels and n classes, as the header states them:
+    {'state', 'g', 'keys', 'slots', 'perm', 'bsum', 'bytes', 'P', 'nb'}."""
+    _lovasz_refused("lovasz_layout", H, W, n)
+    N = H * W
+    P = 4096
+    while P < N:
+        P *= 2
+    nb = (N + 1023) // 1024
+    off, out = 0, {'P': P, 'nb': nb}
+    for name, size in (('state', LOVASZ_STATE_BYTES), ('g', 8 * n * N), ('keys', 8 * n * P), ('slots', 8 * n * nb), ('perm', 4 * n * N),
+                       ('bsum', 4 * n * nb)):
+        out[name] = off
+        off += size
+    out['bytes'] = (off + 7) & ~7
+    return out
+
+
+def new_lovasz_workspace(H, W, n, device):
+    """The scratch of lovasz_forward / lovasz_backward for H x W pixels and n listed classes, as float64 (8-byte aligned); it may
+    hold anything: the kernels write what they read.  A node that keeps pi and g for its backward owns one."""
+    _lovasz_refused("sgan_lovasz_workspace_bytes", H, W, int(n))
+    nbytes = L.lib().sgan_lovasz_workspace_bytes(H, W, int(n))
+    if nbytes < 0:
+        raise L.SganError(f"sgan_lovasz_workspace_bytes({H}, {W}, {n}): {L.lib().sgan_last_error().decode()}")
+    assert nbytes == lovasz_layout(H, W, int(n))['bytes'], (nbytes, lovasz_layout(H, W, int(n)))
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def lovasz_views(work, H, W, n):
+    """(pi int32 [n, N], g float64 [n, N], state float64 [32], G int32 [8]) as views of a Lovasz workspace."""
+    lay, N = lovasz_layout(H, W, n), H * W
+    perm = work.view(torch.int32)[lay['perm'] // 4:lay['perm'] // 4 + n * N].view(n, N)
+    g = work[lay['g'] // 8:lay['g'] // 8 + n * N].view(n, N)
+    state = work[:LOVASZ_STATE_BYTES // 8]
+    return perm, g, state, state.view(torch.int32)[48:56]
+
+
+def _lovasz_prediction(p, what):
+    """[C, H, W] fp32 view of the prediction with positive strides and rows that do not overlap, inside its storage."""
+    require_gpu(p, what)
+    if p.dim() == 4:
+        assert p.shape[0] == 1, p.shape
+        p = p[0]
+    assert p.dim() == 3 and p.dtype == torch.float32, (p.shape, p.dtype)
+    nch, H, W = p.shape
+    if min(p.stride()) < 1 or (H > 1 and p.stride(1) < (W - 1) * p.stride(2) + 1):
+        p = p.contiguous()
+    if (nch - 1) * p.stride(0) + (H - 1) * p.stride(1) + (W - 1) * p.stride(2) + 1 > _avail(p):
+        raise L.SganError(f"{what}: prediction {tuple(p.shape)} / {tuple(p.stride())} does not lie inside its storage; nothing was launched")
+    return p
+
+
+def _lovasz_classes(classes, nch, what):
+    classes = [int(c) for c in classes]
+    if len(set(classes)) != len(classes) or any(not 0 <= c < nch for c in classes):
+        raise L.SganError(f"{what}: classes {classes}: distinct indices below C = {nch} are needed; nothing was launched")
+    return (C.c_int32 * max(len(classes), 1))(*classes)
+
+
+def lovasz_forward(p, label, classes, work, loss_out=None):
+    """The Lovasz-softmax loss of the prediction p [1, C, H, W] or [C, H, W] (fp32, read where it lies: NCHW, a window, the channels
+    of an NHWC-backed tensor) against the index label [H, W] (int64) over the listed classes: a float32 device scalar
+    (sgan_lovasz_forward; util.lovasz_ref is the host yardstick).  `work` (new_lovasz_workspace) keeps pi, g and the scales for
+    lovasz_backward.  Only enqueues; the launches depend on (H, W, n) alone."""
+    classes = list(classes)
+    p = _lovasz_prediction(p, "lovasz_forward")
+    nch, H, W = p.shape
+    _lovasz_refused("sgan_lovasz_forward", H, W, len(classes))
+    arr = _lovasz_classes(classes, nch, "sgan_lovasz_forward")
+    dev = p.device
+    require_gpu(label, "lovasz_forward")
+    assert label.dtype == torch.int64 and label.numel() == H * W and label.device == dev, (label.shape, label.dtype)
+    label = label.contiguous()
+    if loss_out is None:
+        loss_out = torch.empty((), dtype=torch.float32, device=dev)
+    assert loss_out.dtype == torch.float32 and loss_out.numel() == 1 and loss_out.device == dev
+    assert work.is_contiguous() and work.device == dev
+    rc = L.lib().sgan_lovasz_forward(_ptr(p), p.stride(0), p.stride(1) if H > 1 else W * p.stride(2), p.stride(2), _ptr(label), arr, len(classes),
+                                     nch, H, W, _ptr(loss_out), _ptr(work), work.numel() * work.element_size(), _stream())
+    if rc == 1:
+        raise L.SganError(f"sgan_lovasz_forward: {L.lib().sgan_last_error().decode()}; nothing was launched")
+    L.check(rc, "sgan_lovasz_forward")
+    return loss_out
+
+
+def lovasz_backward(p, classes, work, dp=None, gout=None):
+    """dp [1, C, H, W] (dense) = gout * d L / d p of Lovasz-softmax from the workspace lovasz_forward(p, ..., work) left and the same
+    p: listed planes scattered through pi, every other plane zero (sgan_lovasz_backward, one launch); gout: a float32 device scalar,
+    None = 1."""
+    classes = list(classes)
+    p = _lovasz_prediction(p, "lovasz_backward")
+    nch, H, W = p.shape
+    _lovasz_refused("sgan_lovasz_backward", H, W, len(classes))
+    arr = _lovasz_classes(classes, nch, "sgan_lovasz_backward")
+    dev = p.device
+    if dp is None:
+        dp = torch.empty((1, nch, H, W), dtype=torch.float32, device=dev)
+    assert dp.dtype == torch.float32 and dp.is_contiguous() and dp.numel() == nch * H * W and dp.device == dev, (dp.shape, dp.dtype)
+    assert gout is None or (gout.dtype == torch.float32 and gout.numel() == 1 and gout.device == dev)
+    assert work.is_contiguous() and work.device == dev
+    rc = L.lib().sgan_lovasz_backward(_ptr(p), p.stride(0), p.stride(1) if H > 1 else W * p.stride(2), p.stride(2), arr, len(classes), nch, H, W,
+                                      _ptr(gout), _ptr(dp), _ptr(work), work.numel() * work.element_size(), _stream())
+    if rc == 1:
+        raise L.SganError(f"sgan_lovasz_backward: {L.lib().sgan_last_error().decode()}; nothing was launched")
+    L.check(rc, "sgan_lovasz_backward")
+    return dp
+
+
 def clean_workspace(H, W, device):
     """The scratch of clean_wall for H x W planes (edt_sq's workspace, one int32 plane for dsq / labels, the area table and the
     complement plane), cached per (H, W, device) like edt_workspace; the kernels initialise what they use."""

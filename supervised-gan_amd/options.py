@@ -140,6 +140,7 @@ class BaseOptions:
         self.opt.isTrain = self.isTrain
         check_border_options(self.opt)
         check_cldice_options(self.opt)
+        check_lovasz_options(self.opt)
         check_clean_options(self.opt, self.parser)
         check_topo_options(self.opt, self.parser)
         check_elastic_options(self.opt)
@@ -199,6 +200,23 @@ def check_cldice_options(opt):
         getattr(opt, 'model', None)
     assert 1 <= opt.cldice_iters <= 16, "--cldice_iters: 1..16 (got %d)" % opt.cldice_iters
     assert opt.cldice_class >= 0, "--cldice_class: a class index (got %d)" % opt.cldice_class
+
+
+def check_lovasz_options(opt):
+    """--lovasz_weight LAMBDA adds the Lovasz-softmax term over --lovasz_classes to the generator loss of --model segmentation (any
+    head, with or without discriminators); LAMBDA >= 0 with 0 = off, 1..8 distinct class indices.  Another model refuses it.  With
+    the weight at 0 nothing is looked at and nothing is changed."""
+    weight = getattr(opt, 'lovasz_weight', 0.0)
+    if weight == 0.0:
+        return
+    assert weight > 0.0, "--lovasz_weight LAMBDA: a weight >= 0, 0 = off (got %g)" % weight      # a NaN fails the comparison
+    assert getattr(opt, 'model', None) == 'segmentation', \
+        "--lovasz_weight adds the Lovasz-softmax term to the segmentation trainer's generator loss: it needs --model segmentation (got '%s')" % \
+        getattr(opt, 'model', None)
+    classes = list(opt.lovasz_classes)
+    assert 1 <= len(classes) <= 8, "--lovasz_classes: 1..8 classes (got %d)" % len(classes)
+    assert all(c >= 0 for c in classes), "--lovasz_classes: class indices (got %s)" % classes
+    assert len(set(classes)) == len(classes), "--lovasz_classes: distinct classes (got %s)" % classes
 
 
 def check_clean_options(opt, parser=None):
@@ -408,6 +426,12 @@ class TrainOptions(BaseOptions):
                'generator loss (with or without discriminators, softmax or sigmoid head); 0 = off')
         a('--cldice_iters', type=int, default=5, metavar='K', help='soft-skeleton iterations of --cldice_weight, 1..16')
         a('--cldice_class', type=int, default=0, help='the class whose plane the soft-clDice term reads (the wall, as the label-based scores)')
+        # the Lovasz-softmax term of the segmentation trainers (Berman, Triki, Blaschko, CVPR 2018; not in the reference)
+        a('--lovasz_weight', type=float, default=0.0, metavar='LAMBDA',
+          help='--model segmentation: add LAMBDA * Lovasz-softmax (the Lovasz extension of the Jaccard loss, classes present in the '
+               'crop only) of the --lovasz_classes planes to the generator loss (with or without discriminators, softmax or sigmoid '
+               'head); 0 = off')
+        a('--lovasz_classes', type=int, default=[0], nargs='+', metavar='C', help='the 1..8 classes of --lovasz_weight (default 0, the wall)')
         # random elastic deformation of every training crop, on the device (not in the reference, which augments with crop, flip and rot90)
         a('--elastic', type=float, default=None, nargs=2, metavar=('G', 'SIGMA'),
           help='image-folder feeders: deform every training crop by a smooth random field -- (G + 3)^2 displacement vectors drawn from '

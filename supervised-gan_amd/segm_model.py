@@ -17,8 +17,8 @@ import torch
 
 from . import networks, ops, util
 from .cgan_model import CGANModel
-from .losses import (ClDiceBuffers, class_probability_plane, cross_entropy_logits, seg_head, sigmoid_channels, soft_cldice, softmax_channels,
-                     weighted_bce)
+from .losses import (ClDiceBuffers, LovaszBuffers, class_probability_plane, cross_entropy_logits, lovasz_softmax, seg_head, sigmoid_channels,
+                     soft_cldice, softmax_channels, weighted_bce)
 from .options import check_tile_options
 from .seg_metrics import SegMetrics, SegMetricsMixin
 
@@ -60,6 +60,14 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
             self.cldice = (float(opt.cldice_weight), int(opt.cldice_iters), int(opt.cldice_class))
             self._cld_truth = self._cld_tskel = self._cld_bufs = None      # persistent: the truth plane, its skeleton, the node's buffers
             self.loss_G_clDice = 0
+        self.lovasz = None      # (lambda, classes) of the Lovasz-softmax term, or None: then nothing of it runs
+        if self.isTrain and getattr(opt, 'lovasz_weight', 0.0) > 0.0:
+            classes = tuple(int(c) for c in opt.lovasz_classes)
+            assert all(c < self.num_classes for c in classes), "--lovasz_classes %s: there are %d classes" % (list(classes), self.num_classes)
+            assert opt.batchSize == 1 and self.device.type == 'cuda', "--lovasz_weight: batch 1 on the device, like every kernel of this path"
+            self.lovasz = (float(opt.lovasz_weight), classes)
+            self._lov_bufs = None      # persistent: the node's buffers
+            self.loss_G_Lovasz = 0
         self.seg_metrics = SegMetrics(opt, self.device, self.num_classes)
         self.reset_accs()
         self._tiling = not self.isTrain and getattr(opt, 'tiling', False)      # test(): whole-image inference (check_tile_options)
@@ -125,6 +133,23 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
         p = class_probability_plane(self.logit, cls, self.use_sigmoid_ss) if self.no_netD else self.fake_B[0, cls]
         self.loss_G_clDice = soft_cldice(p, self._cld_truth, K, t_skel=self._cld_tskel, buffers=self._cld_bufs)
         return loss + lam * self.loss_G_clDice
+
+    def _with_lovasz(self, loss):
+        """loss + lambda * Lovasz-softmax over the listed classes; the loss unchanged with the option off.  With discriminators the
+        term reads fake_B; without them its own softmax / sigmoid of the logits of the last forward(), as the soft-clDice term: the
+        fused head's p takes no gradient.  The prediction is read where it lies and the node returns the gradient of all of it."""
+        if self.lovasz is None:
+            return loss
+        lam, classes = self.lovasz
+        if self.no_netD:
+            p = sigmoid_channels(self.logit) if self.use_sigmoid_ss else softmax_channels(self.logit)
+        else:
+            p = self.fake_B
+        shape = tuple(p.shape[1:])
+        if self._lov_bufs is None or not self._lov_bufs.fits(*shape, len(classes), p.device):
+            self._lov_bufs = LovaszBuffers(*shape, len(classes), p.device)
+        self.loss_G_Lovasz = lovasz_softmax(p, self.label[0], classes, buffers=self._lov_bufs)
+        return loss + lam * self.loss_G_Lovasz
 
     def _border_weight_map(self):
         """The U-Net border term of the current label into self.bmap: the pixels of --border_class are the wall, its complement is
@@ -240,7 +265,7 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
         if self.no_netD:      # :202-203,227: loss_G_GAN = 0, the cross-entropy forward() left behind is the whole loss
             self.loss_G_GAN = 0
             self.loss_G_CE = self._head_loss
-            self.loss_G = self._with_cldice(self.loss_G_CE)
+            self.loss_G = self._with_lovasz(self._with_cldice(self.loss_G_CE))
             self._backward(self.loss_G)
             return
         skip = getattr(self.opt, 'skip_wasted_D_wgrad', False)
@@ -251,11 +276,13 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
         self.loss_G_GAN, self._each_G = self._d_losses([(d, fake, True) for d in self.netD], list(self.opt.lambda_D))
         for netD in self.netD:
             netD.compute_param_grads = True
-        self.loss_G = self._with_cldice(self.loss_G_GAN + self.compute_cross_entropy_loss(weighted=True))
+        self.loss_G = self._with_lovasz(self._with_cldice(self.loss_G_GAN + self.compute_cross_entropy_loss(weighted=True)))
         self._backward(self.loss_G)
 
     def get_current_errors(self):
         extra = [('G_clDice', float(self.loss_G_clDice.detach() if torch.is_tensor(self.loss_G_clDice) else 0.0))] if self.cldice is not None else []
+        if self.lovasz is not None:
+            extra = extra + [('G_Lovasz', float(self.loss_G_Lovasz.detach() if torch.is_tensor(self.loss_G_Lovasz) else 0.0))]
         if self.no_netD:                                     # :253-257
             return OrderedDict([('G_CE', float(self.loss_G_CE.detach()))] + extra)
         return OrderedDict([('G_CE', float(self.loss_G_CE.detach())), ('G_GAN', float(self.loss_G_GAN.detach())),

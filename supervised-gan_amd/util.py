@@ -1236,3 +1236,55 @@ def soft_cldice_ref(P, T, iters):
                 G = G + _cldice_scatter(sign * E[j - 1], dsel[j - 1], CLDICE_DILATE_ORDER)
         grads.append(G + (abs(gC) if absolute else gC) * ST)
     return L, grads[0], SP, ST, I, grads[1]
+
+
+def lovasz_ref(P, label, classes):
+    """Lovasz-softmax (Berman, Triki, Blaschko, CVPR 2018, with classes = 'present') of the prediction P [C, H, W] or [1, C, H, W],
+    read as fp32, against the index label [H, W] over the listed `classes`, in the semantics of include/sgan_hip.h,
+    "Lovasz-softmax": (L, dL/dP [C, H, W], pi [n, N] int32, g [n, N], L_c [n], M).  Per listed class: fg = (label == c); a class
+    without foreground takes no part (its g and L_c are 0); e = |fg - p| in fp32; pi sorts e descending, ties by the pixel index
+    ascending -- the unique key ((0xFFFFFFFF - bits(e)) << 32) | i; with c_k the foreground among the first k + 1 sorted pixels,
+    I = G - c_k and U = G + (k + 1 - c_k) in exact integers, g_k = 1 / U on a foreground pixel and I / (U (U - 1)) elsewhere, one
+    fp64 division; L_c = sum e g in fp64; L the mean over the m present classes; dL/dp_pi(k) = sign(p - fg) g_k / m.  M = |dL/dP|,
+    the scale of a rounding of the gradient."""
+    P32 = np.ascontiguousarray(P, dtype=np.float32)
+    if P32.ndim == 4:
+        assert P32.shape[0] == 1, P32.shape
+        P32 = P32[0]
+    C, H, W = P32.shape
+    N = H * W
+    lab = np.asarray(label).reshape(N)
+    classes = [int(c) for c in classes]
+    assert len(set(classes)) == len(classes) and all(0 <= c < C for c in classes), classes
+    n = len(classes)
+    perm, g, Lc = np.zeros((n, N), np.int32), np.zeros((n, N), np.float64), np.zeros(n, np.float64)
+    present = np.zeros(n, bool)
+    sign = np.zeros((n, N), np.float64)
+    idx = np.arange(N, dtype=np.uint64)
+    for a, c in enumerate(classes):
+        fg = lab == c
+        p = P32[c].reshape(N)
+        e = np.abs(fg.astype(np.float32) - p)                                # one fp32 subtraction
+        key = ((np.uint64(0xFFFFFFFF) - e.view(np.uint32).astype(np.uint64)) << np.uint64(32)) | idx
+        pi = np.argsort(key, kind="stable")
+        perm[a] = pi
+        sign[a] = np.sign(p.astype(np.float64) - fg)[pi]
+        G = int(fg.sum())
+        present[a] = G > 0
+        if G == 0:
+            continue
+        f = fg[pi]
+        ck = np.cumsum(f, dtype=np.int64)
+        k1 = np.arange(1, N + 1, dtype=np.int64)
+        I, U = G - ck, G + (k1 - ck)
+        den = np.where(f, U, U * (U - 1))
+        g[a] = np.where(f, 1, I).astype(np.float64) / den.astype(np.float64)
+        Lc[a] = float(np.sum(e[pi].astype(np.float64) * g[a]))
+    m = int(present.sum())
+    dP = np.zeros((C, N), np.float64)
+    for a, c in enumerate(classes):
+        if present[a]:
+            dP[c, perm[a]] = sign[a] * g[a] / m
+    L = float(Lc.sum() / m) if m else 0.0
+    dP = dP.reshape(C, H, W)
+    return L, dP, perm, g, Lc, np.abs(dP)
