@@ -484,7 +484,8 @@ int sgan_factd_loss_multi_fwd(const sgan_factd_loss_job* jobs, int32_t n, int32_
 int sgan_factd_loss_multi_bwd(const sgan_factd_loss_job* jobs, int32_t n, int32_t mode, const float* gout, void* stream);
 
 /* ---- standalone nn.Sigmoid on channel 0 of a logits map (models/networks.py:836-837) --------
- * Only needed when a caller wants the probability map itself; the GAN loss above consumes logits. */
+ * Only needed when a caller wants the probability map itself; the GAN loss above consumes logits.
+ * Every pixel stride (ld, pld, dpld, dxld) is >= 1; the whole pld / dxld floats of a pixel are written (channel 0, then zeros). */
 int sgan_sigmoid_fwd(const float* x, int32_t ld, int32_t npix, float* p, int32_t pld, void* stream);
 int sgan_sigmoid_bwd(const float* dp, int32_t dpld, const float* p, int32_t pld, int32_t npix, float* dx,
                      int32_t dxld, void* stream);

@@ -1733,7 +1733,7 @@ __global__ __launch_bounds__(256) void sg_sigmoid_bwd_kernel(const float* dp, in
 }
 
 extern "C" int sgan_sigmoid_fwd(const float* x, int32_t ld, int32_t npix, float* p, int32_t pld, void* stream) {
-    SGAN_CHECK(x && p && npix > 0, "bad argument");
+    SGAN_CHECK(x && p && npix > 0 && ld >= 1 && pld >= 1, "bad argument");
     int blocks = sg_cdiv(npix, 256);
     if (blocks > 256) blocks = 256;
     hipLaunchKernelGGL(sg_sigmoid_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, ld, npix, p, pld);
@@ -1743,7 +1743,7 @@ extern "C" int sgan_sigmoid_fwd(const float* x, int32_t ld, int32_t npix, float*
 
 extern "C" int sgan_sigmoid_bwd(const float* dp, int32_t dpld, const float* p, int32_t pld, int32_t npix, float* dx,
                                 int32_t dxld, void* stream) {
-    SGAN_CHECK(dp && p && dx && npix > 0, "bad argument");
+    SGAN_CHECK(dp && p && dx && npix > 0 && dpld >= 1 && pld >= 1 && dxld >= 1, "bad argument");
     int blocks = sg_cdiv(npix, 256);
     if (blocks > 256) blocks = 256;
     hipLaunchKernelGGL(sg_sigmoid_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dp, dpld, p, pld, npix, dx, dxld);

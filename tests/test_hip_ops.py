@@ -822,6 +822,18 @@ def test_c_abi_error_paths(hip):
     with pytest.raises(SganError, match="does not match the descriptor"):
         ops.conv_wgrad(ops.conv_desc(0, 7, 1, 3, 16, 16, 8, 16, 16, 8), x, None, y, torch.zeros(49 * 64, device="cuda"), None)
     assert float(y.abs().max()) == 0.0 and float(y16.abs().max()) == 0.0           # nothing ran
+    # a pixel stride of 0 or below in the standalone sigmoid: refused like the GAN-loss entry points refuse it, before any launch
+    import ctypes
+    sx, sp = torch.full((64,), 2.0, device="cuda"), torch.full((64,), 7.0, device="cuda")
+    px, pp, st = ctypes.c_void_p(sx.data_ptr()), ctypes.c_void_p(sp.data_ptr()), ops._stream()
+    for ld, pld in ((0, 1), (1, 0), (-1, 1), (1, -4)):
+        assert L_raw().sgan_sigmoid_fwd(px, ld, 16, pp, pld, st) < 0 and b"bad argument" in L_raw().sgan_last_error()
+    for dpld, pld, dxld in ((0, 1, 1), (1, 0, 1), (1, 1, 0), (-4, 1, 1), (1, -1, 1), (1, 1, -1)):
+        assert L_raw().sgan_sigmoid_bwd(px, dpld, px, pld, 16, pp, dxld, st) < 0 and b"bad argument" in L_raw().sgan_last_error()
+    with pytest.raises(SganError, match="sgan_sigmoid_fwd"):
+        ops.sigmoid_fwd(sx.as_strided((1, 16, 1), (0, 0, 1)), sp.view(1, 16, 4))
+    torch.cuda.synchronize()
+    assert float((sp - 7.0).abs().max()) == 0.0 and float((sx - 2.0).abs().max()) == 0.0          # nothing ran
     D = N.define_D(2, 8, "dcgan", gpu_ids=[0])             # five k4 s2 p1 convs, then k4 s1 p0 on what must be a 4x4 map
     with pytest.raises(SganError, match="too small"):
         D.forward(torch.rand(1, 2, 32, 32, device="cuda"))
