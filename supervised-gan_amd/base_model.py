@@ -12,6 +12,7 @@ from collections import OrderedDict
 import torch
 
 from . import ops
+from ._lib import SganError
 
 
 class BaseModel:
@@ -167,7 +168,16 @@ class BaseModel:
             elif self.grad_sync is not None:
                 self.grad_sync(item[1])
 
+    def refuse_eager_step(self, what):
+        """A trainer whose step graph_step.GraphedStep captured with prefetch keeps one generator forward alive between two steps, in
+        buffers the graphs point into (netG._kept, its statistics arena): an eager forward() or optimize_parameters() would allocate
+        that forward anew and zero the arena under them.  Raises before anything is launched unless GraphedStep itself is calling."""
+        if getattr(self, '_prefetch', False) and not getattr(self, '_graphed_call', False):
+            raise SganError("%s() on a trainer whose step was captured with prefetch: the captured graphs read the generator forward "
+                            "this call would replace; run GraphedStep.step() (test() is safe between two steps)" % what)
+
     def optimize_parameters(self):
+        self.refuse_eager_step('optimize_parameters')
         ops.begin_step(self.step_zeroing())      # one launch zeroes every statistics arena of the step
         self.forward()
         self.run_program(self.step_program())

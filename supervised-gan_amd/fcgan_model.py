@@ -134,6 +134,7 @@ class FCGANModel(BaseModel):
         self.image_paths = input.get('A_paths' if AorB else 'B_paths')
 
     def forward(self):
+        self.refuse_eager_step('forward')
         self.real = self.input
         self.noise = self._draw_noise()
         self.netG._keep_next = getattr(self, '_prefetch', False)      # graphed step: forward_pair() refills THIS call's buffers
@@ -179,9 +180,19 @@ class FCGANModel(BaseModel):
         self.noise = self.noise_
         self.fake = self._fake_next
 
+    def _draw_test_noise(self):
+        """test()'s latent, next in the trainer's stream.  Under the graphed step's prefetch `_noise_buf` is the input of the kept
+        forward -- the next step's first-layer backward-weight reads it -- so the draw goes into a buffer of its own."""
+        if not getattr(self, '_prefetch', False):
+            return self._draw_noise()
+        if getattr(self, '_noise_buf_test', None) is None:
+            self._noise_buf_test = torch.zeros_like(self._noise_buf)
+        ops.normal_fill_nhwc(self._noise_buf_test, self.opt.noise_nc, self._rng_seed, self._rng_offset)
+        return ops.logical_view(self._noise_buf_test, self.opt.noise_nc)
+
     def test(self):
         with torch.no_grad():
-            self.noise = self._draw_noise()
+            self.noise = self._draw_test_noise()
             self.fake = self._eval_netG().forward(self.noise)
 
     def get_image_paths(self):

@@ -254,3 +254,98 @@ def test_three_rate_schedule(case, tmp_path, capsys):
         for tag, groups in rates.items():
             for name, rate in groups:
                 assert rate == getattr(m, follows[name or tag]), (tag, name)
+
+
+# ---- GraphedStep.step(replay=False): the captured calls, launch by launch ------------------------------------------------------------
+class _FakeGraph:
+    """torch.cuda.CUDAGraph for a host without a GPU: what ran while it was 'captured' is its content, replay() logs its number."""
+    made = []
+
+    def __init__(self):
+        self.captured, self.no = None, len(_FakeGraph.made)
+        _FakeGraph.made.append(self)
+
+    def pool(self):
+        return None
+
+    def replay(self):
+        self.log.append("replay:%d" % self.no)
+
+
+class _FakeStream:
+    def __init__(self, *a, **k):
+        pass
+
+    def wait_stream(self, other):
+        pass
+
+
+def _fake_cuda(monkeypatch, log):
+    import contextlib
+
+    @contextlib.contextmanager
+    def graph(g, **kw):
+        start = len(log)
+        yield
+        g.captured, g.log = log[start:], log
+        del log[start:]
+
+    _FakeGraph.made = []
+    monkeypatch.setattr(torch.cuda, "CUDAGraph", _FakeGraph)
+    monkeypatch.setattr(torch.cuda, "graph", graph)
+    monkeypatch.setattr(torch.cuda, "Stream", _FakeStream)
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a: _FakeStream())
+    monkeypatch.setattr(torch.cuda, "stream", lambda s: contextlib.nullcontext())
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a: None)
+
+
+LAUNCHES = {"fcgan": (FCGAN, False), "fcgan_prefetch": (FCGAN, True), "twostage_cycle": (TWOSTAGE, False), "cgan_g2": (CGAN, False)}
+
+
+@pytest.mark.parametrize("sync", [False, True], ids=["alone", "grad_sync"])
+@pytest.mark.parametrize("case", list(LAUNCHES))
+def test_launch_by_launch_step_calls_what_was_captured(case, sync, tmp_path, monkeypatch):
+    """step(replay=False) makes, in order, exactly the calls each graph was captured from, with the pool copies and the gradient
+    exchanges where step() has them; the step(replay=True) after it first re-installs the captured step's tensors."""
+    from supervised_gan_amd import ops
+    from supervised_gan_amd.graph_step import GraphedStep
+    argv, prefetch = LAUNCHES[case]
+    m = _build(argv, tmp_path)
+    log, begun = _record(m, monkeypatch, sync)
+    _fake_cuda(monkeypatch, log)
+    rec = lambda label: lambda *a, **k: log.append(label)      # noqa: E731
+    m.set_input = lambda data: None
+    m.sample_noise_and_prefetch, m.adopt_prefetched = rec("sample_noise_and_prefetch"), rec("adopt_prefetched")
+    img = torch.zeros(1, 2, 8, 8)
+    for name in ("real_A", "real_B", "fake", "fake_A", "fake_B", "fake_B_from_real_A", "fake_B_from_fake_A"):
+        setattr(m, name, img)
+    m._fake_next = m._noise_alt = img
+    m.transform = m.transform_inverse = lambda x: x
+    monkeypatch.setattr(ops, "as_nhwc", lambda x: x.permute(0, 2, 3, 1)[0])
+    monkeypatch.setattr(ops, "slice_nhwc", lambda q, c0, n, out=None: log.append("pool_copy"))
+    gs = GraphedStep(m)
+    gs._prefetch = prefetch
+    gs.capture(None)
+    graphs = list(_FakeGraph.made)
+    updates = sum(n for _, _, n in m.step_stages())
+    assert all(g.captured for g in graphs) and len(graphs) == (0 if prefetch else 1) + (updates + 1 if sync else 1)
+    want = ["adopt_prefetched"] if prefetch else list(graphs[0].captured)
+    want += ["pool_copy"] * len(gs.pools)
+    assert [obj for kind, obj in gs.segs if kind == "graph"] == graphs[0 if prefetch else 1:]
+    for kind, obj in gs.segs:      # the captured pieces with the gradient exchanges between them, as step() walks them
+        want += obj.captured if kind == "graph" else ["sync:" + obj.tag]
+    assert len([c for c in want if c.startswith("sync:")]) == (updates if sync else 0)
+    assert want[:2] == (["adopt_prefetched", "pool_copy"] if prefetch else ["begin_step", "forward"])
+    assert ("sample_noise_and_prefetch" in want) == prefetch and "begin_step" in want
+    del log[:]
+    m.marker = torch.zeros(1)      # an attribute the launches rebind: the next replay must see the captured step's again
+    gs._step_tensors["marker"] = m.marker
+    gs.step(None, replay=False)
+    assert log == want
+    m.marker = torch.ones(1)
+    del log[:]
+    gs.step(None)
+    replays = ["replay:%d" % g.no for g in graphs]
+    assert [c for c in log if c.startswith("replay:")] == replays and not [c for c in log if c in want and c not in ("adopt_prefetched", "pool_copy")
+                                                                               and not c.startswith("sync:")]
+    assert m.marker is gs._step_tensors["marker"]
