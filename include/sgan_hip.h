@@ -1352,6 +1352,45 @@ int sgan_lovasz_forward(const float* p, int64_t p_cs, int64_t p_rs, int64_t p_ps
 int sgan_lovasz_backward(const float* p, int64_t p_cs, int64_t p_rs, int64_t p_ps, const int32_t* classes, int32_t n, int32_t C, int32_t H,
                          int32_t W, const float* gout, float* dp, const void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- Segmentation loss terms: Tversky (soft Dice, focal-Tversky) and focal loss on the LOGITS (not in the reference) ----
+ * util.seg_terms_ref is the NumPy fp64 restatement.  `logits` [npix][ld] fp32 with C <= 16 logical channels, read
+ * where sgan_seg_head reads them; mode SGAN_SEGHEAD_SOFTMAX: `label_or_target` is the int64 label map, p = softmax(z), t_c = [y == c],
+ * and a pixel whose label lies outside [0, C) adds to no sum and gets a zero gradient; SGAN_SEGHEAD_SIGMOID: the float target
+ * [npix][tld] in [0, 1], p_c = sigmoid(z_c).
+ *   Tversky over the n listed classes (`classes`: n distinct indices below C, on the HOST, read during the call; n = 0: term off):
+ *     TP = sum p t, FP = sum p (1 - t), FN = sum (1 - p) t, in fp64 in an order fixed by npix;
+ *     D = TP + alpha FP + beta FN + smooth, TI = (TP + smooth) / D, L_c = (1 - TI)^power, L_T = (1 / n) sum_c L_c;
+ *     a class with D == 0 has L_c = 0 and no gradient; where 1 - TI == 0 the derivative is 0;
+ *     G_c(t) = -(power / n) (1 - TI)^(power - 1) [t / D - (TP + smooth) (t (1 - beta) + alpha (1 - t)) / D^2];
+ *     softmax: dz_k = p_k (G'_k - sum_j p_j G'_j), G'_j = G_j(t_j) on a listed channel, 0 elsewhere; sigmoid: dz_c = p_c (1 - p_c) G_c(t_c).
+ *   Focal (`focal` != 0), class weights class_w (NULL: 1; softmax: nw >= C of them, sigmoid: the first nw <= C channels):
+ *     softmax, pt = p_y, lp = z_y - logsumexp(z): L_F = sum w[y] (1 - pt)^gamma (-lp) / sum w[y],
+ *       dz_k = w[y] / norm [gamma pt (1 - pt)^(gamma - 1) lp - (1 - pt)^gamma] (delta_ky - p_k), the first product left out where
+ *       gamma == 0 or 1 - pt == 0; gamma = 0 is the class-weighted cross-entropy of sgan_seg_head;
+ *     sigmoid: L_F = sum_{p, c} w_c [t (1 - p)^gamma softplus(-z) + (1 - t) p^gamma softplus(z)] / (C npix), dz its derivative.
+ * sgan_seg_terms_forward: one launch.  Writes the state (SGAN_SEGTERMS_STATE_BYTES, doubles: [8 j + 0 .. 7] TP, FP, FN, D, TI, L_c,
+ *   G_c(0), G_c(1) of the j-th listed class, zeros behind the n-th; [64] the focal numerator, [65] its norm, [66] L_T, [67] L_F) and
+ *   both losses as device floats (0 for a term that is off).  `workspace`: SGAN_SEGTERMS_WS_BYTES of 8-byte aligned device scratch,
+ *   ZERO on first use, owned by one stream at a time and left zeroed by every call.
+ * sgan_seg_terms_backward: one launch, from the state the forward left and the same logits and label: dlogits [npix][dld] =
+ *   gout_tversky * dL_T/dz + gout_focal * dL_F/dz, the upstream gradients device floats, NULL = that term is not taken; the padding
+ *   channels dld > C are written as zeros.
+ * The grid depends on npix only; no floating-point atomics, no workgroup waits on another, nothing is read back or allocated: both
+ * calls capture into a hipGraph and give the same bits on every run.  Return 1, the reason in sgan_last_error and nothing launched:
+ * C > 16, n outside 0 .. 8, both terms off, a listed class >= C or repeated, parameters outside alpha, beta >= 0, alpha + beta > 0,
+ * smooth >= 0, 0 < power <= 4, 0 <= gamma <= 8, a NULL required pointer, rows shorter than C. */
+#define SGAN_SEGTERMS_MAX_CLASSES 8
+#define SGAN_SEGTERMS_STATE_BYTES 544
+#define SGAN_SEGTERMS_WS_BYTES 106504
+int sgan_seg_terms_forward(const float* logits, int32_t ld, int32_t npix, int32_t C, int32_t mode, const void* label_or_target, int32_t tld,
+                           const int32_t* classes, int32_t n, double alpha, double beta, double smooth, double power, int32_t focal,
+                           double gamma, const float* class_w, int32_t nw, double* state, float* loss_tversky, float* loss_focal,
+                           void* workspace, void* stream);
+int sgan_seg_terms_backward(const float* logits, int32_t ld, int32_t npix, int32_t C, int32_t mode, const void* label_or_target, int32_t tld,
+                            const int32_t* classes, int32_t n, int32_t focal, double gamma, const float* class_w, int32_t nw,
+                            const double* state, const float* gout_tversky, const float* gout_focal, float* dlogits, int32_t dld,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,7 +94,7 @@ class DiffaugJob(C.Structure):
 
 
 # name -> argtypes; every entry returns int except the two string getters
-_P, _I, _L, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+_P, _I, _L, _F, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 SIGNATURES = {
     "sgan_conv_fwd": [C.POINTER(ConvDesc), _P, _I, C.POINTER(NormDesc), _P, _P, _P, _I, _I, _P, _P, _L, _P],
     "sgan_conv_dgrad": [C.POINTER(ConvDesc), _P, _I, _P, _P, _I, _P, _I, C.POINTER(NormDesc), _P, _P, _L, _P],
@@ -214,6 +214,8 @@ SIGNATURES = {
     "sgan_lovasz_workspace_bytes": [_I, _I, _I],
     "sgan_lovasz_forward": [_P, _L, _L, _L, _P, _P, _I, _I, _I, _I, _P, _P, _L, _P],
     "sgan_lovasz_backward": [_P, _L, _L, _L, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P],
+    "sgan_seg_terms_forward": [_P, _I, _I, _I, _I, _P, _I, _P, _I, _D, _D, _D, _D, _I, _D, _P, _I, _P, _P, _P, _P, _P],
+    "sgan_seg_terms_backward": [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _D, _P, _I, _P, _P, _P, _P, _I, _P],
     "sgan_last_variant": [],
     "sgan_profile_enable": [_I],
     "sgan_profile_count": [],

@@ -561,6 +561,76 @@ def lovasz_softmax(p, label, classes, buffers=None):
     return _LovaszSoftmaxFn.apply(p, label.detach(), classes, buffers)
 
 
+class SegTermsBuffers:
+    """What a Tversky / focal node keeps between calls for [1, C, H, W] logits: the fp64 state the forward writes and the backward
+    reads, the zeroed workspace of the forward's hand-off, the two loss scalars and the gradient buffer the node hands out, so that
+    a step allocates nothing.  One node at a time, as ClDiceBuffers."""
+
+    def __init__(self, C, H, W, device):
+        self.shape = (C, H, W)
+        self.state = ops.new_seg_terms_state(device)
+        self.work = ops.new_seg_terms_workspace(device)
+        self.loss_t = torch.zeros((), dtype=torch.float32, device=device)
+        self.loss_f = torch.zeros((), dtype=torch.float32, device=device)
+        self.dz = torch.empty((H, W, pad4(C)), dtype=torch.float32, device=device)
+
+    def fits(self, C, H, W, device):
+        return self.shape == (C, H, W) and self.dz.device == device
+
+
+class _SegTermsFn(torch.autograd.Function):
+    """(L_T, L_F) from the logits in one launch (sgan_seg_terms_forward); the backward is one launch too (sgan_seg_terms_backward): it
+    takes the two upstream gradients as device scalars -- a term without one is not taken -- and writes the gradient of the logits."""
+
+    @staticmethod
+    def forward(ctx, logits, lt, mode, classes, alpha, beta, smooth, power, gamma, cw, bufs):
+        zb = ops.as_nhwc(logits)
+        C_ = logits.shape[1]
+        lt = lt.reshape(-1).contiguous() if mode == ops.SEGHEAD_SOFTMAX else ops.as_nhwc(lt)
+        ops.seg_terms_forward(zb, C_, mode, lt, classes, alpha, beta, smooth, power, gamma, cw, bufs.state, bufs.loss_t, bufs.loss_f, bufs.work)
+        ctx.zb, ctx.lt, ctx.C, ctx.mode, ctx.classes, ctx.gamma, ctx.cw, ctx.bufs = zb, lt, C_, mode, classes, gamma, cw, bufs
+        ctx.set_materialize_grads(False)      # a term nobody uses arrives as None: the kernel then leaves it out
+        return bufs.loss_t.detach(), bufs.loss_f.detach()      # aliases of the persistent scalars, as _SoftClDiceFn's
+
+    @staticmethod
+    def backward(ctx, gt, gf):
+        none = (None,) * 11
+        if (gt is None and gf is None) or not ctx.needs_input_grad[0]:
+            return none
+        gt = None if gt is None or not ctx.classes else gt.contiguous().float()
+        gf = None if gf is None or ctx.gamma is None else gf.contiguous().float()
+        dz = ops.seg_terms_backward(ctx.zb, ctx.C, ctx.mode, ctx.lt, ctx.classes, ctx.gamma, ctx.cw, ctx.bufs.state, gt, gf, ctx.bufs.dz)
+        return (ops.logical_view(dz, ctx.C),) + none[1:]
+
+
+def seg_terms(logits, label_or_target, mode, classes=(), alpha=0.5, beta=0.5, smooth=1.0, power=1.0, focal_gamma=None, class_weights=None,
+              buffers=None):
+    """The Tversky term (soft Dice at alpha = beta = 0.5, focal-Tversky at power < 1) over the listed `classes` and the focal term
+    of the [1, C, H, W] fp32 logits on the device, against the int64 label map (mode ops.SEGHEAD_SOFTMAX) or the [1, C, H, W] float
+    target (ops.SEGHEAD_SIGMOID): (L_T, L_F), float32 device scalars; util.seg_terms_ref states the mathematics.  classes empty: the
+    Tversky term is off and L_T = 0; focal_gamma None: the focal term is off and L_F = 0; one of them must be on.  class_weights: the
+    focal term's (None: 1).  The gradient flows to the logits only, each term's times its own upstream gradient; the logit tensor is
+    taken the way seg_head takes it (NHWC-backed, read where it lies).  buffers: a SegTermsBuffers the caller keeps between steps
+    (None: made here).  One launch forward, one backward; no fallback: off the device, with a batch or above 16 channels it raises."""
+    ops.require_gpu(logits, "seg_terms")
+    if not _bce_envelope(logits):
+        raise SganError(f"seg_terms: not covered ({tuple(logits.shape)} {logits.dtype}: [1, C <= 16, H, W] fp32 logits on the device)")
+    softmax = mode == ops.SEGHEAD_SOFTMAX
+    lt = label_or_target.detach()
+    _, C_, H, W = logits.shape
+    if softmax:
+        assert lt.dtype == torch.int64 and lt.device == logits.device and lt.numel() == H * W, "seg_terms: an int64 label map on the logits' device"
+    else:
+        assert _bce_envelope(lt) and lt.shape == logits.shape, "seg_terms: a [1, C, H, W] fp32 target on the logits' device"
+    classes = tuple(int(c) for c in classes)
+    cw = None if class_weights is None or focal_gamma is None else class_weights.detach().float().contiguous()
+    if buffers is None:
+        buffers = SegTermsBuffers(C_, H, W, logits.device)
+    assert buffers.fits(C_, H, W, logits.device), (buffers.shape, logits.shape)
+    return _SegTermsFn.apply(logits, lt, int(mode), classes, float(alpha), float(beta), float(smooth), float(power),
+                             None if focal_gamma is None else float(focal_gamma), cw, buffers)
+
+
 class GANLossMultiClass(nn.Module):
     """GANLossMultiClass (models/networks.py:188-202): CrossEntropyLoss over the class channel of every pixel of a
     discriminator map against one class: one forward and one backward launch (sgan_ce_fwd / sgan_ce_bwd)."""

@@ -2038,6 +2038,96 @@ def lovasz_backward(p, classes, work, dp=None, gout=None):
     return dp
 
 
+# ---- Tversky / focal loss terms on the logits (sgan_segterms.hip; include/sgan_hip.h, "Segmentation loss terms") --------------------------
+SEGTERMS_MAX_CLASSES = 8         # SGAN_SEGTERMS_MAX_CLASSES
+SEGTERMS_STATE_BYTES = 544       # SGAN_SEGTERMS_STATE_BYTES
+SEGTERMS_WS_BYTES = 106504       # SGAN_SEGTERMS_WS_BYTES
+SEGTERMS_STATE = {'class': 0, 'focal_num': 64, 'focal_norm': 65, 'L_T': 66, 'L_F': 67}      # doubles; per class 8: TP FP FN D TI L_c G(0) G(1)
+
+
+def new_seg_terms_state(device):
+    """The fp64 state seg_terms_forward writes and seg_terms_backward reads (68 doubles, SEGTERMS_STATE)."""
+    return torch.zeros(SEGTERMS_STATE_BYTES // 8, dtype=torch.float64, device=device)
+
+
+def new_seg_terms_workspace(device):
+    """The slots and ticket of seg_terms_forward: zero on first use, left zeroed by every call; one per node and stream."""
+    return torch.zeros(SEGTERMS_WS_BYTES // 8, dtype=torch.float64, device=device)
+
+
+def _seg_terms_args(what, z, Creal, mode, label_or_target, classes, focal_gamma, class_w, state):
+    """The operand checks both calls share: every tensor against its storage, before anything is launched.  Returns
+    (label_or_target, tld, classes array, n, focal, gamma, nw)."""
+    require_gpu(z, what)
+    H, W, _ = z.shape
+    dev = z.device
+
+    def rows_fit(t, name, written):
+        _act(t)
+        row = t.stride(1) if (written or t.stride(1) in (4, 8, 12, 16)) else Creal
+        if (t.device != dev or t.shape[0] * t.shape[1] != H * W or t.shape[2] < Creal or t.stride(1) < Creal
+                or (H * W - 1) * t.stride(1) + row > _avail(t)):
+            raise L.SganError(f"{what} {name}: tensor {tuple(t.shape)} (pixel stride {t.stride(1)}, {_avail(t)} elements of storage) does "
+                              f"not hold {H}x{W} rows of {row}; nothing was launched")
+
+    rows_fit(z, "logits", False)
+    tld = 0
+    if mode == SEGHEAD_SOFTMAX:
+        assert (label_or_target.dtype == torch.int64 and label_or_target.device == dev and label_or_target.is_contiguous()
+                and label_or_target.numel() == H * W), (label_or_target.shape, label_or_target.dtype)
+    else:
+        rows_fit(label_or_target, "target", False)
+        tld = label_or_target.stride(1)
+    classes = [int(c) for c in classes]
+    n = len(classes)
+    focal = focal_gamma is not None
+    nw = 0 if class_w is None else int(class_w.numel())
+    assert class_w is None or (class_w.dtype == torch.float32 and class_w.device == dev and class_w.is_contiguous())
+    if focal and class_w is not None and mode == SEGHEAD_SOFTMAX and nw < Creal:
+        raise L.SganError(f"{what}: {nw} class weights for {Creal} classes; nothing was launched")
+    assert state.dtype == torch.float64 and state.is_contiguous() and state.numel() >= SEGTERMS_STATE_BYTES // 8 and state.device == dev
+    arr = (C.c_int32 * max(n, 1))(*classes)
+    return rows_fit, tld, arr, n, int(focal), float(focal_gamma) if focal else 0.0, min(nw, Creal)
+
+
+def seg_terms_forward(z, Creal, mode, label_or_target, classes, alpha, beta, smooth, power, focal_gamma, class_w, state, loss_t, loss_f,
+                      work):
+    """sgan_seg_terms_forward on an [H, W, Cs] logits buffer: the Tversky term over `classes` (empty: off) and the focal term
+    (focal_gamma None: off) into `state` (new_seg_terms_state) and the float32 device scalars loss_t, loss_f; `label_or_target` as
+    seg_head takes it; `work`: new_seg_terms_workspace.  One launch, only enqueued.  Not covered (SganError, nothing launched):
+    more than 16 channels, more than 8 or repeated or out-of-range classes, both terms off, parameters out of range."""
+    what = "seg_terms_forward"
+    _, tld, arr, n, focal, gamma, nw = _seg_terms_args(what, z, Creal, mode, label_or_target, classes, focal_gamma, class_w, state)
+    H, W, _ = z.shape
+    for t in (loss_t, loss_f):
+        assert t.dtype == torch.float32 and t.numel() == 1 and t.device == z.device
+    assert work.dtype == torch.float64 and work.is_contiguous() and work.numel() * 8 >= SEGTERMS_WS_BYTES and work.device == z.device
+    rc = L.lib().sgan_seg_terms_forward(_ptr(z), z.stride(1), H * W, int(Creal), int(mode), _ptr(label_or_target), tld, arr, n, float(alpha),
+                                        float(beta), float(smooth), float(power), focal, gamma, _ptr(class_w), nw, _ptr(state), _ptr(loss_t),
+                                        _ptr(loss_f), _ptr(work), _stream())
+    if rc == 1:
+        raise L.SganError(f"sgan_seg_terms_forward: {L.lib().sgan_last_error().decode()}; nothing was launched")
+    L.check(rc, "sgan_seg_terms_forward")
+
+
+def seg_terms_backward(z, Creal, mode, label_or_target, classes, focal_gamma, class_w, state, gout_t, gout_f, dz):
+    """dz [H, W, Cs'] = gout_t * dL_T/dz + gout_f * dL_F/dz from the state seg_terms_forward left and the same logits and label
+    (sgan_seg_terms_backward, one launch).  gout_t / gout_f: float32 device scalars, None = that term is not taken (its part of dz
+    is exactly zero); the padding channels of dz are written as zeros."""
+    what = "seg_terms_backward"
+    rows_fit, tld, arr, n, focal, gamma, nw = _seg_terms_args(what, z, Creal, mode, label_or_target, classes, focal_gamma, class_w, state)
+    H, W, _ = z.shape
+    rows_fit(dz, "dlogits", True)
+    for g in (gout_t, gout_f):
+        assert g is None or (g.dtype == torch.float32 and g.numel() == 1 and g.device == z.device)
+    rc = L.lib().sgan_seg_terms_backward(_ptr(z), z.stride(1), H * W, int(Creal), int(mode), _ptr(label_or_target), tld, arr, n, focal, gamma,
+                                         _ptr(class_w), nw, _ptr(state), _ptr(gout_t), _ptr(gout_f), _ptr(dz), dz.stride(1), _stream())
+    if rc == 1:
+        raise L.SganError(f"sgan_seg_terms_backward: {L.lib().sgan_last_error().decode()}; nothing was launched")
+    L.check(rc, "sgan_seg_terms_backward")
+    return dz
+
+
 def clean_workspace(H, W, device):
     """The scratch of clean_wall for H x W planes (edt_sq's workspace, one int32 plane for dsq / labels, the area table and the
     complement plane), cached per (H, W, device) like edt_workspace; the kernels initialise what they use."""

@@ -141,6 +141,8 @@ class BaseOptions:
         check_border_options(self.opt)
         check_cldice_options(self.opt)
         check_lovasz_options(self.opt)
+        check_dice_options(self.opt)
+        check_focal_options(self.opt)
         check_clean_options(self.opt, self.parser)
         check_topo_options(self.opt, self.parser)
         check_elastic_options(self.opt)
@@ -217,6 +219,44 @@ def check_lovasz_options(opt):
     assert 1 <= len(classes) <= 8, "--lovasz_classes: 1..8 classes (got %d)" % len(classes)
     assert all(c >= 0 for c in classes), "--lovasz_classes: class indices (got %s)" % classes
     assert len(set(classes)) == len(classes), "--lovasz_classes: distinct classes (got %s)" % classes
+
+
+def check_dice_options(opt):
+    """--dice_weight LAMBDA adds the Tversky term over --dice_classes to the generator loss of --model segmentation (any head, with
+    or without discriminators): soft Dice at the default --tversky 0.5 0.5, focal-Tversky at --tversky_power below 1.  LAMBDA >= 0
+    with 0 = off, 1..8 distinct class indices, A, B >= 0 with A + B > 0, S >= 0, 0 < E <= 4.  Another model refuses it.  With the
+    weight at 0 nothing is looked at and nothing is changed."""
+    weight = getattr(opt, 'dice_weight', 0.0)
+    if weight == 0.0:
+        return
+    assert weight > 0.0, "--dice_weight LAMBDA: a weight >= 0, 0 = off (got %g)" % weight      # a NaN fails the comparison
+    assert getattr(opt, 'model', None) == 'segmentation', \
+        "--dice_weight adds the Dice / Tversky term to the segmentation trainer's generator loss: it needs --model segmentation (got '%s')" % \
+        getattr(opt, 'model', None)
+    classes = list(opt.dice_classes)
+    assert 1 <= len(classes) <= 8, "--dice_classes: 1..8 classes (got %d)" % len(classes)
+    assert all(c >= 0 for c in classes), "--dice_classes: class indices (got %s)" % classes
+    assert len(set(classes)) == len(classes), "--dice_classes: distinct classes (got %s)" % classes
+    a, b = opt.tversky
+    assert a >= 0.0 and b >= 0.0, "--tversky A B: both >= 0 (got %g %g)" % (a, b)      # a NaN fails the comparison
+    assert a + b > 0.0, "--tversky A B: A + B == 0 leaves no penalty on any error (got %g %g)" % (a, b)
+    assert a < float('inf') and b < float('inf'), "--tversky A B: finite (got %g %g)" % (a, b)
+    assert 0.0 <= opt.dice_smooth < float('inf'), "--dice_smooth S: S >= 0 (got %g)" % opt.dice_smooth
+    assert 0.0 < opt.tversky_power <= 4.0, "--tversky_power E: 0 < E <= 4 (got %g)" % opt.tversky_power
+
+
+def check_focal_options(opt):
+    """--focal_weight LAMBDA adds the focal loss (Lin et al., ICCV 2017) with --focal_gamma G and the class weights of --weights to
+    the generator loss of --model segmentation (any head, with or without discriminators); LAMBDA >= 0 with 0 = off, 0 <= G <= 8.
+    Another model refuses it.  With the weight at 0 nothing is looked at and nothing is changed."""
+    weight = getattr(opt, 'focal_weight', 0.0)
+    if weight == 0.0:
+        return
+    assert weight > 0.0, "--focal_weight LAMBDA: a weight >= 0, 0 = off (got %g)" % weight      # a NaN fails the comparison
+    assert getattr(opt, 'model', None) == 'segmentation', \
+        "--focal_weight adds the focal loss to the segmentation trainer's generator loss: it needs --model segmentation (got '%s')" % \
+        getattr(opt, 'model', None)
+    assert 0.0 <= opt.focal_gamma <= 8.0, "--focal_gamma G: 0 <= G <= 8 (got %g)" % opt.focal_gamma
 
 
 def check_clean_options(opt, parser=None):
@@ -432,6 +472,20 @@ class TrainOptions(BaseOptions):
                'crop only) of the --lovasz_classes planes to the generator loss (with or without discriminators, softmax or sigmoid '
                'head); 0 = off')
         a('--lovasz_classes', type=int, default=[0], nargs='+', metavar='C', help='the 1..8 classes of --lovasz_weight (default 0, the wall)')
+        # the Dice / Tversky and focal terms of the segmentation trainers, on the logits (not in the reference)
+        a('--dice_weight', type=float, default=0.0, metavar='LAMBDA',
+          help='--model segmentation: add LAMBDA * Tversky loss (soft Dice at the default --tversky 0.5 0.5) of the --dice_classes '
+               'channels to the generator loss (with or without discriminators, softmax or sigmoid head); 0 = off')
+        a('--dice_classes', type=int, default=[0], nargs='+', metavar='C', help='the 1..8 classes of --dice_weight (default 0, the wall)')
+        a('--tversky', type=float, default=[0.5, 0.5], nargs=2, metavar=('A', 'B'),
+          help='--dice_weight: the weights of false positives (A) and false negatives (B) in the Tversky index; 0.5 0.5 = Dice')
+        a('--dice_smooth', type=float, default=1.0, metavar='S', help='--dice_weight: added to numerator and denominator, >= 0')
+        a('--tversky_power', type=float, default=1.0, metavar='E',
+          help='--dice_weight: the loss is (1 - TI)^E, 0 < E <= 4; 0.75 = the focal-Tversky loss of Abraham & Khan')
+        a('--focal_weight', type=float, default=0.0, metavar='LAMBDA',
+          help='--model segmentation: add LAMBDA * focal loss of the logits (class weights from --weights) to the generator loss '
+               '(with or without discriminators, softmax or sigmoid head); 0 = off')
+        a('--focal_gamma', type=float, default=2.0, metavar='G', help='--focal_weight: the focusing exponent, 0 <= G <= 8 (0 = cross-entropy)')
         # random elastic deformation of every training crop, on the device (not in the reference, which augments with crop, flip and rot90)
         a('--elastic', type=float, default=None, nargs=2, metavar=('G', 'SIGMA'),
           help='image-folder feeders: deform every training crop by a smooth random field -- (G + 3)^2 displacement vectors drawn from '

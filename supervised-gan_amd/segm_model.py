@@ -17,8 +17,8 @@ import torch
 
 from . import networks, ops, util
 from .cgan_model import CGANModel
-from .losses import (ClDiceBuffers, LovaszBuffers, class_probability_plane, cross_entropy_logits, lovasz_softmax, seg_head, sigmoid_channels,
-                     soft_cldice, softmax_channels, weighted_bce)
+from .losses import (ClDiceBuffers, LovaszBuffers, SegTermsBuffers, class_probability_plane, cross_entropy_logits, lovasz_softmax, seg_head,
+                     seg_terms, sigmoid_channels, soft_cldice, softmax_channels, weighted_bce)
 from .options import check_tile_options
 from .seg_metrics import SegMetrics, SegMetricsMixin
 
@@ -68,6 +68,18 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
             self.lovasz = (float(opt.lovasz_weight), classes)
             self._lov_bufs = None      # persistent: the node's buffers
             self.loss_G_Lovasz = 0
+        self.segterms = None      # (lambda_dice, classes, a, b, s, E, lambda_focal, gamma) of the Tversky / focal terms, or None: nothing runs
+        if self.isTrain and (getattr(opt, 'dice_weight', 0.0) > 0.0 or getattr(opt, 'focal_weight', 0.0) > 0.0):
+            lam_d, lam_f = float(getattr(opt, 'dice_weight', 0.0)), float(getattr(opt, 'focal_weight', 0.0))
+            classes = tuple(int(c) for c in opt.dice_classes) if lam_d > 0.0 else ()
+            assert all(c < self.num_classes for c in classes), "--dice_classes %s: there are %d classes" % (list(classes), self.num_classes)
+            assert opt.batchSize == 1 and self.device.type == 'cuda', "--dice_weight / --focal_weight: batch 1 on the device, like every kernel of this path"
+            assert lam_f == 0.0 or opt.weights is None or self.use_sigmoid_ss or len(opt.weights) == self.num_classes, \
+                "--focal_weight with --weights: one per class (%d) for the softmax head" % self.num_classes
+            self.segterms = (lam_d, classes, float(opt.tversky[0]), float(opt.tversky[1]), float(opt.dice_smooth), float(opt.tversky_power),
+                             lam_f, float(opt.focal_gamma) if lam_f > 0.0 else None)
+            self._st_bufs = None      # persistent: the node's buffers
+            self.loss_G_Dice = self.loss_G_Focal = 0
         self.seg_metrics = SegMetrics(opt, self.device, self.num_classes)
         self.reset_accs()
         self._tiling = not self.isTrain and getattr(opt, 'tiling', False)      # test(): whole-image inference (check_tile_options)
@@ -150,6 +162,28 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
             self._lov_bufs = LovaszBuffers(*shape, len(classes), p.device)
         self.loss_G_Lovasz = lovasz_softmax(p, self.label[0], classes, buffers=self._lov_bufs)
         return loss + lam * self.loss_G_Lovasz
+
+    def _with_seg_terms(self, loss):
+        """loss + lambda_dice * Tversky + lambda_focal * focal; the loss unchanged with both options off.  The node reads the logits
+        of the last forward() whether discriminators exist or not and hands the gradient of the logits back: it needs no prediction
+        and no softmax of its own.  A term whose weight is 0 is switched off in the call and takes no gradient."""
+        if self.segterms is None:
+            return loss
+        lam_d, classes, a, b, s, E, lam_f, gamma = self.segterms
+        shape = tuple(self.logit.shape[1:])
+        if self._st_bufs is None or not self._st_bufs.fits(*shape, self.logit.device):
+            self._st_bufs = SegTermsBuffers(*shape, self.logit.device)
+        if self.use_sigmoid_ss:
+            mode, lt = ops.SEGHEAD_SIGMOID, self.real_B
+        else:
+            mode, lt = ops.SEGHEAD_SOFTMAX, self.label
+        self.loss_G_Dice, self.loss_G_Focal = seg_terms(self.logit, lt, mode, classes, a, b, s, E, gamma, self.class_weights,
+                                                        buffers=self._st_bufs)
+        if lam_d > 0.0:
+            loss = loss + lam_d * self.loss_G_Dice
+        if lam_f > 0.0:
+            loss = loss + lam_f * self.loss_G_Focal
+        return loss
 
     def _border_weight_map(self):
         """The U-Net border term of the current label into self.bmap: the pixels of --border_class are the wall, its complement is
@@ -265,7 +299,7 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
         if self.no_netD:      # :202-203,227: loss_G_GAN = 0, the cross-entropy forward() left behind is the whole loss
             self.loss_G_GAN = 0
             self.loss_G_CE = self._head_loss
-            self.loss_G = self._with_lovasz(self._with_cldice(self.loss_G_CE))
+            self.loss_G = self._with_seg_terms(self._with_lovasz(self._with_cldice(self.loss_G_CE)))
             self._backward(self.loss_G)
             return
         skip = getattr(self.opt, 'skip_wasted_D_wgrad', False)
@@ -276,13 +310,18 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
         self.loss_G_GAN, self._each_G = self._d_losses([(d, fake, True) for d in self.netD], list(self.opt.lambda_D))
         for netD in self.netD:
             netD.compute_param_grads = True
-        self.loss_G = self._with_lovasz(self._with_cldice(self.loss_G_GAN + self.compute_cross_entropy_loss(weighted=True)))
+        self.loss_G = self._with_seg_terms(self._with_lovasz(self._with_cldice(self.loss_G_GAN + self.compute_cross_entropy_loss(weighted=True))))
         self._backward(self.loss_G)
 
     def get_current_errors(self):
         extra = [('G_clDice', float(self.loss_G_clDice.detach() if torch.is_tensor(self.loss_G_clDice) else 0.0))] if self.cldice is not None else []
         if self.lovasz is not None:
             extra = extra + [('G_Lovasz', float(self.loss_G_Lovasz.detach() if torch.is_tensor(self.loss_G_Lovasz) else 0.0))]
+        if self.segterms is not None:
+            if self.segterms[0] > 0.0:
+                extra = extra + [('G_Dice', float(self.loss_G_Dice.detach() if torch.is_tensor(self.loss_G_Dice) else 0.0))]
+            if self.segterms[6] > 0.0:
+                extra = extra + [('G_Focal', float(self.loss_G_Focal.detach() if torch.is_tensor(self.loss_G_Focal) else 0.0))]
         if self.no_netD:                                     # :253-257
             return OrderedDict([('G_CE', float(self.loss_G_CE.detach()))] + extra)
         return OrderedDict([('G_CE', float(self.loss_G_CE.detach())), ('G_GAN', float(self.loss_G_GAN.detach())),

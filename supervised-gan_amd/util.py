@@ -1288,3 +1288,100 @@ def lovasz_ref(P, label, classes):
     L = float(Lc.sum() / m) if m else 0.0
     dP = dP.reshape(C, H, W)
     return L, dP, perm, g, Lc, np.abs(dP)
+
+
+def seg_terms_ref(logits, label_or_target, mode, classes=(), alpha=0.5, beta=0.5, smooth=1.0, power=1.0, focal_gamma=None,
+                  class_weights=None):
+    """The Tversky (soft Dice, focal-Tversky) and focal loss terms on the logits in NumPy fp64, in the semantics of
+    include/sgan_hip.h, "Segmentation loss terms": (L_T, L_F, state [68], dz_T [npix, C], dz_F [npix, C]).
+
+    logits [npix, C] (read as fp32); mode 0 (softmax): label_or_target the integer label [npix], p = softmax(z), t_c = [y == c], a
+    pixel with a label outside [0, C) takes no part; mode 1 (sigmoid): the target [npix, C] in [0, 1], p = sigmoid(z).
+    Tversky over the n listed classes (none: term off, L_T = 0): TP = sum p t, FP = sum p (1 - t), FN = sum (1 - p) t,
+    D = TP + alpha FP + beta FN + smooth, TI = (TP + smooth) / D, L_c = (1 - TI)^power, L_T = mean over n; D == 0: L_c = 0, no
+    gradient; 1 - TI == 0: derivative 0; G_c(t) = -(power / n) (1 - TI)^(power - 1) [t / D - (TP + smooth) (t (1 - beta) +
+    alpha (1 - t)) / D^2]; softmax dz_k = p_k (G'_k - sum_j p_j G'_j), sigmoid dz_c = p_c (1 - p_c) G_c(t_c).
+    Focal (focal_gamma None: off, L_F = 0), class weights w (None: 1): softmax, lp = z_y - logsumexp(z), pt = exp(lp):
+    L_F = sum w[y] (1 - pt)^gamma (-lp) / sum w[y], dz_k = w[y] / norm [gamma pt (1 - pt)^(gamma - 1) lp - (1 - pt)^gamma]
+    (delta_ky - p_k), the first product left out where gamma == 0 or 1 - pt == 0; sigmoid: L_F = sum w_c [t (1 - p)^gamma
+    softplus(-z) + (1 - t) p^gamma softplus(z)] / (C npix) and its analytic derivative.
+    state: [8 j + 0 .. 7] TP, FP, FN, D, TI, L_c, G_c(0), G_c(1) of listed class j; [64] focal numerator, [65] norm, [66] L_T, [67] L_F."""
+    z = np.asarray(logits, dtype=np.float32).astype(np.float64)
+    assert z.ndim == 2, z.shape
+    npix, C = z.shape
+    classes = [int(c) for c in classes]
+    n = len(classes)
+    assert n <= 8 and len(set(classes)) == n and all(0 <= c < C for c in classes), classes
+    softmax = int(mode) == 0
+    state = np.zeros(68, np.float64)
+    dzT, dzF = np.zeros((npix, C), np.float64), np.zeros((npix, C), np.float64)
+    if softmax:
+        y = np.asarray(label_or_target).reshape(npix).astype(np.int64)
+        ok = (y >= 0) & (y < C)
+        ys = np.where(ok, y, 0)
+        m = z.max(axis=1, keepdims=True)
+        lse = m[:, 0] + np.log(np.exp(z - m).sum(axis=1))
+        p = np.exp(z - lse[:, None])
+        t = np.zeros((npix, C), np.float64)
+        t[np.arange(npix)[ok], y[ok]] = 1.0
+        valid = ok.astype(np.float64)[:, None]
+    else:
+        t = np.asarray(label_or_target, dtype=np.float32).astype(np.float64).reshape(npix, C)
+        p = 1.0 / (1.0 + np.exp(-z))
+        q = 1.0 / (1.0 + np.exp(z))      # 1 - p
+        valid = np.ones((npix, 1), np.float64)
+    LT = 0.0
+    Gp = np.zeros((npix, C), np.float64)      # G'_c per pixel, zero on unlisted channels
+    for j, c in enumerate(classes):
+        pc, tc, v = p[:, c], t[:, c], valid[:, 0]
+        TP = float(np.sum(pc * tc * v))
+        FP = float(np.sum(pc * (1.0 - tc) * v))
+        FN = float(np.sum((1.0 - pc) * tc * v))
+        D = ((TP + alpha * FP) + beta * FN) + smooth
+        TI = Lc = G0 = G1 = 0.0
+        if D > 0.0:
+            num = TP + smooth
+            TI = num / D
+            u = max(1.0 - TI, 0.0)
+            if u > 0.0:
+                Lc = u ** power
+                k = -(power / n) * u ** (power - 1.0)
+                G0 = k * (-(num * alpha) / (D * D))
+                G1 = k * (1.0 / D - (num * (1.0 - beta)) / (D * D))
+        state[8 * j:8 * j + 8] = (TP, FP, FN, D, TI, Lc, G0, G1)
+        LT += Lc
+        Gp[:, c] = G0 + tc * (G1 - G0)
+    if n:
+        LT /= n
+        if softmax:
+            dzT = p * (Gp - np.sum(p * Gp, axis=1, keepdims=True)) * valid
+        else:
+            dzT = p * q * Gp
+    LF = 0.0
+    if focal_gamma is not None:
+        g = float(focal_gamma)
+        w = np.ones(C, np.float64)
+        if class_weights is not None:
+            cw = np.asarray(class_weights, dtype=np.float32).astype(np.float64).reshape(-1)
+            w[:min(C, cw.size)] = cw[:C]
+        if softmax:
+            lp = z[np.arange(npix), ys] - lse
+            pt = np.exp(lp)
+            om = -np.expm1(lp)      # 1 - pt
+            wy = w[ys] * ok
+            num, norm = float(np.sum(wy * om ** g * -lp)), float(np.sum(wy))
+            k = -(om ** g)
+            if g != 0.0:
+                nz = om != 0.0
+                k = k + np.where(nz, g * pt * np.where(nz, om, 1.0) ** (g - 1.0) * lp, 0.0)
+            if norm > 0.0:
+                dzF = (wy / norm * k)[:, None] * (t - p) * valid
+        else:
+            spn = np.maximum(-z, 0.0) + np.log1p(np.exp(-np.abs(z)))      # softplus(-z)
+            spp = np.maximum(z, 0.0) + np.log1p(np.exp(-np.abs(z)))       # softplus(z)
+            num, norm = float(np.sum(w * (t * q ** g * spn + (1.0 - t) * p ** g * spp))), float(C) * float(npix)
+            dzF = w / norm * ((1.0 - t) * p ** g * (g * q * spp + p) - t * q ** g * (g * p * spn + q))
+        LF = num / norm if norm > 0.0 else 0.0
+        state[64], state[65] = num, norm
+    state[66], state[67] = LT, LF
+    return LT, LF, state, dzT, dzF
