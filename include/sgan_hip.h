@@ -422,6 +422,7 @@ int sgan_gauss_down_multi_bwd(const sgan_gauss_job* jobs, int32_t n, int32_t C, 
 /* ---- GAN loss on a logits map (channel 0 of an NHWC-4 tensor) --------------------------------
  * mode 0: BCE(sigmoid(x), t) with torch's log clamp at -100 (GANLoss, --no_lsgan);
  * mode 1: MSE(x, t) (lsgan, no sigmoid).  loss_out[0] = mean loss; p_out (optional) = sigmoid(x).
+ * p_out shares `ld` with the logits: p_out[i * ld] is written, so it is a map of the logits' own pixel stride.
  * The backward writes dlogits[p][0] = gout[0] * dloss/dx, other stored channels 0.
  * Replaces: nn.Sigmoid (models/networks.py:836-837) + nn.BCELoss / nn.MSELoss inside GANLoss
  * (models/networks.py:160-163,183-185). */

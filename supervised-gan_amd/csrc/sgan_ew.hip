@@ -623,8 +623,9 @@ __global__ __launch_bounds__(256) void sg_ce_fwd_kernel(const float* logits, int
     for (int p = blockIdx.x * 256 + threadIdx.x; p < npix; p += gridDim.x * 256) {
         float zs[SG_CE_MAXC];
         const float lse = sg_ce_lse(logits + (int64_t)p * ld, C, zs);
-        int y = label ? (int)label[p] : const_label;
-        if (y < 0 || y >= C) continue;      // torch's ignore_index (-100) and anything out of range: no contribution
+        const int64_t y64 = label ? label[p] : (int64_t)const_label;
+        if (y64 < 0 || y64 >= C) continue;  // torch's ignore_index (-100) and anything out of range, judged in 64 bits: no contribution
+        const int y = (int)y64;
         const float w = class_w ? class_w[y] : 1.f;
         float zy = 0.f;
         for (int c = 0; c < C; ++c) zy = c == y ? zs[c] : zy;
@@ -657,8 +658,9 @@ __global__ __launch_bounds__(256) void sg_ce_bwd_kernel(const float* logits, int
     for (int p = blockIdx.x * 256 + threadIdx.x; p < npix; p += gridDim.x * 256) {
         float zs[SG_CE_MAXC];
         const float lse = sg_ce_lse(logits + (int64_t)p * ld, C, zs);
-        const int y = label ? (int)label[p] : const_label;
-        const bool ok = y >= 0 && y < C;
+        const int64_t y64 = label ? label[p] : (int64_t)const_label;
+        const bool ok = y64 >= 0 && y64 < C;      // in 64 bits, before the label is narrowed
+        const int y = ok ? (int)y64 : -1;
         const float w = ok ? (class_w ? class_w[y] : 1.f) * scale : 0.f;
         for (int c = 0; c < dld; ++c) dlogits[(int64_t)p * dld + c] = c < C ? w * (expf(zs[c] - lse) - (c == y ? 1.f : 0.f)) : 0.f;
     }
@@ -672,6 +674,7 @@ extern "C" int sgan_ce_fwd(const float* logits, int32_t ld, int32_t npix, int32_
     hipLaunchKernelGGL(sg_ce_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, logits, ld, npix, C, label, const_label, class_w, acc,
                        ticket, loss_out);
     SGAN_LAUNCH_CHECK();
+    g_sgan_last_kernel = "sg_ce_fwd_kernel";      // tests/test_hip_loss_kernels.py: the wrapper's in-envelope path ends here
     return SGAN_OK;
 }
 
@@ -708,6 +711,7 @@ extern "C" int sgan_softmax_fwd(const float* z, int32_t ld, int32_t npix, int32_
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(sg_softmax_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, z, ld, npix, C, p, pld);
     SGAN_LAUNCH_CHECK();
+    g_sgan_last_kernel = "sg_softmax_fwd_kernel";
     return SGAN_OK;
 }
 extern "C" int sgan_softmax_bwd(const float* dp, int32_t dpld, const float* p, int32_t pld, int32_t npix, int32_t C, float* dz, int32_t dzld,

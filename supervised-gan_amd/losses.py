@@ -263,8 +263,24 @@ class _CEFn(torch.autograd.Function):
 
 def cross_entropy_logits(logits, label=None, const_label=0, class_weights=None):
     """nn.CrossEntropyLoss(weight=class_weights)(logits, label) for a [1, C, H, W] map on the HIP kernel (C <= 16, batch 1); `label`
-    None: every pixel has class `const_label`."""
-    assert logits.dim() == 4 and logits.shape[0] == 1 and logits.shape[1] <= 16, logits.shape
+    None: every pixel has class `const_label`.  The kernel reads an int64 map: a label map of any other integer type is converted,
+    one on another device than the logits raises ValueError.  Anything outside the kernel's envelope (a batch, C > 16, not fp32 on
+    the device) goes to F.cross_entropy, like sigmoid_channels.  On both paths a label outside [0, C) is skipped like torch's
+    ignore_index -100 (the kernels skip it; in front of F.cross_entropy, which would raise, it is set to -100), and a map that
+    is skipped entirely gives 0 with an all-zero gradient."""
+    if label is not None:
+        if label.device != logits.device:
+            raise ValueError(f"cross_entropy_logits: the label map is on {label.device}, the logits are on {logits.device}")
+        if label.dtype != torch.int64:
+            label = label.long()
+    if not _bce_envelope(logits):
+        if label is None:
+            label = torch.full((logits.shape[0],) + tuple(logits.shape[2:]), int(const_label), dtype=torch.int64, device=logits.device)
+        label = torch.where((label < 0) | (label >= logits.shape[1]), torch.full_like(label, -100), label)
+        if not bool((label >= 0).any()):      # every pixel skipped: 0 with an all-zero gradient, as the kernel has it (torch: nan)
+            return logits.sum() * 0.0
+        cw = class_weights.detach().to(logits.dtype) if class_weights is not None else None
+        return F.cross_entropy(logits, label, weight=cw, ignore_index=-100)
     cw = class_weights.detach().float().contiguous() if class_weights is not None else None
     return _CEFn.apply(logits, label, int(const_label), cw)
 
@@ -287,8 +303,9 @@ class _SoftmaxFn(torch.autograd.Function):
 
 def softmax_channels(logits):
     """F.softmax(logits, dim=1) of a [1, C, H, W] map on the HIP kernel (the result is NHWC-backed: the discriminators read it with
-    no layout copy)."""
-    assert logits.dim() == 4 and logits.shape[0] == 1 and logits.shape[1] <= 16, logits.shape
+    no layout copy).  Anything else (a batch, C > 16, not fp32 on the device) goes to F.softmax, like sigmoid_channels."""
+    if not _bce_envelope(logits):
+        return F.softmax(logits, dim=1)
     return _SoftmaxFn.apply(logits)
 
 

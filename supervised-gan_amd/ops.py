@@ -750,7 +750,11 @@ def gauss_down_multi_bwd(jobs, Creal, accumulate=False):
 
 
 def gan_loss_fwd(logits, target, mode, loss_out, p_out=None):
+    """p_out (optional, mode 0): sigmoid(logits) in channel 0 of a map that shares the logits' shape and pixel stride -- the kernel
+    addresses it with the logits' leading dimension."""
     H, W, _ = logits.shape
+    assert p_out is None or (p_out.dtype == torch.float32 and p_out.shape == logits.shape and p_out.stride(1) == logits.stride(1)), \
+        (None if p_out is None else (p_out.dtype, tuple(p_out.shape), p_out.stride()), tuple(logits.shape), logits.stride())
     L.check(L.lib().sgan_gan_loss_fwd(_ptr(_act(logits)), logits.stride(1), H * W, float(target), mode, _ptr(loss_out),
                                       _ptr(p_out), _stream()), "sgan_gan_loss_fwd")
 
