@@ -358,9 +358,12 @@ class _WeightedBceFn(torch.autograd.Function):
 def weighted_bce(p, t, class_weights=None):
     """F.binary_cross_entropy(p, t, weight=wm) with the weight map wm = 1 + sum_i t[:, i] * (class_weights[i] - 1) of the
     segmentation trainers (models/segm_model.py:216-225) on the HIP kernel; class_weights None: unweighted.  `t` is a constant.
-    Outside the kernel's envelope (a batch, C > 16, not fp32 on the device) the torch calls run."""
+    Outside the kernel's envelope (a batch, C > 16, not fp32 on the device) the torch calls run.  class_weights on another device
+    than p raise ValueError, as a label map does in cross_entropy_logits: the kernel would read a host pointer."""
     t = t.detach()
     nw = 0 if class_weights is None else int(class_weights.numel())
+    if nw and class_weights.device != p.device:
+        raise ValueError(f"weighted_bce: class_weights are on {class_weights.device}, p is on {p.device}")
     if not (_bce_envelope(p) and _bce_envelope(t) and p.shape == t.shape and nw <= p.shape[1]):
         wm = None
         if nw:

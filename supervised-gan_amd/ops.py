@@ -867,13 +867,39 @@ def factd_loss_multi_bwd(l1s, l2s, ups, targets, weights, mode, gout, dl1s, dl2s
     L.check(L.lib().sgan_factd_loss_multi_bwd(arr, len(l1s), int(mode), _ptr(gout), _stream()), "sgan_factd_loss_multi_bwd")
 
 
+def _rows_fit(name, npix, Creal, t, what, written):
+    """The check of seg_head's rows_fit for the `--use_sigmoid_ss` kernels, which move scalars: an operand holds `npix` pixels of at
+    least Creal channels, and its last row -- the Creal channels a kernel reads, the whole stored row (pixel stride) where it
+    writes, padding channels included -- ends inside the storage.  Raised before anything is launched."""
+    _act(t)
+    require_gpu(t, name)
+    row = t.stride(1) if written else Creal
+    if t.shape[0] * t.shape[1] != npix or t.shape[2] < Creal or t.stride(1) < Creal or (npix - 1) * t.stride(1) + row > _avail(t):
+        raise L.SganError(f"{name} {what}: tensor {tuple(t.shape)} (pixel stride {t.stride(1)}, {_avail(t)} elements of storage) does "
+                          f"not hold {npix} rows of {row}; nothing was launched")
+
+
+def _class_w_fits(name, class_w, nw, device):
+    """0 <= nw <= 16 weights are read from a contiguous fp32 vector on the operands' device."""
+    if not 0 <= int(nw) <= 16 or (nw and (class_w is None or class_w.dtype != torch.float32 or not class_w.is_contiguous()
+                                         or class_w.device != device or class_w.numel() < nw)):
+        raise L.SganError(f"{name} class_w: {nw} weights need a contiguous float32 vector of at least as many entries on {device}; got "
+                          f"{None if class_w is None else (class_w.dtype, tuple(class_w.shape), class_w.stride(), class_w.device)}; "
+                          "nothing was launched")
+
+
 def sigmoid_nhwc_fwd(z, Creal, p):
     H, W, _ = z.shape
+    _rows_fit("sigmoid_nhwc_fwd", H * W, Creal, z, "logits", False)
+    _rows_fit("sigmoid_nhwc_fwd", H * W, Creal, p, "p", True)
     L.check(L.lib().sgan_sigmoid_nhwc_fwd(_ptr(_act(z)), z.stride(1), H * W, Creal, _ptr(_act(p)), p.stride(1), _stream()), "sgan_sigmoid_nhwc_fwd")
 
 
 def sigmoid_nhwc_bwd(dp, p, Creal, dz):
     H, W, _ = p.shape
+    _rows_fit("sigmoid_nhwc_bwd", H * W, Creal, p, "p", False)
+    _rows_fit("sigmoid_nhwc_bwd", H * W, Creal, dp, "dp", False)
+    _rows_fit("sigmoid_nhwc_bwd", H * W, Creal, dz, "dz", True)
     L.check(L.lib().sgan_sigmoid_nhwc_bwd(_ptr(_act(dp)), dp.stride(1), _ptr(_act(p)), p.stride(1), H * W, Creal, _ptr(_act(dz)),
                                           dz.stride(1), _stream()), "sgan_sigmoid_nhwc_bwd")
 
@@ -882,9 +908,13 @@ BCE_WEIGHTED_WS_BYTES = 1024   # SGAN_BCE_WEIGHTED_WS_BYTES
 
 
 def bce_weighted_fwd(p, t, Creal, class_w, nw, loss_out):
-    """Weighted BCE of two [H, W, Cs] buffers (sgan_bce_weighted_fwd); class_w: device float vector of >= nw entries, or None."""
+    """Weighted BCE of two [H, W, Cs] buffers (sgan_bce_weighted_fwd); class_w: contiguous float32 vector of >= nw entries on p's
+    device, or None.  Every operand is checked against its storage here, before anything is launched."""
     H, W, _ = p.shape
-    assert t.shape[:2] == (H, W) and (nw == 0 or class_w.numel() >= nw)
+    _rows_fit("bce_weighted_fwd", H * W, Creal, p, "p", False)
+    _rows_fit("bce_weighted_fwd", H * W, max(Creal, nw), t, "t", False)
+    _class_w_fits("bce_weighted_fwd", class_w, nw, p.device)
+    assert loss_out.dtype == torch.float32 and loss_out.numel() == 1 and loss_out.device == p.device
     ws = _zeroed_workspace("bce_weighted", p.device, BCE_WEIGHTED_WS_BYTES)
     L.check(L.lib().sgan_bce_weighted_fwd(_ptr(_act(p)), p.stride(1), _ptr(_act(t)), t.stride(1), H * W, Creal, _ptr(class_w), int(nw),
                                           _ptr(loss_out), _ptr(ws), BCE_WEIGHTED_WS_BYTES, _stream()), "sgan_bce_weighted_fwd")
@@ -892,7 +922,11 @@ def bce_weighted_fwd(p, t, Creal, class_w, nw, loss_out):
 
 def bce_weighted_bwd(p, t, Creal, class_w, nw, gout, dp):
     H, W, _ = p.shape
-    assert t.shape[:2] == (H, W) and dp.shape[:2] == (H, W)
+    _rows_fit("bce_weighted_bwd", H * W, Creal, p, "p", False)
+    _rows_fit("bce_weighted_bwd", H * W, max(Creal, nw), t, "t", False)
+    _rows_fit("bce_weighted_bwd", H * W, Creal, dp, "dp", True)
+    _class_w_fits("bce_weighted_bwd", class_w, nw, p.device)
+    assert gout.dtype == torch.float32 and gout.numel() == 1 and gout.device == p.device
     L.check(L.lib().sgan_bce_weighted_bwd(_ptr(_act(p)), p.stride(1), _ptr(_act(t)), t.stride(1), H * W, Creal, _ptr(class_w), int(nw),
                                           _ptr(gout), _ptr(_act(dp)), dp.stride(1), _stream()), "sgan_bce_weighted_bwd")
 
