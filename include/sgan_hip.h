@@ -63,6 +63,10 @@ typedef struct sgan_norm_desc {
     int32_t rep_stride;  /* 0: one copy of the statistics.  > 0: SGAN_STAT_REPLICAS copies, `rep_stride` doubles apart, whose SUM
                           * is the statistic: the producers spread their same-address fp64 atomics over the copies (workgroup b adds
                           * to copy b % SGAN_STAT_REPLICAS), every reader adds the copies up.  All copies start at zero. */
+    const float* mean_rstd; /* [2*C] interleaved (mean_c, rstd_c), or NULL.  The finalised form of `stats` (sgan_norm_finalise_job): a kernel
+                          * that finds it loads the pair of its channel instead of deriving it from the fp64 sums -- the same floats, bit for
+                          * bit.  `stats` must still be given (it says that the tensor is normalised); sq_stride / rep_stride are not
+                          * looked at by a reader of the table.  Only for statistics that are final: the backward pass of a training step */
 } sgan_norm_desc;
 #define SGAN_STAT_REPLICAS 8
 
@@ -450,6 +454,26 @@ typedef struct sgan_gan_loss_job {
 int sgan_gan_loss_multi_fwd(const sgan_gan_loss_job* jobs, int32_t n, int32_t mode, float* each_out, float* total_out,
                             void* workspace, int64_t workspace_bytes, void* stream);
 int sgan_gan_loss_multi_bwd(const sgan_gan_loss_job* jobs, int32_t n, int32_t mode, const float* gout, void* stream);
+
+/* ---- finalised normalisation statistics (sgan_norm_desc.mean_rstd) ----------------------------------------------------
+ * One job turns the fp64 (sum, sum of squares) of one tensor -- `sq_stride` and `rep_stride` as in sgan_norm_desc -- into
+ * mean_rstd[2 c] = mean_c, mean_rstd[2 c + 1] = rstd_c (2*C floats, 8-byte aligned) with the expression every kernel uses on
+ * load: entry c holds, bit for bit, what a kernel reading `stats` derives for channel c.
+ * sgan_gan_loss_multi_fwd_fin is sgan_gan_loss_multi_fwd with up to SGAN_NORM_FIN_MAX such jobs carried by extra workgroups of
+ * the SAME launch: the loss of a pass runs after the last forward launch of the pass and before its first backward launch, the
+ * one place where the statistics are final and not yet read again.  The statistics must be complete when the launch starts
+ * (stream order).  nfin == 0 is sgan_gan_loss_multi_fwd.
+ * sgan_norm_mean_rstd_probe (diagnostics, tests): out[2 c], out[2 c + 1] = what a kernel reading tensor `d` derives for channel c
+ * (one workgroup; from `d->mean_rstd` when that is given, else from `d->stats`). */
+typedef struct sgan_norm_finalise_job {
+    const double* stats; int32_t C; int32_t count; float eps; int32_t sq_stride; int32_t rep_stride;
+    float* mean_rstd;
+} sgan_norm_finalise_job;
+#define SGAN_NORM_FIN_MAX 48
+int sgan_gan_loss_multi_fwd_fin(const sgan_gan_loss_job* jobs, int32_t n, int32_t mode, float* each_out, float* total_out,
+                                void* workspace, int64_t workspace_bytes, const sgan_norm_finalise_job* fin, int32_t nfin,
+                                void* stream);
+int sgan_norm_mean_rstd_probe(const sgan_norm_desc* d, int32_t C, float* out, void* stream);
 
 /* ---- every factored-discriminator GAN-loss term of one backward pass at once -----------------------------
  * Term i multiplies two discriminator maps before the criterion (models/twostage_factD_model.py:256-296,352-383, util.mul):

@@ -17,7 +17,12 @@ CONV, CONVT = 0, 1
 class NormDesc(C.Structure):
     _fields_ = [("stats", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
                 ("count", C.c_int32), ("eps", C.c_float), ("act", C.c_int32), ("slope", C.c_float), ("sq_stride", C.c_int32),
-                ("rep_stride", C.c_int32)]
+                ("rep_stride", C.c_int32), ("mean_rstd", C.c_void_p)]
+
+
+class NormFinaliseJob(C.Structure):
+    _fields_ = [("stats", C.c_void_p), ("C", C.c_int32), ("count", C.c_int32), ("eps", C.c_float), ("sq_stride", C.c_int32),
+                ("rep_stride", C.c_int32), ("mean_rstd", C.c_void_p)]
 
 
 class ConvDesc(C.Structure):
@@ -135,6 +140,8 @@ SIGNATURES = {
     "sgan_gan_loss_bwd": [_P, _I, _I, _F, _I, _P, _P, _I, _P],
     "sgan_gan_loss_multi_fwd": [C.POINTER(GanLossJob), _I, _I, _P, _P, _P, C.c_int64, _P],
     "sgan_gan_loss_multi_bwd": [C.POINTER(GanLossJob), _I, _I, _P, _P],
+    "sgan_gan_loss_multi_fwd_fin": [C.POINTER(GanLossJob), _I, _I, _P, _P, _P, C.c_int64, C.POINTER(NormFinaliseJob), _I, _P],
+    "sgan_norm_mean_rstd_probe": [C.POINTER(NormDesc), _I, _P, _P],
     "sgan_factd_loss_multi_fwd": [C.POINTER(FactdLossJob), _I, _I, _P, _P, _P, C.c_int64, _P],
     "sgan_factd_loss_multi_bwd": [C.POINTER(FactdLossJob), _I, _I, _P, _P],
     "sgan_sigmoid_fwd": [_P, _I, _I, _P, _I, _P],

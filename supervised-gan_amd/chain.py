@@ -79,6 +79,8 @@ class _BwdArena:
         self.buf, self.dev = buf, (buf.device if buf is not None else dev)      # buf None: every backward takes its sums from the step's pool
         self.rep = rep           # replica stride of the forward statistics AND of `buf` (they share one ops.stat_arena)
         self.rep_bwd = rep       # replica stride of what take() handed out last
+        self.norm_tables = None  # {stats.data_ptr(): float[2 C] (mean, rstd)} once a loss launch has finalised this forward's statistics
+                                 # (ops.norm_tables_register); None: the backward kernels derive them from the fp64 sums
 
     def take(self, n):
         buf, self.buf = self.buf, None
@@ -376,17 +378,31 @@ class ChainNet(nn.Module):
         b = self._gflat[L.b_off: L.b_off + L.cout_s] if L.bias else None
         return w, b
 
-    def _norm_of(self, li, stats, count, drop=()):
+    def _norm_of(self, li, stats, count, drop=(), bwd=False):
         """How a consumer reads layer li's raw output: its norm (from `stats`) + activation.  li in drop: the consumer reads the
-        materialised dropout tensor of layer li instead, and only the activation is left to apply."""
+        materialised dropout tensor of layer li instead, and only the activation is left to apply.  bwd: the consumer is a backward
+        kernel -- the statistics are final, and where a loss launch has finalised them (stats[-1].norm_tables) it gets the table.
+        The forward consumers never do: the launch right before them has only just completed the sums."""
         L = self.layers[li]
         if L.norm is None or li in drop:
             return ops.norm_desc(None, None, None, count, 0.0, L.act, L.slope)
         st = stats[li]
         rep = getattr(stats[-1], "rep", 0)      # the statistics live in an ops.stat_arena (replicated sums)
+        table = None
+        if bwd:
+            table = (getattr(stats[-1], "norm_tables", None) or {}).get(st.data_ptr())
+            ops.NORM_TABLE_LOG["with_table" if table is not None else "without_table"] += 1
         if L.norm == "bn":
-            return ops.norm_desc(st, *self._bn_affine(L), count, BN_EPS, L.act, L.slope, 0, rep)
-        return ops.norm_desc(st, None, None, count, IN_EPS, L.act, L.slope, 0, rep)
+            return ops.norm_desc(st, *self._bn_affine(L), count, BN_EPS, L.act, L.slope, 0, rep, table)
+        return ops.norm_desc(st, None, None, count, IN_EPS, L.act, L.slope, 0, rep, table)
+
+    def _kept_table(self, n, device):
+        """Storage of the finalised (mean, rstd) tables of the KEPT forward: one allocation for as long as the kept buffers live, so
+        that a refill of those buffers (forward_pair) is finalised into the memory a captured backward reads."""
+        t = getattr(self, "_kept_tab", None)
+        if t is None or t.numel() != max(n, 1) or t.device != device:
+            t = self._kept_tab = torch.empty(max(n, 1), dtype=torch.float32, device=device)
+        return t
 
     # ---- forward / backward programs ----------------------------------------------------------
     def _kept_arena(self, n_stats, device, zeroed=False):
@@ -435,7 +451,7 @@ class ChainNet(nn.Module):
         drop[li] = (t, mask)
         return t, drawn
 
-    def run_forward(self, x: torch.Tensor, update_running=True, keep=False):
+    def run_forward(self, x: torch.Tensor, update_running=True, keep=False, tables=False):
         """x: [H, W, Cs] NHWC buffer.  Returns (outs, stats): raw conv outputs and per-layer stats.
         keep: remember this call's buffers as `self._kept` (input, outputs, statistics in an allocation of their own, backward sums
         taken from the pool at backward time) so that forward_pair() can later write another forward of this net into them."""
@@ -443,7 +459,8 @@ class ChainNet(nn.Module):
         if self._flat.device != x.device:
             raise SganError(f"module parameters are on {self._flat.device}, input on {x.device}")
         assert x.shape[2] == self.layers[0].cin_s, (x.shape[2], self.layers[0].cin_s)
-        outs, stats = _grouped_forward([self], [x], update_running=update_running, final_act=self._take_call_act(), keep=keep)
+        outs, stats = _grouped_forward([self], [x], update_running=update_running, final_act=self._take_call_act(), keep=keep,
+                                       tables=tables)
         return outs[0], stats[0]
 
     def run_backward(self, x, outs, stats, dout, need_dx: bool, want_wgrad: bool):
@@ -508,7 +525,10 @@ class _ChainFn(torch.autograd.Function):
     def forward(ctx, net: "ChainNet", x_logical, *params):
         xb = net._prepare_input(x_logical)
         keep, net._keep_next = getattr(net, "_keep_next", False), False      # one-shot: set by the caller right before forward()
-        outs, stats = net.run_forward(xb["chain_in"], keep=True) if keep else net.run_forward(xb["chain_in"])
+        kw = dict(keep=True) if keep else {}
+        if any(ctx.needs_input_grad) and type(net).run_forward is ChainNet.run_forward:
+            kw["tables"] = True      # a backward can follow: the next loss launch finalises this forward's statistics (plain chains)
+        outs, stats = net.run_forward(xb["chain_in"], **kw)
         ctx.net, ctx.xb, ctx.outs, ctx.stats = net, xb, outs, stats
         ctx.want_wgrad = net.compute_param_grads and any(ctx.needs_input_grad[2:])
         ctx.need_dx = ctx.needs_input_grad[1]
@@ -558,7 +578,7 @@ def forward_pair(net: "ChainNet", x_a, x_b, arena_zeroed=False):
     stats_b.append(_BwdArena(None, ops.stat_rep(arena), xb.device, net.final_act))
     kept["stats"], kept["final_act"] = stats_b, net.final_act
     with torch.no_grad():
-        outs, _ = _grouped_forward([net, net], [xa, xb], given=[None, (kept["outs"], stats_b)])
+        outs, _ = _grouped_forward([net, net], [xa, xb], given=[None, (kept["outs"], stats_b)], tables=True)
     ya = net._wrap_output(ops.logical_view(outs[0][-1], net.layers[-1].cout))
     yb = net._wrap_output(_AdoptFn.apply(net, x_b, *list(net.model.parameters())))
     return ya, yb
@@ -585,14 +605,16 @@ def _carve(layers, arena, base=0):
     return out
 
 
-def _grouped_forward(nets, xs, given=None, update_running=True, final_act=None, keep=False):
+def _grouped_forward(nets, xs, given=None, update_running=True, final_act=None, keep=False, tables=False):
     """The forward walk of every plain chain: nets[j] applied to xs[j] ([H,W,Cs] buffers), J >= 1 nets of one architecture; per layer
     ONE grouped launch.  Returns per-job (outs, stats); stats[j][-1] is the _BwdArena (backward sums, `final_act`, `drop`, strides).
     given[j] = (outs, stats) of job j supplied by the caller (forward_pair: the buffers of a kept forward, statistics zeroed), None = fresh.
     update_running=False: the BatchNorm running statistics are left alone (a train-mode forward does not read them; latent
     reconstruction runs thousands of forwards through a generator it must hand back unchanged).
     final_act: activation fused into the last layer (None: nets[0].final_act; a single chain passes its per-call value).
-    keep (one chain): the statistics live in the net's kept arena, not in the step's pool, and the call is recorded as net._kept."""
+    keep (one chain): the statistics live in the net's kept arena, not in the step's pool, and the call is recorded as net._kept.
+    tables: a backward pass of a training step can follow (the autograd nodes say so when an input needs a gradient; forward_pair for
+    the forward it refills): the normalised tensors are handed to the next loss launch to be finalised (_register_norm_tables)."""
     dev, J = xs[0].device, len(nets)
     given = given or [None] * J
     final_act = nets[0].final_act if final_act is None else final_act
@@ -636,7 +658,30 @@ def _grouped_forward(nets, xs, given=None, update_running=True, final_act=None, 
             ops.bn_running_update(net._bn_running_jobs(geos[j], stats[j]), BN_MOMENTUM)
     if keep:
         nets[0]._kept = dict(x=xs[0], outs=outs[0], stats=stats[0], n_stats=per_job, final_act=final_act)
+    if tables:
+        _register_norm_tables(nets, geos, stats, given, keep, per_job, dev)
     return outs, stats
+
+
+def _register_norm_tables(nets, geos, stats, given, keep, per_job, dev):
+    """Hand the normalised tensors of a training-mode forward to the next loss launch (ops.norm_tables_register): one finalise job
+    per tensor, grouped by the _BwdArena its backward will look the tables up in.  A refilled kept forward (given[j]) and a kept one
+    bring the net's own table storage; the no-grad companion of a refill (forward_pair's x_a) has no backward and no jobs."""
+    if ops.NO_NORM_TABLE or not all(n.training for n in nets):
+        return
+    refill = any(g is not None for g in given)
+    owners = {}
+    for j, net in enumerate(nets):
+        if refill and given[j] is None:
+            continue
+        own = stats[j][-1]
+        buf = net._kept_table(per_job, dev) if (keep or given[j] is not None) else None
+        fin = owners.setdefault(id(own), (own, [], buf))[1]
+        for li, L in enumerate(net.layers):
+            if L.norm:
+                fin.append((stats[j][li], L.cout_s, geos[j][li][3] * geos[j][li][4], BN_EPS if L.norm == "bn" else IN_EPS, 0, own.rep))
+    for own, fin, buf in owners.values():
+        ops.norm_tables_register(own, fin, buf)
 
 
 def _grouped_backward(nets, xs, outs, stats, douts, need_dx, want_wgrad, dx_out=None, final_act=None, single_chain=False):
@@ -674,14 +719,14 @@ def _grouped_backward(nets, xs, outs, stats, douts, need_dx, want_wgrad, dx_out=
             P, sm = net.layers[li - 1], sums[j][li - 1]
             drop = drops[j].get(li - 1)      # (t, mask): layer li read the materialised dropout tensor of layer li - 1
             src = drop[0] if drop else outs[j][li - 1]
-            norm = net._norm_of(li - 1, stats[j], h * w, drops[j])
+            norm = net._norm_of(li - 1, stats[j], h * w, drops[j], bwd=True)
             din = torch.empty((h, w, P.cout_s), dtype=torch.float32, device=dev)
             jobs.append((desc, dcur[j], net._wt(net.layers[li]), din, src, norm, None if drop else sm, 0, False, True, brep))
             if want_wgrad[j]:
                 wjobs.append((desc, src, norm, dcur[j]) + net._gwb(net.layers[li]))
             dg, db = net._bn_affine(P, grads=True) if (P.norm == "bn" and want_wgrad[j]) else (None, None)
             if drop:
-                masked.append((din, outs[j][li - 1], net._norm_of(li - 1, stats[j], h * w), sm, dg, db, drop[1]))
+                masked.append((din, outs[j][li - 1], net._norm_of(li - 1, stats[j], h * w, bwd=True), sm, dg, db, drop[1]))
             elif P.norm:
                 nb.append((din, src, norm, sm, dg, db, 0, brep))
             dins.append(din)
@@ -733,7 +778,7 @@ class _MultiChainFn(torch.autograd.Function):
                for net, x in zip(nets, xlog)]
         for creal in sorted({c for c, _ in gauss}):
             ops.gauss_down_multi_fwd([job for c, job in gauss if c == creal], creal)
-        outs, stats = _grouped_forward(nets, [xb["chain_in"] for xb in xbs])
+        outs, stats = _grouped_forward(nets, [xb["chain_in"] for xb in xbs], tables=any(ctx.needs_input_grad))
         ctx.nets, ctx.xbs, ctx.outs, ctx.stats = nets, xbs, outs, stats
         ctx.in_keys = [(x.data_ptr(), tuple(x.shape), tuple(x.stride())) for x in xlog]
         ctx.need_dx = [bool(ctx.needs_input_grad[1 + j]) for j in range(J)]

@@ -129,6 +129,7 @@ struct SgNorm {  // device-side copy of sgan_norm_desc
     float slope;
     int32_t sq_stride;  // 0 = C
     int32_t rep_stride; // 0 = one copy; else SGAN_STAT_REPLICAS copies this many doubles apart, summed on read
+    const float* mean_rstd;  // finalised (mean, rstd) pairs [2*C] (sgan_norm_desc.mean_rstd), or null: derive them from `stats`
 };
 
 static inline SgNorm sg_norm_from(const sgan_norm_desc* d) {
@@ -136,10 +137,10 @@ static inline SgNorm sg_norm_from(const sgan_norm_desc* d) {
     if (d) {
         n.stats = d->stats; n.gamma = d->gamma; n.beta = d->beta;
         n.count = d->count; n.eps = d->eps; n.act = d->act; n.slope = d->slope; n.sq_stride = d->sq_stride;
-        n.rep_stride = d->rep_stride;
+        n.rep_stride = d->rep_stride; n.mean_rstd = d->mean_rstd;
     } else {
         n.stats = nullptr; n.gamma = nullptr; n.beta = nullptr;
-        n.count = 1; n.eps = 0.f; n.act = SGAN_ACT_NONE; n.slope = 0.f; n.sq_stride = 0; n.rep_stride = 0;
+        n.count = 1; n.eps = 0.f; n.act = SGAN_ACT_NONE; n.slope = 0.f; n.sq_stride = 0; n.rep_stride = 0; n.mean_rstd = nullptr;
     }
     return n;
 }
@@ -165,14 +166,29 @@ __device__ __forceinline__ double* sg_stat_replica(double* base, int rep, unsign
     return base + (int64_t)(rep ? (b & (SGAN_STAT_REPLICAS - 1)) : 0) * rep;
 }
 
-__device__ __forceinline__ void sg_mean_rstd(const SgNorm& n, int C, int c, float& mean, float& rstd) {
-    double s = sg_stat_sum(n.stats, c, n.rep_stride), q = sg_stat_sum(n.stats, (n.sq_stride ? n.sq_stride : C) + c, n.rep_stride);
-    double inv = 1.0 / (double)n.count;
+// the one expression behind every (mean, rstd): the in-kernel path below and the producer of the finalised table
+// (sg_norm_finalise, sgan_ew.hip) both go through it, so a table entry holds the very floats a kernel would have derived
+__device__ __forceinline__ void sg_mean_rstd_sums(const double* stats, int C, int c, int count, float eps, int sq_stride, int rep_stride,
+                                                  float& mean, float& rstd) {
+    double s = sg_stat_sum(stats, c, rep_stride), q = sg_stat_sum(stats, (sq_stride ? sq_stride : C) + c, rep_stride);
+    double inv = 1.0 / (double)count;
     double m = s * inv;
     double var = q * inv - m * m;
     if (var < 0.0) var = 0.0;
     mean = (float)m;
-    rstd = (float)(1.0 / sqrt(var + (double)n.eps));
+    rstd = (float)(1.0 / sqrt(var + (double)eps));
+}
+
+// with a finalised table (backward kernels of a training step: the statistics were final long before) one 8-byte load per channel;
+// `sq_stride` and `rep_stride` describe `stats` only and are not looked at then
+__device__ __forceinline__ void sg_mean_rstd(const SgNorm& n, int C, int c, float& mean, float& rstd) {
+    if (n.mean_rstd) {
+        const f32x2 v = *reinterpret_cast<const f32x2*>(n.mean_rstd + 2 * c);
+        mean = v[0];
+        rstd = v[1];
+        return;
+    }
+    sg_mean_rstd_sums(n.stats, C, c, n.count, n.eps, n.sq_stride, n.rep_stride, mean, rstd);
 }
 
 // fp16 planes: scale 2^s that brings a tensor of maximum magnitude `amax` under 2^15 (s = 14 - floor(log2 amax)); 0 / denormal -> 1

@@ -220,6 +220,23 @@ extern "C" int sgan_norm_bwd_apply(float* dy, int32_t dy_ld, const float* x, int
     return sgan_norm_bwd_apply_multi(&j, 1, stream);
 }
 
+// what a kernel derives on load for every channel of a normalised tensor (diagnostics / tests: sgan_norm_mean_rstd_probe)
+__global__ __launch_bounds__(256) void sg_mean_rstd_probe_kernel(SgNorm n, int C, float* out) {
+    for (int c = threadIdx.x; c < C; c += 256) {
+        float mean, rstd;
+        sg_mean_rstd(n, C, c, mean, rstd);
+        out[2 * c] = mean;
+        out[2 * c + 1] = rstd;
+    }
+}
+
+extern "C" int sgan_norm_mean_rstd_probe(const sgan_norm_desc* d, int32_t C, float* out, void* stream) {
+    SGAN_CHECK(d && d->stats && out && C > 0 && d->count > 0, "bad argument");
+    hipLaunchKernelGGL(sg_mean_rstd_probe_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, sg_norm_from(d), C, out);
+    SGAN_LAUNCH_CHECK();
+    return SGAN_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // U-Net up path: normalise (+ dropout) (+ noise) into a concat slice; and the first backward pass
 // ------------------------------------------------------------------------------------------
@@ -1599,7 +1616,29 @@ struct SgLossMulti {
 // the trainers call backward() on).  The workgroup that arrives last at the counter behind `part` turns the partials into
 // each[] and the weighted total and leaves the counter at zero for the next call: one launch, no zero fill per call.
 #define SG_LOSS_BLOCKS 16
-__global__ __launch_bounds__(256) void sg_gan_loss_multi_fwd_kernel(SgLossMulti J, double* part, unsigned* counter, float* each, float* total) {
+
+// Finalise jobs riding in the loss launch (sgan_gan_loss_multi_fwd_fin): rows of the grid behind the J.n loss rows.  The loss of a
+// pass runs after every forward launch of that pass and before its first backward launch, so the statistics it reads are final;
+// each job turns one tensor's fp64 (sum, sum of squares) replicas into float (mean, rstd) pairs with sg_mean_rstd_sums -- the
+// expression the kernels themselves run -- and the backward kernels of the pass load those instead (sgan_norm_desc.mean_rstd).
+// One workgroup per job, a channel per thread; these workgroups take no part in the loss reduction or its ticket.
+struct SgFinJob { const double* stats; float* dst; int32_t C, count, sq_stride, rep_stride; float eps; int32_t pad_; };
+struct SgFinTable { int32_t n, pad_; SgFinJob j[SGAN_NORM_FIN_MAX]; };
+
+__global__ __launch_bounds__(256) void sg_gan_loss_multi_fwd_kernel(SgLossMulti J, double* part, unsigned* counter, float* each, float* total,
+                                                                    SgFinTable F) {
+    if ((int)blockIdx.y >= J.n) {
+        const int f = ((int)blockIdx.y - J.n) * SG_LOSS_BLOCKS + (int)blockIdx.x;
+        if (f >= F.n) return;
+        const SgFinJob& Q = F.j[f];
+        for (int c = threadIdx.x; c < Q.C; c += 256) {
+            float mean, rstd;
+            sg_mean_rstd_sums(Q.stats, Q.C, c, Q.count, Q.eps, Q.sq_stride, Q.rep_stride, mean, rstd);
+            f32x2 v = {mean, rstd};
+            *reinterpret_cast<f32x2*>(Q.dst + 2 * c) = v;
+        }
+        return;
+    }
     sg_warm_kernargs<(int)sizeof(SgLossMulti)>();      // sgan_common.h: the scalar-cache misses of the parameter block, taken together
     __shared__ double wsum[4];
     __shared__ int last;
@@ -1685,6 +1724,23 @@ static int sg_fill_loss(SgLossMulti& J, const sgan_gan_loss_job* jobs, int n, in
 
 extern "C" int sgan_gan_loss_multi_fwd(const sgan_gan_loss_job* jobs, int32_t n, int32_t mode, float* each_out,
                                        float* total_out, void* workspace, int64_t workspace_bytes, void* stream) {
+    return sgan_gan_loss_multi_fwd_fin(jobs, n, mode, each_out, total_out, workspace, workspace_bytes, nullptr, 0, stream);
+}
+
+extern "C" int sgan_gan_loss_multi_fwd_fin(const sgan_gan_loss_job* jobs, int32_t n, int32_t mode, float* each_out, float* total_out,
+                                           void* workspace, int64_t workspace_bytes, const sgan_norm_finalise_job* fin, int32_t nfin,
+                                           void* stream) {
+    SgFinTable F;
+    memset(&F, 0, sizeof(F));
+    SGAN_CHECK(nfin >= 0 && nfin <= SGAN_NORM_FIN_MAX && (fin || nfin == 0), "0..%d finalise jobs", SGAN_NORM_FIN_MAX);
+    F.n = nfin;
+    for (int i = 0; i < nfin; ++i) {
+        const sgan_norm_finalise_job& S = fin[i];
+        SGAN_CHECK(S.stats && S.mean_rstd && S.C > 0 && S.count > 0 && S.sq_stride >= 0 && S.rep_stride >= 0 && ((uintptr_t)S.mean_rstd & 7) == 0,
+                   "bad finalise job %d", i);
+        SgFinJob& Q = F.j[i];
+        Q.stats = S.stats; Q.dst = S.mean_rstd; Q.C = S.C; Q.count = S.count; Q.sq_stride = S.sq_stride; Q.rep_stride = S.rep_stride; Q.eps = S.eps;
+    }
     SgLossMulti J;
     int rc = sg_fill_loss(J, jobs, n, mode, false);
     if (rc) return rc;
@@ -1695,8 +1751,8 @@ extern "C" int sgan_gan_loss_multi_fwd(const sgan_gan_loss_job* jobs, int32_t n,
     static_assert((8 * SG_LOSS_BLOCKS + 1) * sizeof(double) <= SGAN_GAN_LOSS_WS_BYTES, "workspace size");
     double* part = static_cast<double*>(workspace);
     unsigned* counter = reinterpret_cast<unsigned*>(part + 8 * SG_LOSS_BLOCKS);
-    hipLaunchKernelGGL(sg_gan_loss_multi_fwd_kernel, dim3(SG_LOSS_BLOCKS, n), dim3(256), 0, (hipStream_t)stream, J, part, counter, each_out,
-                       total_out);
+    hipLaunchKernelGGL(sg_gan_loss_multi_fwd_kernel, dim3(SG_LOSS_BLOCKS, n + sg_cdiv(nfin, SG_LOSS_BLOCKS)), dim3(256), 0, (hipStream_t)stream, J,
+                       part, counter, each_out, total_out, F);
     SGAN_LAUNCH_CHECK();
     return SGAN_OK;
 }

@@ -33,7 +33,7 @@
 
 struct SgHeadProb {
     const float* x; float* din; const float* dz; const float* w; float* dw; float* dbias; double* sums;
-    const double* xn_stats; const float* xn_gamma; const float* xn_beta;
+    const double* xn_stats; const float* xn_gamma; const float* xn_beta; const float* xn_tab;      // xn_tab: sgan_norm_desc.mean_rstd or null
     int32_t H, W, x_ld, din_ld, Ho, Wo, dz_ld, xn_count, xn_sq, xn_rep, sums_sq, sums_rep, tile0, tiles_x;
 };
 struct SgHeadParams {
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void sg_head_bwd_kernel(const SgHeadParams G) 
     if (xnorm) {
         SgNorm n;
         n.stats = Q.xn_stats; n.gamma = Q.xn_gamma; n.beta = Q.xn_beta; n.count = Q.xn_count; n.eps = G.xn_eps; n.act = G.xn_act;
-        n.slope = G.xn_slope; n.sq_stride = Q.xn_sq; n.rep_stride = Q.xn_rep;
+        n.slope = G.xn_slope; n.sq_stride = Q.xn_sq; n.rep_stride = Q.xn_rep; n.mean_rstd = Q.xn_tab;
         sg_mean_rstd(n, C, cc, mean, rstd);
         gam = Q.xn_gamma ? Q.xn_gamma[cc] : 1.f;
         bet = Q.xn_beta ? Q.xn_beta[cc] : 0.f;
@@ -215,6 +215,7 @@ extern "C" int sgan_conv_head_bwd(const sgan_conv_dgrad_job* djobs, const sgan_c
         Q.sums = J.bwd_sums;
         Q.xn_stats = xn ? xn->stats : nullptr; Q.xn_gamma = xn ? xn->gamma : nullptr; Q.xn_beta = xn ? xn->beta : nullptr;
         Q.xn_count = xn ? xn->count : 1; Q.xn_sq = xn ? xn->sq_stride : 0; Q.xn_rep = xn ? xn->rep_stride : 0;
+        Q.xn_tab = (xn && xn->stats) ? xn->mean_rstd : nullptr;
         Q.H = d->Hin; Q.W = d->Win; Q.x_ld = J.x_ld; Q.din_ld = J.din_ld; Q.Ho = d->Hout; Q.Wo = d->Wout; Q.dz_ld = J.dout_ld;
         Q.sums_sq = J.bwd_sums_sq_stride; Q.sums_rep = J.bwd_sums_rep_stride;
         Q.tiles_x = (d->Win + SGH_TX - 1) / SGH_TX;

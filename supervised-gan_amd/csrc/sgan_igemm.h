@@ -23,6 +23,8 @@ struct SgProb {
     const double* xn_stats;   // norm the forward consumer applied to xref (or null)
     const float* xn_gamma;
     const float* xn_beta;
+    const float* pro_tab;     // finalised (mean, rstd) table of the prologue norm / of xn (sgan_norm_desc.mean_rstd), or null
+    const float* xn_tab;
     const float* amax;  // split kernels with fp16 planes: device scalar max|gathered tensor| (backward-data: sgan_conv_dgrad_job.dout_amax) or null
     int32_t Hin, Win, in_ld;     // gathered tensor geometry
     int32_t Hout, Wout, out_ld;  // result tensor geometry
@@ -77,10 +79,10 @@ __device__ __forceinline__ SgLocal sg_local(const SgIgemmParams& G, int g) {
     P.out_ld = Q.out_ld; P.xref_ld = Q.xref_ld; P.is = G.is; P.os = G.os; P.w_ns = G.w_ns; P.w_ks = G.w_ks;
     P.out_act = G.out_act; P.ksplit = G.ksplit; P.slab = G.slab; P.slab_stride = G.slab_stride;
     P.pro.stats = Q.pro_stats; P.pro.gamma = Q.pro_gamma; P.pro.beta = Q.pro_beta; P.pro.count = Q.pro_count;
-    P.pro.eps = G.pro_eps; P.pro.act = G.pro_act; P.pro.slope = G.pro_slope; P.pro.sq_stride = Q.pro_sq; P.pro.rep_stride = Q.pro_rep;
+    P.pro.eps = G.pro_eps; P.pro.act = G.pro_act; P.pro.slope = G.pro_slope; P.pro.sq_stride = Q.pro_sq; P.pro.rep_stride = Q.pro_rep; P.pro.mean_rstd = Q.pro_tab;
     P.stats_sq = Q.stats_sq ? Q.stats_sq : G.N; P.accum = Q.accum; P.stats_rep = Q.stats_rep;
     P.xn.stats = Q.xn_stats; P.xn.gamma = Q.xn_gamma; P.xn.beta = Q.xn_beta; P.xn.count = Q.xn_count;
-    P.xn.eps = G.xn_eps; P.xn.act = G.xn_act; P.xn.slope = G.xn_slope; P.xn.sq_stride = Q.xn_sq; P.xn.rep_stride = Q.xn_rep;
+    P.xn.eps = G.xn_eps; P.xn.act = G.xn_act; P.xn.slope = G.xn_slope; P.xn.sq_stride = Q.xn_sq; P.xn.rep_stride = Q.xn_rep; P.xn.mean_rstd = Q.xn_tab;
     // fp16 planes: the packed weights hold w * 2^SGAN_F16_WEIGHT_SHIFT; a gathered gradient is scaled up by its own power of two
     const int sh = (G.planes_f16 && Q.amax) ? sg_f16_shift(*Q.amax) : 0;
     P.a_scale = sg_pow2(sh);

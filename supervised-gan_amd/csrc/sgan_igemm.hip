@@ -1300,13 +1300,14 @@ static int sg_group_geometry(SgIgemmParams& P, const sgan_conv_desc* const* desc
 }
 
 static void sg_set_norm(const sgan_norm_desc* d, const double** stats, const float** gamma, const float** beta, int32_t* count,
-                        int32_t* sq, int32_t* rep) {
+                        int32_t* sq, int32_t* rep, const float** tab) {
     *stats = d ? d->stats : nullptr;
     *gamma = d ? d->gamma : nullptr;
     *beta = d ? d->beta : nullptr;
     *count = d ? d->count : 1;
     *sq = d ? d->sq_stride : 0;
     *rep = d ? d->rep_stride : 0;
+    *tab = d && d->stats ? d->mean_rstd : nullptr;
 }
 
 extern "C" int sgan_conv_fwd_grouped(const sgan_conv_fwd_job* jobs, int32_t n, int32_t out_act, void* workspace,
@@ -1338,7 +1339,7 @@ extern "C" int sgan_conv_fwd_grouped(const sgan_conv_fwd_job* jobs, int32_t n, i
         Q.in = J.in; Q.out = J.out; Q.w = J.w; Q.wp = J.w_packed; Q.bias = J.bias; Q.xref = nullptr; Q.stats = J.out_stats;
         Q.amax = nullptr;
         Q.Hin = J.d->Hin; Q.Win = J.d->Win; Q.in_ld = J.in_ld; Q.Hout = J.d->Hout; Q.Wout = J.d->Wout; Q.out_ld = J.out_ld;
-        sg_set_norm(J.in_norm, &Q.pro_stats, &Q.pro_gamma, &Q.pro_beta, &Q.pro_count, &Q.pro_sq, &Q.pro_rep);
+        sg_set_norm(J.in_norm, &Q.pro_stats, &Q.pro_gamma, &Q.pro_beta, &Q.pro_count, &Q.pro_sq, &Q.pro_rep, &Q.pro_tab);
         Q.xn_count = 1;
         Q.stats_sq = J.out_stats_sq_stride;
         Q.stats_rep = J.out_stats_rep_stride;
@@ -1388,7 +1389,7 @@ int sg_build_dgrad_params(const sgan_conv_dgrad_job* jobs, int32_t n, SgIgemmPar
         Q.Hin = J.d->Hout; Q.Win = J.d->Wout; Q.in_ld = J.dout_ld; Q.Hout = J.d->Hin; Q.Wout = J.d->Win; Q.out_ld = J.din_ld;
         Q.xref_ld = J.x_ld;
         Q.pro_count = 1;
-        sg_set_norm(xn, &Q.xn_stats, &Q.xn_gamma, &Q.xn_beta, &Q.xn_count, &Q.xn_sq, &Q.xn_rep);
+        sg_set_norm(xn, &Q.xn_stats, &Q.xn_gamma, &Q.xn_beta, &Q.xn_count, &Q.xn_sq, &Q.xn_rep, &Q.xn_tab);
         Q.stats_sq = J.bwd_sums_sq_stride;
         Q.stats_rep = J.bwd_sums_rep_stride;
         Q.accum = J.accumulate;

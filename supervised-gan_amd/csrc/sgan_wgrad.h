@@ -12,6 +12,7 @@ struct SgWgradProb {
     const double* pro_stats;
     const float* pro_gamma;
     const float* pro_beta;
+    const float* pro_tab;   // finalised (mean, rstd) table of the prologue norm (sgan_norm_desc.mean_rstd), or null
     const float* amax;   // fp16 planes: device scalar max|dout| (sgan_conv_wgrad_job.dout_amax), or null
     int32_t Hin, Win, in_ld;
     int32_t Hout, Wout, dout_ld;

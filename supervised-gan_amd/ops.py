@@ -259,16 +259,90 @@ def stat_rep(arena):
     return arena.numel() if _STAT_REPLICATED else 0
 
 
-def norm_desc(stats=None, gamma=None, beta=None, count=1, eps=1e-5, act=ACT_NONE, slope=0.0, sq_stride=0, rep_stride=0):
+def norm_desc(stats=None, gamma=None, beta=None, count=1, eps=1e-5, act=ACT_NONE, slope=0.0, sq_stride=0, rep_stride=0, table=None):
     """None when the read is a plain one (no norm, no activation).  `sq_stride`: distance from a channel's sum to its
     sum of squares inside `stats` (0 = the channel count of the tensor being read; wider when `stats` is a slice);
-    `rep_stride`: `stats` is a slice of a stat_arena of that length (0: a plain array)."""
+    `rep_stride`: `stats` is a slice of a stat_arena of that length (0: a plain array).  `table`: the finalised (mean, rstd) pairs
+    of `stats` (norm_tables_register), for a backward reader."""
     if stats is None and act == ACT_NONE:
         return None
+    if stats is None:
+        table = None
     d = L.NormDesc(_ptr(stats).value, _ptr(gamma).value, _ptr(beta).value, int(count), float(eps), int(act), float(slope),
-                   int(sq_stride), int(rep_stride) if stats is not None else 0)
-    d._keep = (stats, gamma, beta)
+                   int(sq_stride), int(rep_stride) if stats is not None else 0, _ptr(table).value)
+    d._keep = (stats, gamma, beta, table)
     return d
+
+
+# ---- finalised normalisation statistics (sgan_norm_desc.mean_rstd) ------------------------------------------------------------
+# A forward walk registers the normalised tensors it produced; the next GAN-loss forward launch on the same stream -- which every
+# trainer issues between a pass's last forward launch and its first backward launch -- carries them as finalise jobs and hands each
+# owner its table.  The backward walk passes the table to its kernels when its forward has one; whoever never meets such a launch
+# (inference, the L-BFGS reconstructor, a stand-alone conv call) has none and runs on the fp64 sums as before.
+NORM_FIN_MAX = 48      # SGAN_NORM_FIN_MAX
+NO_NORM_TABLE = __import__("os").environ.get("SGAN_NO_NORM_TABLE", "0") not in ("", "0")      # switch: no tables anywhere
+_fin_pending = []      # weakrefs to owners, oldest first
+# tensors finalised; tensors that found no room in a launch (they stay on the fp64 path); the most one launch carried; normalised
+# tensors the backward walk handed to its kernels with / without a table
+NORM_TABLE_LOG = {"finalised": 0, "dropped": 0, "max_jobs": 0, "with_table": 0, "without_table": 0}
+
+
+def norm_tables_register(owner, jobs, buf=None):
+    """owner: any object (the walk's _BwdArena) that lives as long as the forward's statistics; jobs: [(stats, C, count, eps,
+    sq_stride, rep_stride)] of the normalised tensors of that forward, complete in stream order at this point.  After the next loss
+    launch on this stream owner.norm_tables maps stats.data_ptr() -> float[2 C] table (until then, and for ever under
+    SGAN_NO_NORM_TABLE=1: None).  buf: float storage for the tables (a forward whose buffers are refilled in place brings its own, so
+    that the refilled statistics land in the same table); None: allocated when the jobs run."""
+    owner.norm_tables = None
+    if NO_NORM_TABLE or not jobs:
+        return
+    owner._fin = (list(jobs), torch.cuda.current_stream().cuda_stream, buf)
+    _fin_pending[:] = [r for r in _fin_pending if r() is not None and r() is not owner]
+    _fin_pending.append(weakref.ref(owner))
+
+
+def _take_finalise_jobs(device):
+    """The pending finalise jobs of this stream and device for the launch being built: (ctypes array or None, n, commit).  Newest
+    owners first, an owner's jobs all or none, at most NORM_FIN_MAX: what does not fit stays without a table.  commit() after the
+    launch hands the tables out."""
+    here, cur, taken, n = [], torch.cuda.current_stream().cuda_stream, [], 0
+    for r in reversed(_fin_pending):
+        o = r()
+        if o is None or getattr(o, "_fin", None) is None:
+            continue
+        jobs, stream, buf = o._fin
+        if stream != cur or jobs[0][0].device != device:
+            here.append(r)      # another stream's: left for a loss launch there
+        elif n + len(jobs) <= NORM_FIN_MAX:
+            taken.append(o)
+            n += len(jobs)
+        else:
+            o._fin = None       # no room: this forward stays on the fp64 path
+            NORM_TABLE_LOG["dropped"] += len(jobs)
+    _fin_pending[:] = list(reversed(here))
+    if not n:
+        return None, 0, lambda: None
+    arr, i, tables = (L.NormFinaliseJob * n)(), 0, []
+    for o in taken:
+        jobs, _, buf = o._fin
+        need = sum(2 * j[1] for j in jobs)
+        if buf is None or buf.numel() < need:
+            buf = torch.empty(need, dtype=torch.float32, device=device)
+        tab, off = {}, 0
+        for st, Cs, count, eps, sq, rep in jobs:
+            t = buf[off: off + 2 * Cs]
+            off += 2 * Cs
+            arr[i] = L.NormFinaliseJob(_ptr(st).value, int(Cs), int(count), float(eps), int(sq), int(rep), _ptr(t).value)
+            tab[st.data_ptr()] = t
+            i += 1
+        tables.append((o, tab))
+
+    def commit():
+        for o, tab in tables:
+            o.norm_tables, o._fin = tab, None
+        NORM_TABLE_LOG["finalised"] += n
+        NORM_TABLE_LOG["max_jobs"] = max(NORM_TABLE_LOG["max_jobs"], n)
+    return arr, n, commit
 
 
 def _nd(d):
@@ -803,8 +877,10 @@ def gan_loss_multi_fwd(logits, targets, weights, mode, each_out, total_out, dlog
         arr[i] = L.GanLossJob(_ptr(_act(lb)).value, lb.stride(1), lb.shape[0] * lb.shape[1], float(t), float(w),
                               _ptr(_act(d)).value if d is not None else None, d.stride(1) if d is not None else 0)
     ws = _gan_loss_workspace(each_out.device)
-    L.check(L.lib().sgan_gan_loss_multi_fwd(arr, len(logits), mode, _ptr(each_out), _ptr(total_out), _ptr(ws), GAN_LOSS_WS_BYTES,
-                                            _stream()), "sgan_gan_loss_multi_fwd")
+    fin, nfin, commit = _take_finalise_jobs(each_out.device)      # the normalised tensors of the forwards this loss closes
+    L.check(L.lib().sgan_gan_loss_multi_fwd_fin(arr, len(logits), mode, _ptr(each_out), _ptr(total_out), _ptr(ws), GAN_LOSS_WS_BYTES,
+                                                fin, nfin, _stream()), "sgan_gan_loss_multi_fwd_fin")
+    commit()
 
 
 def gan_loss_multi_bwd(logits, targets, weights, mode, gout, dlogits):
