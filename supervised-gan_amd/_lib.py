@@ -1,248 +1,154 @@
-"""ctypes binding of libsgan_hip.so (include/sgan_hip.h).  There is NO fallback: if the library is
-missing or a call fails, this raises."""
+"""ctypes binding of libsgan_hip.so, read from include/sgan_hip.h at import: the header is the one statement of the C ABI and
+this module holds no second copy of it.  There is NO fallback: if the library is missing or a call fails, or the
+header holds a declaration the reader does not understand, this raises."""
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# SGAN_HIP_LIB: diagnostics only (e.g. an -DSG_ABLATE build of the same sources)
+# SGAN_HIP_LIB: diagnostics only (e.g. an -DSG_ABLATE build of the same sources, hence of the same header)
 LIB_PATH = os.environ.get("SGAN_HIP_LIB") or os.path.join(_HERE, "csrc", "libsgan_hip.so")
-
-ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
-MATH_F32, MATH_BF16X3, MATH_BF16X1 = 0, 1, 2
-FACTD_SIG1, FACTD_SIG2, FACTD_MSE = 1, 2, 4
-SEGHEAD_SOFTMAX, SEGHEAD_SIGMOID = 0, 1
-CONV, CONVT = 0, 1
-
-
-class NormDesc(C.Structure):
-    _fields_ = [("stats", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
-                ("count", C.c_int32), ("eps", C.c_float), ("act", C.c_int32), ("slope", C.c_float), ("sq_stride", C.c_int32),
-                ("rep_stride", C.c_int32), ("mean_rstd", C.c_void_p)]
-
-
-class NormFinaliseJob(C.Structure):
-    _fields_ = [("stats", C.c_void_p), ("C", C.c_int32), ("count", C.c_int32), ("eps", C.c_float), ("sq_stride", C.c_int32),
-                ("rep_stride", C.c_int32), ("mean_rstd", C.c_void_p)]
-
-
-class ConvDesc(C.Structure):
-    _fields_ = [("kind", C.c_int32), ("k", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32),
-                ("Hin", C.c_int32), ("Win", C.c_int32), ("Cin", C.c_int32),
-                ("Hout", C.c_int32), ("Wout", C.c_int32), ("Cout", C.c_int32),
-                ("Cin_logical", C.c_int32), ("Cout_logical", C.c_int32), ("math", C.c_int32)]
-
-
-class GaussJob(C.Structure):
-    _fields_ = [("image", C.c_void_p), ("image_ld", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
-                ("down", C.c_void_p), ("down_ld", C.c_int32), ("Ho", C.c_int32), ("Wo", C.c_int32),
-                ("g", C.c_void_p), ("g_chan_stride", C.c_int32), ("k", C.c_int32), ("pad", C.c_int32), ("s", C.c_int32)]
-
-
-class ConvFwdJob(C.Structure):
-    _fields_ = [("d", C.POINTER(ConvDesc)), ("inp", C.c_void_p), ("in_ld", C.c_int32), ("in_norm", C.POINTER(NormDesc)),
-                ("w", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p), ("out_ld", C.c_int32), ("out_stats", C.c_void_p),
-                ("out_stats_sq_stride", C.c_int32), ("w_packed", C.c_void_p), ("out_stats_rep_stride", C.c_int32)]
-
-
-class ConvDgradJob(C.Structure):
-    _fields_ = [("d", C.POINTER(ConvDesc)), ("dout", C.c_void_p), ("dout_ld", C.c_int32), ("w", C.c_void_p),
-                ("din", C.c_void_p), ("din_ld", C.c_int32), ("x", C.c_void_p), ("x_ld", C.c_int32),
-                ("x_norm", C.POINTER(NormDesc)), ("bwd_sums", C.c_void_p), ("bwd_sums_sq_stride", C.c_int32),
-                ("accumulate", C.c_int32), ("w_transposed", C.c_int32), ("w_packed", C.c_void_p), ("bwd_sums_rep_stride", C.c_int32),
-                ("dout_amax", C.c_void_p), ("w_packed_f16", C.c_void_p)]
-
-
-class WtSeg(C.Structure):
-    _fields_ = [("off", C.c_int64), ("taps", C.c_int32), ("cout", C.c_int32), ("cin", C.c_int32)]
-
-
-class ConvWgradJob(C.Structure):
-    _fields_ = [("d", C.POINTER(ConvDesc)), ("inp", C.c_void_p), ("in_ld", C.c_int32), ("in_norm", C.POINTER(NormDesc)),
-                ("dout", C.c_void_p), ("dout_ld", C.c_int32), ("dw", C.c_void_p), ("dbias", C.c_void_p), ("dout_amax", C.c_void_p)]
-
-
-class NormBwdJob(C.Structure):
-    _fields_ = [("dy", C.c_void_p), ("dy_ld", C.c_int32), ("x", C.c_void_p), ("x_ld", C.c_int32), ("npix", C.c_int32),
-                ("C", C.c_int32), ("x_norm", C.POINTER(NormDesc)), ("bwd_sums", C.c_void_p), ("bwd_sums_sq_stride", C.c_int32),
-                ("dgamma", C.c_void_p), ("dbeta", C.c_void_p), ("bwd_sums_rep_stride", C.c_int32), ("amax_out", C.c_void_p)]
-
-
-class GanLossJob(C.Structure):
-    _fields_ = [("logits", C.c_void_p), ("ld", C.c_int32), ("npix", C.c_int32), ("target", C.c_float), ("weight", C.c_float),
-                ("dlogits", C.c_void_p), ("dld", C.c_int32)]
-
-
-class FactdLossJob(C.Structure):
-    _fields_ = [("l1", C.c_void_p), ("ld1", C.c_int32), ("h1", C.c_int32), ("w1", C.c_int32),
-                ("l2", C.c_void_p), ("ld2", C.c_int32), ("H2", C.c_int32), ("W2", C.c_int32),
-                ("up", C.c_int32), ("target", C.c_float), ("weight", C.c_float),
-                ("dl1", C.c_void_p), ("dld1", C.c_int32), ("dl2", C.c_void_p), ("dld2", C.c_int32)]
-
-
-class BnRunningDesc(C.Structure):
-    _fields_ = [("stats", C.c_void_p), ("running_mean", C.c_void_p), ("running_var", C.c_void_p),
-                ("num_batches_tracked", C.c_void_p), ("C", C.c_int32), ("count", C.c_int32), ("sq_stride", C.c_int32),
-                ("rep_stride", C.c_int32)]
-
-
-class AdamSeg(C.Structure):
-    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64)]
-
-
-class EmaSeg(C.Structure):
-    _fields_ = [("shadow", C.c_void_p), ("p", C.c_void_p), ("n", C.c_int64)]
-
-
-class DiffaugJob(C.Structure):
-    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("Cs", C.c_int32),
-                ("colour_mask", C.c_uint32)]
-
-
-# name -> argtypes; every entry returns int except the two string getters
-_P, _I, _L, _F, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
-SIGNATURES = {
-    "sgan_conv_fwd": [C.POINTER(ConvDesc), _P, _I, C.POINTER(NormDesc), _P, _P, _P, _I, _I, _P, _P, _L, _P],
-    "sgan_conv_dgrad": [C.POINTER(ConvDesc), _P, _I, _P, _P, _I, _P, _I, C.POINTER(NormDesc), _P, _P, _L, _P],
-    "sgan_conv_wgrad": [C.POINTER(ConvDesc), _P, _I, C.POINTER(NormDesc), _P, _I, _P, _P, _P, _L, _P],
-    "sgan_conv_fwd_grouped": [C.POINTER(ConvFwdJob), _I, _I, _P, _L, _P],
-    "sgan_conv_dgrad_grouped": [C.POINTER(ConvDgradJob), _I, _P, _L, _P],
-    "sgan_conv_wgrad_grouped": [C.POINTER(ConvWgradJob), _I, _P, _L, _P],
-    "sgan_conv_bwd_fused": [C.POINTER(ConvDgradJob), _I, C.POINTER(ConvWgradJob), _I, _I, _P],
-    "sgan_conv_bwd_thin_pair": [C.POINTER(ConvDgradJob), _I, C.POINTER(ConvWgradJob), _I, _P],
-    "sgan_conv_bwd_fused_ws": [C.POINTER(ConvDgradJob), _I, C.POINTER(ConvWgradJob), _I, _I, _P, C.c_int64, _P],
-    "sgan_norm_bwd_apply": [_P, _I, _P, _I, _I, _I, C.POINTER(NormDesc), _P, _I, _P, _P, _P],
-    "sgan_norm_bwd_apply_multi": [C.POINTER(NormBwdJob), _I, _P],
-    "sgan_transpose_weights": [_P, _P, C.POINTER(WtSeg), _I, _P],
-    "sgan_pack_weights": [_P, _P, _P, _P, _P, C.POINTER(WtSeg), _I, _P],
-    "sgan_bce01_fwd": [_P, _I, _P, _I, _I, _I, _P, _P, _I, _P, C.c_int64, _P],
-    "sgan_bilinear_up2_fwd": [_P, _I, _I, _I, _I, _P, _I, _P, _I, _P],
-    "sgan_bilinear_up2_bwd": [_P, _I, _I, _I, _I, _P, _I, _P],
-    "sgan_avgpool_pyramid_fwd": [_P, _I, _I, _I, _P, _P, _P],
-    "sgan_avgpool_pyramid_bwd": [_P, _P, _I, _I, _P, _I, _I, _P],
-    "sgan_norm_apply_fwd": [_P, _I, C.POINTER(NormDesc), _P, _P, _F, _P, _I, _I, _I, _P],
-    "sgan_norm_apply_bwd_sums": [_P, _I, _P, _P, _I, C.POINTER(NormDesc), _P, _I, _I, _P],
-    "sgan_pad_reflect_fwd": [_P, _I, _I, _I, _I, C.POINTER(NormDesc), _P, _I, _P, _I, _P],
-    "sgan_pad_reflect_bwd": [_P, _I, _I, _I, _I, _I, _P, _I, C.POINTER(NormDesc), _P, _P, _I, _P, _I, _P],
-    "sgan_dropout_mask": [_P, _L, _F, C.c_uint64, _P, _I, _P],
-    "sgan_rng_advance": [_P, C.c_uint64, _P],
-    "sgan_l1w_fwd": [_P, _I, _P, _I, _I, _I, _P, _I, _P, _I, _F, _P, _P, _I, _P, C.c_int64, _P],
-    "sgan_scale": [_P, _P, _P, _L, _P],
-    "sgan_bn_running_update": [C.POINTER(BnRunningDesc), _I, _F, _P],
-    "sgan_image_prep": [_P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P],
-    "sgan_image_prep_elastic": [_P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P],
-    "sgan_image_resize": [_P, _I, _I, _I, _P, _I, _I, _I, _P, _L, _P],
-    "sgan_image_resize_workspace": [_I, _I, _I, _I, _I, _I],
-    "sgan_gauss_down_fwd": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P],
-    "sgan_gauss_down_multi_fwd": [C.POINTER(GaussJob), _I, _I, _I, _P],
-    "sgan_gauss_down_multi_bwd": [C.POINTER(GaussJob), _I, _I, _I, _I, _P],
-    "sgan_gauss_down_bwd": [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _P],
-    "sgan_gan_loss_fwd": [_P, _I, _I, _F, _I, _P, _P, _P],
-    "sgan_gan_loss_bwd": [_P, _I, _I, _F, _I, _P, _P, _I, _P],
-    "sgan_gan_loss_multi_fwd": [C.POINTER(GanLossJob), _I, _I, _P, _P, _P, C.c_int64, _P],
-    "sgan_gan_loss_multi_bwd": [C.POINTER(GanLossJob), _I, _I, _P, _P],
-    "sgan_gan_loss_multi_fwd_fin": [C.POINTER(GanLossJob), _I, _I, _P, _P, _P, C.c_int64, C.POINTER(NormFinaliseJob), _I, _P],
-    "sgan_norm_mean_rstd_probe": [C.POINTER(NormDesc), _I, _P, _P],
-    "sgan_factd_loss_multi_fwd": [C.POINTER(FactdLossJob), _I, _I, _P, _P, _P, C.c_int64, _P],
-    "sgan_factd_loss_multi_bwd": [C.POINTER(FactdLossJob), _I, _I, _P, _P],
-    "sgan_sigmoid_fwd": [_P, _I, _I, _P, _I, _P],
-    "sgan_sigmoid_bwd": [_P, _I, _P, _I, _I, _P, _I, _P],
-    "sgan_tanh_bwd": [_P, _P, _P, _L, _P],
-    "sgan_stat_replicas": [],
-    "sgan_set_device": [_I],
-    "sgan_stream_device": [_P, C.POINTER(C.c_int32)],
-    "sgan_add_act_fwd": [_P, _P, _P, _L, _I, _P],
-    "sgan_to_nhwc": [_P, _L, _L, _L, _I, _I, _I, _P, _I, _I, _P],
-    "sgan_concat_nhwc": [_P, _I, _I, _P, _I, _I, _L, _P, _I, _I, _P],
-    "sgan_slice_nhwc": [_P, _I, _I, _I, _L, _P, _I, _I, _P],
-    "sgan_adam_multi": [C.POINTER(AdamSeg), _I, _P, _F, _F, _F, _P, _P],
-    "sgan_sgd_multi": [C.POINTER(AdamSeg), _I, _P, _F, _P],
-    "sgan_ema_multi": [C.POINTER(EmaSeg), _I, _F, _I, _P, _P],
-    "sgan_adam_pack": [_P, _P, _P, _P, _L, _P, _F, _F, _F, _P, _P, _P, _P, _P, C.POINTER(WtSeg), _I, _I, _P],
-    "sgan_zero_multi": [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), _I, _P],
-    "sgan_conv_head_bwd": [C.POINTER(ConvDgradJob), C.POINTER(ConvWgradJob), _I, _P],
-    "sgan_ce_fwd": [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P],
-    "sgan_ce_bwd": [_P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P],
-    "sgan_softmax_fwd": [_P, _I, _I, _I, _P, _I, _P],
-    "sgan_softmax_bwd": [_P, _I, _P, _I, _I, _I, _P, _I, _P],
-    "sgan_sigmoid_nhwc_fwd": [_P, _I, _I, _I, _P, _I, _P],
-    "sgan_sigmoid_nhwc_bwd": [_P, _I, _P, _I, _I, _I, _P, _I, _P],
-    "sgan_bce_weighted_fwd": [_P, _I, _P, _I, _I, _I, _P, _I, _P, _P, C.c_int64, _P],
-    "sgan_bce_weighted_bwd": [_P, _I, _P, _I, _I, _I, _P, _I, _P, _P, _I, _P],
-    "sgan_label_weight_sum": [_P, _I, _I, _P, _P, _P, _P],
-    "sgan_seg_head": [_P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P],
-    "sgan_pixel_weight_sum": [_P, _I, _I, _P, _P, _P, _P, _P],
-    "sgan_seg_head_pw": [_P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P],
-    "sgan_normal_fill": [_P, _L, C.c_uint64, _P, _I, _P],
-    "sgan_normal_fill_nhwc": [_P, _I, _I, _I, _I, C.c_uint64, _P, _I, _P],
-    "sgan_normal_fill_nhwc_pair": [_P, _P, _I, _I, _I, _I, C.c_uint64, _P, _P, C.c_int64, _P],
-    "sgan_lbfgs_advance": [_P, _I, _L, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _I, _P],
-    "sgan_ccl_label": [_P, _L, _I, _I, _P, _P, _P],
-    "sgan_rand_f_workspace": [_I, _I],
-    "sgan_rand_f_accumulate": [_P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _P],
-    "sgan_vinfo_workspace": [_I, _I],
-    "sgan_vinfo_accumulate": [_P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _P],
-    "sgan_object_match_workspace": [_I, _I],
-    "sgan_object_match_accumulate": [_P, _P, _I, _I, _I, _P, _L, _P, _P, _P, _P, _P, _P],
-    "sgan_edt_workspace": [_I, _I],
-    "sgan_edt_sq": [_P, _L, _I, _I, _P, _P, _L, _P, _P],
-    "sgan_boundary_workspace": [_I, _I],
-    "sgan_boundary_accumulate": [_P, _P, _I, _I, _P, _L, _P, _P, _P, _P, _P, _P],
-    "sgan_clean_workspace": [_I, _I],
-    "sgan_clean_wall": [_P, _L, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P],
-    "sgan_split_workspace": [_I, _I],
-    "sgan_topo_workspace_bytes": [_I, _I, _I, _I],
-    "sgan_topo_accumulate": [_P, _L, _P, _L, _P, _P, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P],
-    "sgan_split_cells": [_P, _L, _I, _I, _I, _I, _P, _P, _P, _L, _P, _P],
-    "sgan_image_prep_tile": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P],
-    "sgan_tile_blend": [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P],
-    "sgan_tile_finish": [_P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _P, _I, _P],
-    "sgan_diffaug_workspace": [_I],
-    "sgan_diffaug_draw": [_P, C.POINTER(C.c_int32), _I, _I, C.c_double, C.c_double, C.c_uint64, _P, _I, _P],
-    "sgan_diffaug_multi_fwd": [C.POINTER(DiffaugJob), _I, _P, _P, _P],
-    "sgan_diffaug_multi_bwd": [C.POINTER(DiffaugJob), _I, _P, _P, _P],
-    "sgan_confusion_accumulate": [_P, _I, _I, _P, _P, _I, _I, _L, _P, _P, _P],
-    "sgan_thin_workspace": [_I, _I],
-    "sgan_thin": [_P, _L, _I, _I, _P, _I, _P, _L, _P, _P, _P],
-    "sgan_region_stats_workspace": [_I, _I],
-    "sgan_region_stats": [_P, _I, _I, _P, _I, _P, _P, _L, _P, _P],
-    "sgan_border_weight": [_P, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P],
-    "sgan_lap_pyramid": [_I, _P, _L, _P, _L, _I, _I, _I, _P, _L, _P],
-    "sgan_swd_gather": [_P, _L, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P],
-    "sgan_swd_workspace": [_I, _I, _I],
-    "sgan_swd_distances": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _L, _I, _P],
-    "sgan_prd_workspace": [_I, _I, _I],
-    "sgan_knn_radii": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _L, _I, _P],
-    "sgan_prd_rows": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _I, _P],
-    "sgan_prd_finish": [_P, _P, _P, _P, _I, _P, _P],
-    "sgan_cldice_workspace_bytes": [_I, _I, _I, _I],
-    "sgan_soft_skeleton": [_P, _L, _L, _I, _I, _I, _P, _P, _L, _P],
-    "sgan_cldice_finish": [_P, _P, _L, _L, _P, _P, _L, _L, _I, _I, _P, _P, _P],
-    "sgan_cldice_backward": [_P, _L, _L, _P, _P, _P, _I, _I, _I, _P, _P, _L, _P],
-    "sgan_lovasz_workspace_bytes": [_I, _I, _I],
-    "sgan_lovasz_forward": [_P, _L, _L, _L, _P, _P, _I, _I, _I, _I, _P, _P, _L, _P],
-    "sgan_lovasz_backward": [_P, _L, _L, _L, _P, _I, _I, _I, _I, _P, _P, _P, _L, _P],
-    "sgan_seg_terms_forward": [_P, _I, _I, _I, _I, _P, _I, _P, _I, _D, _D, _D, _D, _I, _D, _P, _I, _P, _P, _P, _P, _P],
-    "sgan_seg_terms_backward": [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _D, _P, _I, _P, _P, _P, _P, _I, _P],
-    "sgan_last_variant": [],
-    "sgan_profile_enable": [_I],
-    "sgan_profile_count": [],
-    "sgan_profile_mark": [_P],
-    "sgan_profile_read": [_I, C.POINTER(C.c_char_p), C.POINTER(C.c_float)],
-}
-
-RESTYPES = {"sgan_last_variant": C.c_char_p, "sgan_image_resize_workspace": C.c_int64, "sgan_rand_f_workspace": C.c_int64,
-            "sgan_vinfo_workspace": C.c_int64, "sgan_thin_workspace": C.c_int64,
-            "sgan_region_stats_workspace": C.c_int64, "sgan_object_match_workspace": C.c_int64,
-            "sgan_edt_workspace": C.c_int64, "sgan_boundary_workspace": C.c_int64, "sgan_clean_workspace": C.c_int64,
-            "sgan_split_workspace": C.c_int64, "sgan_topo_workspace_bytes": C.c_int64,
-            "sgan_diffaug_workspace": C.c_int64, "sgan_swd_workspace": C.c_int64,
-            "sgan_prd_workspace": C.c_int64, "sgan_cldice_workspace_bytes": C.c_int64,
-            "sgan_lovasz_workspace_bytes": C.c_int64}      # everything else returns an int status
-_lib = None
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sgan_hip.h")      # csrc/Makefile: ../../include/sgan_hip.h
 
 
 class SganError(RuntimeError):
     pass
+
+
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
+            "float": C.c_float, "double": C.c_double}
+_POINTEES = ("void", "char", "unsigned char")      # besides the scalars and the structs: what a pointer may point at
+_RESTYPES = {"int": C.c_int, "int64_t": C.c_int64, "constchar*": C.c_char_p}      # keyed without white space
+_FIELD_RENAMES = {"in": "inp"}      # the one Python keyword among the fields
+# structs that live in device memory: the binding passes their address, so a pointer to one is a c_void_p like any device pointer
+_DEVICE_STRUCTS = ("sgan_lbfgs_state", "sgan_diffaug_rec")
+# (function, parameter) -> argtype, where the caller hands over a ctypes object of the host and the type says which
+_ARG_OVERRIDES = {
+    ("sgan_stream_device", "device_id"): C.POINTER(C.c_int32),      # byref(c_int32()): an out-parameter on the host
+    ("sgan_profile_read", "name"): C.POINTER(C.c_char_p),           # likewise
+    ("sgan_profile_read", "ms"): C.POINTER(C.c_float),              # likewise
+    ("sgan_zero_multi", "ptrs"): C.POINTER(C.c_void_p),             # a host (c_void_p * n) array
+    ("sgan_zero_multi", "bytes"): C.POINTER(C.c_int64),             # a host (c_int64 * n) array
+    ("sgan_diffaug_draw", "shapes"): C.POINTER(C.c_int32),          # a host (c_int32 * 2 n) array
+}
+# bound by their return type alone, as they always were: no row in SIGNATURES
+_RESTYPE_ONLY = ("sgan_version", "sgan_last_error", "sgan_last_kernel")
+
+_PREPROCESSOR = re.compile(r"^[ \t]*#[^\n]*", re.M)
+_DEFINE = re.compile(r"\s*#\s*define\s+(SGAN_\w+)(.*)")
+_INT_EXPR = re.compile(r"(?:\s*(?:0[xX][0-9a-fA-F]+|\d+|<<|[()|+*-]))+\s*")      # all the header uses; C and Python agree on precedence
+_TYPEDEF = re.compile(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*;)\s*\}\s*(\w+)\s*;")
+_PROTOTYPE = re.compile(r"(const\s+char\s*\*|int64_t|int)\s+(sgan_\w+)\s*\(([^()]*)\)\s*;")
+_EXTERN_C = re.compile(r'extern\s+"C"\s*\{|\}')      # the two ends of the extern "C" bracket
+_DECLARATION = re.compile(r"\s*([\w\s*]*[\s*])(\w+)\s*((?:\[\d+\])?)\s*")      # type, name, [N]
+_DECLARATOR = re.compile(r"\s*(\w+)\s*((?:\[\d+\])?)\s*")
+_SPACE = re.compile(r"\s*")
+
+
+def read_header(text, name="sgan_hip.h"):
+    """(defines, structs, prototypes) of a header in the style of include/sgan_hip.h.
+    defines: {SGAN_X: int} for every `#define SGAN_X <integer constant expression>`; a define without a value (the include guard)
+    is not a constant and is left out; any other value -- a float, a string, a macro with arguments -- is refused.
+    structs: {C name: ctypes.Structure subclass}; prototypes: {function: (restype, [(parameter, argtype)])}, both in header order.
+    The other preprocessor lines and the extern "C" bracket are skipped; everything else must be a typedef'd struct or a prototype
+    of these forms, or SganError names the line."""
+    def blank(m):
+        return " " + "\n" * m.group().count("\n")
+    code = re.sub(r"/\*.*?\*/|//[^\n]*", blank, text, flags=re.S)      # comments out, every line keeps its number
+    defines, structs, prototypes = {}, {}, {}
+
+    def fail(pos, what):
+        line = code.count("\n", 0, pos) + 1
+        raise SganError(f"{name}:{line}: cannot read this {what}: {text.splitlines()[line - 1].strip()!r}")
+
+    def pieces(m, group, sep):
+        """(piece, where its first word starts) of a match group split at `sep`."""
+        at = m.start(group)
+        for piece in m.group(group).split(sep):
+            yield piece, at + len(piece) - len(piece.lstrip())
+            at += len(piece) + len(sep)
+
+    def declaration(decl, pos, typed, what):
+        """'const float* w' -> ('w', c_void_p, ''): name, ctypes type and array suffix of a parameter or a field's first declarator.
+        A pointer to one of the `typed` structs keeps its type; every other pointer is an address."""
+        m = _DECLARATION.fullmatch(decl)
+        if not m:
+            fail(pos, what)
+        words = [w for w in re.findall(r"\w+|\*", m.group(1)) if w != "const"]
+        stars, base = words.count("*"), " ".join(w for w in words if w != "*")
+        if stars == 0 and base in _SCALARS:
+            return m.group(2), _SCALARS[base], m.group(3)
+        if stars == 1 and base in typed:
+            return m.group(2), C.POINTER(structs[base]), m.group(3)
+        if stars >= 1 and (base in _SCALARS or base in _POINTEES or base in structs):
+            return m.group(2), C.c_void_p, m.group(3)
+        fail(pos, what + " (type)")
+
+    for m in _PREPROCESSOR.finditer(code):
+        d = _DEFINE.fullmatch(m.group())
+        if d and d.group(2).strip():
+            try:
+                if not _INT_EXPR.fullmatch(d.group(2)):
+                    raise ValueError
+                defines[d.group(1)] = int(eval(d.group(2), {"__builtins__": {}}))      # digits, parentheses, | + * - << and nothing else
+            except (ValueError, SyntaxError, ArithmeticError, TypeError):
+                fail(m.start(), "integer define")
+    code = _PREPROCESSOR.sub(blank, code)
+    pos = _SPACE.match(code).end()
+    while pos < len(code):
+        m = _EXTERN_C.match(code, pos) or _TYPEDEF.match(code, pos) or _PROTOTYPE.match(code, pos)
+        if not m:
+            fail(pos, "declaration")
+        if m.re is _TYPEDEF:
+            if m.group(1) != m.group(3):
+                fail(pos, "typedef")
+            fields = []
+            for decl, at in list(pieces(m, 2, ";"))[:-1]:
+                first, *more = decl.split(",")
+                fname, ftype, dim = declaration(first, at, structs, "field")
+                if more and ftype is C.c_void_p:      # `float* a, b`: refused, not guessed
+                    fail(at, "field")
+                for d in [_DECLARATOR.fullmatch(fname + dim)] + [_DECLARATOR.fullmatch(x) for x in more]:
+                    if not d:
+                        fail(at, "field")
+                    fields.append((_FIELD_RENAMES.get(d.group(1), d.group(1)), ftype * int(d.group(2)[1:-1]) if d.group(2) else ftype))
+            structs[m.group(1)] = type(m.group(1), (C.Structure,), {"_fields_": fields})
+        elif m.re is _PROTOTYPE:
+            typed = [s for s in structs if s not in _DEVICE_STRUCTS]
+            args = []
+            for decl, at in ([] if m.group(3).strip() == "void" else pieces(m, 3, ",")):
+                pname, ptype, dim = declaration(decl, at, typed, "parameter")
+                if dim:
+                    fail(at, "parameter")
+                args.append((pname, _ARG_OVERRIDES.get((m.group(2), pname), ptype)))
+            prototypes[m.group(2)] = (_RESTYPES["".join(m.group(1).split())], args)
+        pos = _SPACE.match(code, m.end()).end()
+    return defines, structs, prototypes
+
+
+with open(HEADER_PATH) as _f:
+    DEFINES, STRUCTS, _PROTOTYPES = read_header(_f.read(), HEADER_PATH)
+for _fn, _p in _ARG_OVERRIDES:
+    if _p not in dict(_PROTOTYPES.get(_fn, (None, []))[1]):
+        raise SganError(f"_ARG_OVERRIDES names {_fn}({_p}), which {HEADER_PATH} does not declare")
+
+# name -> argtypes, and name -> restype for what does not return an int status
+SIGNATURES = {n: [t for _, t in args] for n, (_, args) in _PROTOTYPES.items() if n not in _RESTYPE_ONLY}
+RESTYPES = {n: res for n, (res, _) in _PROTOTYPES.items() if res is not C.c_int}
+
+ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = (DEFINES["SGAN_ACT_" + n] for n in ("NONE", "RELU", "LRELU", "TANH"))
+MATH_F32, MATH_BF16X3, MATH_BF16X1 = (DEFINES["SGAN_MATH_" + n] for n in ("F32", "BF16X3", "BF16X1"))
+FACTD_SIG1, FACTD_SIG2, FACTD_MSE = (DEFINES["SGAN_FACTD_" + n] for n in ("SIG1", "SIG2", "MSE"))
+SEGHEAD_SOFTMAX, SEGHEAD_SIGMOID = DEFINES["SGAN_SEGHEAD_SOFTMAX"], DEFINES["SGAN_SEGHEAD_SIGMOID"]
+CONV, CONVT = DEFINES["SGAN_CONV"], DEFINES["SGAN_CONVT"]
+
+NormDesc, NormFinaliseJob, ConvDesc = STRUCTS["sgan_norm_desc"], STRUCTS["sgan_norm_finalise_job"], STRUCTS["sgan_conv_desc"]
+GaussJob, ConvFwdJob, ConvDgradJob = STRUCTS["sgan_gauss_job"], STRUCTS["sgan_conv_fwd_job"], STRUCTS["sgan_conv_dgrad_job"]
+WtSeg, ConvWgradJob, NormBwdJob = STRUCTS["sgan_wt_seg"], STRUCTS["sgan_conv_wgrad_job"], STRUCTS["sgan_norm_bwd_job"]
+GanLossJob, FactdLossJob, BnRunningDesc = STRUCTS["sgan_gan_loss_job"], STRUCTS["sgan_factd_loss_job"], STRUCTS["sgan_bn_running_desc"]
+AdamSeg, EmaSeg, DiffaugJob = STRUCTS["sgan_adam_seg"], STRUCTS["sgan_ema_seg"], STRUCTS["sgan_diffaug_job"]
+
+_lib = None
 
 
 def lib():
@@ -262,9 +168,8 @@ def lib():
             fn = getattr(l, name)
             fn.argtypes = args
             fn.restype = RESTYPES.get(name, C.c_int)
-        l.sgan_version.restype = C.c_char_p
-        l.sgan_last_error.restype = C.c_char_p
-        l.sgan_last_kernel.restype = C.c_char_p
+        for name in _RESTYPE_ONLY:
+            getattr(l, name).restype = RESTYPES[name]
         _lib = l
     return _lib
 

@@ -18,26 +18,17 @@ import math
 
 import torch
 
-PHASE_START, PHASE_AFTER_MOVE = 0, 1
+from ._lib import DEFINES, STRUCTS
+
+PHASE_START, PHASE_AFTER_MOVE = DEFINES["SGAN_LBFGS_PHASE_START"], DEFINES["SGAN_LBFGS_PHASE_AFTER_MOVE"]
 # why the last finished step() ended (state.last_exit)
-EXIT_NONE, EXIT_OPT_START, EXIT_GTD, EXIT_MAX_ITER, EXIT_MAX_EVAL, EXIT_OPT_COND, EXIT_SMALL_STEP, EXIT_NO_PROGRESS = range(8)
+EXIT_NONE, EXIT_OPT_START, EXIT_GTD, EXIT_MAX_ITER, EXIT_MAX_EVAL, EXIT_OPT_COND, EXIT_SMALL_STEP, EXIT_NO_PROGRESS = (
+    DEFINES["SGAN_LBFGS_EXIT_" + n]
+    for n in ("NONE", "OPT_START", "GTD", "MAX_ITER", "MAX_EVAL", "OPT_COND", "SMALL_STEP", "NO_PROGRESS"))
 EXIT_NAMES = ["none", "opt_cond at step start", "gtd > -tolerance_change", "max_iter", "max_eval", "opt_cond", "|d t| small",
               "no progress"]
-MAX_HISTORY = 1024      # SGAN_LBFGS_MAX_HISTORY
-
-
-class LbfgsState(C.Structure):
-    """sgan_lbfgs_state (include/sgan_hip.h): one problem's hyperparameters, counters and scalars, 128 bytes."""
-    _fields_ = [("lr", C.c_float), ("tolerance_grad", C.c_float), ("tolerance_change", C.c_double),
-                ("max_iter", C.c_int32), ("max_eval", C.c_int32), ("history_size", C.c_int32), ("n_steps", C.c_int32),
-                ("func_evals", C.c_int32), ("n_iter", C.c_int32), ("steps", C.c_int32), ("phase", C.c_int32),
-                ("done", C.c_int32), ("iter_in_step", C.c_int32), ("evals_in_step", C.c_int32), ("hist_len", C.c_int32),
-                ("hist_head", C.c_int32), ("last_exit", C.c_int32), ("n_skipped", C.c_int32), ("reserved0", C.c_int32),
-                ("t", C.c_float), ("h_diag", C.c_float), ("prev_loss", C.c_double), ("reserved", C.c_int32 * 8)]
-
-
-assert C.sizeof(LbfgsState) == 128
-
+MAX_HISTORY = DEFINES["SGAN_LBFGS_MAX_HISTORY"]
+LbfgsState = STRUCTS["sgan_lbfgs_state"]      # one problem's hyperparameters, counters and scalars, 128 bytes
 
 COUNTERS = ("func_evals", "n_iter", "steps", "phase", "done", "iter_in_step", "evals_in_step", "hist_len", "last_exit", "n_skipped")
 

@@ -279,7 +279,7 @@ def norm_desc(stats=None, gamma=None, beta=None, count=1, eps=1e-5, act=ACT_NONE
 # trainer issues between a pass's last forward launch and its first backward launch -- carries them as finalise jobs and hands each
 # owner its table.  The backward walk passes the table to its kernels when its forward has one; whoever never meets such a launch
 # (inference, the L-BFGS reconstructor, a stand-alone conv call) has none and runs on the fp64 sums as before.
-NORM_FIN_MAX = 48      # SGAN_NORM_FIN_MAX
+NORM_FIN_MAX = L.DEFINES["SGAN_NORM_FIN_MAX"]
 NO_NORM_TABLE = __import__("os").environ.get("SGAN_NO_NORM_TABLE", "0") not in ("", "0")      # switch: no tables anywhere
 _fin_pending = []      # weakrefs to owners, oldest first
 # tensors finalised; tensors that found no room in a launch (they stay on the fp64 path); the most one launch carried; normalised
@@ -630,7 +630,7 @@ def rng_advance(offset_dev, by):
     L.check(L.lib().sgan_rng_advance(_ptr(offset_dev), C.c_uint64(int(by)), _stream()), "sgan_rng_advance")
 
 
-IMAGE_LOSS_WS_BYTES = 2048   # SGAN_IMAGE_LOSS_WS_BYTES
+IMAGE_LOSS_WS_BYTES = L.DEFINES["SGAN_IMAGE_LOSS_WS_BYTES"]
 
 
 def l1w_fwd(x, y, Creal, a, weights_dev, nweights, lam, loss_out, g):
@@ -766,7 +766,7 @@ def tile_finish(canvas, Creal, Wy, Wx, n_tta, prob, logp):
                                      prob.stride(1), _ptr(_act(logp)), logp.stride(1), _stream()), "sgan_tile_finish")
 
 
-RESAMPLE = {"bilinear": 2, "bicubic": 3}      # Pillow's Image.BILINEAR / Image.BICUBIC
+RESAMPLE = {n: L.DEFINES["SGAN_RESAMPLE_" + n.upper()] for n in ("bilinear", "bicubic")}      # Pillow's Image.BILINEAR / Image.BICUBIC
 
 
 def image_resize(img_u8, wo, ho, resample):
@@ -839,7 +839,7 @@ def gan_loss_bwd(logits, target, mode, gout, dlogits):
                                       _ptr(_act(dlogits)), dlogits.stride(1), _stream()), "sgan_gan_loss_bwd")
 
 
-GAN_LOSS_WS_BYTES = 2048   # SGAN_GAN_LOSS_WS_BYTES
+GAN_LOSS_WS_BYTES = L.DEFINES["SGAN_GAN_LOSS_WS_BYTES"]
 _zeroed_ws = {}
 _unit_grads = []           # weak references to gradient tensors known to hold 1.0 (BaseModel._backward's cached root gradient)
 
@@ -891,7 +891,7 @@ def gan_loss_multi_bwd(logits, targets, weights, mode, gout, dlogits):
     L.check(L.lib().sgan_gan_loss_multi_bwd(arr, len(logits), mode, _ptr(gout), _stream()), "sgan_gan_loss_multi_bwd")
 
 
-FACTD_LOSS_WS_BYTES = 2048   # SGAN_FACTD_LOSS_WS_BYTES
+FACTD_LOSS_WS_BYTES = L.DEFINES["SGAN_FACTD_LOSS_WS_BYTES"]
 
 
 def _factd_loss_workspace(device):
@@ -980,7 +980,7 @@ def sigmoid_nhwc_bwd(dp, p, Creal, dz):
                                           dz.stride(1), _stream()), "sgan_sigmoid_nhwc_bwd")
 
 
-BCE_WEIGHTED_WS_BYTES = 1024   # SGAN_BCE_WEIGHTED_WS_BYTES
+BCE_WEIGHTED_WS_BYTES = L.DEFINES["SGAN_BCE_WEIGHTED_WS_BYTES"]
 
 
 def bce_weighted_fwd(p, t, Creal, class_w, nw, loss_out):
@@ -1007,7 +1007,7 @@ def bce_weighted_bwd(p, t, Creal, class_w, nw, gout, dp):
                                           _ptr(gout), _ptr(_act(dp)), dp.stride(1), _stream()), "sgan_bce_weighted_bwd")
 
 
-SEGHEAD_WS_BYTES = 8192   # SGAN_SEGHEAD_WS_BYTES
+SEGHEAD_WS_BYTES = L.DEFINES["SGAN_SEGHEAD_WS_BYTES"]
 SEGHEAD_SOFTMAX, SEGHEAD_SIGMOID = L.SEGHEAD_SOFTMAX, L.SEGHEAD_SIGMOID
 
 
@@ -1175,8 +1175,8 @@ def ema_multi(segs, decay, warmup, state):
 # Differentiable augmentation of discriminator inputs (sgan_diffaug.hip).  A record is 8 words of device memory,
 # {b, a, ty, tx, cy0, cy1, cx0, cx1}: `records` below is an int32 [n, 8] tensor whose first two columns hold the bits of two floats.
 # ------------------------------------------------------------------------------------------------
-DIFFAUG_BITS = {'translation': 1, 'cutout': 2, 'brightness': 4, 'contrast': 8}      # SGAN_DIFFAUG_* of include/sgan_hip.h
-DIFFAUG_MAX_JOBS = 8
+DIFFAUG_BITS = {n: L.DEFINES['SGAN_DIFFAUG_' + n.upper()] for n in ('translation', 'cutout', 'brightness', 'contrast')}
+DIFFAUG_MAX_JOBS = L.DEFINES['SGAN_DIFFAUG_MAX_JOBS']
 
 
 def _diffaug_records(records, n, what):
@@ -1417,13 +1417,13 @@ def as_nhwc(t: torch.Tensor) -> torch.Tensor:
 # ------------------------------------------------------------------------------------------------
 _metric_err = {}
 _metric_ws = {}       # (C symbol of the size query, H, W, device index) -> the int64 scratch of that size
-REGION_COLS = 16      # int64 per row of a region table (include/sgan_hip.h, sgan_region_stats)
+REGION_COLS = L.DEFINES["SGAN_REGION_COLS"]      # int64 per row of a region table (include/sgan_hip.h, sgan_region_stats)
 # acc_i / counts_out and acc_f / sums_out of object_match_accumulate (SGAN_OBJ_* of include/sgan_hip.h); TP_k: matches at IoU > (10 + k) / 20
 OBJECT_COUNTS = tuple('TP_%d' % k for k in range(10)) + ('N_t', 'N_s', 'images', 'SEGn', 'zero14', 'zero15')
 OBJECT_SUMS = ('SIoU', 'SSEG')
 # acc_i / counts_out and acc_f / sums_out of boundary_accumulate (SGAN_BND_* of include/sgan_hip.h); bin k: (k - 1)^2 < distance^2 <= k^2,
 # bin 31: farther than 30 pixels, or the other map has no wall
-BOUNDARY_BINS = 32
+BOUNDARY_BINS = L.DEFINES["SGAN_BND_BINS"]
 BOUNDARY_COUNTS = (tuple('hist_s_%d' % k for k in range(BOUNDARY_BINS)) + tuple('hist_t_%d' % k for k in range(BOUNDARY_BINS))
                    + ('N_s', 'N_t', 'images', 'haus_images', 'defined_s', 'defined_t', 'max_dsq_s', 'max_dsq_t')
                    + tuple('zero%d' % k for k in range(72, 80)))
@@ -1919,8 +1919,8 @@ def topo_accumulate(t, s, acc_i, t_thin=None, s_thin=None, window=64, stride=Non
 
 
 # ---- soft-clDice (sgan_cldice.hip; include/sgan_hip.h, "soft-clDice"): the loss whose hard form topo_accumulate scores ---------------
-CLDICE_MAX_ITERS = 16          # SGAN_CLDICE_MAX_ITERS
-CLDICE_STATE_BYTES = 4096      # SGAN_CLDICE_STATE_BYTES
+CLDICE_MAX_ITERS = L.DEFINES["SGAN_CLDICE_MAX_ITERS"]
+CLDICE_STATE_BYTES = L.DEFINES["SGAN_CLDICE_STATE_BYTES"]
 CLDICE_STATE = ('A', 'B', 'C', 'D', 'L', 'gA', 'gB', 'gC')      # the first doubles of the state sgan_cldice_finish writes
 _cldice_ws = {}                # (H, W, iters, backward, device index) -> the float32 scratch
 
@@ -2031,9 +2031,9 @@ def cldice_backward(t, st, state, iters, work, dp=None, gout=None):
 
 
 # ---- Lovasz-softmax (sgan_lovasz.hip; include/sgan_hip.h, "Lovasz-softmax") ------------------------------------------------------------
-LOVASZ_MAX_CLASSES = 8           # SGAN_LOVASZ_MAX_CLASSES
-LOVASZ_MAX_PIXELS = 1 << 20      # SGAN_LOVASZ_MAX_PIXELS
-LOVASZ_STATE_BYTES = 256         # SGAN_LOVASZ_STATE_BYTES
+LOVASZ_MAX_CLASSES = L.DEFINES["SGAN_LOVASZ_MAX_CLASSES"]
+LOVASZ_MAX_PIXELS = L.DEFINES["SGAN_LOVASZ_MAX_PIXELS"]
+LOVASZ_STATE_BYTES = L.DEFINES["SGAN_LOVASZ_STATE_BYTES"]
 LOVASZ_STATE = {'L': 0, 'm': 1, 'Lc': 2, 'scale': 10}      # doubles of the state; the int32 G of the listed classes at byte 192
 
 
@@ -2153,9 +2153,9 @@ def lovasz_backward(p, classes, work, dp=None, gout=None):
 
 
 # ---- Tversky / focal loss terms on the logits (sgan_segterms.hip; include/sgan_hip.h, "Segmentation loss terms") --------------------------
-SEGTERMS_MAX_CLASSES = 8         # SGAN_SEGTERMS_MAX_CLASSES
-SEGTERMS_STATE_BYTES = 544       # SGAN_SEGTERMS_STATE_BYTES
-SEGTERMS_WS_BYTES = 106504       # SGAN_SEGTERMS_WS_BYTES
+SEGTERMS_MAX_CLASSES = L.DEFINES["SGAN_SEGTERMS_MAX_CLASSES"]
+SEGTERMS_STATE_BYTES = L.DEFINES["SGAN_SEGTERMS_STATE_BYTES"]
+SEGTERMS_WS_BYTES = L.DEFINES["SGAN_SEGTERMS_WS_BYTES"]
 SEGTERMS_STATE = {'class': 0, 'focal_num': 64, 'focal_norm': 65, 'L_T': 66, 'L_F': 67}      # doubles; per class 8: TP FP FN D TI L_c G(0) G(1)
 
 
