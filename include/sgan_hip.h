@@ -1416,6 +1416,55 @@ int sgan_seg_terms_backward(const float* logits, int32_t ld, int32_t npix, int32
                             const double* state, const float* gout_tversky, const float* gout_focal, float* dlogits, int32_t dld,
                             void* stream);
 
+/* ---- Distance-map loss terms: boundary loss and Hausdorff loss of one class on the LOGITS (not in the reference) ----
+ * What the boundary scores (BoundF, HausD, ASSD) rank, as a loss: the boundary loss of Kervadec et al. (MIDL 2019) and the
+ * distance-transform Hausdorff loss HD_DT of Karimi & Salcudean (TMI 2019).  util.signed_edt_sq and util.dist_terms_ref are the NumPy
+ * restatements.
+ *
+ * sgan_signed_edt_workspace: bytes of the workspace sgan_signed_edt_sq needs for an H x W plane (< 0: bad shape).
+ * sgan_signed_edt_sq: the signed squared Euclidean distance map.  The plane is read exactly as sgan_edt_sq reads it, pixel (y, x) at
+ *   plane[(y * W + x) * pix_stride]; a pixel is inside when its value is > 0.5 (a NaN and an exact 0.5 are outside).
+ *   sdsq, int32 [H * W], exact: on an outside pixel +(the smallest dy^2 + dx^2 to an inside pixel), >= 1; on an inside pixel -(the
+ *   smallest dy^2 + dx^2 to an outside pixel), <= -1; 0 everywhere when the plane has no inside pixel or no outside pixel, decided on
+ *   the device from sgan_edt_sq's -1, nothing read back.  sgan_edt_sq of the plane into sdsq, a pass that writes the complement plane,
+ *   sgan_edt_sq of that, a pass that combines the two: ten launches whose grids depend on (H, W) only, so the call captures into a
+ *   hipGraph, replays on any other plane and gives the same bits on every run.  The workspace may hold anything on entry.  Shapes
+ *   as sgan_edt_sq: H, W <= 32768 and H W < 2^30.  dev_err as sgan_edt_sq: required, no bit set.  A null pointer, a bad shape, a
+ *   pixel stride < 1 and a short or misaligned (16 bytes) workspace return 1 with sgan_last_error set and nothing launched.
+ *
+ * The loss node.  `logits`, ld, npix, C, mode, `label_or_target` and tld as sgan_seg_terms_forward takes them (C <= 16 logical
+ *   channels; SGAN_SEGHEAD_SOFTMAX: the int64 label map, SGAN_SEGHEAD_SIGMOID: the float target [npix][tld]).  One class `cls` < C:
+ *   p = softmax(z)_cls or sigmoid(z_cls), computed in registers; g = [y == cls] or target_cls; N = npix.  A pixel whose label lies
+ *   outside [0, C) adds to no sum and gets a zero gradient.  t_sdsq, p_sdsq: int32 [npix], the signed maps (sgan_signed_edt_sq) of
+ *   the truth and of the thresholded prediction, both constants of the node; p_sdsq may be NULL when the Hausdorff term is off.
+ *   Boundary (`boundary` != 0), s = t_sdsq: phi = sqrt(s) where s > 0, -(sqrt(-s) - 1) where s < 0, 0 where s == 0 (Kervadec's
+ *     published level set);  L_B = sum phi p / N;  dL_B/dp = phi / N.
+ *   Hausdorff (`hausdorff` != 0), 0 < alpha <= 4: F = |t_sdsq|^(alpha / 2) + |p_sdsq|^(alpha / 2), at alpha == 2 the exact integer
+ *     |t_sdsq| + |p_sdsq| without a pow;  L_H = sum (p - g)^2 F / N;  dL_H/dp = 2 (p - g) F / N.
+ *   To the logits, G = gout_boundary dL_B/dp + gout_hausdorff dL_H/dp: softmax dz_k = G p (delta_k,cls - p_k); sigmoid
+ *     dz_cls = G p (1 - p), every other channel 0.  p in fp32, the terms and G in fp64, G rounded once, dz in fp32.
+ * sgan_dist_loss_forward: one launch.  Writes the state (SGAN_DISTLOSS_STATE_BYTES, doubles: [0] sum phi p, [1] sum (p - g)^2 F,
+ *   [2] N, [3] L_B, [4] L_H; [5 .. 7] not written; a sum of a term that is off is 0) and both losses as device floats (0 for a term
+ *   that is off).  The fp64 sums are taken in an order fixed by npix.  `workspace`: SGAN_DISTLOSS_WS_BYTES of 8-byte aligned device
+ *   scratch, ZERO on first use, owned by one stream at a time and left zeroed by every call.
+ * sgan_dist_loss_backward: one launch, from the same logits, label and maps: dlogits [npix][dld] as above, the upstream gradients
+ *   device floats, NULL = that term is not taken; the padding channels dld > C are written as zeros.
+ * The grid depends on npix only; no floating-point atomics, no workgroup waits on another, nothing is read back or allocated: both
+ * calls capture into a hipGraph and give the same bits on every run and in every row layout.  Return 1, the reason in
+ * sgan_last_error and nothing launched: C > 16, cls outside [0, C), both terms off, alpha outside (0, 4] with the Hausdorff term on,
+ * a NULL required pointer (p_sdsq with the Hausdorff term on), rows shorter than C, a misaligned state or workspace. */
+#define SGAN_DISTLOSS_STATE_BYTES 64
+#define SGAN_DISTLOSS_WS_BYTES 8200
+int64_t sgan_signed_edt_workspace(int32_t H, int32_t W);
+int sgan_signed_edt_sq(const float* plane, int64_t pix_stride, int32_t H, int32_t W, int32_t* sdsq, void* workspace,
+                       int64_t workspace_bytes, int32_t* dev_err, void* stream);
+int sgan_dist_loss_forward(const float* logits, int32_t ld, int32_t npix, int32_t C, int32_t mode, const void* label_or_target, int32_t tld,
+                           int32_t cls, const int32_t* t_sdsq, const int32_t* p_sdsq, int32_t boundary, int32_t hausdorff, double alpha,
+                           double* state, float* loss_boundary, float* loss_hausdorff, void* workspace, void* stream);
+int sgan_dist_loss_backward(const float* logits, int32_t ld, int32_t npix, int32_t C, int32_t mode, const void* label_or_target, int32_t tld,
+                            int32_t cls, const int32_t* t_sdsq, const int32_t* p_sdsq, int32_t boundary, int32_t hausdorff, double alpha,
+                            const float* gout_boundary, const float* gout_hausdorff, float* dlogits, int32_t dld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

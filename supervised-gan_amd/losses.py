@@ -651,6 +651,74 @@ def seg_terms(logits, label_or_target, mode, classes=(), alpha=0.5, beta=0.5, sm
                              None if focal_gamma is None else float(focal_gamma), cw, buffers)
 
 
+class DistLossBuffers:
+    """What a boundary / Hausdorff node keeps between calls for [1, C, H, W] logits: the fp64 state the forward writes, the zeroed
+    workspace of the forward's hand-off, the two loss scalars and the gradient buffer the node hands out, so that a step allocates
+    nothing.  One node at a time, as SegTermsBuffers."""
+
+    def __init__(self, C, H, W, device):
+        self.shape = (C, H, W)
+        self.state = ops.new_dist_loss_state(device)
+        self.work = ops.new_dist_loss_workspace(device)
+        self.loss_b = torch.zeros((), dtype=torch.float32, device=device)
+        self.loss_h = torch.zeros((), dtype=torch.float32, device=device)
+        self.dz = torch.empty((H, W, pad4(C)), dtype=torch.float32, device=device)
+
+    def fits(self, C, H, W, device):
+        return self.shape == (C, H, W) and self.dz.device == device
+
+
+class _DistTermsFn(torch.autograd.Function):
+    """(L_B, L_H) from the logits in one launch (sgan_dist_loss_forward); the backward is one launch too (sgan_dist_loss_backward): it
+    takes the two upstream gradients as device scalars -- a term without one is not taken -- and writes the gradient of the logits."""
+
+    @staticmethod
+    def forward(ctx, logits, lt, mode, cls, t_sdsq, p_sdsq, boundary, alpha, bufs):
+        zb = ops.as_nhwc(logits)
+        C_ = logits.shape[1]
+        lt = lt.reshape(-1).contiguous() if mode == ops.SEGHEAD_SOFTMAX else ops.as_nhwc(lt)
+        ops.dist_loss_forward(zb, C_, mode, lt, cls, t_sdsq, p_sdsq, boundary, alpha, bufs.state, bufs.loss_b, bufs.loss_h, bufs.work)
+        ctx.zb, ctx.lt, ctx.C, ctx.mode, ctx.cls, ctx.maps, ctx.boundary, ctx.alpha, ctx.bufs = zb, lt, C_, mode, cls, (t_sdsq, p_sdsq), boundary, alpha, bufs
+        ctx.set_materialize_grads(False)      # a term nobody uses arrives as None: the kernel then leaves it out
+        return bufs.loss_b.detach(), bufs.loss_h.detach()      # aliases of the persistent scalars, as _SegTermsFn's
+
+    @staticmethod
+    def backward(ctx, gb, gh):
+        none = (None,) * 9
+        if (gb is None and gh is None) or not ctx.needs_input_grad[0]:
+            return none
+        gb = None if gb is None or not ctx.boundary else gb.contiguous().float()
+        gh = None if gh is None or ctx.alpha is None else gh.contiguous().float()
+        dz = ops.dist_loss_backward(ctx.zb, ctx.C, ctx.mode, ctx.lt, ctx.cls, ctx.maps[0], ctx.maps[1], ctx.boundary, ctx.alpha, gb, gh,
+                                    ctx.bufs.dz)
+        return (ops.logical_view(dz, ctx.C),) + none[1:]
+
+
+def dist_terms(logits, label_or_target, mode, cls, t_sdsq, p_sdsq=None, boundary=True, hausdorff_alpha=None, buffers=None):
+    """The boundary loss (Kervadec et al., MIDL 2019) and the distance-transform Hausdorff loss (Karimi & Salcudean, TMI 2019) of
+    class `cls` of the [1, C, H, W] fp32 logits on the device, against the int64 label map (mode ops.SEGHEAD_SOFTMAX) or the
+    [1, C, H, W] float target (ops.SEGHEAD_SIGMOID): (L_B, L_H), float32 device scalars; util.dist_terms_ref states the mathematics.
+    t_sdsq / p_sdsq: the signed squared distance maps (ops.signed_edt_sq, int32 [H, W]) of the truth plane and of the thresholded
+    prediction, constants of the node.  boundary False: that term is off and L_B = 0; hausdorff_alpha None: the Hausdorff term is off,
+    L_H = 0 and p_sdsq is not read; one of them must be on.  The gradient flows to the logits only, each term's times its own
+    upstream gradient.  buffers: a DistLossBuffers the caller keeps between steps (None: made here).  One launch forward, one
+    backward; no fallback: off the device, with a batch or above 16 channels it raises."""
+    ops.require_gpu(logits, "dist_terms")
+    if not _bce_envelope(logits):
+        raise SganError(f"dist_terms: not covered ({tuple(logits.shape)} {logits.dtype}: [1, C <= 16, H, W] fp32 logits on the device)")
+    lt = label_or_target.detach()
+    _, C_, H, W = logits.shape
+    if mode == ops.SEGHEAD_SOFTMAX:
+        assert lt.dtype == torch.int64 and lt.device == logits.device and lt.numel() == H * W, "dist_terms: an int64 label map on the logits' device"
+    else:
+        assert _bce_envelope(lt) and lt.shape == logits.shape, "dist_terms: a [1, C, H, W] fp32 target on the logits' device"
+    if buffers is None:
+        buffers = DistLossBuffers(C_, H, W, logits.device)
+    assert buffers.fits(C_, H, W, logits.device), (buffers.shape, logits.shape)
+    return _DistTermsFn.apply(logits, lt, int(mode), int(cls), t_sdsq, None if hausdorff_alpha is None else p_sdsq, bool(boundary),
+                              None if hausdorff_alpha is None else float(hausdorff_alpha), buffers)
+
+
 class GANLossMultiClass(nn.Module):
     """GANLossMultiClass (models/networks.py:188-202): CrossEntropyLoss over the class channel of every pixel of a
     discriminator map against one class: one forward and one backward launch (sgan_ce_fwd / sgan_ce_bwd)."""

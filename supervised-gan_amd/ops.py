@@ -2242,6 +2242,118 @@ def seg_terms_backward(z, Creal, mode, label_or_target, classes, focal_gamma, cl
     return dz
 
 
+# ---- distance-map loss terms on the logits (sgan_distloss.hip; include/sgan_hip.h, "Distance-map loss terms") ------------------------------
+DISTLOSS_STATE_BYTES = L.DEFINES["SGAN_DISTLOSS_STATE_BYTES"]
+DISTLOSS_WS_BYTES = L.DEFINES["SGAN_DISTLOSS_WS_BYTES"]
+DISTLOSS_STATE = {'sum_B': 0, 'sum_H': 1, 'N': 2, 'L_B': 3, 'L_H': 4}      # doubles
+
+
+def signed_edt_workspace(H, W, device):
+    """The scratch of signed_edt_sq for H x W planes (edt_sq's workspace, the complement plane and the second transform), cached per
+    (H, W, device) like edt_workspace; the kernels initialise what they use."""
+    return _metric_workspace("sgan_signed_edt_workspace", H, W, device)
+
+
+def signed_edt_sq(plane, out=None, workspace=None):
+    """The signed squared Euclidean distance map of the pixels of `plane` [H, W] that are > 0.5 (sgan_signed_edt_sq;
+    util.signed_edt_sq is the host yardstick): int32 [H, W], +(dy^2 + dx^2 to the nearest inside pixel) outside, -(dy^2 + dx^2 to the
+    nearest outside pixel) inside, 0 everywhere when the plane is empty or full.  Only enqueues -- the launch sequence depends on the
+    shape alone -- and reads `plane` in place when its rows are W pixel strides apart."""
+    plane = _plane(plane, "signed_edt_sq")
+    H, W = plane.shape
+    dev = plane.device
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.int32, device=dev)
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() == H * W and out.device == dev
+    ws = signed_edt_workspace(H, W, dev) if workspace is None else workspace
+    L.check(L.lib().sgan_signed_edt_sq(_ptr(plane), plane.stride(1), H, W, _ptr(out), _ptr(ws), ws.numel() * ws.element_size(),
+                                       _ptr(metric_err(dev)), _stream()), "sgan_signed_edt_sq")
+    return out
+
+
+def new_dist_loss_state(device):
+    """The fp64 state dist_loss_forward writes (8 doubles, DISTLOSS_STATE)."""
+    return torch.zeros(DISTLOSS_STATE_BYTES // 8, dtype=torch.float64, device=device)
+
+
+def new_dist_loss_workspace(device):
+    """The slots and ticket of dist_loss_forward: zero on first use, left zeroed by every call; one per node and stream."""
+    return torch.zeros(DISTLOSS_WS_BYTES // 8, dtype=torch.float64, device=device)
+
+
+def _dist_loss_args(what, z, Creal, mode, label_or_target, t_sdsq, p_sdsq, hausdorff_alpha):
+    """The operand checks both calls share: every tensor against its storage, before anything is launched.  Returns
+    (rows_fit, tld, hausdorff, alpha)."""
+    require_gpu(z, what)
+    H, W, _ = z.shape
+    dev = z.device
+
+    def rows_fit(t, name, written):
+        _act(t)
+        row = t.stride(1) if (written or t.stride(1) in (4, 8, 12, 16)) else Creal
+        if (t.device != dev or t.shape[0] * t.shape[1] != H * W or t.shape[2] < Creal or t.stride(1) < Creal
+                or (H * W - 1) * t.stride(1) + row > _avail(t)):
+            raise L.SganError(f"{what} {name}: tensor {tuple(t.shape)} (pixel stride {t.stride(1)}, {_avail(t)} elements of storage) does "
+                              f"not hold {H}x{W} rows of {row}; nothing was launched")
+
+    rows_fit(z, "logits", False)
+    tld = 0
+    if mode == SEGHEAD_SOFTMAX:
+        assert (label_or_target.dtype == torch.int64 and label_or_target.device == dev and label_or_target.is_contiguous()
+                and label_or_target.numel() == H * W), (label_or_target.shape, label_or_target.dtype)
+    else:
+        rows_fit(label_or_target, "target", False)
+        tld = label_or_target.stride(1)
+    hausdorff = hausdorff_alpha is not None
+    for m, name in ((t_sdsq, "t_sdsq"), (p_sdsq, "p_sdsq")):
+        if m is None and name == "p_sdsq" and not hausdorff:
+            continue
+        if m is None:
+            raise L.SganError(f"{what}: {name} is required; nothing was launched")
+        assert m.dtype == torch.int32 and m.is_contiguous() and m.numel() == H * W and m.device == dev, (name, m.shape, m.dtype)
+    return rows_fit, tld, int(hausdorff), float(hausdorff_alpha) if hausdorff else 2.0
+
+
+def dist_loss_forward(z, Creal, mode, label_or_target, cls, t_sdsq, p_sdsq, boundary, hausdorff_alpha, state, loss_b, loss_h, work):
+    """sgan_dist_loss_forward on an [H, W, Cs] logits buffer: the boundary term (`boundary` False: off) and the Hausdorff term with
+    exponent hausdorff_alpha (None: off) of class `cls` against the signed maps t_sdsq / p_sdsq (int32 [H, W], signed_edt_sq; p_sdsq
+    None with the Hausdorff term off) into `state` (new_dist_loss_state) and the float32 device scalars loss_b, loss_h;
+    `label_or_target` as seg_head takes it; `work`: new_dist_loss_workspace.  One launch, only enqueued.  Not covered (SganError,
+    nothing launched): more than 16 channels, a class out of range, both terms off, alpha outside (0, 4]."""
+    what = "dist_loss_forward"
+    _, tld, hausdorff, alpha = _dist_loss_args(what, z, Creal, mode, label_or_target, t_sdsq, p_sdsq, hausdorff_alpha)
+    H, W, _ = z.shape
+    for t in (loss_b, loss_h):
+        assert t.dtype == torch.float32 and t.numel() == 1 and t.device == z.device
+    assert state.dtype == torch.float64 and state.is_contiguous() and state.numel() * 8 >= DISTLOSS_STATE_BYTES and state.device == z.device
+    assert work.dtype == torch.float64 and work.is_contiguous() and work.numel() * 8 >= DISTLOSS_WS_BYTES and work.device == z.device
+    rc = L.lib().sgan_dist_loss_forward(_ptr(z), z.stride(1), H * W, int(Creal), int(mode), _ptr(label_or_target), tld, int(cls), _ptr(t_sdsq),
+                                        _ptr(p_sdsq) if hausdorff else _ptr(None), int(bool(boundary)), hausdorff, alpha, _ptr(state),
+                                        _ptr(loss_b), _ptr(loss_h), _ptr(work), _stream())
+    if rc == 1:
+        raise L.SganError(f"sgan_dist_loss_forward: {L.lib().sgan_last_error().decode()}; nothing was launched")
+    L.check(rc, "sgan_dist_loss_forward")
+
+
+def dist_loss_backward(z, Creal, mode, label_or_target, cls, t_sdsq, p_sdsq, boundary, hausdorff_alpha, gout_b, gout_h, dz):
+    """dz [H, W, Cs'] = gout_b * dL_B/dz + gout_h * dL_H/dz from the same logits, label and maps as dist_loss_forward
+    (sgan_dist_loss_backward, one launch).  gout_b / gout_h: float32 device scalars, None = that term is not taken (its part of dz is
+    exactly zero); the padding channels of dz are written as zeros."""
+    what = "dist_loss_backward"
+    rows_fit, tld, hausdorff, alpha = _dist_loss_args(what, z, Creal, mode, label_or_target, t_sdsq, p_sdsq, hausdorff_alpha)
+    H, W, _ = z.shape
+    rows_fit(dz, "dlogits", True)
+    for g in (gout_b, gout_h):
+        assert g is None or (g.dtype == torch.float32 and g.numel() == 1 and g.device == z.device)
+    rc = L.lib().sgan_dist_loss_backward(_ptr(z), z.stride(1), H * W, int(Creal), int(mode), _ptr(label_or_target), tld, int(cls), _ptr(t_sdsq),
+                                         _ptr(p_sdsq) if hausdorff else _ptr(None), int(bool(boundary)), hausdorff, alpha, _ptr(gout_b),
+                                         _ptr(gout_h), _ptr(dz), dz.stride(1), _stream())
+    if rc == 1:
+        raise L.SganError(f"sgan_dist_loss_backward: {L.lib().sgan_last_error().decode()}; nothing was launched")
+    L.check(rc, "sgan_dist_loss_backward")
+    return dz
+
+
 def clean_workspace(H, W, device):
     """The scratch of clean_wall for H x W planes (edt_sq's workspace, one int32 plane for dsq / labels, the area table and the
     complement plane), cached per (H, W, device) like edt_workspace; the kernels initialise what they use."""

@@ -143,6 +143,7 @@ class BaseOptions:
         check_lovasz_options(self.opt)
         check_dice_options(self.opt)
         check_focal_options(self.opt)
+        check_dist_options(self.opt)
         check_clean_options(self.opt, self.parser)
         check_topo_options(self.opt, self.parser)
         check_elastic_options(self.opt)
@@ -257,6 +258,24 @@ def check_focal_options(opt):
         "--focal_weight adds the focal loss to the segmentation trainer's generator loss: it needs --model segmentation (got '%s')" % \
         getattr(opt, 'model', None)
     assert 0.0 <= opt.focal_gamma <= 8.0, "--focal_gamma G: 0 <= G <= 8 (got %g)" % opt.focal_gamma
+
+
+def check_dist_options(opt):
+    """--boundary_loss_weight LAMBDA adds the boundary loss (Kervadec et al., MIDL 2019) and --hausdorff_weight LAMBDA the
+    distance-transform Hausdorff loss (Karimi & Salcudean, TMI 2019) with exponent --hausdorff_alpha A of the --dist_class channel to
+    the generator loss of --model segmentation (any head, with or without discriminators); LAMBDA >= 0 with 0 = off, 0 < A <= 4, a
+    class index.  Another model refuses them.  With both weights at 0 nothing is looked at and nothing is changed."""
+    wb, wh = getattr(opt, 'boundary_loss_weight', 0.0), getattr(opt, 'hausdorff_weight', 0.0)
+    if wb == 0.0 and wh == 0.0:
+        return
+    assert wb >= 0.0, "--boundary_loss_weight LAMBDA: a weight >= 0, 0 = off (got %g)" % wb      # a NaN fails the comparison
+    assert wh >= 0.0, "--hausdorff_weight LAMBDA: a weight >= 0, 0 = off (got %g)" % wh
+    assert getattr(opt, 'model', None) == 'segmentation', \
+        "--boundary_loss_weight / --hausdorff_weight add distance-map terms to the segmentation trainer's generator loss: they need " \
+        "--model segmentation (got '%s')" % getattr(opt, 'model', None)
+    if wh > 0.0:
+        assert 0.0 < opt.hausdorff_alpha <= 4.0, "--hausdorff_alpha A: 0 < A <= 4 (got %g)" % opt.hausdorff_alpha
+    assert opt.dist_class >= 0, "--dist_class: a class index (got %d)" % opt.dist_class
 
 
 def check_clean_options(opt, parser=None):
@@ -486,6 +505,16 @@ class TrainOptions(BaseOptions):
           help='--model segmentation: add LAMBDA * focal loss of the logits (class weights from --weights) to the generator loss '
                '(with or without discriminators, softmax or sigmoid head); 0 = off')
         a('--focal_gamma', type=float, default=2.0, metavar='G', help='--focal_weight: the focusing exponent, 0 <= G <= 8 (0 = cross-entropy)')
+        # the distance-map terms of the segmentation trainers, on the logits (Kervadec et al., MIDL 2019; Karimi & Salcudean, TMI 2019; not in the reference)
+        a('--boundary_loss_weight', type=float, default=0.0, metavar='LAMBDA',
+          help='--model segmentation: add LAMBDA * boundary loss (the --dist_class probability weighted by the signed distance to the '
+               'true boundary) to the generator loss (with or without discriminators, softmax or sigmoid head); 0 = off')
+        a('--hausdorff_weight', type=float, default=0.0, metavar='LAMBDA',
+          help='--model segmentation: add LAMBDA * distance-transform Hausdorff loss ((p - g)^2 weighted by the distance maps of the '
+               'truth and of the thresholded prediction, recomputed every step) of --dist_class to the generator loss; 0 = off')
+        a('--hausdorff_alpha', type=float, default=2.0, metavar='A', help='--hausdorff_weight: the exponent of the distances, 0 < A <= 4')
+        a('--dist_class', type=int, default=0, metavar='C',
+          help='the class of --boundary_loss_weight / --hausdorff_weight (default 0, the wall)')
         # random elastic deformation of every training crop, on the device (not in the reference, which augments with crop, flip and rot90)
         a('--elastic', type=float, default=None, nargs=2, metavar=('G', 'SIGMA'),
           help='image-folder feeders: deform every training crop by a smooth random field -- (G + 3)^2 displacement vectors drawn from '

@@ -17,8 +17,8 @@ import torch
 
 from . import networks, ops, util
 from .cgan_model import CGANModel
-from .losses import (ClDiceBuffers, LovaszBuffers, SegTermsBuffers, class_probability_plane, cross_entropy_logits, lovasz_softmax, seg_head,
-                     seg_terms, sigmoid_channels, soft_cldice, softmax_channels, weighted_bce)
+from .losses import (ClDiceBuffers, DistLossBuffers, LovaszBuffers, SegTermsBuffers, class_probability_plane, cross_entropy_logits, dist_terms,
+                     lovasz_softmax, seg_head, seg_terms, sigmoid_channels, soft_cldice, softmax_channels, weighted_bce)
 from .options import check_tile_options
 from .seg_metrics import SegMetrics, SegMetricsMixin
 
@@ -80,6 +80,14 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
                              lam_f, float(opt.focal_gamma) if lam_f > 0.0 else None)
             self._st_bufs = None      # persistent: the node's buffers
             self.loss_G_Dice = self.loss_G_Focal = 0
+        self.distterms = None      # (lambda_boundary, lambda_hausdorff, alpha, class) of the distance-map terms, or None: nothing runs
+        if self.isTrain and (getattr(opt, 'boundary_loss_weight', 0.0) > 0.0 or getattr(opt, 'hausdorff_weight', 0.0) > 0.0):
+            assert opt.dist_class < self.num_classes, "--dist_class %d: there are %d classes" % (opt.dist_class, self.num_classes)
+            assert opt.batchSize == 1 and self.device.type == 'cuda', \
+                "--boundary_loss_weight / --hausdorff_weight: batch 1 on the device, like every kernel of this path"
+            self.distterms = (float(opt.boundary_loss_weight), float(opt.hausdorff_weight), float(opt.hausdorff_alpha), int(opt.dist_class))
+            self._dl_truth = self._dl_tsdsq = self._dl_psdsq = self._dl_bufs = None      # persistent: the truth plane, both maps, the node's buffers
+            self.loss_G_Boundary = self.loss_G_Hausdorff = 0
         self.seg_metrics = SegMetrics(opt, self.device, self.num_classes)
         self.reset_accs()
         self._tiling = not self.isTrain and getattr(opt, 'tiling', False)      # test(): whole-image inference (check_tile_options)
@@ -120,6 +128,8 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
                 ops.label_weight_sum(self.label.reshape(-1), self.num_classes, self.class_weights, self.norm)
         if getattr(self, 'cldice', None) is not None:
             self._cldice_truth()
+        if getattr(self, 'distterms', None) is not None:
+            self._dist_truth()
 
     def _cldice_truth(self):
         """The truth plane of --cldice_class (1.0 where the label is that class) and its soft skeleton into persistent buffers, once per
@@ -134,6 +144,46 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
         torch.eq(self.label[0], cls, out=self._cld_is)
         self._cld_truth.copy_(self._cld_is)
         ops.soft_skeleton(self._cld_truth, K, out=self._cld_tskel)
+
+    def _dist_truth(self):
+        """The truth plane of --dist_class (1.0 where the label is that class) and its signed squared distance map into persistent
+        buffers, once per set_input like the soft-clDice truth: a captured step keeps reading them.  Enqueues only."""
+        cls = self.distterms[3]
+        hw = tuple(self.label.shape[1:])
+        if self._dl_truth is None or tuple(self._dl_truth.shape) != hw:
+            self._dl_is = torch.empty(hw, dtype=torch.bool, device=self.device)
+            self._dl_truth = torch.empty(hw, dtype=torch.float32, device=self.device)
+            self._dl_tsdsq = torch.empty(hw, dtype=torch.int32, device=self.device)
+            self._dl_psdsq = torch.empty(hw, dtype=torch.int32, device=self.device) if self.distterms[1] > 0.0 else None
+        torch.eq(self.label[0], cls, out=self._dl_is)
+        self._dl_truth.copy_(self._dl_is)
+        ops.signed_edt_sq(self._dl_truth, out=self._dl_tsdsq)
+
+    def _with_dist_terms(self, loss):
+        """loss + lambda_boundary * boundary loss + lambda_hausdorff * Hausdorff loss of the --dist_class channel; the loss unchanged
+        with both options off.  The node reads the logits of the last forward() whether discriminators exist or not and hands the
+        gradient of the logits back.  The truth's map is the one set_input left; with the Hausdorff term on, the map of the
+        prediction is taken here, inside the step, from the detached --dist_class plane of fake_B thresholded at > 0.5 like every
+        metric: a graph replay computes it again.  A term whose weight is 0 is switched off in the call and takes no gradient."""
+        if self.distterms is None:
+            return loss
+        lam_b, lam_h, alpha, cls = self.distterms
+        shape = tuple(self.logit.shape[1:])
+        if self._dl_bufs is None or not self._dl_bufs.fits(*shape, self.logit.device):
+            self._dl_bufs = DistLossBuffers(*shape, self.logit.device)
+        if lam_h > 0.0:
+            ops.signed_edt_sq(self.fake_B.detach()[0, cls], out=self._dl_psdsq)
+        if self.use_sigmoid_ss:
+            mode, lt = ops.SEGHEAD_SIGMOID, self.real_B
+        else:
+            mode, lt = ops.SEGHEAD_SOFTMAX, self.label
+        self.loss_G_Boundary, self.loss_G_Hausdorff = dist_terms(self.logit, lt, mode, cls, self._dl_tsdsq, self._dl_psdsq, lam_b > 0.0,
+                                                                 alpha if lam_h > 0.0 else None, buffers=self._dl_bufs)
+        if lam_b > 0.0:
+            loss = loss + lam_b * self.loss_G_Boundary
+        if lam_h > 0.0:
+            loss = loss + lam_h * self.loss_G_Hausdorff
+        return loss
 
     def _with_cldice(self, loss):
         """loss + lambda * soft-clDice of the class plane; the loss unchanged with the option off.  With discriminators fake_B is the
@@ -299,7 +349,7 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
         if self.no_netD:      # :202-203,227: loss_G_GAN = 0, the cross-entropy forward() left behind is the whole loss
             self.loss_G_GAN = 0
             self.loss_G_CE = self._head_loss
-            self.loss_G = self._with_seg_terms(self._with_lovasz(self._with_cldice(self.loss_G_CE)))
+            self.loss_G = self._with_dist_terms(self._with_seg_terms(self._with_lovasz(self._with_cldice(self.loss_G_CE))))
             self._backward(self.loss_G)
             return
         skip = getattr(self.opt, 'skip_wasted_D_wgrad', False)
@@ -310,7 +360,8 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
         self.loss_G_GAN, self._each_G = self._d_losses([(d, fake, True) for d in self.netD], list(self.opt.lambda_D))
         for netD in self.netD:
             netD.compute_param_grads = True
-        self.loss_G = self._with_seg_terms(self._with_lovasz(self._with_cldice(self.loss_G_GAN + self.compute_cross_entropy_loss(weighted=True))))
+        self.loss_G = self._with_dist_terms(self._with_seg_terms(self._with_lovasz(self._with_cldice(
+            self.loss_G_GAN + self.compute_cross_entropy_loss(weighted=True)))))
         self._backward(self.loss_G)
 
     def get_current_errors(self):
@@ -322,6 +373,11 @@ class SegmentationModel(SegMetricsMixin, CGANModel):
                 extra = extra + [('G_Dice', float(self.loss_G_Dice.detach() if torch.is_tensor(self.loss_G_Dice) else 0.0))]
             if self.segterms[6] > 0.0:
                 extra = extra + [('G_Focal', float(self.loss_G_Focal.detach() if torch.is_tensor(self.loss_G_Focal) else 0.0))]
+        if self.distterms is not None:
+            if self.distterms[0] > 0.0:
+                extra = extra + [('G_Boundary', float(self.loss_G_Boundary.detach() if torch.is_tensor(self.loss_G_Boundary) else 0.0))]
+            if self.distterms[1] > 0.0:
+                extra = extra + [('G_Hausdorff', float(self.loss_G_Hausdorff.detach() if torch.is_tensor(self.loss_G_Hausdorff) else 0.0))]
         if self.no_netD:                                     # :253-257
             return OrderedDict([('G_CE', float(self.loss_G_CE.detach()))] + extra)
         return OrderedDict([('G_CE', float(self.loss_G_CE.detach())), ('G_GAN', float(self.loss_G_GAN.detach())),

@@ -653,6 +653,18 @@ def edt_sq(mask):
     return out.astype(np.int32)
 
 
+def signed_edt_sq(mask):
+    """The signed squared Euclidean distance map of a [H, W] mask (bool, or a map thresholded at > 0.5; a NaN and an exact 0.5 are
+    outside), from two edt_sq: int32 [H, W], +(the smallest dy^2 + dx^2 to an inside pixel) on an outside pixel, -(the smallest
+    dy^2 + dx^2 to an outside pixel) on an inside pixel, 0 everywhere when the mask has no inside or no outside pixel.  The host
+    yardstick of ops.signed_edt_sq."""
+    inside = _wall_mask(mask)
+    assert inside.ndim == 2, inside.shape
+    if not inside.any() or inside.all():
+        return np.zeros(inside.shape, dtype=np.int32)
+    return np.where(inside, -edt_sq(~inside), edt_sq(inside)).astype(np.int32)
+
+
 CLEAN_COUNTS = ('closed_pixels', 'wall_components_removed', 'wall_pixels_removed', 'cells_filled', 'cell_pixels_filled', 'images')
 
 
@@ -1385,3 +1397,70 @@ def seg_terms_ref(logits, label_or_target, mode, classes=(), alpha=0.5, beta=0.5
         state[64], state[65] = num, norm
     state[66], state[67] = LT, LF
     return LT, LF, state, dzT, dzF
+
+
+def dist_level_set(sdsq):
+    """Kervadec's level set from a signed squared distance map (signed_edt_sq): the distance outside, -(distance - 1) inside, 0
+    where the map is 0; float64."""
+    s = np.asarray(sdsq).astype(np.float64)
+    return np.where(s > 0, np.sqrt(np.abs(s)), np.where(s < 0, 1.0 - np.sqrt(np.abs(s)), 0.0))
+
+
+def dist_terms_ref(logits, label_or_target, mode, cls, t_sdsq, p_sdsq=None, boundary=True, hausdorff_alpha=None):
+    """The boundary loss (Kervadec et al., MIDL 2019) and the distance-transform Hausdorff loss (Karimi & Salcudean, TMI 2019, HD_DT)
+    of one class on the logits in NumPy fp64, in the semantics of include/sgan_hip.h, "Distance-map loss terms":
+    (L_B, L_H, state [5], dz_B [npix, C], dz_H [npix, C]), dz_X = dL_X/dz.
+
+    logits [npix, C] (read as fp32); mode 0 (softmax): label_or_target the integer label [npix], p = softmax(z)_cls, g = [y == cls],
+    a pixel with a label outside [0, C) takes no part; mode 1 (sigmoid): the target [npix, C], p = sigmoid(z_cls), g = target_cls.
+    t_sdsq, p_sdsq: the signed squared distance maps (signed_edt_sq) of the truth and of the thresholded prediction, [npix] integers,
+    constants.  N = npix.  Boundary (boundary False: off, L_B = 0): phi = dist_level_set(t_sdsq), L_B = sum phi p / N.  Hausdorff
+    (hausdorff_alpha None: off, L_H = 0): F = |t_sdsq|^(alpha / 2) + |p_sdsq|^(alpha / 2), L_H = sum (p - g)^2 F / N.  With
+    G = dL/dp: softmax dz_k = G p (delta_k,cls - p_k), sigmoid dz_cls = G p (1 - p).  state: sum phi p, sum (p - g)^2 F, N, L_B, L_H."""
+    z = np.asarray(logits, dtype=np.float32).astype(np.float64)
+    assert z.ndim == 2, z.shape
+    npix, C = z.shape
+    cls = int(cls)
+    assert 0 <= cls < C, (cls, C)
+    t_s = np.asarray(t_sdsq).reshape(npix).astype(np.int64)
+    if int(mode) == 0:
+        y = np.asarray(label_or_target).reshape(npix).astype(np.int64)
+        valid = ((y >= 0) & (y < C)).astype(np.float64)
+        m = z.max(axis=1, keepdims=True)
+        E = np.exp(z - m)
+        P = E / E.sum(axis=1, keepdims=True)
+        p = P[:, cls]
+        g = (y == cls).astype(np.float64)
+        dpdz = -p[:, None] * P
+        dpdz[:, cls] = p * (np.delete(E, cls, axis=1).sum(axis=1) / E.sum(axis=1))      # 1 - p without the cancellation
+    else:
+        t = np.asarray(label_or_target, dtype=np.float32).astype(np.float64).reshape(npix, C)
+        valid = np.ones(npix, np.float64)
+        p = 1.0 / (1.0 + np.exp(-z[:, cls]))
+        q = 1.0 / (1.0 + np.exp(z[:, cls]))      # 1 - p
+        g = t[:, cls]
+        dpdz = np.zeros((npix, C), np.float64)
+        dpdz[:, cls] = p * q
+    N = float(npix)
+    state = np.zeros(5, np.float64)
+    state[2] = N
+    dzB, dzH = np.zeros((npix, C), np.float64), np.zeros((npix, C), np.float64)
+    LB = LH = 0.0
+    if boundary:
+        phi = dist_level_set(t_s)
+        state[0] = float(np.sum(phi * p * valid))
+        LB = state[0] / N
+        dzB = (phi * valid / N)[:, None] * dpdz
+    if hausdorff_alpha is not None:
+        a = float(hausdorff_alpha)
+        assert 0.0 < a <= 4.0, a
+        p_s = np.asarray(p_sdsq).reshape(npix).astype(np.int64)
+        if a == 2.0:
+            F = (np.abs(t_s) + np.abs(p_s)).astype(np.float64)
+        else:
+            F = np.abs(t_s).astype(np.float64) ** (a / 2.0) + np.abs(p_s).astype(np.float64) ** (a / 2.0)
+        state[1] = float(np.sum((p - g) ** 2 * F * valid))
+        LH = state[1] / N
+        dzH = (2.0 * (p - g) * F * valid / N)[:, None] * dpdz
+    state[3], state[4] = LB, LH
+    return LB, LH, state, dzB, dzH
