@@ -631,6 +631,47 @@ int sgan_image_prep_elastic(const unsigned char* img, int32_t H0, int32_t W0, in
                             const float* ctrl, int32_t G, int32_t nearest_mask, float* dst, int32_t dst_ld, int32_t Cstore,
                             float* field_out /* may be NULL */, void* stream);
 
+/* ---- photometric augmentation of a prepared crop (not in the reference: the "gray value variations" of the U-Net baseline and the
+ * blur / gamma / contrast / noise / missing-data transforms of the EM pipelines) --------------------------------------------------
+ * Out of place: `src` -> `dst`, both padded NHWC fp32 [H][W][Cstore] with values in [-1, 1] (what sgan_image_prep* writes) and their
+ * own pixel strides.  Bit c of `channel_mask` marks channel c as an image channel (as in `nearest_mask`); the other channels -- the
+ * labels, the padding -- are copied bit for bit.  util.photo_ref / util.photo_bounds are the NumPy restatement.  The host draws the
+ * parameters; the entry reads `*rec_host` before it returns and hands the record to the kernel by value.  Per masked channel, in
+ * this order, a stage whose parameter is neutral being SKIPPED, not computed (the all-neutral call copies every bit):
+ *   1 blur      separable Gaussian of radius R (0 = neutral, <= SGAN_PHOTO_MAX_R, <= min(H, W) - 1), taps w[0 .. R]; rows first, then
+ *               columns; indices mirrored into the crop without repeating the edge.  A pass is acc = w[0] x0, then for k = 1 .. R
+ *               acc = fmaf(w[k], x(-k) + x(+k), acc); the row pass is rounded to fp32 once.
+ *   2 gamma     (1 = neutral, 0.5 .. 2) u = clamp(fmaf(0.5, s, 0.5), 0, 1), u = powf(u, gamma), s = fmaf(2, u, -1)
+ *   3 contrast, brightness   (contrast == 1 and brightness == 0 = neutral, contrast > 0) s = fmaf(contrast, s, 2 brightness)
+ *   4 noise     (noise == NULL or sigma_n == 0 = neutral, sigma_n >= 0) s = fmaf(sigma_n, noise[j][h][w], s), `noise` a dense
+ *               [popcount(channel_mask)][H][W] fp32 buffer (j counts the masked channels upwards) that the caller filled, e.g. with
+ *               sgan_normal_fill: the kernel holds no random number generator
+ *   5 clamp     to [-1, 1], only when stage 2, 3 or 4 ran
+ *   6 occlusion nbox <= SGAN_PHOTO_MAX_BOX boxes, rows [box_y0, box_y1) x columns [box_x0, box_x1) clipped to the crop (empty boxes
+ *               allowed): every masked channel becomes box_value; a later box wins.
+ * One workgroup per 32 x 32 tile; the tile and its R-pixel halo are staged in LDS once, the row pass goes to a second LDS buffer.  No
+ * atomics, the same bits on every run.  One 16-byte load and store per pixel when Cstore == 4, both strides are multiples of 4, both
+ * pointers 16-byte aligned and at most 3 channels are masked; a scalar path otherwise.
+ * Returns 1, the reason in sgan_last_error and nothing launched, for: a null src, dst or record; H, W < 1 or above 2^22; Cstore < 1
+ * or a stride below it; src and dst overlapping; R outside 0 .. min(SGAN_PHOTO_MAX_R, min(H, W) - 1); gamma outside [0.5, 2];
+ * contrast <= 0; sigma_n < 0; any non-finite parameter (the taps 0 .. R included); nbox outside 0 .. SGAN_PHOTO_MAX_BOX; a mask bit
+ * at or above Cstore. */
+#define SGAN_PHOTO_MAX_R 12
+#define SGAN_PHOTO_MAX_BOX 4
+typedef struct sgan_photo_rec {
+    int32_t R;       /* blur radius; 0: no blur */
+    float w[13];     /* w[0 .. R]: the centre tap and one side of the symmetric kernel (SGAN_PHOTO_MAX_R + 1 entries) */
+    float gamma;
+    float contrast;
+    float brightness;
+    float sigma_n;
+    int32_t nbox;
+    int32_t box_y0[4], box_y1[4], box_x0[4], box_x1[4];      /* SGAN_PHOTO_MAX_BOX entries each */
+    float box_value[4];
+} sgan_photo_rec;
+int sgan_image_photo(const float* src, int32_t src_ld, float* dst, int32_t dst_ld, int32_t H, int32_t W, int32_t Cstore,
+                     int32_t channel_mask, const sgan_photo_rec* rec_host, const float* noise /* may be NULL */, void* stream);
+
 /* ---- Image.resize in front of the crop (data/base_dataset.py:19-21 transforms.Scale(.., BILINEAR), :43-50 __scale_width;
  * data/aligned_dataset.py:25 AB.resize((2 loadSize, loadSize), BICUBIC)) --------------------------
  * `src` [H][W][C] uint8 (C <= 4, interleaved) -> `dst` [Ho][Wo][C] uint8, both in device memory, bit-exact with Pillow's 8-bit

@@ -13,6 +13,11 @@ here as x then y.
 of a smooth field after its other draws, uploads these few hundred floats, and the same single kernel gathers through the field
 (`sgan_image_prep_elastic`).  One field for both halves of an aligned pair, one per image otherwise.
 
+`--photo_aug LIST` (train options; not in the reference) varies the grey values of every training crop: after all the draws above the
+feeder draws the parameters of blur, gamma, contrast, brightness, noise and occlusion boxes (util.photo_draw), and one more kernel
+(`sgan_image_photo`) applies them to the image channels of the prepared crop.  One record for both halves of an aligned pair (each
+half with noise planes of its own), one per image otherwise.  Withheld wherever `--elastic` is.
+
 `--whole_image` / `--tta d4` (test options; not in the reference): the single-image feeder also yields the uint8 device image under
 'A_u8', and under `--whole_image` 'A' is the whole resized image, not a crop (`sgan_image_prep_tile`)."""
 import os
@@ -77,6 +82,35 @@ class _FolderDataset:
         from .options import elastic_nearest_mask
         return ops.image_prep_elastic(dev, x0, y0, n, flip, rot, ctrl, elastic_nearest_mask(self.opt))
 
+    def _draw_photo(self):
+        """--photo_aug on a training feeder: the util.PhotoRec of one crop (util.photo_draw documents the draws), drawn on the calling
+        thread AFTER the item's other draws, the elastic field included (none of which moves).  None when the option is off or the
+        feeder does not train: then no draw is made."""
+        if not self.opt.isTrain or getattr(self.opt, 'photo_aug', None) is None:
+            return None
+        from .util import photo_draw
+        return photo_draw(self.opt, self.opt.fineSize, rng=random)
+
+    def _photo(self, crops, rec):
+        """The prepared crops that share the record `rec` through sgan_image_photo.  The noise stage reads N(0, 1) planes that
+        ops.normal_fill writes into a scratch buffer of the feeder from the record's seed: crop 0 from stream offset 0, crop 1 (the
+        second half of an aligned pair) from the offset the first fill left behind."""
+        if rec is None:
+            return crops
+        from .options import photo_channel_mask
+        mask = photo_channel_mask(self.opt)
+        planes = None
+        if rec.sigma_n != 0.0:
+            n, P = crops[0].shape[0], bin(mask).count('1')
+            if getattr(self, '_photo_noise', None) is None or tuple(self._photo_noise.shape) != (2, P, n, n):
+                self._photo_noise = torch.empty((2, P, n, n), dtype=torch.float32, device=self.device)
+                self._photo_offset = torch.zeros(1, dtype=torch.int64, device=self.device)
+            self._photo_offset.zero_()
+            for i in range(len(crops)):
+                ops.normal_fill(self._photo_noise[i], rec.seed, self._photo_offset, advance=True)
+            planes = self._photo_noise
+        return [ops.image_photo(c, rec, mask, noise=None if planes is None else planes[i]) for i, c in enumerate(crops)]
+
     # An item is made in two halves: _host(index) -- file read, decode, resize: no random draws, safe on worker threads (PIL drops
     # the GIL while it decodes) -- and _device(index, host) -- the random draws in the reference's order, the upload, the kernel.
     def __getitem__(self, index):
@@ -121,6 +155,7 @@ class SingleFolderDataset(_FolderDataset):
             return self._device_tiled(img, path)
         draw = self._draw(img, path)
         A = self._prep(img, draw, self._draw_elastic())        # --elastic: the field after every other draw of the item
+        A, = self._photo([A], self._draw_photo())              # --photo_aug: its draws after the field's
         return {'A': ops.logical_view(A, 3), 'A_paths': [path]}
 
     def _device_tiled(self, img, path):
@@ -211,7 +246,9 @@ class UnalignedFolderDataset(SingleFolderDataset):
         da = self._draw(imgs[0], a)                  # A's draws first, then B's (unaligned_dataset.py:32-33)
         db = self._draw(imgs[1], b)
         ca, cb = self._draw_elastic(), self._draw_elastic()      # --elastic: one field per image, after every other draw of the item
-        A, B = self._prep(imgs[0], da, ca), self._prep(imgs[1], db, cb)
+        ra, rb = self._draw_photo(), self._draw_photo()          # --photo_aug: one record per image, after both fields
+        A, = self._photo([self._prep(imgs[0], da, ca)], ra)
+        B, = self._photo([self._prep(imgs[1], db, cb)], rb)
         return {'A': ops.logical_view(A, 3), 'B': ops.logical_view(B, 3), 'A_paths': [a], 'B_paths': [b]}
 
 
@@ -241,6 +278,7 @@ class AlignedFolderDataset(_FolderDataset):
         ctrl = self._draw_elastic()                            # --elastic: one field for both halves, after every other draw of the item
         A = self._image_prep(dev, w_offset, h_offset, n, flip, 0, ctrl)
         B = self._image_prep(dev, w + w_offset, h_offset, n, flip, 0, ctrl)
+        A, B = self._photo([A, B], self._draw_photo())         # --photo_aug: one record for both halves, its draws after the field's
         return {'A': ops.logical_view(A, 3), 'B': ops.logical_view(B, 3), 'A_paths': [path], 'B_paths': [path]}
 
 

@@ -721,6 +721,41 @@ def image_prep_elastic(img_u8, x0, y0, n, flip, rot, ctrl, nearest_mask, out=Non
     return out
 
 
+def photo_record(rec):
+    """util.PhotoRec -> the sgan_photo_rec the C entry reads (the seed stays with the caller: the kernel draws nothing)."""
+    r = L.STRUCTS["sgan_photo_rec"]()
+    r.R = rec.R
+    for k, v in enumerate(rec.w):
+        r.w[k] = float(v)
+    r.gamma, r.contrast, r.brightness, r.sigma_n, r.nbox = rec.gamma, rec.contrast, rec.brightness, rec.sigma_n, len(rec.boxes)
+    if len(rec.boxes) > len(r.box_value):
+        raise L.SganError("image_photo: %d boxes (0 .. %d)" % (len(rec.boxes), len(r.box_value)))
+    for b, (y0, y1, x0, x1, value) in enumerate(rec.boxes):
+        r.box_y0[b], r.box_y1[b], r.box_x0[b], r.box_x1[b], r.box_value[b] = y0, y1, x0, x1, value
+    return r
+
+
+def image_photo(src, rec, mask, noise=None, out=None):
+    """Photometric augmentation of a prepared crop (sgan_image_photo; util.photo_ref / util.photo_bounds are the host yardsticks):
+    src [H, W, Cs] fp32 NHWC in [-1, 1], as image_prep* leaves it -> out (a new [H, W, Cs] buffer unless given; never src).  rec: a
+    util.PhotoRec; mask: bit c set = channel c is an image channel, every other channel is copied bit for bit; noise: a contiguous
+    [popcount(mask), H, W] fp32 device tensor of N(0, 1) values (ops.normal_fill) for the noise stage, or None."""
+    require_gpu(src, "image_photo")
+    H, W, Cs = src.shape
+    assert src.stride(0) == W * src.stride(1), (src.shape, src.stride())
+    if out is None:
+        out = torch.empty((H, W, Cs), dtype=torch.float32, device=src.device)
+    require_gpu(out, "image_photo")
+    assert tuple(out.shape) == (H, W, Cs) and out.stride(0) == W * out.stride(1), (out.shape, out.stride())
+    if noise is not None:
+        require_gpu(noise, "image_photo")
+        assert noise.dtype == torch.float32 and noise.is_contiguous() and tuple(noise.shape) == (bin(int(mask)).count("1"), H, W), \
+            (noise.shape, noise.dtype, mask)
+    L.check(L.lib().sgan_image_photo(_ptr(_act(src)), src.stride(1), _ptr(_act(out)), out.stride(1), H, W, Cs, int(mask),
+                                     C.byref(photo_record(rec)), _ptr(noise), _stream()), "sgan_image_photo")
+    return out
+
+
 def image_prep_tile(img_u8, x0, y0, h, w, flip, rot, out=None):
     """image_prep whose h x w window at (x0, y0) may reach outside the image (indices reflected without repeating the edge, like
     F.pad(mode='reflect')) and may be rectangular (rot 0 only): [H0, W0, 3] uint8 device tensor -> [h, w, 4] fp32 NHWC buffer

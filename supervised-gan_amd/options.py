@@ -147,6 +147,7 @@ class BaseOptions:
         check_clean_options(self.opt, self.parser)
         check_topo_options(self.opt, self.parser)
         check_elastic_options(self.opt)
+        check_photo_options(self.opt)
         check_tile_options(self.opt, self.parser)
         check_ema_options(self.opt, self.parser)
         check_diffaug_options(self.opt, self.parser)
@@ -420,6 +421,50 @@ def elastic_nearest_mask(opt):
     return sum(1 << 'rgb'.index(ch) for ch in set(opt.elastic_label_channels))
 
 
+def check_photo_options(opt):
+    """--photo_aug LIST varies the grey values of the crops of the image-folder feeders (data.py, util.photo_draw): a comma list of
+    blur, gamma, contrast, brightness, noise, occlude.  Refuses unknown or repeated stage names and out-of-range parameters, and a
+    --photo_blur whose largest radius min(12, ceil(3 SMAX)) the --fineSize cannot hold.  Leaves opt.photo_aug as a tuple of stage
+    names in the order they are drawn and applied in, and opt.photo_occlude as (int K, float FRAC)."""
+    if getattr(opt, 'photo_aug', None) is None:
+        return
+    import math
+    from .util import PHOTO_MAX_BOX, PHOTO_MAX_R, PHOTO_STAGES
+    names = [s.strip() for s in opt.photo_aug.split(',')] if isinstance(opt.photo_aug, str) else list(opt.photo_aug)
+    assert names and all(s in PHOTO_STAGES for s in names) and len(set(names)) == len(names), \
+        "--photo_aug: a comma list of %s, each at most once (got '%s')" % (', '.join(PHOTO_STAGES), opt.photo_aug)
+    assert opt.dataroot != 'synthetic', \
+        "--photo_aug varies the crops of the image-folder feeders; the synthetic feeder has none (give --dataroot a folder)"
+    finite = all(math.isfinite(float(v)) for v in (opt.photo_prob, opt.photo_blur, opt.photo_gamma, opt.photo_contrast, opt.photo_brightness,
+                                                   opt.photo_noise, *opt.photo_occlude))
+    assert finite, "--photo_*: every value must be finite"
+    assert 0.0 <= opt.photo_prob <= 1.0, "--photo_prob: a probability (got %g)" % opt.photo_prob
+    assert 0.5 <= opt.photo_blur <= 4.0, "--photo_blur SMAX: sigma ~ U(0.5, SMAX), 0.5 <= SMAX <= 4 (got %g)" % opt.photo_blur
+    assert 1.0 <= opt.photo_gamma <= 2.0, "--photo_gamma G: gamma = exp(U(-ln G, ln G)), 1 <= G <= 2 (got %g)" % opt.photo_gamma
+    assert 0.0 <= opt.photo_contrast < 1.0, "--photo_contrast C: c ~ U(1 - C, 1 + C), 0 <= C < 1 (got %g)" % opt.photo_contrast
+    assert opt.photo_brightness >= 0.0, "--photo_brightness B must not be negative (got %g)" % opt.photo_brightness
+    assert opt.photo_noise >= 0.0, "--photo_noise S must not be negative (got %g)" % opt.photo_noise
+    k, frac = opt.photo_occlude
+    assert float(k) == int(k) and 1 <= int(k) <= PHOTO_MAX_BOX and 0.0 < frac <= 1.0, \
+        "--photo_occlude K FRAC: K boxes, a whole number 1..%d, of sides up to FRAC of the crop, 0 < FRAC <= 1 (got %g %g)" % (PHOTO_MAX_BOX, k, frac)
+    assert opt.photo_channels and set(opt.photo_channels) <= set('rgb') and len(set(opt.photo_channels)) == len(opt.photo_channels), \
+        "--photo_channels: letters of r, g, b (got '%s')" % opt.photo_channels
+    assert not set(opt.photo_channels) & set(opt.elastic_label_channels), \
+        "--photo_channels '%s' and --elastic_label_channels '%s' share a channel: a label channel takes no grey value variation" % (
+            opt.photo_channels, opt.elastic_label_channels)
+    if 'blur' in names:
+        r = min(PHOTO_MAX_R, int(math.ceil(3.0 * opt.photo_blur)))
+        assert r <= opt.fineSize - 1, \
+            "--photo_blur %g reaches %d pixels, more than a --fineSize %d crop can mirror (at most fineSize - 1)" % (opt.photo_blur, r, opt.fineSize)
+    opt.photo_aug = tuple(s for s in PHOTO_STAGES if s in names)
+    opt.photo_occlude = (int(k), float(frac))
+
+
+def photo_channel_mask(opt):
+    """The channel mask of ops.image_photo for --photo_channels: bit c set = channel c of RGB holds the image."""
+    return sum(1 << 'rgb'.index(ch) for ch in set(opt.photo_channels))
+
+
 class TrainOptions(BaseOptions):
     def initialize(self):
         BaseOptions.initialize(self)
@@ -523,6 +568,22 @@ class TrainOptions(BaseOptions):
         a('--elastic_label_channels', type=str, default='rg',
           help='letters of the RGB channels that hold labels and are sampled at the nearest pixel under --elastic; the others are '
                'sampled bilinearly (default rg: the reference keeps labels in r and g and the image in b)')
+        # photometric augmentation of every training crop, on the device (not in the reference): check_photo_options, DESIGN.md R38
+        a('--photo_aug', type=str, default=None, metavar='LIST',
+          help='image-folder feeders: vary the grey values of the image channels of every training crop -- a comma list of blur, '
+               'gamma, contrast, brightness, noise, occlude; each listed stage fires with probability --photo_prob, and they apply '
+               'in that order after the crop / flip / rot90 / --elastic kernel (not in the reference; default off)')
+        a('--photo_prob', type=float, default=0.5, metavar='P', help='--photo_aug: the probability of each listed stage')
+        a('--photo_blur', type=float, default=2.0, metavar='SMAX', help='--photo_aug blur: Gaussian blur of sigma ~ U(0.5, SMAX) pixels, SMAX <= 4')
+        a('--photo_gamma', type=float, default=1.5, metavar='G', help='--photo_aug gamma: gamma = exp(U(-ln G, ln G)) on the [0, 1] grey value, G <= 2')
+        a('--photo_contrast', type=float, default=0.25, metavar='C', help='--photo_aug contrast: c ~ U(1 - C, 1 + C) about mid-grey, C < 1')
+        a('--photo_brightness', type=float, default=0.1, metavar='B', help='--photo_aug brightness: b ~ U(-B, B) in [0, 1] grey value units')
+        a('--photo_noise', type=float, default=0.05, metavar='S', help='--photo_aug noise: additive N(0, sigma_n^2), sigma_n ~ U(0, S) in [-1, 1] units')
+        a('--photo_occlude', type=float, default=(2, 0.25), nargs=2, metavar=('K', 'FRAC'),
+          help='--photo_aug occlude: K <= 4 boxes of sides U(1, FRAC fineSize) filled with a value ~ U(-1, 1)')
+        a('--photo_channels', type=str, default='b',
+          help='letters of the RGB channels that hold the image and are varied by --photo_aug; must not share a letter with '
+               '--elastic_label_channels (default b: the reference keeps labels in r and g and the image in b)')
         # exponential moving average of the generator's weights (not in the reference, which evaluates the last iterate)
         a('--ema_decay', type=float, default=None, metavar='D',
           help='fcgan / cgan / cgan2 / segmentation: keep an exponential moving average of the generator, shadow += (1 - D) (G - shadow) '

@@ -6,8 +6,11 @@ border term of the U-Net loss (`border_weight_map`, the yardstick of the device'
 a training crop (`elastic_field`, `elastic_prep`, the yardsticks of the device's sgan_image_prep_elastic), and the geometry of
 whole-image inference (`tile_plan`, `tile_window`, `prep_tile_ref`, `blend_tiles_ref`, the yardsticks of sgan_image_prep_tile /
 sgan_tile_blend / sgan_tile_finish), and the augmentation of discriminator inputs (`diffaug_params`, `diffaug_ref`,
-`diffaug_bwd_ref`, the yardsticks of sgan_diffaug_draw / sgan_diffaug_multi_fwd / sgan_diffaug_multi_bwd)."""
+`diffaug_bwd_ref`, the yardsticks of sgan_diffaug_draw / sgan_diffaug_multi_fwd / sgan_diffaug_multi_bwd), and the photometric
+augmentation of a training crop (`photo_draw`, the draw of the feeders; `photo_taps`, `photo_ref`, `photo_bounds`, the yardsticks of
+sgan_image_photo)."""
 import os
+import random
 
 import numpy as np
 
@@ -1464,3 +1467,175 @@ def dist_terms_ref(logits, label_or_target, mode, cls, t_sdsq, p_sdsq=None, boun
         dzH = (2.0 * (p - g) * F * valid / N)[:, None] * dpdz
     state[3], state[4] = LB, LH
     return LB, LH, state, dzB, dzH
+
+
+# ---- photometric augmentation of a training crop (--photo_aug): the parameter draw of the feeders and the yardsticks
+# of sgan_image_photo --------------------------------------------------------------------------------------------------------------
+PHOTO_STAGES = ('blur', 'gamma', 'contrast', 'brightness', 'noise', 'occlude')      # the order they are drawn and applied in
+PHOTO_MAX_R, PHOTO_MAX_BOX = 12, 4      # SGAN_PHOTO_MAX_R, SGAN_PHOTO_MAX_BOX
+PHOTO_POW_ULP = 4       # what the bounds allow powf, in ulps of its result (chosen before any run: DESIGN.md R38)
+# one fp32 rounding, relative; the factor pays for the float64 evaluation of the end points themselves
+PHOTO_U = 2.0 ** -24 * (1.0 + 2.0 ** -20)
+_PHOTO_TINY = 2.0 ** -149
+
+
+def _f32(v):
+    return float(np.float32(v))
+
+
+class PhotoRec:
+    """The parameters of one sgan_image_photo call, as the fp32 values the device receives (sgan_photo_rec), and the 64-bit `seed`
+    of the noise planes, which the caller of ops.normal_fill uses and the kernel never sees.  boxes: (y0, y1, x0, x1, value), rows
+    [y0, y1) x columns [x0, x1).  The defaults are the neutral values: PhotoRec() is the bitwise copy."""
+
+    def __init__(self, taps=(1.0,), gamma=1.0, contrast=1.0, brightness=0.0, sigma_n=0.0, boxes=(), seed=0):
+        self.w = np.asarray(taps, dtype=np.float32).reshape(-1)
+        assert 1 <= len(self.w) <= PHOTO_MAX_R + 1, len(self.w)
+        self.gamma, self.contrast, self.brightness, self.sigma_n = _f32(gamma), _f32(contrast), _f32(brightness), _f32(sigma_n)
+        self.boxes = [(int(y0), int(y1), int(x0), int(x1), _f32(v)) for y0, y1, x0, x1, v in boxes]
+        self.seed = int(seed) & (2 ** 64 - 1)
+
+    @property
+    def R(self):
+        return len(self.w) - 1
+
+    def point_stages(self, noise):
+        """(gamma, contrast / brightness, noise) run: the device's rule for skipping a neutral stage."""
+        return self.gamma != 1.0, self.contrast != 1.0 or self.brightness != 0.0, noise is not None and self.sigma_n != 0.0
+
+    def __repr__(self):
+        return 'PhotoRec(R=%d, gamma=%r, contrast=%r, brightness=%r, sigma_n=%r, boxes=%r, seed=%d)' % (
+            self.R, self.gamma, self.contrast, self.brightness, self.sigma_n, self.boxes, self.seed)
+
+
+def photo_taps(sigma):
+    """The fp32 taps w[0 .. R] of the blur: R = min(12, ceil(3 sigma)), w_k = exp(-k^2 / (2 sigma^2)) in float64, normalised so that
+    w_0 + 2 sum_{k >= 1} w_k = 1, then rounded to fp32."""
+    sigma = float(sigma)
+    assert sigma > 0.0, sigma
+    R = min(PHOTO_MAX_R, int(np.ceil(3.0 * sigma)))
+    w = np.exp(-np.arange(R + 1, dtype=np.float64) ** 2 / (2.0 * sigma * sigma))
+    return (w / (w[0] + 2.0 * w[1:].sum())).astype(np.float32)
+
+
+def photo_draw(opt, n, rng=random):
+    """The PhotoRec of one n x n training crop under --photo_aug, from Python's `random` (or `rng`: anything with random() and
+    getrandbits(64)).  The six stages are visited in the order of PHOTO_STAGES.  A stage that --photo_aug does not list draws nothing.
+    A listed stage draws its gate g = random() and fires when g < --photo_prob; a stage that does not fire draws nothing else.  A stage
+    that fires then draws, with r = random() anew each time:
+        blur        sigma = 0.5 + (SMAX - 0.5) r                                                   -> photo_taps(sigma)
+        gamma       gamma = exp((2 r - 1) ln G)
+        contrast    c = 1 - C + 2 C r
+        brightness  b = (2 r - 1) B
+        noise       sigma_n = S r, then seed = getrandbits(64)
+        occlude     for each of the K boxes: h = int(1 + r (m - 1)), w = int(1 + r (m - 1)) with m = max(1, FRAC n), then
+                    y0 = int(r (n - h + 1)), x0 = int(r (n - w + 1)), value = 2 r - 1              (five draws a box)
+    so a call makes len(--photo_aug) gate draws and 1, 1, 1, 1, 2, 5 K further ones for the stages that fire."""
+    stages, prob = opt.photo_aug, float(opt.photo_prob)
+    kw = {}
+    for stage in PHOTO_STAGES:
+        if stage not in stages or not rng.random() < prob:
+            continue
+        if stage == 'blur':
+            kw['taps'] = photo_taps(0.5 + (float(opt.photo_blur) - 0.5) * rng.random())
+        elif stage == 'gamma':
+            kw['gamma'] = float(np.exp((2.0 * rng.random() - 1.0) * np.log(float(opt.photo_gamma))))
+        elif stage == 'contrast':
+            kw['contrast'] = 1.0 - float(opt.photo_contrast) + 2.0 * float(opt.photo_contrast) * rng.random()
+        elif stage == 'brightness':
+            kw['brightness'] = (2.0 * rng.random() - 1.0) * float(opt.photo_brightness)
+        elif stage == 'noise':
+            kw['sigma_n'] = float(opt.photo_noise) * rng.random()
+            kw['seed'] = rng.getrandbits(64)
+        else:
+            K, frac = int(opt.photo_occlude[0]), float(opt.photo_occlude[1])
+            m, boxes = max(1.0, frac * n), []
+            for _ in range(K):
+                h, w = int(1.0 + rng.random() * (m - 1.0)), int(1.0 + rng.random() * (m - 1.0))
+                y0, x0 = int(rng.random() * (n - h + 1)), int(rng.random() * (n - w + 1))
+                boxes.append((y0, y0 + h, x0, x0 + w, 2.0 * rng.random() - 1.0))
+            kw['boxes'] = boxes
+    return PhotoRec(**kw)
+
+
+def _photo_blur_pass(a, w, axis):
+    """w[0] a + sum_k w[k] (a shifted by -k + a shifted by +k) along `axis` of a float64 array, indices mirrored into the array."""
+    N = a.shape[axis]
+    idx = np.arange(N)
+    out = float(w[0]) * a
+    for k in range(1, len(w)):
+        out = out + float(w[k]) * (np.take(a, _mirror_index(idx - k, N), axis=axis) + np.take(a, _mirror_index(idx + k, N), axis=axis))
+    return out
+
+
+def _photo_rn(lo, hi, budget):
+    """The interval after one fp32 rounding to nearest: rounding is monotone and moves x by at most 2^-24 |x|."""
+    if not budget:
+        return lo, hi
+    return lo - PHOTO_U * np.abs(lo) - _PHOTO_TINY, hi + PHOTO_U * np.abs(hi) + _PHOTO_TINY
+
+
+def _photo_channel(lo, hi, rec, nz, yy, xx, budget):
+    """One masked channel through the six stages as the interval [lo, hi] of float64 [H, W] planes.  Every stage is monotone
+    (non-negative taps, pow on [0, 1], contrast > 0, an added constant, clamps), so a stage maps end point to end point; with
+    `budget` every device rounding then widens the interval (DESIGN.md R38 counts them), without it lo == hi is the float64 value."""
+    R = rec.R
+    if R > 0:
+        for axis in (1, 0):      # rows first, then columns
+            mag = max(1.0, float(np.abs(lo).max()), float(np.abs(hi).max()))
+            lo, hi = _photo_blur_pass(lo, rec.w, axis), _photo_blur_pass(hi, rec.w, axis)
+            if budget:      # (2 R + 2) roundings a pass, each of a value no larger than the largest input (the taps sum to 1)
+                e = (2 * R + 2) * PHOTO_U * mag
+                lo, hi = lo - e, hi + e
+    do_gamma, do_cb, do_noise = rec.point_stages(nz)
+    if do_gamma:
+        lo, hi = _photo_rn(0.5 * lo + 0.5, 0.5 * hi + 0.5, budget)
+        lo, hi = np.clip(lo, 0.0, 1.0) ** rec.gamma, np.clip(hi, 0.0, 1.0) ** rec.gamma
+        if budget:      # powf: PHOTO_POW_ULP ulps of the result, an ulp being at most 2^-23 of it
+            lo, hi = lo - PHOTO_POW_ULP * 2.0 * PHOTO_U * lo - _PHOTO_TINY, hi + PHOTO_POW_ULP * 2.0 * PHOTO_U * hi + _PHOTO_TINY
+            lo = np.maximum(lo, 0.0)      # powf of a value in [0, 1] is not negative
+        lo, hi = _photo_rn(2.0 * lo - 1.0, 2.0 * hi - 1.0, budget)
+    if do_cb:
+        lo, hi = _photo_rn(rec.contrast * lo + 2.0 * rec.brightness, rec.contrast * hi + 2.0 * rec.brightness, budget)
+    if do_noise:
+        lo, hi = _photo_rn(lo + rec.sigma_n * nz, hi + rec.sigma_n * nz, budget)
+    if do_gamma or do_cb or do_noise:
+        lo, hi = np.clip(lo, -1.0, 1.0), np.clip(hi, -1.0, 1.0)
+    for y0, y1, x0, x1, value in rec.boxes:      # a later box wins
+        inside = (yy >= y0) & (yy < y1) & (xx >= x0) & (xx < x1)
+        lo, hi = np.where(inside, value, lo), np.where(inside, value, hi)
+    return lo, hi
+
+
+def _photo_run(x, rec, mask, noise, budget):
+    x = np.asarray(x)
+    assert x.dtype == np.float32 and x.ndim == 3, (x.dtype, x.shape)
+    H, W, C = x.shape
+    chans = [c for c in range(C) if (int(mask) >> c) & 1]
+    assert int(mask) >> C == 0 and 0 <= rec.R <= min(PHOTO_MAX_R, H - 1, W - 1) and len(rec.boxes) <= PHOTO_MAX_BOX, (mask, C, rec)
+    if noise is not None:
+        noise = np.asarray(noise)
+        assert noise.dtype == np.float32 and noise.shape == (len(chans), H, W), (noise.dtype, noise.shape)
+    yy, xx = np.mgrid[:H, :W]
+    with np.errstate(invalid='ignore'):      # a channel that is only copied may hold any bits, a signalling NaN among them
+        lo, hi = x.astype(np.float64), x.astype(np.float64)
+    for j, c in enumerate(chans):
+        plane = x[..., c].astype(np.float64)
+        assert np.abs(plane).max() <= 1.0, "image channels hold values in [-1, 1]"
+        nz = None if noise is None else noise[j].astype(np.float64)
+        lo[..., c], hi[..., c] = _photo_channel(plane, plane.copy(), rec, nz, yy, xx, budget)
+    return lo, hi
+
+
+def photo_ref(x, rec, mask, noise=None):
+    """The host yardstick of ops.image_photo (sgan_image_photo) in float64: x [H, W, C] fp32 with values in [-1, 1] in the channels
+    whose bit is set in `mask`, rec a PhotoRec, noise [popcount(mask), H, W] fp32 or None -> float64 [H, W, C].  The six stages on the
+    fp32 parameters, a neutral stage skipped as on the device; every other channel is x.  The trainers do not call it."""
+    return _photo_run(x, rec, mask, noise, False)[0]
+
+
+def photo_bounds(x, rec, mask, noise=None):
+    """(lo, hi), float64 [H, W, C]: the interval every element of the device's result must lie in, lo <= got <= hi -- photo_ref with
+    the device's fp32 roundings counted stage by stage, no tuned tolerance.  Channels outside the mask, and every
+    channel of the all-neutral record, have lo == hi == x: the bits."""
+    return _photo_run(x, rec, mask, noise, True)

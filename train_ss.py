@@ -51,10 +51,10 @@ def should_save_best(best_metric, accs, best):
 
 def validation_options(opt):
     """The second option set of train_ss.py:33-42: phase val, batch 1, in order, no flip, no rotation, loaded and cropped at valSize;
-    no elastic deformation either (--elastic augments the training crops only)."""
+    no elastic deformation and no photometric variation either (--elastic and --photo_aug augment the training crops only)."""
     val = copy.copy(opt)
     val.phase, val.nThreads, val.batchSize, val.serial_batches, val.no_flip, val.no_rotate = 'val', 1, 1, True, True, True
-    val.elastic = None
+    val.elastic = val.photo_aug = None
     val.valSize = val.valSize or val.loadSize
     val.loadSize = val.fineSize = val.valSize
     return val
