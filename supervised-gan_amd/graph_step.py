@@ -123,7 +123,7 @@ class GraphedStep:
         else:
             self.gA = torch.cuda.CUDAGraph()
             self.fnsA = [self._begin, m.forward]      # _begin: the statistics arenas of the whole step (graph A and every piece of graph B), one launch
-            with torch.cuda.graph(self.gA, capture_error_mode=self._mode):
+            with ops.graph_capture(self.gA, capture_error_mode=self._mode):
                 for f in self.fnsA:
                     f()
                 self._fakeA = sources()
@@ -161,7 +161,7 @@ class GraphedStep:
         g = torch.cuda.CUDAGraph()
         if pool is None:
             pool = getattr(self, "_pool", None)
-        with torch.cuda.graph(g, pool=pool, stream=getattr(self, "_cap_stream", None), capture_error_mode=mode):
+        with ops.graph_capture(g, pool=pool, stream=getattr(self, "_cap_stream", None), capture_error_mode=mode):
             for f in fns:
                 f()
         self._pool = g.pool()

@@ -5,6 +5,7 @@ multiple of 4; `tensor.stride(1)` is the pixel stride so channel slices of wider
 Everything here launches on torch's current stream and never synchronises."""
 import contextlib
 import ctypes as C
+import gc
 import weakref
 
 import torch
@@ -237,6 +238,24 @@ def arena_scope(pool, begin=True):
         yield pool
     finally:
         _ARENAS = saved
+
+
+@contextlib.contextmanager
+def graph_capture(graph, **kw):
+    """torch.cuda.graph(graph, **kw) with the cycle collector out of the way: dead cycles are collected BEFORE the capture begins and
+    the collector stays off until it ends.  torch no longer collects on entry, and a trainer, a GraphedStep or a reconstructor that
+    has gone out of use is a reference cycle: it lives until some later allocation happens to start a collection.  If that is an
+    allocation made while a stream is capturing, the dead object's graphs and their memory pool are destroyed in the middle of the
+    capture, which a capture in the (default) global error mode refuses; the destructor cannot raise, so the process aborts."""
+    gc.collect()
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, **kw):
+            yield
+    finally:
+        if was_on:
+            gc.enable()
 
 
 def begin_step(also_zero=()):

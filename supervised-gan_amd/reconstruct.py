@@ -102,7 +102,7 @@ class LatentReconstructor:
         stream.synchronize()
         self._graph = torch.cuda.CUDAGraph()
         with ops.arena_scope(self._arenas, begin=False):
-            with torch.cuda.graph(self._graph, stream=stream):
+            with ops.graph_capture(self._graph, stream=stream):
                 self._program()
         torch.cuda.current_stream().wait_stream(stream)
 
